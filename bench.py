@@ -21,12 +21,18 @@ RCCL all-gather per batch of images -- also on ONE GPU (a one-rank "nccl" group)
 code path as N = 8.
 
 Prints ONE compact JSON line on rank 0 (< 4 KB: the contract's keys, `roofline` for the dominant kernel -- the fp32-MFMA
-fc GEMMs, timed by the launches themselves during the timed steps --, `cpu_baseline` = the oracle's NumPy / C / BLAS
-restatement on the host cores, `path_floor`, `value_200_steps`, `box` = what THIS box sustains).  Everything else that is
-measured -- the kernel table, and with --extras the side legs: `one_pass`, `tz_sweep`, `calibrated_tz`, `stream_tz` (distinct
-images at a tuned threshold, lockstep batches), `deep_tree` (BASELINE config 4, both network scales), `shared_detection`
-(config 3), `nms`, `end_to_end`, `cli` -- goes to bench_extras.json beside this script (and gpurun_out/ when that exists),
-never into the printed line: round 5's 30 KB line came back from the driver as `parsed: null`.
+fc GEMMs, timed by the launches themselves during the timed steps --, `path_floor`).  A plain run does only that: set up,
+warm up, time the --steps steps, write the last step's outputs (--dump-outputs DIR), print the line.  The conv5_3 maps it
+times on are VGG16's on the synthetic images, computed on the host CPU (bitwise the same from run to run, whatever the GPU
+libraries would pick), so that two builds of the project can be compared output for output.
+
+--full adds everything else that is measured: in the line `cpu_baseline` = the oracle's NumPy / C / BLAS restatement on
+the host cores, `value_200_steps`, `box` = what THIS box sustains; in the record file (--extras-file, default
+bench_extras.json beside this script) the kernel table and the side legs: `one_pass`, `tz_sweep`, `calibrated_tz`,
+`stream_tz` (distinct images at a tuned threshold, lockstep batches), `deep_tree` (BASELINE config 4, both network scales),
+`shared_detection` (config 3), `nms`, `end_to_end` (the PyTorch-ROCm backbone on the GPU), `cli`.  The --no-* switches
+leave parts of it out.  None of it goes into the printed line: round 5's 30 KB line came back from the driver as
+`parsed: null`.
 """
 import argparse
 import json
@@ -202,6 +208,31 @@ def write_extras(out, path=None):
     return done
 
 
+DUMP_LIMIT = 64 << 20         # bytes: --dump-outputs writes at most this much
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: each array as DIR/<name>.npy, float32 or float64 as computed; returns the bytes written."""
+    os.makedirs(outdir, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        total += a.nbytes
+        assert total <= DUMP_LIMIT, total
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    return total
+
+
+def host_blob(im, scale):
+    """_get_image_blob (lib/detect/test.py:27-59) on the host for an image the test scale leaves as it is (scale 1: the
+    resize is the identity): BGR minus the (float64) pixel means, rounded once to float32, [1, 3, H, W]."""
+    from detect.config import cfg
+    assert scale == 1.0, scale
+    b = (im.astype(np.float64) - cfg.PIXEL_MEANS).astype(np.float32)
+    return np.ascontiguousarray(b.transpose(2, 0, 1)[None])
+
+
 def cpu_baseline(head, fmap, Tz, budget_s=20.0):
     """The oracle (kind "port") on the host, as SURVEY 8(d) specifies the CPU baseline: NumPy geometry exactly as
     lib/detect/test.py (one thread), C divide_region / RoIPool, and the fc head through torch CPU `addmm` as the stand-in for
@@ -301,10 +332,16 @@ def main():
                     help="the batch exchange as the library's own ncclAllGather on the ctx stream (az_gather_records) instead "
                          "of torch.distributed's all_gather_into_tensor")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--extras", action="store_true",
-                    help="also run the side measurements (other search forms, Tz sweeps, streams of distinct images, BASELINE configs "
-                         "3 / 4, NMS sizes, backbone + search end to end, the CLI loop); every one of them lands in the extras "
-                         "file, never in the printed line.  The default run is the headline + roofline + cpu_baseline only")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything besides the headline: the CPU baseline, the box calibration, the kernel table, "
+                         "the 200-step loop behind a short run, and the side measurements (other search forms, Tz sweeps, "
+                         "streams of distinct images, BASELINE configs 3 / 4, NMS sizes, backbone + search end to end, the CLI "
+                         "loop); the --no-* switches leave parts out.  They land in the extras file, never in the printed line. "
+                         "Without it: set-up, warm-up, the timed steps and the line only")
+    ap.add_argument("--extras", action="store_true", help="the earlier name of --full")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (its proposals, float64 [n, 4], "
+                         "and scores, float32 [n]) as DIR/<name>.npy")
     ap.add_argument("--extras-file", default=None,
                     help="where the full record goes (default: bench_extras.json beside this script, and a copy under gpurun_out/ "
                          "when that directory exists)")
@@ -346,10 +383,11 @@ def main():
                     help="HIP events around the fc GEMM launches of every n-th timed step (1: every step, ~30 us/step of stream time)")
     ap.add_argument("--maps", type=int, default=4, help="distinct images (conv5_3 maps) per GPU rotated through the timed loop")
     args = ap.parse_args()
-    if not args.extras:
-        # the side legs are opt-in (round 5's line with all of them was 30 KB; the driver keeps 8 KB of stdout)
+    args.full = args.full or args.extras
+    if not args.full:
+        # a plain run measures the headline only: every side measurement is --full's
         for k in ("no_e2e", "no_pipelined", "no_two_pass", "no_fast", "no_one_pass", "no_level_loop", "no_calibrated",
-                  "no_one_lane", "no_stream", "no_sweep", "no_extras"):
+                  "no_one_lane", "no_stream", "no_sweep", "no_extras", "no_cpu_baseline", "no_box"):
             setattr(args, k, True)
 
     if (args.gpus > 1 or args.launcher) and "WORLD_SIZE" not in os.environ:
@@ -398,25 +436,36 @@ def main():
     dist_on = rccl["backend"] is not None
 
     head = synth.make_head(seed=1234, **synth.FULL_DIMS)
-    # (plumbing: conv5_3 comes out [H][W][C] and is borrowed in place; channels_last compute + MIOpen's benchmark search,
-    #  set before the first forward, is the fastest fp32 configuration found for the fixed 600x1000 shape)
-    torch.backends.cudnn.benchmark = True
-    backbone = VGG16Conv5(device=dev, seed=4321, channels_last_out=True, channels_last_compute=True)
-    net = HipAZNet(head, backbone=backbone, device=local_rank, name="vgg16_az_net_hip", max_regions=4096)
-    net.ctx.set_lanes(args.lanes)
-    from detect.test import _get_image_blob
+    from detect.test import _get_image_blob, _im_scale
     # images owned by this rank: seeds rank, rank + world, ... (BASELINE config 5 is one image per GPU; the
     # timed loop rotates through args.maps of them so that no step re-reads the previous step's map)
     ims = [synth.make_image(rank + world * j, H_IM, W_IM) for j in range(max(1, args.maps))]
     im = ims[0]
-    blob, scales = _get_image_blob(im, net)                  # HIP front-end kernel -> CUDA tensor
-    backbone.normalize_output(blob)                          # random-init weights: unit-RMS conv5_3
-    # resident in HBM from here on, channel-last (what the backbone hands over with channels_last_out=True)
-    blobs = [_get_image_blob(x, net)[0] for x in ims]
-    convs = [net.compute_conv(b).clone().contiguous(memory_format=torch.channels_last) for b in blobs]
+    scale0 = float(_im_scale(im.shape)[0])
+    # The hot path's input, conv5_3 of each image: the seeded VGG16 on the host CPU, its last layer scaled to a unit-RMS map
+    # on the first image (random-init weights; stands in for training).  Computed there, the maps are the same bits from
+    # run to run; MIOpen's algorithm search on the GPU is not (and may compile for a while on first use).
+    host_bb = VGG16Conv5(device="cpu", seed=4321)
+    host_blobs = [host_blob(x, scale0) for x in ims]
+    host_bb.normalize_output(host_blobs[0])
+    # resident in HBM from here on, channel-last (the layout RoIPool reads, as the GPU backbone hands it over)
+    convs = [host_bb(b).to(dev).contiguous(memory_format=torch.channels_last) for b in host_blobs]
+    del host_bb, host_blobs
     conv = convs[0]
+    backbone = blob = blobs = None
+    if args.full:
+        # the PyTorch-ROCm backbone of the end-to-end legs (plumbing: conv5_3 comes out [H][W][C] and is borrowed in place;
+        # channels_last compute + MIOpen's benchmark search, set before the first forward, is the fastest fp32
+        # configuration found for the fixed 600x1000 shape)
+        torch.backends.cudnn.benchmark = True
+        backbone = VGG16Conv5(device=dev, seed=4321, channels_last_out=True, channels_last_compute=True)
+    net = HipAZNet(head, backbone=backbone, device=local_rank, name="vgg16_az_net_hip", max_regions=4096)
+    net.ctx.set_lanes(args.lanes)
+    if args.full:
+        blob = _get_image_blob(im, net)[0]                   # HIP front-end kernel -> CUDA tensor
+        backbone.normalize_output(blob)                      # random-init weights: unit-RMS conv5_3
+        blobs = [_get_image_blob(x, net)[0] for x in ims]
     net.set_conv(conv)
-    scale0 = float(scales[0])
     one_pass_main = bool(args.one_pass) and args.tz <= 0.0
 
     def mk(static):
@@ -498,7 +547,8 @@ def main():
                 while launched < min(nsteps, i + depth):
                     launch(launched)
                     launched += 1
-                reruns[0] += int(net.ctx.propose_fetch(want_scores=True, want_stats=True)[2].n_reruns)
+                last[0] = net.ctx.propose_fetch(want_scores=True, want_stats=True)
+                reruns[0] += int(last[0][2].n_reruns)
                 done(i)
                 if trace is not None:
                     trace.append((time.perf_counter() - t_i) * 1e3)
@@ -508,17 +558,18 @@ def main():
         for i in range(nsteps):
             n = nets[i % len(nets)]
             if len(q) == len(nets):
-                q.pop(0).ctx.propose_fetch(want_scores=True)
+                last[0] = q.pop(0).ctx.propose_fetch(want_scores=True, want_stats=True)
             n.ctx.propose_launch(prm, fmap=convs[i % len(convs)], producer_done=True)
             q.append(n)
         for m in q:
-            m.ctx.propose_fetch(want_scores=True)
+            last[0] = m.ctx.propose_fetch(want_scores=True, want_stats=True)
 
     # searches launched and not yet fetched in the loops below
     # (one lane: the lane's queue holds three -- its stage-1 kernels of the next two images sit behind the current one's, so
     #  neither the host's turn-around nor the batch exchange ever leaves the stream empty: 1.156 -> 1.126 ms per image)
     depth = 1 if args.no_queue_ahead else (args.queue_depth if args.queue_depth > 0 else 3)
     reruns = [0]                       # searches of the loop that had to be run twice (az_stats.n_reruns)
+    last = [None]                      # (boxes, scores, stats) of the loop's last step, as its caller receives them
     ev_every = [0]                     # > 0: HIP events around the fc GEMM launches of every ev_every-th step
     step_trace = []                    # host-side wall time of every step of the loop (diagnostics: median / tail in the line)
 
@@ -565,6 +616,9 @@ def main():
     barrier()
     dt = maxr(time.perf_counter() - t0)
     reruns_timed = reruns[0]
+    Y_last, S_last, st_last = last[0]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"proposals": Y_last, "scores": S_last})
     steps_ms = np.array(step_trace[:args.steps]) if step_trace else np.zeros(1)
     ev_every[0] = 0
     n_timed_steps = args.steps
@@ -572,10 +626,10 @@ def main():
     for n in nets:
         ktimes += n.ctx.last_kernel_times()
         n.ctx.set_profiling(0)
-    # `value` is EXACTLY --steps steps (the contract); a short run (the driver's 20 steps are a 25 ms timed region) is
-    # backed by the same loop over 200 steps, reported beside it
+    # `value` is EXACTLY --steps steps (the contract); with --full a short run (the driver's 20 steps are a 25 ms timed
+    # region) is backed by the same loop over 200 steps, reported beside it
     long_run = None
-    if args.steps < 100 and args.inflight == 1:
+    if args.full and args.steps < 100 and args.inflight == 1:
         barrier()
         t0 = time.perf_counter()
         run(200, params)
@@ -585,21 +639,24 @@ def main():
                     "unit": "proposals/s", "note": "the same timed loop over 200 steps, right behind the --steps run"}
     box = None
     gc.enable()
-    # every launch group of the search against ITS bound, from HIP events on a few extra, untimed steps (an event pair
-    # per launch group perturbs the stream by ~7 us each, so these steps are not part of `value`)
-    net.set_conv(conv)
-    for i in range(30):                # (reading the spans back left the GPU idle for a few ms: back to working clocks first)
-        net.ctx.propose_launch(params, fmap=convs[i % len(convs)], producer_done=True)
-        net.ctx.propose_fetch()
-    net.ctx.set_profiling(2 | 4)
-    n_tab = 6
-    for i in range(n_tab):
-        net.ctx.propose_launch(params, fmap=convs[i % len(convs)], producer_done=True)
-        net.ctx.propose_fetch()
-    tab_times = net.ctx.last_kernel_times()
-    net.ctx.set_profiling(0)
-    net.set_conv(conv)                 # (the loops left their last map in the context)
-    Y, S, st = net.propose(params, want_scores=True, want_stats=True)
+    n_tab, tab_times = 6, []
+    if args.full:
+        # every launch group of the search against ITS bound, from HIP events on a few extra, untimed steps (an event pair
+        # per launch group perturbs the stream by ~7 us each, so these steps are not part of `value`)
+        net.set_conv(conv)
+        for i in range(30):            # (reading the spans back left the GPU idle for a few ms: back to working clocks first)
+            net.ctx.propose_launch(params, fmap=convs[i % len(convs)], producer_done=True)
+            net.ctx.propose_fetch()
+        net.ctx.set_profiling(2 | 4)
+        for i in range(n_tab):
+            net.ctx.propose_launch(params, fmap=convs[i % len(convs)], producer_done=True)
+            net.ctx.propose_fetch()
+        tab_times = net.ctx.last_kernel_times()
+        net.ctx.set_profiling(0)
+        net.set_conv(conv)             # (the loops left their last map in the context)
+        Y, S, st = net.propose(params, want_scores=True, want_stats=True)
+    else:
+        Y, S, st = Y_last, S_last, st_last                   # (the search's figures: those of the last timed step)
     uniq = [int(st.level_unique[l]) for l in range(st.n_levels)]
     regions = [int(st.level_regions[l]) for l in range(st.n_levels)]
     spec_rows = int(st.spec_rows)
@@ -1214,7 +1271,7 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        paths = write_extras(out, args.extras_file)
+        paths = write_extras(out, args.extras_file) if args.full else []
         real_stdout.write(compact_line(out, extras_file=(os.path.relpath(paths[0], REPO) if paths else None)) + "\n")
         real_stdout.flush()
 

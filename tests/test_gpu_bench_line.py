@@ -15,8 +15,10 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_prints_one_compact_line(tmp_path):
     extras = tmp_path / "extras.json"
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2",
-                        "--no-cpu-baseline", "--no-box", "--extras-file", str(extras)],
+    # (--full: the 200-step loop, the kernel table and the record file; its side legs, CPU baseline and box calibration off)
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--full",
+                        "--no-cpu-baseline", "--no-box", "--no-e2e", "--no-one-lane", "--no-one-pass", "--no-two-pass",
+                        "--no-fast", "--no-calibrated", "--no-sweep", "--no-stream", "--no-extras", "--extras-file", str(extras)],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -40,3 +42,32 @@ def test_bench_prints_one_compact_line(tmp_path):
     assert 0.5 < d["path_floor"]["frac"] <= 1.0
     full = json.load(open(extras))
     assert full["value"] == pytest.approx(d["value"], rel=1e-5) and "kernel_table" in full
+
+
+def test_plain_run_times_the_steps_and_dumps_the_same_outputs_twice(tmp_path):
+    """A plain run (no --full): the contract's keys, `value` over exactly --steps steps, none of --full's measurements; with
+    --dump-outputs the last timed step's proposals and scores as .npy, the same bits from run to run (same inputs)."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    got = []
+    for i in range(2):
+        d = tmp_path / ("out%d" % i)
+        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "1",
+                            "--dump-outputs", str(d)],
+                           env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, r.stdout[:2000]
+        line = json.loads(lines[0], parse_constant=lambda c: pytest.fail("non-strict JSON constant %s" % c))
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "roofline"):
+            assert k in line, k
+        for k in ("cpu_baseline", "value_200_steps", "box", "extras_file"):
+            assert k not in line, k
+        assert line["steps"] == 5 and line["warmup"] == 1 and line["unit"] == "proposals/s" and line["dtype"] == "f32"
+        assert abs(line["value"] - 300.0 / (line["ms_per_step"] * 1e-3)) < 1e-3 * line["value"]
+        assert sorted(os.listdir(d)) == ["proposals.npy", "scores.npy"]
+        boxes, scores = np.load(d / "proposals.npy"), np.load(d / "scores.npy")
+        assert boxes.dtype == np.float64 and boxes.shape == (300, 4) and np.isfinite(boxes).all()
+        assert scores.dtype == np.float32 and scores.shape == (300,) and np.isfinite(scores).all()
+        got.append((boxes, scores))
+    assert np.array_equal(got[0][0], got[1][0]) and np.array_equal(got[0][1], got[1][1])
