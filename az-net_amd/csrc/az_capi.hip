@@ -86,6 +86,7 @@ int az_destroy(az_ctx *c)
     if (c->h_nmsg) hipHostFree(c->h_nmsg);
     if (c->nms_done) hipFree(c->nms_done);
     if (c->h_Y) { hipHostFree(c->h_Y); hipHostFree(c->h_S); }
+    if (c->dseg_host) hipHostFree(c->dseg_host);
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
     return AZ_OK;

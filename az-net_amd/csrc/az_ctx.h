@@ -266,6 +266,9 @@ struct az_ctx {
     unsigned short *dW6p = nullptr; float *dgscale = nullptr; float det_w6_scale = 0.f;
     float *dh6 = nullptr, *dh7 = nullptr, *dpart = nullptr, *dprob_u = nullptr, *ddelta_u = nullptr, *dprob = nullptr;
     double *dpred_u = nullptr, *dpred = nullptr;
+    // az_detect_batch: one pass's AzDetSeg + boxes (pinned staging and its device copy), per-row image sizes
+    unsigned char *dseg_host = nullptr, *dseg_dev = nullptr;
+    int *drow_hw = nullptr;
     // nms scratch (grown on demand)
     int nms_cap = 0;
     float *nms_dets = nullptr, *nms_sdets = nullptr;

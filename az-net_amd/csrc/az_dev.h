@@ -115,6 +115,22 @@ void azk_rois_dedup(hipStream_t s, const double *B, const int *Pptr, int cap, do
 void azk_dedup_rois(hipStream_t s, const long long *key, const int *grp, const int *Nptr, int cap,
                     unsigned char *first, const float *rois, const double *B, int *index, int *inv,
                     float *urois, double *ubox, int *Uptr);
+// az_detect_batch: the images of one pass, uploaded in one copy together with their boxes (which follow the struct)
+struct AzDetSeg {
+    int n;                                    // images in the pass
+    int off[AZ_BATCH_MAX + 1];                // image b's boxes are rows [off[b], off[b+1]); off[n] = boxes of the pass
+    int chunk0[AZ_BATCH_MAX];                 // global id of image b's first batch_size dedup chunk
+    int im_hw[2 * AZ_BATCH_MAX];              // image sizes (what each image's boxes are clipped to)
+    int feat_hw[2 * AZ_BATCH_MAX];            // map sizes (RoIPool)
+    double scale[AZ_BATCH_MAX];
+    const float *feats[AZ_BATCH_MAX];         // channel-last maps (RoIPool)
+};
+// roi projection + 1/16 dedup of a pass over several images: chunks never span two images, roi column 0 is the
+// image's index in the pass; unique rows come out image by image, each image's in az_detect's order.
+// row_hw [U][2]: the image size of every unique row.
+void azk_rois_dedup_seg(hipStream_t s, const double *B, const AzDetSeg *seg, int n, int cap, float dedup, int batch,
+                        float *rois, long long *key, int *grp, unsigned char *first, int *index, int *inv, float *urois,
+                        double *ubox, int *Uptr, int *row_hw);
 void azk_flags_compact(hipStream_t s, AzCounts *cnt, int level, int capR, int capCand,
                        const double *B, const int *inv, const double *pred_u, const float *score_u,
                        const float *zoom_u, double Tz, double min_side, int force_root,
@@ -373,7 +389,7 @@ int azk_fc_split(int K);
 // softmax + per-class box decode per unique roi, then the un-dedup gather.
 void azk_det_epilogue(hipStream_t s, const float *part, int S, int ncls, const float *bt, const double *ubox,
                       const int *Uptr, int capU, int im_h, int im_w, double eps, float *prob_u, float *delta_u,
-                      double *pred_u);
+                      double *pred_u, const int *row_hw = nullptr);   // row_hw [row][2]: per-row image size (NULL: im_h x im_w)
 void azk_det_gather(hipStream_t s, const int *Pptr, const int *inv, int ncls, const float *prob_u,
                     const double *pred_u, float *prob, double *pred);
 

@@ -133,6 +133,54 @@ __global__ void k_dedup_rois(const long long *__restrict__ key, const int *__res
     if (lane == 0 && nfirst) atomicAdd(Uptr, nfirst);
 }
 
+// k_first_rois for the boxes of several images (az_detect_batch): element i belongs to image b (off[b] <= i < off[b+1]),
+// its roi and key are what az_detect computes for local row i - off[b] at that image's scale, its chunk id is global
+// (chunk0[b] + local chunk), so no chunk spans two images and k_dedup_rois orders the unique rows image by image.  Roi
+// column 0 is b: the RoIPool table's index of the image's map (Caffe's roi_batch_ind); the key is taken with column 0 =
+// 0, as az_detect takes it.
+__global__ void k_first_rois_seg(const double *__restrict__ B, const AzDetSeg *__restrict__ seg, float dedup, int batch,
+                                 float *rois, long long *key, int *grp, unsigned char *first)
+{
+    const int n = seg->n;
+    const int P = seg->off[n];
+    const int lane = lane_id();
+    const int nwaves = (gridDim.x * blockDim.x) >> 6;
+    for (int i = (blockIdx.x * blockDim.x + threadIdx.x) >> 6; i < P; i += nwaves) {
+        int b = 0;
+        while (b + 1 < n && seg->off[b + 1] <= i) ++b;     // (n <= AZ_BATCH_MAX; skips images without boxes)
+        const int o = seg->off[b], li = i - o;
+        const double scale = seg->scale[b];
+        float roi5[5];
+        const long long ki = roi_and_key(B + 4 * (size_t)i, scale, dedup, roi5, li);
+        const int lc = li / batch;
+        if (lane == 0) { key[i] = ki; grp[i] = seg->chunk0[b] + lc; }
+        roi5[0] = (float)b;
+        if (lane < 5) rois[5 * (size_t)i + lane] = roi5[lane];
+        bool dup = false;
+        for (int j0 = o + lc * batch; j0 < i; j0 += 64) {   // only the same chunk of the same image can hold a duplicate
+            const int j = j0 + lane;
+            if (j < i) {
+                float r5[5];
+                dup |= (roi_and_key(B + 4 * (size_t)j, scale, dedup, r5, j - o) == ki);
+            }
+            if (__any(dup)) break;
+        }
+        const bool any_dup = __any(dup);
+        if (lane == 0) first[i] = any_dup ? 0 : 1;
+    }
+}
+
+__global__ void k_seg_row_hw(const AzDetSeg *__restrict__ seg, const float *__restrict__ urois, const int *Uptr,
+                             int *row_hw)
+{
+    const int U = *Uptr;
+    for (int u = blockIdx.x * blockDim.x + threadIdx.x; u < U; u += gridDim.x * blockDim.x) {
+        const int b = (int)urois[5 * (size_t)u];
+        row_hw[2 * u] = seg->im_hw[2 * b];
+        row_hw[2 * u + 1] = seg->im_hw[2 * b + 1];
+    }
+}
+
 // _sift_dup output (lib/utils/div.pyx:85-89): regions[index] in ascending hash order.
 __global__ void k_dedup_regions(const long long *__restrict__ key, const int *Nptr, int capOut,
                                 const unsigned char *__restrict__ first, const double *__restrict__ child,
@@ -361,6 +409,17 @@ void azk_rois_dedup(hipStream_t s, const double *B, const int *Pptr, int cap, do
                        urois, ubox, Uptr);
 }
 
+void azk_rois_dedup_seg(hipStream_t s, const double *B, const AzDetSeg *seg, int n, int cap, float dedup, int batch,
+                        float *rois, long long *key, int *grp, unsigned char *first, int *index, int *inv, float *urois,
+                        double *ubox, int *Uptr, int *row_hw)
+{
+    const int g = grid_for(cap, TB / 64);      // one wave per element
+    const int *Pptr = seg->off + n;            // (device address: the boxes of the pass)
+    hipLaunchKernelGGL(k_first_rois_seg, dim3(g), dim3(TB), 0, s, B, seg, dedup, batch, rois, key, grp, first);
+    hipLaunchKernelGGL(k_dedup_rois, dim3(g), dim3(TB), 0, s, key, grp, Pptr, first, rois, B, index, inv,
+                       urois, ubox, Uptr);
+    hipLaunchKernelGGL(k_seg_row_hw, dim3(grid_for(cap, TB)), dim3(TB), 0, s, seg, urois, Uptr, row_hw);
+}
 void azk_dedup_rois(hipStream_t s, const long long *key, const int *grp, const int *Nptr, int cap,
                     unsigned char *first, const float *rois, const double *B, int *index, int *inv,
                     float *urois, double *ubox, int *Uptr)

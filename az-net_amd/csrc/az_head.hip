@@ -1022,7 +1022,7 @@ k_tail_fused(const float *__restrict__ part7, int S7, size_t slab7, const float 
 __global__ void __launch_bounds__(256)
 k_det_epilogue(const float *__restrict__ part, int capM, int S, int ncls, const float *__restrict__ bt,
                const double *__restrict__ ubox, const int *Uptr, int im_h, int im_w, double eps,
-               float *prob_u, float *delta_u, double *pred_u)
+               float *prob_u, float *delta_u, double *pred_u, const int *__restrict__ row_hw)
 {
     const int U = *Uptr;
     const int NO = 5 * ncls;
@@ -1032,6 +1032,8 @@ k_det_epilogue(const float *__restrict__ part, int capM, int S, int ncls, const 
     const int nslot = (ncls + 63) >> 6;                    // classes per lane (wave-uniform, <= 4)
     for (int u = (blockIdx.x * blockDim.x + threadIdx.x) >> 6; u < U; u += nwaves) {
         const float *row = part + (size_t)u * NO;
+        // (az_detect_batch: the rows of several images, each clipped to its own image)
+        const int rh = row_hw ? row_hw[2 * u] : im_h, rw = row_hw ? row_hw[2 * u + 1] : im_w;
         auto out = [&](int o) {
             float a = row[o];
             for (int s = 1; s < S; ++s) a += row[o + s * slab];
@@ -1067,7 +1069,7 @@ k_det_epilogue(const float *__restrict__ part, int capM, int S, int ncls, const 
                     d4[k] = out(ncls + 4 * c + k);
                     delta_u[(size_t)u * 4 * ncls + 4 * c + k] = d4[k];
                 }
-                az_decode_box(ubox + 4 * (size_t)u, d4, im_h, im_w, eps, pred_u + ((size_t)u * ncls + c) * 4);
+                az_decode_box(ubox + 4 * (size_t)u, d4, rh, rw, eps, pred_u + ((size_t)u * ncls + c) * 4);
             }
         }
     }
@@ -1185,10 +1187,10 @@ void azk_tail(hipStream_t s, const float *part7, int S7, const float *b7, int n7
 
 void azk_det_epilogue(hipStream_t s, const float *part, int S, int ncls, const float *bt, const double *ubox,
                       const int *Uptr, int capU, int im_h, int im_w, double eps, float *prob_u, float *delta_u,
-                      double *pred_u)
+                      double *pred_u, const int *row_hw)
 {
     hipLaunchKernelGGL(k_det_epilogue, dim3(256), dim3(256), 0, s, part, capU, S, ncls, bt, ubox, Uptr, im_h, im_w,
-                       eps, prob_u, delta_u, pred_u);
+                       eps, prob_u, delta_u, pred_u, row_hw);
 }
 
 void azk_det_gather(hipStream_t s, const int *Pptr, const int *inv, int ncls, const float *prob_u,

@@ -292,6 +292,9 @@ int az_nms(az_ctx *c, const float *dets, int n, double thresh, int64_t *keep, in
 
 // --------------------------------------------------------------------------------------
 // Fast R-CNN head on the shared conv map (lib/detect/test.py:259-318,432-445).
+static const size_t DET_SEG_HDR = (sizeof(AzDetSeg) + 255) / 256 * 256;
+static size_t det_seg_bytes(const az_ctx *c) { return DET_SEG_HDR + (size_t)c->maxR * 4 * sizeof(double); }
+
 int az_load_det_head(az_ctx *c, int C, int n6, int n7, int ncls, const float *W6, const float *b6,
                      const float *W7, const float *b7, const float *Wc, const float *bc, const float *Wb,
                      const float *bb)
@@ -322,6 +325,9 @@ int az_load_det_head(az_ctx *c, int C, int n6, int n7, int ncls, const float *W6
         A(dpart, pm);
     }
     A(dprob_u, R * ncls); A(ddelta_u, R * 4 * ncls); A(dpred_u, R * ncls * 4); A(dprob, R * ncls); A(dpred, R * ncls * 4);
+    A(dseg_dev, det_seg_bytes(c)); A(drow_hw, R * 2);
+    if (c->dseg_host) { hipHostFree(c->dseg_host); c->dseg_host = nullptr; }
+    HIPCHK(c, hipHostMalloc((void **)&c->dseg_host, det_seg_bytes(c)));
     if (!c->pool5) { A(pool5, R * K6); }     // normally the AZ head's buffer is shared
     c->dW6p = nullptr; c->dgscale = nullptr;
     if (c->gemm_parts && c->pool5p && azk_fc_terms_prepare(c->gemm_parts) == 0) {
@@ -371,7 +377,9 @@ int az_load_det_head(az_ctx *c, int C, int n6, int n7, int ncls, const float *W6
 
 // the detection head on the `U` rois in ctx->urois / ctx->ubox
 // (rows_bound: what the host knows about the row count -- the number of boxes before the 1/16 dedup)
-static void launch_det_head(az_ctx *c, const int *Uptr, int im_h, int im_w, double eps, int rows_bound)
+// (feats / feat_hw / row_hw: the rows of several images, az_detect_batch -- RoIPool's map table, per-row image sizes)
+static void launch_det_head(az_ctx *c, const int *Uptr, int im_h, int im_w, double eps, int rows_bound,
+                            const float *const *feats = nullptr, const int *feat_hw = nullptr, const int *row_hw = nullptr)
 {
     AzHeadDims d = c->d;
     const int K6 = d.C * 49, NO = 5 * c->det_ncls;
@@ -389,7 +397,7 @@ static void launch_det_head(az_ctx *c, const int *Uptr, int im_h, int im_w, doub
     { Timed t(c, "det_roi_pool", 0);
       azk_roi_pool(c->stream, c->feat, d, c->spatial_scale, c->urois, Uptr, c->maxR, c->pool5, terms ? c->pool5p : nullptr,
                    terms ? azk_act_plane_elems(c->maxR, K6) : 0, terms ? c->gemm_parts : 0, 0, 0,
-                   (terms && c->gemm_parts == 2) ? c->dgscale : nullptr); }
+                   (terms && c->gemm_parts == 2) ? c->dgscale : nullptr, feats, feat_hw); }
     { Timed t(c, "det_fc6_gemm", 0, 1);
       if (terms)
           azk_fc_gemm_terms(c->stream, c->pool5p, K6, azk_act_plane_elems(c->maxR, K6), c->dW6p, K6,
@@ -408,7 +416,7 @@ static void launch_det_head(az_ctx *c, const int *Uptr, int im_h, int im_w, doub
                   c->dpart); }
     { Timed t(c, "det_epilogue", 0);
       azk_det_epilogue(c->stream, c->dpart, AZK_TAIL_SPLIT, c->det_ncls, c->dbt, c->ubox, Uptr, c->maxR, im_h, im_w,
-                       eps, c->dprob_u, c->ddelta_u, c->dpred_u); }
+                       eps, c->dprob_u, c->ddelta_u, c->dpred_u, row_hw); }
 }
 
 static int check_det(az_ctx *c)
@@ -457,6 +465,81 @@ int az_detect(az_ctx *c, const double *boxes, int P, double scale, double dedup,
     const size_t nc = (size_t)c->det_ncls;
     if (scores_out) HIPCHK(c, hipMemcpy(scores_out, c->dprob, (size_t)P * nc * 4, hipMemcpyDeviceToHost));
     if (boxes_out) HIPCHK(c, hipMemcpy(boxes_out, c->dpred, (size_t)P * nc * 4 * sizeof(double), hipMemcpyDeviceToHost));
+    return AZ_OK;
+}
+
+// test_net (lib/detect/test.py:541-668) over saved proposals: _frcnn_forward (:259-318) of n images in one pass per
+// region capacity's worth of boxes -- one upload (AzDetSeg + boxes), segmented projection + dedup, RoIPool through the
+// map table, fc6 / fc7 / tail over the rows of all images, the epilogue with per-row image sizes, the un-dedup gather,
+// one download.  Every launch reads its row count from the device; the host waits once per pass.
+int az_detect_batch(az_ctx *c, int n, const float *const *maps, int C, const int32_t *Hs, const int32_t *Ws,
+                    const double *boxes, const int32_t *box_off, const double *scales, const int32_t *im_hw,
+                    double dedup, int batch_size, double eps, float *scores_out, double *boxes_out)
+{
+    if (!c) return AZ_ERR_INVALID;
+    if (!c->det_loaded) return fail(c, AZ_ERR_STATE, "az_load_det_head has not been called");
+    if (c->gemm_parts && c->dW6p)
+        return fail(c, AZ_ERR_STATE, "az_detect_batch: fp32 only (the 16-bit-term modes scale fc6 per map)");
+    if (n < 1 || n > AZ_BATCH_MAX) return fail(c, AZ_ERR_INVALID, "az_detect_batch: 1 <= n <= AZ_BATCH_MAX");
+    if (!box_off || box_off[0] != 0 || batch_size <= 0 || !scales || !im_hw)
+        return fail(c, AZ_ERR_INVALID, "az_detect_batch: bad arguments");
+    if (C != c->d.C) return fail(c, AZ_ERR_INVALID, "az_detect_batch: channel count differs from the detection head's");
+    for (int i = 0; i < n; ++i) {
+        const int P = box_off[i + 1] - box_off[i];
+        if (P < 0) return fail(c, AZ_ERR_INVALID, "az_detect_batch: box offsets not ascending");
+        if (P == 0) continue;
+        if (!maps || !maps[i] || !Hs || !Ws || Hs[i] <= 0 || Ws[i] <= 0)
+            return fail(c, AZ_ERR_INVALID, "az_detect_batch: an image with boxes needs a map");
+        if (!(scales[i] > 0) || im_hw[2 * i] <= 0 || im_hw[2 * i + 1] <= 0)
+            return fail(c, AZ_ERR_INVALID, "az_detect_batch: bad scale or image size");
+        if (P > c->maxR) return fail(c, AZ_ERR_CAPACITY, "az_detect_batch: an image has more boxes than the region capacity");
+    }
+    if (box_off[n] && (!boxes || !scores_out || !boxes_out)) return fail(c, AZ_ERR_INVALID, "az_detect_batch: null pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    if (!(c->profiling & 4)) clear_events(c);
+    const size_t nc = (size_t)c->det_ncls;
+    AzDetSeg *hs = (AzDetSeg *)c->dseg_host;
+    const AzDetSeg *ds = (const AzDetSeg *)c->dseg_dev;
+    double *dB = (double *)(c->dseg_dev + DET_SEG_HDR);
+    // (device addresses of the table fields)
+    const float *const *d_feats = (const float *const *)(c->dseg_dev + offsetof(AzDetSeg, feats));
+    const int *d_feat_hw = (const int *)(c->dseg_dev + offsetof(AzDetSeg, feat_hw));
+    const int *d_off = (const int *)(c->dseg_dev + offsetof(AzDetSeg, off));
+    for (int i0 = 0; i0 < n;) {
+        // a pass: the following images while their boxes fit the region capacity (which bounds the unique rows)
+        int i1 = i0, P = 0;
+        for (; i1 < n && P + (box_off[i1 + 1] - box_off[i1]) <= c->maxR; ++i1) P += box_off[i1 + 1] - box_off[i1];
+        if (P == 0) { i0 = i1; continue; }
+        HIPCHK(c, hipStreamSynchronize(s));                 // (the staging block of the previous pass is free)
+        memset(hs, 0, sizeof(AzDetSeg));
+        hs->n = i1 - i0;
+        int chunks = 0;
+        for (int b = 0; b < hs->n; ++b) {
+            const int i = i0 + b, Pi = box_off[i + 1] - box_off[i];
+            hs->off[b + 1] = hs->off[b] + Pi;
+            hs->chunk0[b] = chunks;
+            chunks += (Pi + batch_size - 1) / batch_size;
+            hs->im_hw[2 * b] = im_hw[2 * i]; hs->im_hw[2 * b + 1] = im_hw[2 * i + 1];
+            hs->scale[b] = scales[i];
+            if (Pi) { hs->feat_hw[2 * b] = Hs[i]; hs->feat_hw[2 * b + 1] = Ws[i]; hs->feats[b] = maps[i]; }
+        }
+        memcpy(c->dseg_host + DET_SEG_HDR, boxes + 4 * (size_t)box_off[i0], (size_t)P * 4 * sizeof(double));
+        HIPCHK(c, hipMemcpyAsync(c->dseg_dev, c->dseg_host, DET_SEG_HDR + (size_t)P * 4 * sizeof(double),
+                                 hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemsetAsync(c->cnt, 0, sizeof(AzCounts), s));
+        { Timed t(c, "det_rois_dedup", 0);
+          azk_rois_dedup_seg(s, dB, ds, hs->n, c->maxR, (float)dedup, batch_size, c->rois, c->key, c->grp, c->first,
+                             c->index, c->inv, c->urois, c->ubox, &c->cnt->U[0], c->drow_hw); }
+        launch_det_head(c, &c->cnt->U[0], 1, 1, eps, P, d_feats, d_feat_hw, c->drow_hw);
+        azk_det_gather(s, d_off + hs->n, c->inv, c->det_ncls, c->dprob_u, c->dpred_u, c->dprob, c->dpred);
+        HIPCHK(c, hipStreamSynchronize(s));
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpy(scores_out + (size_t)box_off[i0] * nc, c->dprob, (size_t)P * nc * 4, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(boxes_out + (size_t)box_off[i0] * nc * 4, c->dpred, (size_t)P * nc * 4 * sizeof(double),
+                            hipMemcpyDeviceToHost));
+        i0 = i1;
+    }
     return AZ_OK;
 }
 

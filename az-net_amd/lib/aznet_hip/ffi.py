@@ -38,6 +38,7 @@ SYMBOLS = [
     "az_rccl_unique_id", "az_rccl_init", "az_gather_records", "az_rccl_destroy", "az_comm_stream",
     "az_bias_relu", "az_bias_relu_pool", "az_batch_launch", "az_batch_fetch", "az_batch_next_stream",
     "az_batch_stage_results_dev", "az_batch_fetch_all", "az_batch_launch_shapes", "az_abi_sizes",
+    "az_detect_batch",
 ]
 
 
@@ -133,6 +134,7 @@ def load_library(path=None):
     L.az_load_det_head.argtypes = [vp, ci, ci, ci, ci] + [fp] * 8
     L.az_det_forward.argtypes = [vp, fp, ci, fp, fp]
     L.az_detect.argtypes = [vp, dp, ci, cd, cd, ci, ci, ci, cd, fp, dp]
+    L.az_detect_batch.argtypes = [vp, ci, ctypes.POINTER(vp), ci, ip, ip, dp, ip, dp, ip, cd, ci, cd, fp, dp]
     L.az_set_profiling.argtypes = [vp, ci]
     L.az_set_graphs.argtypes = [vp, ci]
     L.az_last_kernel_times.argtypes = [vp, ctypes.c_char_p, fp, ip, ci, cip]
@@ -766,6 +768,79 @@ class AzContext(object):
                                    int(batch_size), int(im_h), int(im_w), float(eps), _p(s, ctypes.c_float),
                                    _p(b, ctypes.c_double)))
         return s[:P], b[:P]
+
+    def detect_batch(self, maps, boxes_list, scales, im_shapes, dedup=1. / 16., batch_size=10000, eps=1e-14):
+        """detect() for several images at once (az_detect_batch): maps[i] is image i's conv5_3, a float32 CUDA tensor on
+        this GPU ([1,C,H,W] / [C,H,W]; channels_last ones are read in place, others are converted on torch's current
+        stream), boxes_list[i] its proposals [P_i,4], scales[i] / im_shapes[i] its scale and (h, w, ...).  Returns
+        [(scores f32 [P_i,K], boxes f64 [P_i,4K])], each bit for bit what detect() returns for that image alone.  Up to
+        AZ_BATCH_MAX images go to one call; an image with more boxes than the region capacity is run in pieces that
+        start at a multiple of batch_size (dedup is per chunk, so the bits stay the same)."""
+        import torch
+        n = len(boxes_list)
+        assert len(maps) == n and len(scales) == n and len(im_shapes) == n
+        nc = self.det_dims["ncls"]
+        C = self.det_dims["C"]
+        boxes_list = [_f64(b).reshape(-1, 4) for b in boxes_list]
+        piece = (self.max_regions // int(batch_size)) * int(batch_size)
+        # (item = one call row: image index, first box, box count)
+        items = []
+        for i, b in enumerate(boxes_list):
+            P = b.shape[0]
+            if P <= self.max_regions:
+                items.append((i, 0, P))
+            elif piece <= 0:
+                raise AzError(AZ_ERR_CAPACITY, "detect_batch: batch_size %d exceeds the region capacity %d"
+                              % (batch_size, self.max_regions))
+            else:
+                items.extend((i, s0, min(piece, P - s0)) for s0 in range(0, P, piece))
+        views = {}
+        for i, m in enumerate(maps):
+            if boxes_list[i].shape[0] == 0:
+                continue
+            if isinstance(m, np.ndarray):
+                m = torch.from_numpy(_f32(m)).to("cuda:%d" % self.device)
+            t = m if m.dim() == 4 else m.unsqueeze(0)
+            assert t.is_cuda and t.dtype == torch.float32 and t.shape[0] == 1 and t.device.index == self.device, \
+                "maps must be float32 CUDA tensors on this context's GPU"
+            if not t.is_contiguous(memory_format=torch.channels_last):
+                t = t.contiguous(memory_format=torch.channels_last)
+            views[i] = t
+        if views:
+            torch.cuda.current_stream(self.device).synchronize()           # (the maps are complete)
+        outs = [(np.empty((b.shape[0], nc), np.float32), np.empty((b.shape[0], 4 * nc), np.float64)) for b in boxes_list]
+        for k0 in range(0, len(items), AZ_BATCH_MAX):
+            grp = items[k0:k0 + AZ_BATCH_MAX]
+            m = len(grp)
+            ptrs = (ctypes.c_void_p * m)()
+            Hs = np.zeros(m, np.int32)
+            Ws = np.zeros(m, np.int32)
+            off = np.zeros(m + 1, np.int32)
+            sc = np.zeros(m, np.float64)
+            hw = np.zeros((m, 2), np.int32)
+            for k, (i, s0, P) in enumerate(grp):
+                off[k + 1] = off[k] + P
+                sc[k] = float(scales[i])
+                hw[k] = (int(im_shapes[i][0]), int(im_shapes[i][1]))
+                if P:
+                    t = views[i]
+                    ptrs[k] = t.data_ptr()
+                    Hs[k], Ws[k] = int(t.shape[2]), int(t.shape[3])
+                    if int(t.shape[1]) != C:
+                        raise AzError(AZ_ERR_INVALID, "detect_batch: map %d has %d channels, the detection head %d"
+                                      % (i, int(t.shape[1]), C))
+            B = np.ascontiguousarray(np.concatenate([boxes_list[i][s0:s0 + P] for i, s0, P in grp])
+                                     if off[m] else np.zeros((1, 4)), dtype=np.float64)
+            S = np.empty((max(int(off[m]), 1), nc), np.float32)
+            D = np.empty((max(int(off[m]), 1), 4 * nc), np.float64)
+            self._chk(self.L.az_detect_batch(
+                self.h, m, ptrs, C, _p(Hs, ctypes.c_int32), _p(Ws, ctypes.c_int32), _p(B, ctypes.c_double),
+                _p(off, ctypes.c_int32), _p(sc, ctypes.c_double), _p(hw, ctypes.c_int32), float(dedup), int(batch_size),
+                float(eps), _p(S, ctypes.c_float), _p(D, ctypes.c_double)))
+            for k, (i, s0, P) in enumerate(grp):
+                outs[i][0][s0:s0 + P] = S[off[k]:off[k + 1]]
+                outs[i][1][s0:s0 + P] = D[off[k]:off[k + 1]]
+        return outs
 
     # ---- tuner ------------------------------------------------------------------------
     def last_anchors(self):

@@ -154,3 +154,62 @@ class HipDetNet(object):
             self.az_net.set_conv(kw["conv5_3"])
         p, b = self.ctx.det_forward(rois)
         return {"cls_prob": p, "bbox_pred": b}
+
+
+class HipFrcnnNet(object):
+    """Fast R-CNN detection net with its OWN conv layers, for detection over saved proposals: stands where the
+    reference's `nets = {'full': caffe.Net(frcnn/test.prototxt, caffemodel)}` stood (tools/test_det_net.py, used by
+    test_net, lib/detect/test.py:541-668).  It owns an az_ctx with only the detection head loaded (fp32) and a backbone:
+    any callable that maps the [1,3,H,W] data blob (a CUDA tensor) to conv5_3 -- normally a VGG16Conv5 with the
+    detection net's conv weights (caffemodel.backbone_from_layers).
+    `detect` / `detect_batch` run az_detect_batch."""
+
+    def __init__(self, det_head, backbone, device=0, name="vgg16_frcnn_hip", max_regions=None):
+        self.ctx = ffi.AzContext(device, max_regions=max_regions, gemm_mode=0)
+        self.ctx.load_det_head(det_head)
+        if ffi._default_ctx is None or getattr(ffi._default_ctx, "h", None) is None:
+            ffi.set_default_context(self.ctx)      # apply_nms and the other drop-in helpers use this GPU
+        self.backbone = backbone
+        self.device = int(device)
+        self.num_classes = self.ctx.det_dims["ncls"]
+        self.name = name
+        self.blobs = {k: _Blob() for k in ("data", "rois", "conv5_3")}
+
+    def __getitem__(self, k):
+        if k == "full":
+            return self
+        raise KeyError(k)
+
+    def keys(self):
+        return ["full"]
+
+    def __contains__(self, k):
+        return k == "full"
+
+    def _torch_device(self):
+        import torch
+        dev = getattr(self.backbone, "device", None)
+        return torch.device(dev) if dev is not None else torch.device("cuda", self.device)
+
+    def image_blob_enqueue(self, im, pixel_means, scale):
+        """_get_image_blob (lib/detect/test.py:27-59) into a CUDA tensor, enqueued on torch's current stream (where the
+        backbone runs next): no host wait."""
+        import torch
+        dev = self._torch_device()
+        oh, ow = self.ctx.image_blob_size(im.shape[0], im.shape[1], scale)
+        out = torch.empty((1, 3, oh, ow), dtype=torch.float32, device=dev)
+        return self.ctx.image_blob(im, pixel_means, scale, out=out, stream=torch.cuda.current_stream(dev).cuda_stream)
+
+    def compute_conv(self, data_blob):
+        """conv5_3 of one data blob, enqueued on torch's current stream (channels_last: the layout RoIPool reads)."""
+        import torch
+        conv = self.backbone(data_blob)
+        if not conv.is_contiguous(memory_format=torch.channels_last):
+            conv = conv.contiguous(memory_format=torch.channels_last)
+        return conv
+
+    def detect_batch(self, convs, boxes_list, scales, im_shapes, dedup, batch_size, eps):
+        return self.ctx.detect_batch(convs, boxes_list, scales, im_shapes, dedup=dedup, batch_size=batch_size, eps=eps)
+
+    def detect(self, conv, boxes, scale, im_shape, dedup, batch_size, eps):
+        return self.detect_batch([conv], [boxes], [scale], [im_shape], dedup, batch_size, eps)[0]

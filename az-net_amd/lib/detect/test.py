@@ -4,6 +4,7 @@ Same names, arguments and return types as the reference for the proposal path:
     im_propose(net, im, return_conv=False, num_proposals=None)      test.py:346-414
     test_proposals(net, imdb)                                       test.py:486-539
     apply_nms(all_boxes, thresh)                                    test.py:467-484
+    test_net(net, prop_file, imdb)                                  test.py:541-668
     divide_region(regions)                                          test.py:153-161
 `net` is a `HipAZNet` (it also answers net['full'] / net['fc'], so the reference's dict of
 two nets keeps working).  The level loop itself -- roi projection and dedup, RoIPool, fc
@@ -354,10 +355,27 @@ def _prefetched(imdb, indices, depth=2):
                 th.join(0.01)
 
 
+def _is_full_net(net):
+    """The reference's test for a detection net with its own conv layers (test.py:291): no 'fc' net."""
+    return hasattr(net, "keys") and "fc" not in net.keys()
+
+
 def _frcnn_forward(net, im, all_boxes, num_classes, conv=None):
     """Fast R-CNN head over proposals on the cached conv map (test.py:259-318): one az_detect
     call (roi projection + dedup, RoIPool, fc6/fc7, cls_score softmax, bbox_pred decode + clip for
-    every class, un-dedup).  Returns scores [R, K] and boxes [R, 4K] as float64, and conv."""
+    every class, un-dedup).  Returns scores [R, K] and boxes [R, 4K] as float64, and conv.
+    A full net (a HipFrcnnNet, no 'fc' key: test.py:291) runs its own backbone on the image first, then the head
+    (az_detect_batch of one image; more proposals than the region capacity go in pieces of whole dedup chunks)."""
+    if _is_full_net(net):
+        fnet = net["full"]
+        scale = _im_scale(im.shape)
+        if len(scale) != 1:
+            raise NotImplementedError("one test scale (cfg.TEST.SCALES), as in every config of the reference")
+        conv_t = fnet.compute_conv(fnet.image_blob_enqueue(_as_uint8(im), cfg.PIXEL_MEANS, scale[0]))
+        assert num_classes == fnet.num_classes
+        scores, boxes = fnet.detect(conv_t, np.ascontiguousarray(all_boxes[:, 0:4], dtype=np.float64), scale[0],
+                                    im.shape, cfg.DEDUP_BOXES, cfg.SEAR.BATCH_SIZE, cfg.EPS)
+        return scores.astype(np.float64), boxes, {name: conv_t for name in cfg.SEAR.FRCNN_CONV}
     dnet = net["fc"] if isinstance(net, dict) else net
     if conv is not None:
         c = conv[cfg.SEAR.FRCNN_CONV[0]]
@@ -371,8 +389,8 @@ def _frcnn_forward(net, im, all_boxes, num_classes, conv=None):
 
 
 def im_detect(net, im, boxes, num_classes):
-    """Object classes for given proposals (test.py:416-430); the conv map of `im` must already
-    be in the shared context (im_propose / set_conv)."""
+    """Object classes for given proposals (test.py:416-430).  With a HipDetNet the conv map of `im` must already be in
+    the shared context (im_propose / set_conv); a full net (HipFrcnnNet) computes it from the image."""
     scores, pred_boxes, _ = _frcnn_forward(net, im, boxes, num_classes)
     return scores, pred_boxes
 
@@ -558,4 +576,102 @@ def test_net_shared(sc_net, frcnn_net, imdb):
         imdb.evaluate_detections(nms_dets, output_dir)
     print('The average detection time is {:.3f}s'.format(_t['im_detect'].average_time))
     print('On average, {0} boxes per image are proposed'.format(num_boxes / num_images))
+    return nms_dets
+
+
+def _detect_group(net, ims, props, num_classes):
+    """im_detect for consecutive images of test_net in one pass (cfg.TEST.BATCH_IMAGES): every image's upload, front-end
+    and backbone enqueued on torch's stream, then one az_detect_batch over the proposals of all of them.  Per image the
+    same (scores, boxes) as im_detect."""
+    fnet = net["full"]
+    scales = []
+    convs = []
+    for im in ims:
+        scale = _im_scale(im.shape)
+        if len(scale) != 1:
+            raise NotImplementedError("one test scale (cfg.TEST.SCALES), as in every config of the reference")
+        scales.append(scale[0])
+        convs.append(fnet.compute_conv(fnet.image_blob_enqueue(_as_uint8(im), cfg.PIXEL_MEANS, scale[0])))
+    assert num_classes == fnet.num_classes
+    outs = fnet.detect_batch(convs, [np.ascontiguousarray(p[:, 0:4], dtype=np.float64) for p in props], scales,
+                             [im.shape for im in ims], cfg.DEDUP_BOXES, cfg.SEAR.BATCH_SIZE, cfg.EPS)
+    return [(s.astype(np.float64), b) for s, b in outs]
+
+
+def test_net(net, prop_file, imdb):
+    """Detection over saved proposals with a Fast R-CNN net of its own conv layers (test.py:541-668): `net` is
+    {'full': HipFrcnnNet} (or the HipFrcnnNet itself), prop_file a proposals.pkl of test_proposals.  Images without
+    proposals are skipped (not read, no line printed, their detections stay []).  Per class: scores above an adaptive
+    threshold, at most 100 per image and 800 / (K-1) per image on average over the set (min-heap); detections.pkl,
+    NMS (cfg.TEST.NMS) and imdb.evaluate_detections when the imdb has one.
+    cfg.TEST.BATCH_IMAGES > 1 (an extension): up to that many consecutive images with proposals go through one
+    az_detect_batch; same detections, same printed lines in the same order."""
+    import heapq
+    with open(prop_file, 'rb') as f:
+        prop = pickle.load(f)
+    prop_boxes = prop['boxes']
+    num_images = len(imdb.image_index)
+    num_classes = imdb.num_classes
+    max_per_set = 800 // (num_classes - 1) * num_images          # Python-2 integer division (test.py:562)
+    max_per_image = 100
+    thresh = -np.inf * np.ones(num_classes)
+    top_scores = [[] for _ in range(num_classes)]
+    all_boxes = [[[] for _ in range(num_images)] for _ in range(num_classes)]
+    num_boxes = 0.0
+    fnet = net["full"]
+    output_dir = get_output_dir(imdb, fnet)
+    if not os.path.exists(output_dir):
+        os.makedirs(output_dir)
+    _t = {'im_detect': Timer(), 'misc': Timer()}
+    todo = [i for i in range(num_images) if prop_boxes[i].shape[0] != 0]       # test.py:588-589
+    images = _prefetched(imdb, todo, depth=_prefetch_depth())
+    nb = max(1, int(cfg.TEST.get("BATCH_IMAGES", 1)))
+    for g0 in range(0, len(todo), nb):
+        idx = todo[g0:g0 + nb]
+        ims = [next(images) for _ in idx]
+        _t['im_detect'].tic()
+        if nb == 1:
+            results = [im_detect(net, ims[0], prop_boxes[idx[0]], num_classes)]
+        else:
+            results = _detect_group(net, ims, [prop_boxes[i] for i in idx], num_classes)
+        # (a group's time is charged to its first image; the average per image is what the timer reports)
+        det_avg = []
+        for _ in idx:
+            _t['im_detect'].toc()
+            det_avg.append(_t['im_detect'].average_time)
+            _t['im_detect'].tic()
+        for k, i in enumerate(idx):
+            scores, boxes = results[k]
+            num_boxes += scores.shape[0]
+            _t['misc'].tic()
+            for j in range(1, num_classes):
+                inds = np.where((scores[:, j] > thresh[j]))[0]
+                cls_scores = scores[inds, j]
+                cls_boxes = boxes[inds, j * 4:(j + 1) * 4]
+                top_inds = np.argsort(-cls_scores)[:max_per_image]
+                cls_scores = cls_scores[top_inds]
+                cls_boxes = cls_boxes[top_inds, :]
+                for val in cls_scores:
+                    heapq.heappush(top_scores[j], val)
+                if len(top_scores[j]) > max_per_set:
+                    while len(top_scores[j]) > max_per_set:
+                        heapq.heappop(top_scores[j])
+                    thresh[j] = top_scores[j][0]
+                all_boxes[j][i] = np.hstack((cls_boxes, cls_scores[:, np.newaxis])).astype(np.float32, copy=False)
+            _t['misc'].toc()
+            print('im_detect: {:d}/{:d} {:.3f}s {:.3f}s'.format(i + 1, num_images, det_avg[k], _t['misc'].average_time))
+    for j in range(1, num_classes):
+        for i in todo:
+            inds = np.where(all_boxes[j][i][:, -1] > thresh[j])[0]
+            all_boxes[j][i] = all_boxes[j][i][inds, :]
+    det_file = os.path.join(output_dir, 'detections.pkl')
+    with open(det_file, 'wb') as f:
+        pickle.dump(all_boxes, f, pickle.HIGHEST_PROTOCOL)
+    print('Applying NMS to all detections')
+    nms_dets = apply_nms(all_boxes, cfg.TEST.NMS)
+    if hasattr(imdb, "evaluate_detections"):
+        print('Evaluating detections')
+        imdb.evaluate_detections(nms_dets, output_dir)
+    print('The average time is proposal {:.3f}s, detection {:.3f}s'.format(prop['time'], _t['im_detect'].average_time))
+    print('On average, {0} boxes per image are generated'.format(num_boxes / num_images))
     return nms_dets

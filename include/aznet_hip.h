@@ -347,6 +347,21 @@ int az_det_forward(az_ctx *ctx, const float *rois, int R, float *cls_prob, float
  * class, un-dedup.  scores_out [P,ncls] f32, boxes_out [P,4*ncls] f64. */
 int az_detect(az_ctx *ctx, const double *boxes, int P, double scale, double dedup, int batch_size,
               int im_h, int im_w, double eps, float *scores_out, double *boxes_out);
+/* _frcnn_forward (lib/detect/test.py:259-318) for n images at once, as test_net (:541-668) runs it
+ * over saved proposals: image i has its own channel-last map maps_nhwc_dev[i] [Hs[i]][Ws[i]][C]
+ * (device memory, C = the detection head's), proposals boxes[box_off[i] .. box_off[i+1]) ([.,4] f64),
+ * scale scales[i] and size im_hw[2i], im_hw[2i+1].  Rows [box_off[i], box_off[i+1]) of scores_out
+ * [box_off[n],ncls] f32 / boxes_out [box_off[n],4*ncls] f64 are bit for bit what az_detect returns
+ * for image i alone with its map set: the 1/16 dedup and its batch_size chunks are per image, and
+ * the head runs over the unique rows of all images in one pass.  Images without boxes contribute
+ * nothing (their map may be NULL).  1 <= n <= AZ_BATCH_MAX; a batch with more boxes than the
+ * region capacity is run in several passes split at image boundaries; one image with more boxes
+ * than that is AZ_ERR_CAPACITY.  fp32 only: AZ_ERR_STATE in the 16-bit-term GEMM modes.  Every
+ * argument error is reported before anything is enqueued. */
+int az_detect_batch(az_ctx *ctx, int n, const float *const *maps_nhwc_dev, int C, const int32_t *Hs,
+                    const int32_t *Ws, const double *boxes, const int32_t *box_off, const double *scales,
+                    const int32_t *im_hw, double dedup, int batch_size, double eps, float *scores_out,
+                    double *boxes_out);
 
 /* ---- zoom-threshold tuner (lib/detect/tune.py, tools/set_thresh.py) ------------------- */
 /* `Bhis` of the tuner's im_propose (tune.py:303, returned at :316) for the last az_propose run
