@@ -290,7 +290,8 @@ struct az_ctx {
     // grow-on-demand scratch of the evaluation / front-end entry points
     void *ev_a = nullptr, *ev_b = nullptr, *ev_c = nullptr, *ev_d = nullptr, *ev_e = nullptr, *ev_f = nullptr,
          *ev_g = nullptr, *ev_h = nullptr;
-    size_t ev_sz[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    void *ev_voc = nullptr;             // slot 8: the arena of az_voc_eval
+    size_t ev_sz[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     // front-end on a caller's stream (az_image_blob_dev_on): two pinned host slots and two device slots for the uint8 image,
     // used in turn; a slot's event says its last upload + kernel are done
     // upload slots of az_image_blob_dev_on (pinned host + device staging + "slot free" event).  Two to start with; a slot

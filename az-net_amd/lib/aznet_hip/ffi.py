@@ -38,7 +38,7 @@ SYMBOLS = [
     "az_rccl_unique_id", "az_rccl_init", "az_gather_records", "az_rccl_destroy", "az_comm_stream",
     "az_bias_relu", "az_bias_relu_pool", "az_batch_launch", "az_batch_fetch", "az_batch_next_stream",
     "az_batch_stage_results_dev", "az_batch_fetch_all", "az_batch_launch_shapes", "az_abi_sizes",
-    "az_detect_batch",
+    "az_detect_batch", "az_voc_eval",
 ]
 
 
@@ -171,6 +171,8 @@ def load_library(path=None):
     L.az_tune_push.argtypes = [vp, fp, ll]
     L.az_bbox_overlaps.argtypes = [vp, dp, ci, dp, ci, dp]
     L.az_recall_match.argtypes = [vp, ci, dp, ip, dp, ip, dp]
+    L.az_voc_eval.argtypes = [vp, ci, ci, dp, dp, ip, dp, u8p, ip, cd, ci, ctypes.POINTER(ctypes.c_int8), dp, dp,
+                              ctypes.POINTER(ctypes.c_int64), dp, dp]
     L.az_image_blob_size.argtypes = [ci, ci, cd, cip, cip]
     L.az_image_blob_host.argtypes = [vp, u8p, ci, ci, fp, cd, fp, ci, ci]
     L.az_image_blob_dev.argtypes = [vp, u8p, ci, ci, fp, cd, vp, ci, ci]
@@ -906,6 +908,42 @@ class AzContext(object):
         out = np.zeros((int(goff[n]),), dtype=np.float64)
         self._chk(self.L.az_recall_match(self.h, n, _p(b, ctypes.c_double), _p(boff, ctypes.c_int32),
                                          _p(g, ctypes.c_double), _p(goff, ctypes.c_int32), _p(out, ctypes.c_double)))
+        return out
+
+    # ---- detection evaluation (imdb.evaluate_detections, VOC) -------------------------------
+    def voc_eval(self, n_classes, n_images, det_box, det_conf, det_off, gt_box, gt_difficult, gt_off,
+                 min_overlap=0.5, metric_07=True, want_curves=True):
+        """az_voc_eval: VOCevaldet + xVOCap for every class at once.  Segment
+        s = c*n_images + i owns det_box[det_off[s]:det_off[s+1]] ([D,4] 1-based, results-file
+        values) with det_conf, and gt_box[gt_off[s]:gt_off[s+1]] ([G,4] 1-based) with gt_difficult.
+        Returns a dict: npos [C] int64, ap [C], ap_auc [C]; with want_curves also match [D] int8
+        (input order: 1 TP, -1 FP, 0 ignored) and rec / prec [D] (each class's rank order)."""
+        bx = _f64(det_box).reshape(-1, 4)
+        cf = _f64(det_conf).ravel()
+        doff = np.ascontiguousarray(det_off, dtype=np.int32).ravel()
+        gb = _f64(gt_box).reshape(-1, 4)
+        gd = np.ascontiguousarray(gt_difficult, dtype=np.uint8).ravel()
+        goff = np.ascontiguousarray(gt_off, dtype=np.int32).ravel()
+        nseg = int(n_classes) * int(n_images)
+        if doff.size != nseg + 1 or goff.size != nseg + 1:
+            raise AzError(AZ_ERR_INVALID, "voc_eval: offsets need n_classes*n_images+1 entries")
+        D, G = int(doff[-1]), int(goff[-1])
+        if bx.shape[0] != D or cf.size != D or gb.shape[0] != G or gd.size != G:
+            raise AzError(AZ_ERR_INVALID, "voc_eval: array sizes disagree with the offsets")
+        out = {"npos": np.zeros(n_classes, np.int64), "ap": np.zeros(n_classes, np.float64),
+               "ap_auc": np.zeros(n_classes, np.float64)}
+        mp = rp = pp = None
+        if want_curves:
+            out["match"] = np.zeros(D, np.int8)
+            out["rec"] = np.zeros(D, np.float64)
+            out["prec"] = np.zeros(D, np.float64)
+            mp = _p(out["match"], ctypes.c_int8)
+            rp, pp = _p(out["rec"], ctypes.c_double), _p(out["prec"], ctypes.c_double)
+        self._chk(self.L.az_voc_eval(self.h, int(n_classes), int(n_images), _p(bx, ctypes.c_double),
+                                     _p(cf, ctypes.c_double), _p(doff, ctypes.c_int32), _p(gb, ctypes.c_double),
+                                     _p(gd, ctypes.c_uint8), _p(goff, ctypes.c_int32), float(min_overlap),
+                                     1 if metric_07 else 0, mp, rp, pp, _p(out["npos"], ctypes.c_int64),
+                                     _p(out["ap"], ctypes.c_double), _p(out["ap_auc"], ctypes.c_double)))
         return out
 
     # ---- image front-end ---------------------------------------------------------------

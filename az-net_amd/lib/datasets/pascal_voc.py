@@ -1,6 +1,6 @@
-"""PASCAL VOC image set (reference: lib/datasets/pascal_voc.py:19-148): the index file, image
-paths and XML ground truth of VOCdevkit<year>/VOC<year>.  Results files / MATLAB evaluation are
-outside the proposal path."""
+"""PASCAL VOC image set (reference: lib/datasets/pascal_voc.py): the index file, image paths and XML
+ground truth of VOCdevkit<year>/VOC<year>, the results files, and evaluate_detections -- the
+reference's MATLAB step, run natively by datasets.voc_eval (az_voc_eval on the GPU)."""
 import os
 import pickle
 import xml.etree.ElementTree as ET
@@ -25,6 +25,7 @@ class pascal_voc(imdb):
         self._classes = VOC_CLASSES
         self._class_to_ind = {c: i for i, c in enumerate(VOC_CLASSES)}
         self._image_ext = ".jpg"
+        self.config = {"cleanup": True, "use_salt": True}
         if not os.path.isdir(self._data_path):
             raise IOError("VOC data path does not exist: %s" % self._data_path)
         self._image_index = self._read_index()
@@ -76,3 +77,45 @@ class pascal_voc(imdb):
             boxes[k, :] = [float(bb.find(t).text) - 1 for t in ("xmin", "ymin", "xmax", "ymax")]
             gt_classes[k] = self._class_to_ind[obj.find("name").text.lower().strip()]
         return {"boxes": boxes, "gt_classes": gt_classes, "flipped": False}
+
+    # -- detection evaluation (pascal_voc.py:145-190) -----------------------------------------
+    def _get_comp_id(self):
+        return "comp4" + ("-{}".format(os.getpid()) if self.config["use_salt"] else "")
+
+    def _results_path(self, comp_id, cls):
+        # VOCdevkit/results/VOC2007/Main/comp4-44503_det_test_aeroplane.txt (VOCopts.detrespath)
+        return os.path.join(self._devkit_path, "results", "VOC" + self._year, "Main",
+                            comp_id + "_det_" + self._image_set + "_" + cls + ".txt")
+
+    def _write_voc_results_file(self, all_boxes):
+        """One results file per class, lines '<id> <score %.3f> <x1+1 %.1f> ...' (the devkit's 1-based
+        boxes); [] entries are skipped.  Returns the comp_id."""
+        comp_id = self._get_comp_id()
+        d = os.path.dirname(self._results_path(comp_id, "x"))
+        if not os.path.isdir(d):
+            os.makedirs(d)
+        for cls_ind, cls in enumerate(self.classes):
+            if cls == "__background__":
+                continue
+            print("Writing {} VOC results file".format(cls))
+            parts = []
+            for im_ind, index in enumerate(self.image_index):
+                dets = all_boxes[cls_ind][im_ind]
+                if isinstance(dets, list) and len(dets) == 0:
+                    continue
+                b = dets[:, 0:4] + 1
+                for k in range(dets.shape[0]):
+                    parts.append("{:s} {:.3f} {:.1f} {:.1f} {:.1f} {:.1f}\n".format(
+                        index, dets[k, -1], b[k, 0], b[k, 1], b[k, 2], b[k, 3]))
+            with open(self._results_path(comp_id, cls), "wt") as f:
+                f.write("".join(parts))
+        return comp_id
+
+    def evaluate_detections(self, all_boxes, output_dir, ctx=None):
+        from datasets import voc_eval
+        comp_id = self._write_voc_results_file(all_boxes)
+        return voc_eval.voc_eval(self, comp_id, output_dir, self.config["cleanup"], ctx=ctx)
+
+    def competition_mode(self, on):
+        self.config["use_salt"] = not on
+        self.config["cleanup"] = not on

@@ -1,0 +1,94 @@
+#!/usr/bin/env python3
+"""Re-evaluate a saved detections.pkl (test_net's all_boxes, before NMS) without rerunning detection.
+NMS at cfg.TEST.NMS first (as test_net does), unless --no-nms.  A VOC imdb goes through its own
+evaluate_detections (results files, XML ground truth with difficult flags); any other imdb with a
+gt_roidb is evaluated the same way on its ground truth, difficult taken as 0 and the detections rounded
+as a results file would hold them.  Prints voc_eval.m's AP block and writes <cls>_pr.mat to --out."""
+import _init_paths  # noqa: F401
+import argparse
+import os
+import pickle
+
+import numpy as np
+
+
+def _rounded(dets):
+    """('%.3f' score, '%.1f' of x + 1) parsed back: the values a results file carries."""
+    sc = np.array(["{:.3f}".format(v) for v in dets[:, -1].tolist()], dtype=object).astype(np.bytes_).astype(np.float64)
+    b = dets[:, 0:4] + 1
+    bx = np.array(["{:.1f}".format(v) for v in b.ravel().tolist()], dtype=object).astype(np.bytes_).astype(np.float64)
+    return sc, bx.reshape(-1, 4)
+
+
+def eval_on_roidb(imdb, all_boxes, output_dir):
+    from datasets import voc_eval
+    classes = [c for c in imdb.classes if c != "__background__"]
+    roidb = imdb.gt_roidb()
+    n = imdb.num_images
+    recs = []
+    for i in range(n):
+        e = roidb[i]
+        recs.append([(imdb.classes[int(k)], [float(v) + 1 for v in b], 0)
+                     for b, k in zip(np.asarray(e["boxes"], np.float64), e["gt_classes"]) if int(k) > 0])
+    gb, gd, goff = voc_eval.gt_segments(classes, recs)
+    dets = []
+    for j in range(1, imdb.num_classes):
+        img, conf, box = [], [], []
+        for i in range(n):
+            d = all_boxes[j][i]
+            if isinstance(d, list) or d.shape[0] == 0:
+                continue
+            sc, bx = _rounded(np.asarray(d))
+            img.append(np.full(sc.size, i, np.int64))
+            conf.append(sc)
+            box.append(bx)
+        dets.append((np.concatenate([np.zeros(0, np.int64)] + img), np.concatenate([np.zeros(0)] + conf),
+                     np.vstack([np.zeros((0, 4))] + box)))
+    r = voc_eval.evaluate(n, classes, dets, gb, gd, goff, metric_07=True)
+    os.makedirs(output_dir, exist_ok=True)
+    lines, tail = voc_eval.report(classes, r["ap"], r["ap_auc"])
+    co = r["class_off"]
+    for k, c in enumerate(classes):
+        print(lines[k])
+        voc_eval.save_pr(output_dir, c, r["rec"][co[k]:co[k + 1]], r["prec"][co[k]:co[k + 1]], r["ap"][k], r["ap_auc"][k])
+    print("\n".join(tail))
+    return r["ap"], r["ap_auc"]
+
+
+def main():
+    ap = argparse.ArgumentParser(description="Evaluate a saved detections.pkl (PASCAL VOC AP)")
+    ap.add_argument("dets", help="detections.pkl written by test_net")
+    ap.add_argument("--imdb", dest="imdb_name", default="voc_2007_test")
+    ap.add_argument("--out", dest="output_dir", default=None, help="where <cls>_pr.mat go (default: next to dets)")
+    ap.add_argument("--no-nms", dest="no_nms", action="store_true", help="evaluate the detections as saved")
+    ap.add_argument("--comp", dest="comp_mode", action="store_true", help="competition mode (keep results files)")
+    ap.add_argument("--cfg", dest="cfg_file", default=None)
+    ap.add_argument("--gpu", dest="gpu_id", type=int, default=0)
+    args = ap.parse_args()
+    from detect.config import cfg, cfg_from_file
+    if args.cfg_file:
+        cfg_from_file(args.cfg_file)
+    import torch
+    torch.cuda.set_device(args.gpu_id)
+    from datasets.factory import get_imdb
+    from detect.test import apply_nms
+    with open(args.dets, "rb") as f:
+        all_boxes = pickle.load(f)
+    imdb = get_imdb(args.imdb_name)
+    if len(all_boxes) != imdb.num_classes or len(all_boxes[0]) != imdb.num_images:
+        raise SystemExit("error: %s holds %d x %d entries, %s has %d classes x %d images"
+                         % (args.dets, len(all_boxes), len(all_boxes[0]), imdb.name, imdb.num_classes, imdb.num_images))
+    if not args.no_nms:
+        print("Applying NMS to all detections")
+        all_boxes = apply_nms(all_boxes, cfg.TEST.NMS)
+    out = args.output_dir or os.path.dirname(os.path.abspath(args.dets))
+    print("Evaluating detections")
+    if hasattr(imdb, "evaluate_detections"):
+        imdb.competition_mode(args.comp_mode)
+        imdb.evaluate_detections(all_boxes, out)
+    else:
+        eval_on_roidb(imdb, all_boxes, out)
+
+
+if __name__ == "__main__":
+    main()

@@ -396,6 +396,25 @@ int az_bbox_overlaps(az_ctx *ctx, const double *boxes, int N, const double *quer
 int az_recall_match(az_ctx *ctx, int n_images, const double *boxes, const int32_t *box_off,
                     const double *gt, const int32_t *gt_off, double *gt_overlaps_out);
 
+/* ---- detection evaluation (imdb.evaluate_detections, lib/datasets/pascal_voc.py:147-190) -- */
+/* What the reference hands to MATLAB: the VOCdevkit's VOCevaldet.m per class plus the wrapper's
+ * xVOCap.m (VOCdevkit-matlab-wrapper/voc_eval.m), restated in DESIGN §1b, for n_classes x n_images
+ * segments, class-major: segment s = c*n_images + i owns det[det_off[s]:det_off[s+1]] (file order:
+ * the results file's values, boxes 1-based) and gt[gt_off[s]:gt_off[s+1]] (1-based, with the XML's
+ * difficult flag).  Per class: MATLAB's stable sort of -confidence, the greedy match at
+ * ovmax >= min_overlap (a difficult box: neither TP nor FP), rec = tp/npos, prec = tp/(fp+tp),
+ * ap = 11-point AP (metric_07, the VOC2007 devkit) or the area AP (2010+ devkits), ap_auc = xVOCap.
+ * match_out [D] in input order: 1 TP, -1 FP, 0 ignored; rec_out / prec_out [D] in each class's
+ * rank order at that class's offset det_off[c*n_images]; any of the three may be NULL.
+ * Malformed offsets are AZ_ERR_INVALID and n_classes*n_images past int32 is AZ_ERR_CAPACITY, both
+ * before any device work.  Device scratch is kept in the context. */
+int az_voc_eval(az_ctx *ctx, int n_classes, int n_images,
+                const double *det_box, const double *det_conf, const int32_t *det_off,
+                const double *gt_box, const uint8_t *gt_difficult, const int32_t *gt_off,
+                double min_overlap, int metric_07,
+                int8_t *match_out, double *rec_out, double *prec_out,
+                int64_t *npos_out, double *ap_out, double *ap_auc_out);
+
 /* ---- image front-end (_get_image_blob, lib/detect/test.py:27-59) ------------------------- */
 /* uint8 BGR HWC image (host) -> float32 [3, oh, ow] blob: subtract cfg.PIXEL_MEANS, then
  * cv2.resize(fx=fy=scale, INTER_LINEAR) semantics on f32 (half-pixel centres, edge clamp,
