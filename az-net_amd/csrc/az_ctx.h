@@ -291,7 +291,8 @@ struct az_ctx {
     void *ev_a = nullptr, *ev_b = nullptr, *ev_c = nullptr, *ev_d = nullptr, *ev_e = nullptr, *ev_f = nullptr,
          *ev_g = nullptr, *ev_h = nullptr;
     void *ev_voc = nullptr;             // slot 8: the arena of az_voc_eval
-    size_t ev_sz[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    void *ev_coco = nullptr;            // slot 9: the arena of az_coco_eval
+    size_t ev_sz[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     // front-end on a caller's stream (az_image_blob_dev_on): two pinned host slots and two device slots for the uint8 image,
     // used in turn; a slot's event says its last upload + kernel are done
     // upload slots of az_image_blob_dev_on (pinned host + device staging + "slot free" event).  Two to start with; a slot
@@ -754,6 +755,17 @@ int stage_impl(az_ctx *c, void *dst_dev, size_t cap_bytes);
 // AZ_ERR_STATE + *not_taken = 1: this shape / these settings do not take the lockstep form (nothing enqueued)
 int batch_launch_impl(az_ctx *L, az_ctx::Batch &B, int n, az_ctx **slots, const az_params *params /* [n] */, const float *const *maps,
                       const int *Hs, const int *Ws, int *not_taken);
+// ---- az_voc.hip (shared with az_coco.hip) ------------------------------------------------------------------------------
+// Stable LSD radix ranking of D detections by (-score, input order), segment s = class * n_images + image owning
+// [det_off[s], det_off[s+1]) (device arrays): *by_seg lists every segment's detections in rank order, *by_class every
+// class's.  Scratch: key [D], seg [D], perm[4] [D] each, hist [hist_n], sums [sums_n] (rank_scratch_sizes); D > 0.
+struct RankScratch {
+    unsigned long long *key;
+    unsigned *seg, *perm[4], *hist, *sums;
+};
+void rank_scratch_sizes(int D, size_t *hist_n, size_t *sums_n);
+void rank_by_score(hipStream_t s, int D, long long S, int n_images, int n_classes, const double *score, const int *det_off,
+                   const RankScratch &r, const unsigned **by_seg, const unsigned **by_class);
 // ---- az_capi.hip --------------------------------------------------------------------------------------------------------
 int set_feature_map_common(az_ctx *c, const float *src, bool src_is_host, int C, int H, int W, bool wait = true);
 int ensure_lane_head(az_ctx *t);          // the head buffers of a lane / batch slot created without them

@@ -9,6 +9,7 @@
 //                     8 key passes          -> every detection ranked by (-conf, file order)
 //                     + segment-id passes   -> each (class, image) segment's detections in rank order
 //                     + class-id passes     -> each class's detections in rank order (MATLAB's stable sort)
+//                   (rank_by_score, which az_coco.hip shares)
 //   k_voc_match     one wave per (class, image) segment, grid-striding: the segment's detections in rank order, the
 //                   lanes over its ground-truth boxes (64 at a time), f64 overlap in VOCevaldet's operation order, a wave
 //                   arg-max with the first box winning ties, then the claim (bit in a register for the first 2048 boxes,
@@ -371,14 +372,54 @@ __global__ void __launch_bounds__(VT) k_voc_class(int n_images, const int *__res
     }
 }
 
-size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
 int bytes_for(long long v)          // 8-bit digits needed for values 0..v
 {
     int n = 0;
     while (v > 0) { ++n; v >>= 8; }
     return n;
 }
+
+}  // namespace
+
+void rank_scratch_sizes(int D, size_t *hist_n, size_t *sums_n)
+{
+    const size_t nblk = ((size_t)D + VTILE - 1) / VTILE;
+    *hist_n = nblk * 256;
+    *sums_n = (nblk * 256 + SCH - 1) / SCH;
+}
+
+void rank_by_score(hipStream_t s, int D, long long S, int n_images, int n_classes, const double *score, const int *det_off,
+                   const RankScratch &r, const unsigned **by_seg, const unsigned **by_class)
+{
+    const int nblk = (D + VTILE - 1) / VTILE, nsch = (nblk * 256 + SCH - 1) / SCH;
+    hipLaunchKernelGGL(k_voc_prep, dim3((D + VT - 1) / VT), dim3(VT), 0, s, D, (int)S, score, det_off, r.key, r.seg);
+    // a chain of stable passes from `in` (nullptr: identity) through the two buffers `a`, `b` in turn
+    auto passes = [&](int mode, int nbytes, const unsigned *in, unsigned *a, unsigned *b) {
+        const unsigned *cur = in;
+        for (int k = 0; k < nbytes; ++k) {
+            unsigned *out = (k & 1) ? b : a;
+            hipLaunchKernelGGL(k_voc_hist, dim3(nblk), dim3(VT), 0, s, D, mode, 8 * k, cur,
+                               (const unsigned long long *)r.key, (const unsigned *)r.seg, (unsigned)n_images, r.hist);
+            hipLaunchKernelGGL(k_voc_scan_sum, dim3(nsch), dim3(VT), 0, s, (const unsigned *)r.hist, nblk * 256, r.sums);
+            hipLaunchKernelGGL(k_voc_scan, dim3(1), dim3(1024), 0, s, r.sums, nsch);
+            hipLaunchKernelGGL(k_voc_scan_add, dim3(nsch), dim3(VT), 0, s, r.hist, nblk * 256, (const unsigned *)r.sums);
+            hipLaunchKernelGGL(k_voc_scatter, dim3(nblk), dim3(VT), 0, s, D, mode, 8 * k, cur,
+                               (const unsigned long long *)r.key, (const unsigned *)r.seg, (unsigned)n_images,
+                               (const unsigned *)r.hist, out);
+            cur = out;
+        }
+        return cur;
+    };
+    const unsigned *pk = passes(0, 8, nullptr, r.perm[0], r.perm[1]);      // ends in perm[1]
+    const unsigned *pseg = passes(1, bytes_for(S - 1), pk, r.perm[2], r.perm[3]);   // perm[1] (no pass), [2] or [3]
+    unsigned *fa = pseg == r.perm[2] ? r.perm[3] : r.perm[2], *fb = r.perm[0];
+    *by_class = passes(2, bytes_for(n_classes - 1), pk, fa, fb);
+    *by_seg = pseg;
+}
+
+namespace {
+
+size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
 }  // namespace
 
@@ -442,31 +483,10 @@ int az_voc_eval(az_ctx *c, int n_classes, int n_images, const double *det_box, c
     }
     HIPCHK(c, hipMemcpyAsync(doff, det_off, ((size_t)S + 1) * sizeof(int), hipMemcpyHostToDevice, s));
     HIPCHK(c, hipMemcpyAsync(goff, gt_off, ((size_t)S + 1) * sizeof(int), hipMemcpyHostToDevice, s));
-    const unsigned *pk = nullptr, *pseg = nullptr, *pcls = nullptr;
+    const unsigned *pseg = nullptr, *pcls = nullptr;
     if (D) {
-        hipLaunchKernelGGL(k_voc_prep, dim3((D + VT - 1) / VT), dim3(VT), 0, s, D, (int)S, (const double *)dconf,
-                           (const int *)doff, key, seg);
-        // a chain of stable passes from `in` (nullptr: identity) through the two buffers `a`, `b` in turn
-        auto passes = [&](int mode, int nbytes, const unsigned *in, unsigned *a, unsigned *b) {
-            const unsigned *cur = in;
-            for (int k = 0; k < nbytes; ++k) {
-                unsigned *out = (k & 1) ? b : a;
-                hipLaunchKernelGGL(k_voc_hist, dim3(nblk), dim3(VT), 0, s, D, mode, 8 * k, cur,
-                                   (const unsigned long long *)key, (const unsigned *)seg, (unsigned)n_images, hist);
-                hipLaunchKernelGGL(k_voc_scan_sum, dim3(nsch), dim3(VT), 0, s, (const unsigned *)hist, nblk * 256, sums);
-                hipLaunchKernelGGL(k_voc_scan, dim3(1), dim3(1024), 0, s, sums, nsch);
-                hipLaunchKernelGGL(k_voc_scan_add, dim3(nsch), dim3(VT), 0, s, hist, nblk * 256, (const unsigned *)sums);
-                hipLaunchKernelGGL(k_voc_scatter, dim3(nblk), dim3(VT), 0, s, D, mode, 8 * k, cur,
-                                   (const unsigned long long *)key, (const unsigned *)seg, (unsigned)n_images,
-                                   (const unsigned *)hist, out);
-                cur = out;
-            }
-            return cur;
-        };
-        pk = passes(0, 8, nullptr, perm[0], perm[1]);                       // ends in perm[1]
-        pseg = passes(1, bytes_for(S - 1), pk, perm[2], perm[3]);            // perm[1] (no pass), [2] or [3]
-        unsigned *fa = pseg == perm[2] ? perm[3] : perm[2], *fb = perm[0];
-        pcls = passes(2, bytes_for(n_classes - 1), pk, fa, fb);
+        RankScratch rs{key, seg, {perm[0], perm[1], perm[2], perm[3]}, hist, sums};
+        rank_by_score(s, D, S, n_images, n_classes, (const double *)dconf, (const int *)doff, rs, &pseg, &pcls);
         long long nb = (S + (VT / AZ_WAVE) - 1) / (VT / AZ_WAVE);
         if (nb > 4096) nb = 4096;
         hipLaunchKernelGGL(k_voc_match, dim3((unsigned)nb), dim3(VT), 0, s, (int)S, (const int *)doff, pseg,

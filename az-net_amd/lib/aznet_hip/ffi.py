@@ -38,7 +38,7 @@ SYMBOLS = [
     "az_rccl_unique_id", "az_rccl_init", "az_gather_records", "az_rccl_destroy", "az_comm_stream",
     "az_bias_relu", "az_bias_relu_pool", "az_batch_launch", "az_batch_fetch", "az_batch_next_stream",
     "az_batch_stage_results_dev", "az_batch_fetch_all", "az_batch_launch_shapes", "az_abi_sizes",
-    "az_detect_batch", "az_voc_eval",
+    "az_detect_batch", "az_voc_eval", "az_coco_eval",
 ]
 
 
@@ -173,6 +173,7 @@ def load_library(path=None):
     L.az_recall_match.argtypes = [vp, ci, dp, ip, dp, ip, dp]
     L.az_voc_eval.argtypes = [vp, ci, ci, dp, dp, ip, dp, u8p, ip, cd, ci, ctypes.POINTER(ctypes.c_int8), dp, dp,
                               ctypes.POINTER(ctypes.c_int64), dp, dp]
+    L.az_coco_eval.argtypes = [vp, ci, ci, dp, dp, ip, dp, dp, u8p, ip, dp, dp, dp, ip, ctypes.POINTER(ctypes.c_int8)]
     L.az_image_blob_size.argtypes = [ci, ci, cd, cip, cip]
     L.az_image_blob_host.argtypes = [vp, u8p, ci, ci, fp, cd, fp, ci, ci]
     L.az_image_blob_dev.argtypes = [vp, u8p, ci, ci, fp, cd, vp, ci, ci]
@@ -944,6 +945,40 @@ class AzContext(object):
                                      _p(gd, ctypes.c_uint8), _p(goff, ctypes.c_int32), float(min_overlap),
                                      1 if metric_07 else 0, mp, rp, pp, _p(out["npos"], ctypes.c_int64),
                                      _p(out["ap"], ctypes.c_double), _p(out["ap_auc"], ctypes.c_double)))
+        return out
+
+    def coco_eval(self, n_classes, n_images, det_box, det_score, det_off, gt_box, gt_area, gt_crowd, gt_off,
+                  want_matches=False):
+        """az_coco_eval: COCOeval evaluate + accumulate + summarize, iouType 'bbox' (DESIGN §1c), for every category
+        at once.  Segment s = k*n_images + i owns det_box[det_off[s]:det_off[s+1]] ([D,4] xywh, file order) with
+        det_score, and gt_box[gt_off[s]:gt_off[s+1]] ([G,4] xywh) with gt_area and gt_crowd.  Returns a dict:
+        precision [10,101,K,4,3], recall [10,K,4,3], stats [12]; with want_matches also dt_match [4,10,D] int32 (the
+        matched box's position in its segment, -1 none) and dt_ignore [4,10,D] int8 (-1: past the first 100)."""
+        bx = _f64(det_box).reshape(-1, 4)
+        sc = _f64(det_score).ravel()
+        doff = np.ascontiguousarray(det_off, dtype=np.int32).ravel()
+        gb = _f64(gt_box).reshape(-1, 4)
+        ga = _f64(gt_area).ravel()
+        gc = np.ascontiguousarray(gt_crowd, dtype=np.uint8).ravel()
+        goff = np.ascontiguousarray(gt_off, dtype=np.int32).ravel()
+        K = int(n_classes)
+        nseg = K * int(n_images)
+        if doff.size != nseg + 1 or goff.size != nseg + 1:
+            raise AzError(AZ_ERR_INVALID, "coco_eval: offsets need n_classes*n_images+1 entries")
+        D, G = int(doff[-1]), int(goff[-1])
+        if bx.shape[0] != D or sc.size != D or gb.shape[0] != G or ga.size != G or gc.size != G:
+            raise AzError(AZ_ERR_INVALID, "coco_eval: array sizes disagree with the offsets")
+        out = {"precision": np.zeros((10, 101, K, 4, 3)), "recall": np.zeros((10, K, 4, 3)), "stats": np.zeros(12)}
+        mp = ip_ = None
+        if want_matches:
+            out["dt_match"] = np.zeros((4, 10, D), np.int32)
+            out["dt_ignore"] = np.zeros((4, 10, D), np.int8)
+            mp, ip_ = _p(out["dt_match"], ctypes.c_int32), _p(out["dt_ignore"], ctypes.c_int8)
+        self._chk(self.L.az_coco_eval(self.h, K, int(n_images), _p(bx, ctypes.c_double), _p(sc, ctypes.c_double),
+                                      _p(doff, ctypes.c_int32), _p(gb, ctypes.c_double), _p(ga, ctypes.c_double),
+                                      _p(gc, ctypes.c_uint8), _p(goff, ctypes.c_int32),
+                                      _p(out["precision"], ctypes.c_double), _p(out["recall"], ctypes.c_double),
+                                      _p(out["stats"], ctypes.c_double), mp, ip_))
         return out
 
     # ---- image front-end ---------------------------------------------------------------

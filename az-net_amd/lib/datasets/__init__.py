@@ -1,7 +1,7 @@
 """Image databases for the proposal / detection / tuning drivers (reference: lib/datasets).
 Only what those drivers touch is here: names, image paths, ground-truth boxes, the recall
-evaluator and the VOC detection evaluation (voc_eval, run natively where the reference calls
-MATLAB).  COCO, selective-search roidbs and flipped training copies of the reference's
+evaluator and the detection evaluations (voc_eval, run natively where the reference calls
+MATLAB; coco_eval, where it calls pycocotools).  Selective-search roidbs of the reference's
 lib/datasets are outside the proposal path."""
 import os.path as osp
 

@@ -1,5 +1,6 @@
-"""Image databases by name (reference: lib/datasets/factory.py): voc_<year>_<split> as in the
-reference, plus the offline stand-ins synthetic_<H>x<W>_<N> and npy:<directory>."""
+"""Image databases by name (reference: lib/datasets/factory.py): voc_<year>_<split> and coco_<year>_<split>
+as in the reference, plus the offline stand-ins synthetic_<H>x<W>_<N> and npy:<directory>."""
+from datasets.coco import coco
 from datasets.pascal_voc import pascal_voc
 from datasets.synthetic import SyntheticImdb, NpyDirImdb
 
@@ -7,6 +8,9 @@ _makers = {}
 for _year in ("2007", "2012", "07+12"):
     for _split in (("trainval",) if _year == "07+12" else ("train", "val", "trainval", "test")):
         _makers["voc_%s_%s" % (_year, _split)] = (lambda s=_split, y=_year: pascal_voc(s, y))
+for _year, _splits in (("2014", ("train", "val", "test", "trainval")), ("2015", ("test", "test-dev"))):
+    for _split in _splits:
+        _makers["coco_%s_%s" % (_year, _split)] = (lambda s=_split, y=_year: coco(s, y))
 
 
 def get_imdb(name):
@@ -18,7 +22,7 @@ def get_imdb(name):
         return SyntheticImdb(int(h), int(w), int(n), name=name)
     if name.startswith("npy:"):
         return NpyDirImdb(name[4:])
-    raise KeyError("Unknown dataset: %s (COCO readers of the reference are outside the proposal path)" % name)
+    raise KeyError("Unknown dataset: %s" % name)
 
 
 def list_imdbs():

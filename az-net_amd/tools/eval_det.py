@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Re-evaluate a saved detections.pkl (test_net's all_boxes, before NMS) without rerunning detection.
-NMS at cfg.TEST.NMS first (as test_net does), unless --no-nms.  A VOC imdb goes through its own
-evaluate_detections (results files, XML ground truth with difficult flags); any other imdb with a
-gt_roidb is evaluated the same way on its ground truth, difficult taken as 0 and the detections rounded
-as a results file would hold them.  Prints voc_eval.m's AP block and writes <cls>_pr.mat to --out."""
+NMS at cfg.TEST.NMS first (as test_net does), unless --no-nms.  A VOC or COCO imdb goes through its own
+evaluate_detections: VOC results files and XML ground truth with difficult flags (voc_eval.m's AP block,
+<cls>_pr.mat in --out), or the COCO results json in --out and COCOeval's 12 summary lines (box IoU).
+Any other imdb with a gt_roidb is evaluated the VOC way on its ground truth, difficult taken as 0 and the
+detections rounded as a results file would hold them."""
 import _init_paths  # noqa: F401
 import argparse
 import os
@@ -56,10 +57,10 @@ def eval_on_roidb(imdb, all_boxes, output_dir):
 
 
 def main():
-    ap = argparse.ArgumentParser(description="Evaluate a saved detections.pkl (PASCAL VOC AP)")
+    ap = argparse.ArgumentParser(description="Evaluate a saved detections.pkl (PASCAL VOC AP / COCO AP)")
     ap.add_argument("dets", help="detections.pkl written by test_net")
     ap.add_argument("--imdb", dest="imdb_name", default="voc_2007_test")
-    ap.add_argument("--out", dest="output_dir", default=None, help="where <cls>_pr.mat go (default: next to dets)")
+    ap.add_argument("--out", dest="output_dir", default=None, help="where <cls>_pr.mat / the COCO results json go (default: next to dets)")
     ap.add_argument("--no-nms", dest="no_nms", action="store_true", help="evaluate the detections as saved")
     ap.add_argument("--comp", dest="comp_mode", action="store_true", help="competition mode (keep results files)")
     ap.add_argument("--cfg", dest="cfg_file", default=None)

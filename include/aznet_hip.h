@@ -415,6 +415,29 @@ int az_voc_eval(az_ctx *ctx, int n_classes, int n_images,
                 int8_t *match_out, double *rec_out, double *prec_out,
                 int64_t *npos_out, double *ap_out, double *ap_auc_out);
 
+/* ---- detection evaluation (imdb.evaluate_detections, lib/datasets/coco.py:_do_coco_eval) ----------- */
+/* What the reference hands to pycocotools: COCOeval's evaluate + accumulate + summarize with iouType 'bbox' (the
+ * COCO detection metric), restated in DESIGN §1c, for n_classes x n_images segments, class-major: segment
+ * s = k*n_images + i (k-th of the ground truth's sorted category ids, i-th of its sorted image ids) owns
+ * det[det_off[s]:det_off[s+1]] (file order: [x, y, w, h] and score, as the results file holds them; loadRes's
+ * area w*h and iscrowd 0 are implied) and gt[gt_off[s]:gt_off[s+1]] ([x, y, w, h], the annotation's own area field,
+ * iscrowd; ignore = iscrowd).  Per segment: the first 100 detections by stable -score, f64 box IoU (maskApi.c bbIou,
+ * a crowd box's union the detection's area), evaluateImg's greedy match at iouThrs = linspace(.5, .95, 10) for the
+ * area ranges all / small / medium / large (0, 32^2, 96^2, 1e10); per (class, area, maxDets in {1, 10, 100})
+ * accumulate's cumulative TP / FP, recall and the precision envelope at recThrs = linspace(0, 1, 101).
+ * precision_out [10, 101, n_classes, 4, 3] and recall_out [10, n_classes, 4, 3] (-1: no ground truth that counts;
+ * either may be NULL); stats_out [12]: summarize's AP, AP50, AP75, AP small / medium / large, AR1, AR10, AR100,
+ * AR small / medium / large (NumPy's mean of the entries > -1, or -1).  dt_match_out [4, 10, D] int32 / dt_ignore_out
+ * [4, 10, D] int8, both or neither, in input order per (area, threshold): the matched box's position in its segment's
+ * ground truth (-1: none) and dtIgnore (-1 for both: past the segment's first 100, not evaluated).
+ * Malformed offsets are AZ_ERR_INVALID and n_classes*n_images past int32 is AZ_ERR_CAPACITY, both before any device
+ * work.  Device scratch is kept in the context. */
+int az_coco_eval(az_ctx *ctx, int n_classes, int n_images,
+                 const double *det_box, const double *det_score, const int32_t *det_off,
+                 const double *gt_box, const double *gt_area, const uint8_t *gt_crowd, const int32_t *gt_off,
+                 double *precision_out, double *recall_out, double *stats_out,
+                 int32_t *dt_match_out, int8_t *dt_ignore_out);
+
 /* ---- image front-end (_get_image_blob, lib/detect/test.py:27-59) ------------------------- */
 /* uint8 BGR HWC image (host) -> float32 [3, oh, ow] blob: subtract cfg.PIXEL_MEANS, then
  * cv2.resize(fx=fy=scale, INTER_LINEAR) semantics on f32 (half-pixel centres, edge clamp,
