@@ -49,6 +49,12 @@ struct az_ctx {
     unsigned feat_gen = 0;              // bumped when the copies are reallocated
     float *feat_stage = nullptr;        // NCHW staging for host uploads
     size_t feat_owned_elems = 0;
+    // image pyramid (az_pyramid.hip): S borrowed channel-last maps of one padded size and the device table RoIPool reads
+    // them through (roi column 0 = level); pyr_now: a pyramid search / detection is being enqueued
+    int pyr_S = 0, pyr_now = 0;
+    const float **pyr_feats = nullptr;  // [AZ_PYRAMID_MAX] (device)
+    int *pyr_hw = nullptr;              // [AZ_PYRAMID_MAX][2] (device)
+    AzPyrScales pyr_sc{};               // the scales of the pyramid search being enqueued
     // level-loop buffers (HBM)
     AzCounts *cnt = nullptr;
     double *B[2] = {nullptr, nullptr};
@@ -316,6 +322,7 @@ struct az_ctx {
         az_params p{};
         int nlev = 0, is_static = 0, defer = 0, pair_mask = 0, npass = 0, full = 0, reruns = 0;
         int cut = 0;                        // > 0: the search was enqueued up to (not including) this level
+        int pyr = 0;                        // a pyramid search (az_propose_pyramid): kept out of the shape's history
         int pass_src[AZ_MAX_LEVELS + 2] = {0};
         int pass_lv[AZ_MAX_LEVELS + 2] = {0};   // the `level` each head pass was launched for (-1: speculative / whole-tree / one-pass)
         void *stage_dst = nullptr;          // az_propose_stage_result_dev target
@@ -574,7 +581,8 @@ void launch_head(az_ctx *c, const int *Uptr, int level, int im_h, int im_w, doub
     if (roi_after_i7 && c->i7_live) { if (hipStreamWaitEvent(c->stream, c->ev_i7, 0) != hipSuccess) c->async_err = 1; c->i7_live = false; }
     { Timed t(c, "roi_pool", level);
       azk_roi_pool(c->stream, c->feat, d, c->spatial_scale, urois ? urois : c->urois, Uptr, c->maxR, c->pool5, c->pool5p,
-                   azk_act_plane_elems(c->maxR, d.K6), c->gemm_parts, 0, coop_tail, c->gemm_parts == 2 ? c->gscale : nullptr); }
+                   azk_act_plane_elems(c->maxR, d.K6), c->gemm_parts, 0, coop_tail, c->gemm_parts == 2 ? c->gscale : nullptr,
+                   c->pyr_now ? c->pyr_feats : nullptr, c->pyr_now ? c->pyr_hw : nullptr); }
     // (profiling bit 3: the fp32 GEMM launches record their own span instead of an event pair)
     auto span_slot = [&](const char *name) -> unsigned long long * {
         if (!(c->profiling & 8) || !c->span_ring || c->span_next >= az_ctx::SPAN_SLOTS) return nullptr;
@@ -750,6 +758,10 @@ bool nms_keep_tagged(const long long *hk, int n, unsigned tag, long spins)
 int launch_impl(az_ctx *c, const az_params *p);
 int fetch_entry(az_ctx *c, size_t idx, double *boxes_out, float *scores_out, int cap, int *n_out, az_stats *st);
 int stage_impl(az_ctx *c, void *dst_dev, size_t cap_bytes);
+// ---- az_pyramid.hip ------------------------------------------------------------------------------------------------------
+// the scales of a pyramid entry checked (S in [1, AZ_PYRAMID_MAX], every scale positive and finite, fp32 GEMM mode) and
+// packed; the context's error set on failure (`who`: the entry's name)
+int pyramid_args(az_ctx *c, const double *scales, int S, AzPyrScales *sc, const char *who);
 // n images (one shape or several, the same number of levels) in lockstep on lane L (whose head buffers the passes use), image b
 // on slots[b] with parameters params[b] and map maps[b] of Hs[b] x Ws[b] cells;
 // AZ_ERR_STATE + *not_taken = 1: this shape / these settings do not take the lockstep form (nothing enqueued)

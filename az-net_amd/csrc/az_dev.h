@@ -131,6 +131,18 @@ struct AzDetSeg {
 void azk_rois_dedup_seg(hipStream_t s, const double *B, const AzDetSeg *seg, int n, int cap, float dedup, int batch,
                         float *rois, long long *key, int *grp, unsigned char *first, int *index, int *inv, float *urois,
                         double *ubox, int *Uptr, int *row_hw);
+// The slot pass of azk_rois_dedup alone (k_dedup_rois): index / inv / unique rois and anchors from keys, chunk ids and
+// first-occurrence flags another kernel left (az_pyramid.hip).
+void azk_dedup_slots(hipStream_t s, const long long *key, const int *grp, const int *Pptr, int cap,
+                     const unsigned char *first, const float *rois, const double *B, int *index, int *inv, float *urois,
+                     double *ubox, int *Uptr);
+// The scales of an image pyramid, by value in the kernel's arguments (az_pyramid.hip).
+struct AzPyrScales { double s[AZ_PYRAMID_MAX]; int S; };
+// azk_rois_dedup with _project_im_rois over a pyramid (lib/detect/test.py:73-97): roi column 0 = the level, the key
+// gains rint(level * dedup) with weight 1.  S == 1: the bits of azk_rois_dedup.
+void azk_pyramid_rois_dedup(hipStream_t s, const double *B, const int *Pptr, int cap, const AzPyrScales &sc, float dedup,
+                            int batch, float *rois, long long *key, int *grp, unsigned char *first, int *index, int *inv,
+                            float *urois, double *ubox, int *Uptr);
 void azk_flags_compact(hipStream_t s, AzCounts *cnt, int level, int capR, int capCand,
                        const double *B, const int *inv, const double *pred_u, const float *score_u,
                        const float *zoom_u, double Tz, double min_side, int force_root,

@@ -420,6 +420,13 @@ void azk_rois_dedup_seg(hipStream_t s, const double *B, const AzDetSeg *seg, int
                        urois, ubox, Uptr);
     hipLaunchKernelGGL(k_seg_row_hw, dim3(grid_for(cap, TB)), dim3(TB), 0, s, seg, urois, Uptr, row_hw);
 }
+void azk_dedup_slots(hipStream_t s, const long long *key, const int *grp, const int *Pptr, int cap,
+                     const unsigned char *first, const float *rois, const double *B, int *index, int *inv, float *urois,
+                     double *ubox, int *Uptr)
+{
+    hipLaunchKernelGGL(k_dedup_rois, dim3(grid_for(cap, TB / 64)), dim3(TB), 0, s, key, grp, Pptr, first, rois, B, index,
+                       inv, urois, ubox, Uptr);
+}
 void azk_dedup_rois(hipStream_t s, const long long *key, const int *grp, const int *Nptr, int cap,
                     unsigned char *first, const float *rois, const double *B, int *index, int *inv,
                     float *urois, double *ubox, int *Uptr)

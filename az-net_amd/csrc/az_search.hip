@@ -818,8 +818,12 @@ static int enqueue_search(az_ctx *c, const az_params *p, int K, int nlev, int k,
         }
         if (!fused_lv || l > plan.lv_limit) {   // (otherwise the fused predecessor -- spec_levels or level_geom -- has done this already)
           Timed t(c, "rois_dedup", l);
-          azk_rois_dedup(s, c->B[cur], Pptr, c->maxR, p->scale, (float)p->dedup, p->batch_size, c->rois, c->key,
-                         c->grp, c->first, c->index, INV(l), c->urois, c->ubox, Uptr); }
+          if (c->pyr_now)          // (a pyramid search, az_propose_pyramid: always this plain level loop)
+              azk_pyramid_rois_dedup(s, c->B[cur], Pptr, c->maxR, c->pyr_sc, (float)p->dedup, p->batch_size, c->rois, c->key,
+                                     c->grp, c->first, c->index, INV(l), c->urois, c->ubox, Uptr);
+          else
+              azk_rois_dedup(s, c->B[cur], Pptr, c->maxR, p->scale, (float)p->dedup, p->batch_size, c->rois, c->key,
+                             c->grp, c->first, c->index, INV(l), c->urois, c->ubox, Uptr); }
         // The last level of a default search with a fixed proposal count: its candidates, its counters and the final
         // top-k come from ONE launch (az_static.hip: k_final_select) instead of k_flags, k_compact, k_rank_count and
         // k_rank_scatter; the tail kernel emits the selection keys.  (params.reserved bits 1 / 3 keep the separate
@@ -984,7 +988,7 @@ static int launch_impl_body(az_ctx *c, const az_params *p)
     auto enqueue = [&]() { c->npass = 0; prep_scale(c); return stat ? enqueue_static(c, p, nlev, k) : enqueue_search(c, p, K, nlev, k, tune); };
     // az_set_graphs / AZ_GRAPH=1: capture the launch sequence once per (parameters, feature map) and replay it
     // as a hipGraph.  Every size is read on the device, so the sequence never changes for given parameters.
-    if (c->use_graphs && !c->profiling && !(tune && c->pool)) {
+    if (c->use_graphs && !c->profiling && !(tune && c->pool) && !c->pyr_now) {
         // key = the fields themselves (never the struct's bytes: padding is the caller's garbage)
         std::string key;
         auto put = [&key](const void *v, size_t n) { key.append((const char *)v, n); };
@@ -1048,6 +1052,7 @@ static int launch_impl_body(az_ctx *c, const az_params *p)
     q.p = *p; q.nlev = nlev; q.is_static = c->last_static; q.defer = c->last_defer; q.pair_mask = c->last_pair_mask;
     q.full = c->last_full;
     q.cut = c->last_cut;
+    q.pyr = c->pyr_now;
     q.npass = c->npass;
     q.feat = c->feat; q.fH = c->d.H; q.fW = c->d.W; q.feat_gen = c->feat_gen;
     q.feat_is_copy = c->feat && (c->feat == c->feat_owned[0] || c->feat == c->feat_owned[1] || c->feat == c->feat_owned[2]);
@@ -1242,7 +1247,7 @@ int fetch_entry(az_ctx *c, size_t idx, double *boxes_out, float *scores_out, int
         return fail(c, AZ_ERR_CAPACITY,
                     std::string("az_propose: ctx capacity exceeded (flags ") + std::to_string(h.err) +
                         "): raise az_set_limits");
-    if (!q.is_static && !(q.p.reserved & 4)) {
+    if (!q.is_static && !(q.p.reserved & 4) && !q.pyr) {
         hint_load(c, q.p.im_h, q.p.im_w, nlev);           // (the shape's records: a search of another shape may have been launched since)
         if (c->hint_n > 0) {                              // the records move down by one, the oldest drops out
             for (int r = az_ctx::HINT_K - 2; r > 0; --r) c->hint_old[r] = c->hint_old[r - 1];

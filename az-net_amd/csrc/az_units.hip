@@ -85,6 +85,33 @@ int az_roi_dedup(az_ctx *c, const double *boxes, int P, double scale, double ded
     return AZ_OK;
 }
 
+int az_roi_dedup_pyramid(az_ctx *c, const double *boxes, int P, const double *scales, int S, double dedup, int batch_size,
+                         float *rois_out, int32_t *index_out, int32_t *inv_index_out, int *n_unique)
+{
+    int rc = check_geom(c);
+    if (rc) return rc;
+    AzPyrScales sc;
+    if ((rc = pyramid_args(c, scales, S, &sc, "az_roi_dedup_pyramid")) != AZ_OK) return rc;
+    if (P < 0 || (P && !boxes) || !n_unique || batch_size <= 0)
+        return fail(c, AZ_ERR_INVALID, "az_roi_dedup_pyramid: bad arguments");
+    if (P > c->maxR) return fail(c, AZ_ERR_CAPACITY, "az_roi_dedup_pyramid: too many regions");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    HIPCHK(c, hipMemsetAsync(c->cnt, 0, sizeof(AzCounts), s));
+    if (P) HIPCHK(c, hipMemcpyAsync(c->B[0], boxes, (size_t)P * 4 * sizeof(double), hipMemcpyHostToDevice, s));
+    if ((rc = set_count(c, &c->cnt->P[0], P)) != AZ_OK) return rc;
+    azk_pyramid_rois_dedup(s, c->B[0], &c->cnt->P[0], c->maxR, sc, (float)dedup, batch_size, c->rois, c->key, c->grp,
+                           c->first, c->index, c->inv, c->urois, c->ubox, &c->cnt->U[0]);
+    HIPCHK(c, hipMemcpyAsync(c->h_cnt, c->cnt, sizeof(AzCounts), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    const int U = c->h_cnt->U[0];
+    *n_unique = U;
+    if (P && rois_out) HIPCHK(c, hipMemcpy(rois_out, c->rois, (size_t)P * 5 * 4, hipMemcpyDeviceToHost));
+    if (U && index_out) HIPCHK(c, hipMemcpy(index_out, c->index, (size_t)U * 4, hipMemcpyDeviceToHost));
+    if (P && inv_index_out) HIPCHK(c, hipMemcpy(inv_index_out, c->inv, (size_t)P * 4, hipMemcpyDeviceToHost));
+    return AZ_OK;
+}
+
 static int stage_rois(az_ctx *c, const float *rois, int R)
 {
     if (R < 0 || (R && !rois)) return fail(c, AZ_ERR_INVALID, "bad rois");
@@ -105,6 +132,26 @@ int az_roi_pool(az_ctx *c, const float *rois, int R, float *out)
     azk_roi_pool(c->stream, c->feat, c->d, c->spatial_scale, c->urois, &c->cnt->U[0], c->maxR, c->pool5, nullptr, 0, 0,
                  0);
     // the ABI returns Caffe's [R, C, 7, 7] flattening; HBM holds [R, 49, C]
+    if (R) azk_permute_k(c->stream, c->pool5, c->part, R, c->d.C, 0);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (R) HIPCHK(c, hipMemcpy(out, c->part, (size_t)R * c->d.K6 * 4, hipMemcpyDeviceToHost));
+    return AZ_OK;
+}
+
+int az_roi_pool_pyramid(az_ctx *c, const float *rois, int R, float *out)
+{
+    int rc = check_ready(c, true);
+    if (rc) return rc;
+    if (!c->pyr_S) return fail(c, AZ_ERR_STATE, "az_roi_pool_pyramid: no pyramid set (az_set_feature_pyramid_dev_nhwc)");
+    if (R < 0 || (R && (!rois || !out))) return fail(c, AZ_ERR_INVALID, "az_roi_pool_pyramid: bad arguments");
+    for (int r = 0; r < R; ++r) {        // (column 0 indexes the map table)
+        const float lv = rois[5 * (size_t)r];
+        if (!(lv >= 0.0f && lv < (float)c->pyr_S && lv == (float)(int)lv))
+            return fail(c, AZ_ERR_INVALID, "az_roi_pool_pyramid: roi column 0 must be a level of the pyramid set");
+    }
+    if ((rc = stage_rois(c, rois, R)) != AZ_OK) return rc;
+    azk_roi_pool(c->stream, c->feat, c->d, c->spatial_scale, c->urois, &c->cnt->U[0], c->maxR, c->pool5, nullptr, 0, 0,
+                 0, 0, nullptr, c->pyr_feats, c->pyr_hw);
     if (R) azk_permute_k(c->stream, c->pool5, c->part, R, c->d.C, 0);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (R) HIPCHK(c, hipMemcpy(out, c->part, (size_t)R * c->d.K6 * 4, hipMemcpyDeviceToHost));
@@ -459,6 +506,38 @@ int az_detect(az_ctx *c, const double *boxes, int P, double scale, double dedup,
     azk_rois_dedup(s, c->B[0], &c->cnt->P[0], c->maxR, scale, (float)dedup, batch_size, c->rois, c->key, c->grp,
                    c->first, c->index, c->inv, c->urois, c->ubox, &c->cnt->U[0]);
     launch_det_head(c, &c->cnt->U[0], im_h, im_w, eps, P);
+    azk_det_gather(s, &c->cnt->P[0], c->inv, c->det_ncls, c->dprob_u, c->dpred_u, c->dprob, c->dpred);
+    HIPCHK(c, hipStreamSynchronize(s));
+    HIPCHK(c, hipGetLastError());
+    const size_t nc = (size_t)c->det_ncls;
+    if (scores_out) HIPCHK(c, hipMemcpy(scores_out, c->dprob, (size_t)P * nc * 4, hipMemcpyDeviceToHost));
+    if (boxes_out) HIPCHK(c, hipMemcpy(boxes_out, c->dpred, (size_t)P * nc * 4 * sizeof(double), hipMemcpyDeviceToHost));
+    return AZ_OK;
+}
+
+// _frcnn_forward over an image pyramid: az_detect with the pyramid projection and RoIPool through the map table (each
+// roi reads the map of its level); decode and clip in original image pixels as before.
+int az_detect_pyramid(az_ctx *c, const double *boxes, int P, const double *scales, int S, double dedup, int batch_size,
+                      int im_h, int im_w, double eps, float *scores_out, double *boxes_out)
+{
+    int rc = check_det(c);
+    if (rc) return rc;
+    AzPyrScales sc;
+    if ((rc = pyramid_args(c, scales, S, &sc, "az_detect_pyramid")) != AZ_OK) return rc;
+    if (P < 0 || (P && !boxes) || batch_size <= 0) return fail(c, AZ_ERR_INVALID, "az_detect_pyramid: bad arguments");
+    if (c->pyr_S != S)
+        return fail(c, AZ_ERR_STATE, "az_detect_pyramid: no pyramid of that many maps set (az_set_feature_pyramid_dev_nhwc)");
+    if (P > c->maxR) return fail(c, AZ_ERR_CAPACITY, "az_detect_pyramid: too many boxes");
+    if (P == 0) return AZ_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    if (!(c->profiling & 4)) clear_events(c);
+    HIPCHK(c, hipMemsetAsync(c->cnt, 0, sizeof(AzCounts), s));
+    HIPCHK(c, hipMemcpyAsync(c->B[0], boxes, (size_t)P * 4 * sizeof(double), hipMemcpyHostToDevice, s));
+    if ((rc = set_count(c, &c->cnt->P[0], P)) != AZ_OK) return rc;
+    azk_pyramid_rois_dedup(s, c->B[0], &c->cnt->P[0], c->maxR, sc, (float)dedup, batch_size, c->rois, c->key, c->grp,
+                           c->first, c->index, c->inv, c->urois, c->ubox, &c->cnt->U[0]);
+    launch_det_head(c, &c->cnt->U[0], im_h, im_w, eps, P, c->pyr_feats, c->pyr_hw);
     azk_det_gather(s, &c->cnt->P[0], c->inv, c->det_ncls, c->dprob_u, c->dpred_u, c->dprob, c->dpred);
     HIPCHK(c, hipStreamSynchronize(s));
     HIPCHK(c, hipGetLastError());

@@ -18,6 +18,7 @@ AZ_MAX_LEVELS = 16
 AZ_NUM_SUBREG = 11
 AZ_OK = 0
 AZ_BATCH_MAX = 32          # include/aznet_hip.h
+AZ_PYRAMID_MAX = 8         # include/aznet_hip.h
 AZ_ERR_INVALID, AZ_ERR_HIP, AZ_ERR_CAPACITY, AZ_ERR_STATE, AZ_ERR_NO_DEVICE = -1, -2, -3, -4, -5
 _ERR_NAMES = {-1: "AZ_ERR_INVALID", -2: "AZ_ERR_HIP", -3: "AZ_ERR_CAPACITY", -4: "AZ_ERR_STATE",
               -5: "AZ_ERR_NO_DEVICE"}
@@ -39,6 +40,8 @@ SYMBOLS = [
     "az_bias_relu", "az_bias_relu_pool", "az_batch_launch", "az_batch_fetch", "az_batch_next_stream",
     "az_batch_stage_results_dev", "az_batch_fetch_all", "az_batch_launch_shapes", "az_abi_sizes",
     "az_detect_batch", "az_voc_eval", "az_coco_eval",
+    "az_set_feature_pyramid_dev_nhwc", "az_roi_dedup_pyramid", "az_roi_pool_pyramid", "az_propose_pyramid",
+    "az_detect_pyramid",
 ]
 
 
@@ -134,6 +137,11 @@ def load_library(path=None):
     L.az_load_det_head.argtypes = [vp, ci, ci, ci, ci] + [fp] * 8
     L.az_det_forward.argtypes = [vp, fp, ci, fp, fp]
     L.az_detect.argtypes = [vp, dp, ci, cd, cd, ci, ci, ci, cd, fp, dp]
+    L.az_set_feature_pyramid_dev_nhwc.argtypes = [vp, ctypes.POINTER(ctypes.c_void_p), ci, ci, ci, ci]
+    L.az_roi_dedup_pyramid.argtypes = [vp, dp, ci, dp, ci, cd, ci, fp, ip, ip, cip]
+    L.az_roi_pool_pyramid.argtypes = [vp, fp, ci, fp]
+    L.az_propose_pyramid.argtypes = [vp, ctypes.POINTER(AzParams), dp, ci, dp, fp, ci, cip, ctypes.POINTER(AzStats)]
+    L.az_detect_pyramid.argtypes = [vp, dp, ci, dp, ci, cd, ci, ci, ci, cd, fp, dp]
     L.az_detect_batch.argtypes = [vp, ci, ctypes.POINTER(vp), ci, ip, ip, dp, ip, dp, ip, cd, ci, cd, fp, dp]
     L.az_set_profiling.argtypes = [vp, ci]
     L.az_set_graphs.argtypes = [vp, ci]
@@ -363,6 +371,86 @@ class AzContext(object):
         if want_stats:
             out.append(st)
         return out[0] if len(out) == 1 else tuple(out)
+
+    # ---- multi-scale test pyramids (cfg.TEST.SCALES with several entries) --------------------------------------------
+    def set_feature_pyramid(self, maps, producer_done=False):
+        """maps: the S conv5_3 maps of one padded image blob (_get_image_blob of a pyramid), CUDA float32 tensors
+        [1,C,H,W] in torch.channels_last memory (or [H][W][C] views), all of one size; borrowed (kept alive here) as
+        set_feature_map borrows a channel-last map.  Level 0 also becomes the context's single map."""
+        import torch
+        maps = list(maps)
+        if not 1 <= len(maps) <= AZ_PYRAMID_MAX:
+            raise ValueError("a pyramid has 1 to %d levels, got %d" % (AZ_PYRAMID_MAX, len(maps)))
+        views = []
+        for m in maps:
+            t, cl = self._torch_map(m)
+            if not cl:
+                raise ValueError("pyramid maps must be channels_last CUDA tensors (the layout RoIPool reads)")
+            views.append(t)
+        shapes = {tuple(int(x) for x in t.shape) for t in views}
+        if len(shapes) != 1:
+            raise ValueError("the maps of a pyramid must all have one (padded) size, got %s" % sorted(shapes))
+        C, H, W = shapes.pop()
+        if not producer_done:
+            torch.cuda.current_stream(views[0].device).synchronize()
+        tab = (ctypes.c_void_p * len(views))(*[t.data_ptr() for t in views])
+        self._chk(self.L.az_set_feature_pyramid_dev_nhwc(self.h, tab, len(views), C, H, W))
+        self._feat_keepalive = maps
+        self.feat_shape = (C, H, W)
+        self.pyramid_levels = len(views)
+
+    def roi_dedup_pyramid(self, boxes, scales, dedup=1. / 16., batch_size=10000):
+        """_get_rois_blob over a pyramid + np.unique per batch_size chunk: (rois [P,5] f32 with the level in column 0,
+        index [U], inverse [P])."""
+        boxes = _f64(boxes).reshape(-1, 4)
+        sc = _f64(np.asarray(scales, dtype=np.float64).reshape(-1))
+        P = boxes.shape[0]
+        rois = np.empty((max(P, 1), 5), dtype=np.float32)
+        index = np.empty((max(P, 1),), dtype=np.int32)
+        inv = np.empty((max(P, 1),), dtype=np.int32)
+        n = ctypes.c_int(0)
+        self._chk(self.L.az_roi_dedup_pyramid(self.h, _p(boxes, ctypes.c_double), P, _p(sc, ctypes.c_double), sc.size,
+                                              float(dedup), int(batch_size), _p(rois, ctypes.c_float),
+                                              _p(index, ctypes.c_int32), _p(inv, ctypes.c_int32), ctypes.byref(n)))
+        return rois[:P].copy(), index[:n.value].copy(), inv[:P].copy()
+
+    def roi_pool_pyramid(self, rois):
+        rois = _f32(rois).reshape(-1, 5)
+        R = rois.shape[0]
+        out = np.empty((max(R, 1), self.dims["K6"]), dtype=np.float32)
+        self._chk(self.L.az_roi_pool_pyramid(self.h, _p(rois, ctypes.c_float), R, _p(out, ctypes.c_float)))
+        return out[:R]
+
+    def propose_pyramid(self, params, scales, want_scores=False, want_stats=False):
+        """propose() over the pyramid set (az_propose_pyramid: the plain level loop); params.scale is ignored."""
+        sc = _f64(np.asarray(scales, dtype=np.float64).reshape(-1))
+        cap = params.num_proposals if params.fixed_num else self.max_candidates
+        boxes = np.empty((max(cap, 1), 4), dtype=np.float64)
+        scores = np.empty((max(cap, 1),), dtype=np.float32)
+        n = ctypes.c_int(0)
+        st = AzStats()
+        self._chk(self.L.az_propose_pyramid(self.h, ctypes.byref(params), _p(sc, ctypes.c_double), sc.size,
+                                            _p(boxes, ctypes.c_double), _p(scores, ctypes.c_float), cap,
+                                            ctypes.byref(n), ctypes.byref(st)))
+        out = [boxes[:n.value].copy()]
+        if want_scores:
+            out.append(scores[:n.value].copy())
+        if want_stats:
+            out.append(st)
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def detect_pyramid(self, boxes, scales, im_h, im_w, dedup=1. / 16., batch_size=10000, eps=1e-14):
+        """detect() over the pyramid set (az_detect_pyramid)."""
+        boxes = _f64(boxes).reshape(-1, 4)
+        sc = _f64(np.asarray(scales, dtype=np.float64).reshape(-1))
+        P = boxes.shape[0]
+        nc = self.det_dims["ncls"]
+        s = np.empty((max(P, 1), nc), dtype=np.float32)
+        b = np.empty((max(P, 1), 4 * nc), dtype=np.float64)
+        self._chk(self.L.az_detect_pyramid(self.h, _p(boxes, ctypes.c_double), P, _p(sc, ctypes.c_double), sc.size,
+                                           float(dedup), int(batch_size), int(im_h), int(im_w), float(eps),
+                                           _p(s, ctypes.c_float), _p(b, ctypes.c_double)))
+        return s[:P], b[:P]
 
     def _ext(self, handle):
         """torch view of one of the context's HIP streams (by raw handle)."""

@@ -16,6 +16,36 @@ import numpy as np
 from aznet_hip import ffi
 
 
+def pyramid_blob(ctx, device, im, pixel_means, scales):
+    """_get_image_blob of an image pyramid (lib/detect/test.py:27-59 with several cfg.TEST.SCALES) on the GPU: every
+    scale's mean-subtracted, INTER_LINEAR-resized image (the front-end kernel, az_image_blob_dev_on) written into one
+    zeroed [S,3,Hmax,Wmax] tensor at its top-left corner -- im_list_to_blob's padding at the bottom and right to the
+    per-axis maximum of the scaled shapes.  Enqueued on torch's current stream."""
+    import torch
+    stream = torch.cuda.current_stream(device)
+    sizes = [ctx.image_blob_size(im.shape[0], im.shape[1], s) for s in scales]
+    Hm, Wm = max(h for h, _ in sizes), max(w for _, w in sizes)
+    blob = torch.zeros((len(scales), 3, Hm, Wm), dtype=torch.float32, device=device)
+    for i, (s, (oh, ow)) in enumerate(zip(scales, sizes)):
+        part = torch.empty((1, 3, oh, ow), dtype=torch.float32, device=device)
+        ctx.image_blob(im, pixel_means, float(s), out=part, stream=stream.cuda_stream)
+        blob[i, :, :oh, :ow].copy_(part[0])
+    return blob
+
+
+def pyramid_maps(backbone, blob):
+    """conv5_3 of every level of a padded pyramid blob, each a [1,C,h,w] channels_last tensor (the layout RoIPool reads)
+    of the padded size: the backbone sees the padded image, as Caffe's batch does."""
+    import torch
+    maps = []
+    for i in range(blob.shape[0]):
+        conv = backbone(blob[i:i + 1])
+        if not conv.is_contiguous(memory_format=torch.channels_last) or conv.is_contiguous():
+            conv = conv.contiguous(memory_format=torch.channels_last)
+        maps.append(conv)
+    return maps
+
+
 class _Blob(object):
     def __init__(self):
         self.shape = None
@@ -86,6 +116,25 @@ class HipAZNet(object):
         self.set_conv(conv)                                    # (synchronises torch's stream first)
         return conv
 
+    def compute_pyramid(self, im, pixel_means, scales):
+        """An image pyramid (several cfg.TEST.SCALES) through the front-end and the backbone: the S padded conv5_3 maps
+        (channels_last CUDA tensors of one size), handed to the context as its pyramid set.  Returns the list of maps."""
+        if self.backbone is None:
+            raise RuntimeError("HipAZNet has no backbone: supply the pyramid maps with set_pyramid()")
+        blob = pyramid_blob(self.ctx, self.backbone.device, im, pixel_means, scales)
+        maps = pyramid_maps(self.backbone, blob)
+        self.set_pyramid(maps)
+        return maps
+
+    def set_pyramid(self, maps):
+        """Hand the S padded conv5_3 maps of a pyramid to the context (torch's stream is synchronised first)."""
+        self.ctx.set_feature_pyramid(maps)
+        self._conv = maps
+
+    def propose_pyramid(self, params, scales, want_scores=False, want_stats=False):
+        """im_propose over the pyramid set (az_propose_pyramid: the plain level loop)."""
+        return self.ctx.propose_pyramid(params, scales, want_scores=want_scores, want_stats=want_stats)
+
     # ---- whole search ------------------------------------------------------------------
     def propose(self, params, want_scores=False, want_stats=False, stage=None):
         """stage (multi-GPU): a callable run between launch and fetch, e.g. DeviceGather.stage(j), which
@@ -148,6 +197,11 @@ class HipDetNet(object):
     def detect(self, boxes, scale, im_shape, dedup, batch_size, eps):
         return self.ctx.detect(boxes, scale, im_shape[0], im_shape[1], dedup=dedup, batch_size=batch_size, eps=eps)
 
+    def detect_pyramid(self, boxes, scales, im_shape, dedup, batch_size, eps):
+        """_frcnn_forward over the pyramid set the shared context holds (HipAZNet.compute_pyramid / set_pyramid)."""
+        return self.ctx.detect_pyramid(boxes, scales, im_shape[0], im_shape[1], dedup=dedup, batch_size=batch_size,
+                                       eps=eps)
+
     def forward(self, blobs=None, **kw):
         rois = np.ascontiguousarray(kw["rois"], dtype=np.float32)
         if "conv5_3" in kw and kw["conv5_3"] is not self.az_net._conv:
@@ -207,6 +261,21 @@ class HipFrcnnNet(object):
         if not conv.is_contiguous(memory_format=torch.channels_last):
             conv = conv.contiguous(memory_format=torch.channels_last)
         return conv
+
+    def compute_pyramid(self, im, pixel_means, scales):
+        """An image pyramid through the front-end and this net's backbone; the S padded conv5_3 maps become the
+        context's pyramid set.  Returns the list of maps."""
+        dev = self._torch_device()
+        maps = pyramid_maps(self.backbone, pyramid_blob(self.ctx, dev, im, pixel_means, scales))
+        self.ctx.set_feature_pyramid(maps)
+        return maps
+
+    def detect_pyramid(self, maps, boxes, scales, im_shape, dedup, batch_size, eps):
+        """_frcnn_forward of one image over its pyramid maps (az_detect_pyramid)."""
+        if maps is not None:
+            self.ctx.set_feature_pyramid(maps)
+        return self.ctx.detect_pyramid(boxes, scales, im_shape[0], im_shape[1], dedup=dedup, batch_size=batch_size,
+                                       eps=eps)
 
     def detect_batch(self, convs, boxes_list, scales, im_shapes, dedup, batch_size, eps):
         return self.ctx.detect_batch(convs, boxes_list, scales, im_shapes, dedup=dedup, batch_size=batch_size, eps=eps)

@@ -54,14 +54,30 @@ def _get_image_blob(im, net=None):
     (az_image_blob_*); with `net` (a HipAZNet that owns a backbone) the blob stays on the GPU.
     Computed once per image; the reference recomputes it at every level."""
     scales = _im_scale(im.shape)
-    if len(scales) != 1:
-        raise NotImplementedError("one test scale (cfg.TEST.SCALES), as in every config of the reference")
     src = _as_uint8(im)
+    if len(scales) > 1:
+        return _get_pyramid_blob(src, scales, net), np.array(scales)
     if net is not None:
         blob = net.image_blob(src, cfg.PIXEL_MEANS, scales[0])
     else:
         blob = ffi.default_context().image_blob(src, cfg.PIXEL_MEANS, scales[0])
     return blob, np.array(scales)
+
+
+def _get_pyramid_blob(src, scales, net=None):
+    """_get_image_blob of several test scales: every scale's image (the same front-end kernel) zero-padded at the bottom
+    and right to the per-axis maximum of the scaled shapes, one [S,3,Hmax,Wmax] blob (utils/blob.py im_list_to_blob).
+    On the GPU with a `net` that owns a backbone, else a NumPy array."""
+    if net is not None and getattr(net, "backbone", None) is not None:
+        from aznet_hip.net import pyramid_blob
+        return pyramid_blob(net.ctx, net.backbone.device, src, cfg.PIXEL_MEANS, scales)
+    ctx = ffi.default_context()
+    parts = [ctx.image_blob(src, cfg.PIXEL_MEANS, s) for s in scales]
+    parts = [p[0] if p.ndim == 4 else p for p in parts]
+    blob = np.zeros((len(parts), 3, max(p.shape[1] for p in parts), max(p.shape[2] for p in parts)), dtype=np.float32)
+    for i, p in enumerate(parts):
+        blob[i, :, :p.shape[1], :p.shape[2]] = p
+    return blob
 
 
 def divide_region(regions):
@@ -104,6 +120,13 @@ def im_propose(net, im, return_conv=False, num_proposals=None, conv=None, stage=
     return_conv is set."""
     hnet = net["full"] if isinstance(net, dict) else net
     scales = _im_scale(im.shape)
+    if len(scales) > 1:
+        Y, st, conv = _pyramid_search(hnet, im, scales, num_proposals, conv, stage)
+        print('{0} proposals, evaluate {1} regions, reaches depth {2}.'
+              .format(Y.shape[0], st.num_eval, st.depth))
+        if return_conv:
+            return Y, conv
+        return Y
     if conv is None:
         blob, _ = _get_image_blob(im, hnet)
         conv_t = hnet.compute_conv(blob)
@@ -125,6 +148,30 @@ def im_propose(net, im, return_conv=False, num_proposals=None, conv=None, stage=
     return Y
 
 
+def _pyramid_search(hnet, im, scales, num_proposals=None, conv=None, stage=None):
+    """im_propose over an image pyramid (several cfg.TEST.SCALES; test.py:27-97): the padded blob's S conv5_3 maps (or
+    the cached ones in `conv`), then one az_propose_pyramid call -- the plain level loop, each level's regions projected
+    to the pyramid level whose scaled area is closest to 224 x 224.  Synchronous.  Returns (Y, stats, conv dict); Y is
+    what im_propose returns (APPEND_BOXES applied)."""
+    if stage is not None:
+        raise NotImplementedError("multi-GPU result staging of a pyramid search (cfg.TEST.SCALES with several entries): "
+                                  "run one GPU per process without staging")
+    if conv is None:
+        maps = hnet.compute_pyramid(_as_uint8(im), cfg.PIXEL_MEANS, scales)
+        conv = {name: maps for name in cfg.SEAR.FRCNN_CONV}
+    else:
+        hnet.set_pyramid(conv[cfg.SEAR.AZ_CONV[0]])
+    params = _params(im.shape, scales[0], num_proposals)
+    Y, st = hnet.propose_pyramid(params, scales, want_stats=True)
+    if cfg.SEAR.APPEND_BOXES:
+        Y = _append_boxes(Y)
+        Y[:, 0::4] = np.maximum(Y[:, 0::4], 0)
+        Y[:, 1::4] = np.maximum(Y[:, 1::4], 0)
+        Y[:, 2::4] = np.minimum(Y[:, 2::4], im.shape[1] - 1)
+        Y[:, 3::4] = np.minimum(Y[:, 3::4], im.shape[0] - 1)
+    return Y, st, conv
+
+
 # ---- the same search as two halves, so that a loop over images keeps the GPU fed -------------------------------------
 # im_propose is synchronous (the reference's contract): image -> blob -> backbone -> search -> boxes, the host waiting at
 # every arrow.  A dataset loop does not need the boxes of image i before it may START image i+1: _propose_start enqueues an
@@ -142,8 +189,11 @@ def _propose_start(net, im, num_proposals=None, after=None, stage=None):
     import torch
     hnet = net["full"] if isinstance(net, dict) else net
     scale = _im_scale(im.shape)
-    if len(scale) != 1:
-        raise NotImplementedError("one test scale (cfg.TEST.SCALES), as in every config of the reference")
+    if len(scale) > 1:
+        # (an image pyramid takes the one-image synchronous route; _propose_finish prints its line, so the order of the
+        #  printed lines is the queued loop's)
+        Y, st, conv = _pyramid_search(hnet, im, scale, num_proposals, stage=stage)
+        return {"shape": im.shape, "pyramid": (Y, st), "conv": conv, "done": None}
     params = _params(im.shape, scale[0], num_proposals)
     dev = hnet.backbone.device
     if after is not None:
@@ -162,6 +212,11 @@ def _propose_start(net, im, num_proposals=None, after=None, stage=None):
 def _propose_finish(net, h, return_conv=False):
     """Second half of im_propose: wait for the search launched by _propose_start, format as im_propose does."""
     hnet = net["full"] if isinstance(net, dict) else net
+    if "pyramid" in h:
+        Y, st = h["pyramid"]
+        print('{0} proposals, evaluate {1} regions, reaches depth {2}.'
+              .format(Y.shape[0], st.num_eval, st.depth))
+        return (Y, h["conv"]) if return_conv else Y
     Y, st = hnet.ctx.propose_fetch(want_stats=True)
     shape = h["shape"]
     if cfg.SEAR.APPEND_BOXES:
@@ -188,8 +243,7 @@ def _batch_backbones(net, ims, after=None):
     convs, blobs = [], []
     for im in ims:
         scale = _im_scale(im.shape)
-        if len(scale) != 1:
-            raise NotImplementedError("one test scale (cfg.TEST.SCALES), as in every config of the reference")
+        assert len(scale) == 1, "image pyramids take the one-image route (test_proposals, test_net_shared)"
         blob = hnet.image_blob_enqueue(_as_uint8(im), cfg.PIXEL_MEANS, scale[0])
         blobs.append(blob)
         conv = hnet.backbone(blob)
@@ -369,14 +423,30 @@ def _frcnn_forward(net, im, all_boxes, num_classes, conv=None):
     if _is_full_net(net):
         fnet = net["full"]
         scale = _im_scale(im.shape)
-        if len(scale) != 1:
-            raise NotImplementedError("one test scale (cfg.TEST.SCALES), as in every config of the reference")
+        if len(scale) > 1:
+            # an image pyramid: its padded maps, each roi pooled from the level its scaled area is closest to 224^2 at
+            maps = fnet.compute_pyramid(_as_uint8(im), cfg.PIXEL_MEANS, scale)
+            assert num_classes == fnet.num_classes
+            scores, boxes = fnet.detect_pyramid(None, np.ascontiguousarray(all_boxes[:, 0:4], dtype=np.float64), scale,
+                                                im.shape, cfg.DEDUP_BOXES, cfg.SEAR.BATCH_SIZE, cfg.EPS)
+            return scores.astype(np.float64), boxes, {name: maps for name in cfg.SEAR.FRCNN_CONV}
         conv_t = fnet.compute_conv(fnet.image_blob_enqueue(_as_uint8(im), cfg.PIXEL_MEANS, scale[0]))
         assert num_classes == fnet.num_classes
         scores, boxes = fnet.detect(conv_t, np.ascontiguousarray(all_boxes[:, 0:4], dtype=np.float64), scale[0],
                                     im.shape, cfg.DEDUP_BOXES, cfg.SEAR.BATCH_SIZE, cfg.EPS)
         return scores.astype(np.float64), boxes, {name: conv_t for name in cfg.SEAR.FRCNN_CONV}
     dnet = net["fc"] if isinstance(net, dict) else net
+    scales = _im_scale(im.shape)
+    if len(scales) > 1:
+        # shared detection on the pyramid the AZ search left in the context (or the cached one in `conv`)
+        if conv is not None:
+            c = conv[cfg.SEAR.FRCNN_CONV[0]]
+            if c is not dnet.az_net._conv:
+                dnet.az_net.set_pyramid(c)
+        assert num_classes == dnet.num_classes
+        scores, boxes = dnet.detect_pyramid(np.ascontiguousarray(all_boxes[:, 0:4], dtype=np.float64), scales, im.shape,
+                                            cfg.DEDUP_BOXES, cfg.SEAR.BATCH_SIZE, cfg.EPS)
+        return scores.astype(np.float64), boxes, conv
     if conv is not None:
         c = conv[cfg.SEAR.FRCNN_CONV[0]]
         if c is not dnet.az_net._conv:
@@ -440,7 +510,7 @@ def test_proposals(net, imdb):
     num_boxes = 0.0
     images = _prefetched(imdb, list(range(num_images)), depth=_prefetch_depth())
     nb = int(cfg.TEST.get("BATCH_IMAGES", 1))
-    if nb > 1 and _can_queue(hnet) and cfg.SEAR.FIXED_PROPOSAL_NUM:
+    if nb > 1 and _can_queue(hnet) and cfg.SEAR.FIXED_PROPOSAL_NUM and len(cfg.TEST.SCALES) == 1:
         # cfg.TEST.BATCH_IMAGES (an extension: the reference has no such key): up to that many CONSECUTIVE images of one
         # shape walk their zoom trees in lockstep (az_batch_launch).  Every image's boxes are what im_propose gives for it
         # alone, the printed lines and their order are the reference's; while one batch is searched the host enqueues the
@@ -517,7 +587,8 @@ def test_net_shared(sc_net, frcnn_net, imdb):
     # cfg.TEST.BATCH_IMAGES > 1 (an extension): the proposals of consecutive images of one shape in lockstep batches
     # (az_batch_launch), the detection head image by image as before; same detections, same printed lines
     nb = int(cfg.TEST.get("BATCH_IMAGES", 1))
-    batched = nb > 1 and queued and bool(cfg.SEAR.FIXED_PROPOSAL_NUM)
+    # (image pyramids, several cfg.TEST.SCALES: never in lockstep batches -- the one-image route below)
+    batched = nb > 1 and queued and bool(cfg.SEAR.FIXED_PROPOSAL_NUM) and len(cfg.TEST.SCALES) == 1
     gen = _batched_proposals(sc_net, images, num_images, nb, launch_ahead=False) if batched else None
     pend, im = None, None
     if queued and not batched:
@@ -588,8 +659,7 @@ def _detect_group(net, ims, props, num_classes):
     convs = []
     for im in ims:
         scale = _im_scale(im.shape)
-        if len(scale) != 1:
-            raise NotImplementedError("one test scale (cfg.TEST.SCALES), as in every config of the reference")
+        assert len(scale) == 1, "image pyramids take the one-image route (test_net)"
         scales.append(scale[0])
         convs.append(fnet.compute_conv(fnet.image_blob_enqueue(_as_uint8(im), cfg.PIXEL_MEANS, scale[0])))
     assert num_classes == fnet.num_classes
@@ -630,8 +700,9 @@ def test_net(net, prop_file, imdb):
         idx = todo[g0:g0 + nb]
         ims = [next(images) for _ in idx]
         _t['im_detect'].tic()
-        if nb == 1:
-            results = [im_detect(net, ims[0], prop_boxes[idx[0]], num_classes)]
+        if nb == 1 or len(cfg.TEST.SCALES) > 1:
+            # (image pyramids: image by image, az_detect_pyramid)
+            results = [im_detect(net, im, prop_boxes[i], num_classes) for im, i in zip(ims, idx)]
         else:
             results = _detect_group(net, ims, [prop_boxes[i] for i in idx], num_classes)
         # (a group's time is charged to its first image; the average per image is what the timer reports)

@@ -16,7 +16,7 @@ import pickle
 import numpy as np
 
 from detect.config import cfg, get_output_dir
-from detect.test import _im_scale, _get_image_blob
+from detect.test import _im_scale, _get_image_blob, _as_uint8
 from utils.timer import Timer
 from aznet_hip import ffi
 
@@ -30,6 +30,13 @@ def _tune_params(im_shape, scale):
 
 def _search(hnet, im, conv=None):
     scales = _im_scale(im.shape)
+    if len(scales) > 1:
+        # an image pyramid (several cfg.TEST.SCALES): its padded maps and az_propose_pyramid with the tuner flag
+        if conv is None:
+            hnet.compute_pyramid(_as_uint8(im), cfg.PIXEL_MEANS, scales)
+        else:
+            hnet.set_pyramid(conv[cfg.SEAR.AZ_CONV[0]])
+        return hnet.propose_pyramid(_tune_params(im.shape, scales[0]), scales, want_scores=True, want_stats=True)
     if conv is None:
         blob, _ = _get_image_blob(im, hnet)
         hnet.compute_conv(blob)

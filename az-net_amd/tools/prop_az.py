@@ -114,6 +114,9 @@ def main():
         if args.recall:
             report_recall(prop_file)
         return
+    if len(cfg.TEST.SCALES) > 1:
+        raise NotImplementedError("image pyramids (cfg.TEST.SCALES with several entries) run on one GPU: the multi-GPU "
+                                  "result staging serves single-scale searches only")
     # one rank per GPU: rank r owns images r, r + world, ...; proposals are gathered on every rank
     import torch.distributed as dist
     from aznet_hip import dist as azdist

@@ -363,6 +363,34 @@ int az_detect_batch(az_ctx *ctx, int n, const float *const *maps_nhwc_dev, int C
                     const int32_t *im_hw, double dedup, int batch_size, double eps, float *scores_out,
                     double *boxes_out);
 
+/* ---- multi-scale test pyramids (cfg.TEST.SCALES with several entries) ------------------------ */
+/* _get_image_blob (lib/detect/test.py:27-59) stacks every scale's image in ONE zero-padded blob, so the backbone gives
+ * S conv5_3 maps of one padded size; _project_im_rois (:73-97) sends each roi to the level whose scaled area is closest
+ * to 224 x 224, and roi column 0 holds that level.  Every entry below refuses a bad argument before any device work:
+ * S outside [1, AZ_PYRAMID_MAX], a scale that is not positive and finite, a pyramid of another S than the one set, the
+ * 16-bit-term GEMM modes (AZ_ERR_STATE).  S == 1 gives the bits of the single-scale entries. */
+#define AZ_PYRAMID_MAX 8
+/* S channel-last maps [H][W][C] (device memory, all of one size: the padded blob's conv5_3), borrowed as
+ * az_set_feature_map_dev_nhwc borrows one; level 0 also becomes the context's single map. */
+int az_set_feature_pyramid_dev_nhwc(az_ctx *ctx, const float *const *maps_nhwc_dev, int S, int C, int H, int W);
+/* _get_rois_blob with a pyramid + the feature-space dedup of one chunked level (test.py:61-97,210-218): rois_out [P,5]
+ * f32 (column 0 = level, before dedup), index_out [P] (first n_unique valid), inv_index_out [P]. */
+int az_roi_dedup_pyramid(az_ctx *ctx, const double *boxes, int P, const double *scales, int S, double dedup,
+                         int batch_size, float *rois_out, int32_t *index_out, int32_t *inv_index_out, int *n_unique);
+/* RoIPool over the pyramid set: each roi [R,5] reads the map of its level (column 0, an integer in [0, S)) and
+ * clamps to that map's padded size.  out [R, C*49] f32 (Caffe's flattening). */
+int az_roi_pool_pyramid(az_ctx *ctx, const float *rois, int R, float *out);
+/* im_propose / tune.im_propose (params.reserved bit 2) over the pyramid set: the plain level loop, each level's regions
+ * projected into the pyramid; the speculative, whole-tree, one-pass, fused, pair-row, early-end and graph forms are never
+ * taken.  Synchronous, on the context's first lane; az_last_candidates and az_last_anchors answer for it as for
+ * az_propose.  scales [S] as _get_image_blob returns them (p->scale is ignored). */
+int az_propose_pyramid(az_ctx *ctx, const az_params *p, const double *scales, int S, double *boxes_out,
+                       float *scores_out, int cap, int *n_out, az_stats *stats);
+/* az_detect over the pyramid set: projection + dedup as az_roi_dedup_pyramid, RoIPool on each roi's level, the
+ * detection head, decode + clip in original image pixels, un-dedup. */
+int az_detect_pyramid(az_ctx *ctx, const double *boxes, int P, const double *scales, int S, double dedup,
+                      int batch_size, int im_h, int im_w, double eps, float *scores_out, double *boxes_out);
+
 /* ---- zoom-threshold tuner (lib/detect/tune.py, tools/set_thresh.py) ------------------- */
 /* `Bhis` of the tuner's im_propose (tune.py:303, returned at :316) for the last az_propose run
  * with params.reserved bit 2: every region evaluated, level-major, with its zoom score.
