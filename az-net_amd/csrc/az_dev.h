@@ -107,14 +107,6 @@ struct AzSpan {
 
 // ---- launchers (az_geom.hip) -----------------------------------------------------------
 void azk_init_root(hipStream_t s, AzCounts *cnt, double *B0, int im_h, int im_w);
-void azk_rois_keys(hipStream_t s, const double *B, const int *Pptr, int cap, double scale, float dedup,
-                   int batch, float *rois, long long *key, int *grp);
-void azk_rois_dedup(hipStream_t s, const double *B, const int *Pptr, int cap, double scale, float dedup, int batch,
-                    float *rois, long long *key, int *grp, unsigned char *first, int *index, int *inv, float *urois,
-                    double *ubox, int *Uptr);
-void azk_dedup_rois(hipStream_t s, const long long *key, const int *grp, const int *Nptr, int cap,
-                    unsigned char *first, const float *rois, const double *B, int *index, int *inv,
-                    float *urois, double *ubox, int *Uptr);
 // az_detect_batch: the images of one pass, uploaded in one copy together with their boxes (which follow the struct)
 struct AzDetSeg {
     int n;                                    // images in the pass
@@ -125,24 +117,21 @@ struct AzDetSeg {
     double scale[AZ_BATCH_MAX];
     const float *feats[AZ_BATCH_MAX];         // channel-last maps (RoIPool)
 };
-// roi projection + 1/16 dedup of a pass over several images: chunks never span two images, roi column 0 is the
-// image's index in the pass; unique rows come out image by image, each image's in az_detect's order.
-// row_hw [U][2]: the image size of every unique row.
-void azk_rois_dedup_seg(hipStream_t s, const double *B, const AzDetSeg *seg, int n, int cap, float dedup, int batch,
-                        float *rois, long long *key, int *grp, unsigned char *first, int *index, int *inv, float *urois,
-                        double *ubox, int *Uptr, int *row_hw);
-// The slot pass of azk_rois_dedup alone (k_dedup_rois): index / inv / unique rois and anchors from keys, chunk ids and
-// first-occurrence flags another kernel left (az_pyramid.hip).
-void azk_dedup_slots(hipStream_t s, const long long *key, const int *grp, const int *Pptr, int cap,
-                     const unsigned char *first, const float *rois, const double *B, int *index, int *inv, float *urois,
-                     double *ubox, int *Uptr);
-// The scales of an image pyramid, by value in the kernel's arguments (az_pyramid.hip).
+// The scales of an image pyramid, by value in the kernel's arguments.
 struct AzPyrScales { double s[AZ_PYRAMID_MAX]; int S; };
-// azk_rois_dedup with _project_im_rois over a pyramid (lib/detect/test.py:73-97): roi column 0 = the level, the key
-// gains rint(level * dedup) with weight 1.  S == 1: the bits of azk_rois_dedup.
-void azk_pyramid_rois_dedup(hipStream_t s, const double *B, const int *Pptr, int cap, const AzPyrScales &sc, float dedup,
-                            int batch, float *rois, long long *key, int *grp, unsigned char *first, int *index, int *inv,
-                            float *urois, double *ubox, int *Uptr);
+// roi projection + 1/16 dedup (lib/detect/test.py:61-97,210-218) in two launches, k_first_rois (rois, keys, chunk ids,
+// first occurrences) and k_dedup_rois (index / inv / unique rois and anchors), for three projection rules:
+// - one map: roi = f32(box * scale), column 0 = 0; with `pyr`, _project_im_rois over that pyramid instead (roi column
+//   0 = the level, the key gains rint(level * dedup) with weight 1; S == 1: the one-scale bits; `scale` unused);
+// - the images of an az_detect_batch pass: chunks never span two images, roi column 0 is the image's index in the pass;
+//   unique rows come out image by image, each image's in az_detect's order.  row_hw [U][2]: the image size of every
+//   unique row.
+void azk_rois_dedup(hipStream_t s, const double *B, const int *Pptr, int cap, double scale, const AzPyrScales *pyr,
+                    float dedup, int batch, float *rois, long long *key, int *grp, unsigned char *first, int *index,
+                    int *inv, float *urois, double *ubox, int *Uptr);
+void azk_rois_dedup(hipStream_t s, const double *B, const AzDetSeg *seg, int n, int cap, float dedup, int batch,
+                    float *rois, long long *key, int *grp, unsigned char *first, int *index, int *inv, float *urois,
+                    double *ubox, int *Uptr, int *row_hw);
 void azk_flags_compact(hipStream_t s, AzCounts *cnt, int level, int capR, int capCand,
                        const double *B, const int *inv, const double *pred_u, const float *score_u,
                        const float *zoom_u, double Tz, double min_side, int force_root,

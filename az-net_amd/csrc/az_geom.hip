@@ -23,18 +23,6 @@ __global__ void k_init_root(AzCounts *cnt, double *B0, int im_h, int im_w)
     }
 }
 
-// lib/detect/test.py:61-97 (_get_rois_blob: f64 box * scale -> f32) and :212-214 (hash of
-// np.round(rois * DEDUP_BOXES) . [1,1e3,1e6,1e9,1e12]; exact integers, so int64 here).
-__global__ void k_rois_keys(const double *__restrict__ B, const int *Pptr, double scale, float dedup,
-                            int batch, float *rois, long long *key, int *grp)
-{
-    const int P = *Pptr;
-    for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < P; r += gridDim.x * blockDim.x) {
-        key[r] = roi_and_key(B + 4 * (size_t)r, scale, dedup, rois + 5 * (size_t)r, r);
-        grp[r] = r / batch;                        // dedup is per BATCH_SIZE chunk (test.py:195-218)
-    }
-}
-
 // first[i] = no j < i carries the same (grp, key): np.unique(return_index=True) keeps the
 // first occurrence.  One wave per element, lanes stride over j (coalesced key reads served
 // by L2), wave vote at the end: O(N^2 / 64) wave-steps, N is a few thousand at most.
@@ -58,28 +46,90 @@ __global__ void k_first(const long long *__restrict__ key, const int *__restrict
     }
 }
 
-// k_rois_keys and k_first in one launch for the roi dedup: a wave derives the keys it compares against
-// from the regions themselves (a key is four multiplies and roundings), so there is no grid-wide
-// dependency on a key array; it also stores its own element's roi / key / chunk id for k_dedup_rois.
-__global__ void k_first_rois(const double *__restrict__ B, const int *Pptr, double scale, float dedup, int batch,
+// ---- roi projection + first occurrences: k_first_rois over a projection rule --------------------------------------------
+// RoiRow<Proj> binds a rule to row i: roi_key() is row i's roi and key, key(j) the key of a row j of i's chunk, chunk()
+// i's chunk id and row0(chunk()) that chunk's first row (dedup is per BATCH_SIZE chunk, test.py:195-218).
+__device__ __forceinline__ long long project(const double *box, double scale, float dedup, float *roi5, int r)
+{
+    return roi_and_key(box, scale, dedup, roi5, r);
+}
+__device__ __forceinline__ long long project(const double *box, const AzPyrScales &sc, float dedup, float *roi5, int r)
+{
+    return pyramid_roi_and_key(box, sc, dedup, roi5, r);
+}
+
+// One map at one scale (double) or an image pyramid (AzPyrScales): the rows of one image, chunks of `batch` rows.
+template <class Proj> struct RoiRow {
+    const Proj &p;
+    int i, batch;
+    __device__ __forceinline__ RoiRow(const Proj &p_, int i_, int batch_) : p(p_), i(i_), batch(batch_) {}
+    __device__ __forceinline__ int chunk() const { return i / batch; }
+    __device__ __forceinline__ int row0(int gi) const { return gi * batch; }
+    __device__ __forceinline__ long long roi_key(const double *B, float dedup, float *roi5) const
+    {
+        return project(B + 4 * (size_t)i, p, dedup, roi5, i);
+    }
+    __device__ __forceinline__ long long key(const double *B, int j, float dedup) const
+    {
+        float r5[5];
+        return project(B + 4 * (size_t)j, p, dedup, r5, j);
+    }
+};
+
+// The boxes of several images (az_detect_batch): row i belongs to image b (off[b] <= i < off[b+1]); its roi and key are
+// what az_detect computes for local row li = i - off[b] at that image's scale, its chunk id is global (chunk0[b] + local
+// chunk), so no chunk spans two images and k_dedup_rois orders the unique rows image by image.  Roi column 0 is b: the
+// RoIPool table's index of the image's map (Caffe's roi_batch_ind); the key is taken with column 0 = 0, as az_detect
+// takes it.
+template <> struct RoiRow<const AzDetSeg *> {
+    double scale;
+    int i, o, b, grp, j0;
+    __device__ __forceinline__ RoiRow(const AzDetSeg *seg, int i_, int batch) : i(i_), b(0)
+    {
+        const int n = seg->n;
+        while (b + 1 < n && seg->off[b + 1] <= i) ++b;     // (n <= AZ_BATCH_MAX; skips images without boxes)
+        o = seg->off[b];
+        scale = seg->scale[b];
+        const int lc = (i - o) / batch;
+        grp = seg->chunk0[b] + lc;
+        j0 = o + lc * batch;
+    }
+    __device__ __forceinline__ int chunk() const { return grp; }
+    __device__ __forceinline__ int row0(int) const { return j0; }
+    __device__ __forceinline__ long long roi_key(const double *B, float dedup, float *roi5) const
+    {
+        const long long k = roi_and_key(B + 4 * (size_t)i, scale, dedup, roi5, i - o);
+        roi5[0] = (float)b;
+        return k;
+    }
+    __device__ __forceinline__ long long key(const double *B, int j, float dedup) const
+    {
+        float r5[5];
+        return roi_and_key(B + 4 * (size_t)j, scale, dedup, r5, j - o);
+    }
+};
+
+// The projection and k_first in one launch for the roi dedup: a wave derives the keys it compares against from the
+// regions themselves (a key is four multiplies and roundings), so there is no grid-wide dependency on a key array; it
+// also stores its own element's roi / key / chunk id for k_dedup_rois.
+template <class Proj>
+__global__ void k_first_rois(const double *__restrict__ B, const int *Pptr, Proj proj, float dedup, int batch,
                              float *rois, long long *key, int *grp, unsigned char *first)
 {
     const int P = *Pptr;
     const int lane = lane_id();
     const int nwaves = (gridDim.x * blockDim.x) >> 6;
     for (int i = (blockIdx.x * blockDim.x + threadIdx.x) >> 6; i < P; i += nwaves) {
+        const RoiRow<Proj> row(proj, i, batch);
         float roi5[5];
-        const long long ki = roi_and_key(B + 4 * (size_t)i, scale, dedup, roi5, i);
-        const int gi = i / batch;                      // dedup is per BATCH_SIZE chunk (test.py:195-218)
+        const long long ki = row.roi_key(B, dedup, roi5);
+        const int gi = row.chunk();
         if (lane == 0) { key[i] = ki; grp[i] = gi; }
         if (lane < 5) rois[5 * (size_t)i + lane] = roi5[lane];
         bool dup = false;
-        for (int j0 = gi * batch; j0 < i; j0 += 64) {  // only the same chunk can hold a duplicate
+        for (int j0 = row.row0(gi); j0 < i; j0 += 64) {  // only the same chunk can hold a duplicate
             const int j = j0 + lane;
-            if (j < i) {
-                float r5[5];
-                dup |= (roi_and_key(B + 4 * (size_t)j, scale, dedup, r5, j) == ki);
-            }
+            if (j < i) dup |= (row.key(B, j, dedup) == ki);
             if (__any(dup)) break;
         }
         const bool any_dup = __any(dup);               // vote with all lanes active
@@ -131,43 +181,6 @@ __global__ void k_dedup_rois(const long long *__restrict__ key, const int *__res
         }
     }
     if (lane == 0 && nfirst) atomicAdd(Uptr, nfirst);
-}
-
-// k_first_rois for the boxes of several images (az_detect_batch): element i belongs to image b (off[b] <= i < off[b+1]),
-// its roi and key are what az_detect computes for local row i - off[b] at that image's scale, its chunk id is global
-// (chunk0[b] + local chunk), so no chunk spans two images and k_dedup_rois orders the unique rows image by image.  Roi
-// column 0 is b: the RoIPool table's index of the image's map (Caffe's roi_batch_ind); the key is taken with column 0 =
-// 0, as az_detect takes it.
-__global__ void k_first_rois_seg(const double *__restrict__ B, const AzDetSeg *__restrict__ seg, float dedup, int batch,
-                                 float *rois, long long *key, int *grp, unsigned char *first)
-{
-    const int n = seg->n;
-    const int P = seg->off[n];
-    const int lane = lane_id();
-    const int nwaves = (gridDim.x * blockDim.x) >> 6;
-    for (int i = (blockIdx.x * blockDim.x + threadIdx.x) >> 6; i < P; i += nwaves) {
-        int b = 0;
-        while (b + 1 < n && seg->off[b + 1] <= i) ++b;     // (n <= AZ_BATCH_MAX; skips images without boxes)
-        const int o = seg->off[b], li = i - o;
-        const double scale = seg->scale[b];
-        float roi5[5];
-        const long long ki = roi_and_key(B + 4 * (size_t)i, scale, dedup, roi5, li);
-        const int lc = li / batch;
-        if (lane == 0) { key[i] = ki; grp[i] = seg->chunk0[b] + lc; }
-        roi5[0] = (float)b;
-        if (lane < 5) rois[5 * (size_t)i + lane] = roi5[lane];
-        bool dup = false;
-        for (int j0 = o + lc * batch; j0 < i; j0 += 64) {   // only the same chunk of the same image can hold a duplicate
-            const int j = j0 + lane;
-            if (j < i) {
-                float r5[5];
-                dup |= (roi_and_key(B + 4 * (size_t)j, scale, dedup, r5, j - o) == ki);
-            }
-            if (__any(dup)) break;
-        }
-        const bool any_dup = __any(dup);
-        if (lane == 0) first[i] = any_dup ? 0 : 1;
-    }
 }
 
 __global__ void k_seg_row_hw(const AzDetSeg *__restrict__ seg, const float *__restrict__ urois, const int *Uptr,
@@ -391,50 +404,35 @@ void azk_init_root(hipStream_t s, AzCounts *cnt, double *B0, int im_h, int im_w)
     hipLaunchKernelGGL(k_init_root, dim3(1), dim3(64), 0, s, cnt, B0, im_h, im_w);
 }
 
-void azk_rois_keys(hipStream_t s, const double *B, const int *Pptr, int cap, double scale, float dedup,
-                   int batch, float *rois, long long *key, int *grp)
+// roi projection + feature-space dedup in two launches (keys + first occurrences, then slots)
+template <class Proj>
+static void rois_dedup(hipStream_t s, const double *B, const int *Pptr, int cap, Proj proj, float dedup, int batch,
+                       float *rois, long long *key, int *grp, unsigned char *first, int *index, int *inv, float *urois,
+                       double *ubox, int *Uptr)
 {
-    hipLaunchKernelGGL(k_rois_keys, dim3(grid_for(cap, TB)), dim3(TB), 0, s, B, Pptr, scale, dedup, batch,
-                       rois, key, grp);
+    const int g = grid_for(cap, TB / 64);      // one wave per element
+    hipLaunchKernelGGL(k_first_rois<Proj>, dim3(g), dim3(TB), 0, s, B, Pptr, proj, dedup, batch, rois, key, grp, first);
+    hipLaunchKernelGGL(k_dedup_rois, dim3(g), dim3(TB), 0, s, key, grp, Pptr, first, rois, B, index, inv, urois, ubox,
+                       Uptr);
 }
 
-// roi projection + feature-space dedup of one level in two launches (keys + first occurrences, then slots)
-void azk_rois_dedup(hipStream_t s, const double *B, const int *Pptr, int cap, double scale, float dedup, int batch,
+void azk_rois_dedup(hipStream_t s, const double *B, const int *Pptr, int cap, double scale, const AzPyrScales *pyr,
+                    float dedup, int batch, float *rois, long long *key, int *grp, unsigned char *first, int *index,
+                    int *inv, float *urois, double *ubox, int *Uptr)
+{
+    if (pyr)
+        rois_dedup(s, B, Pptr, cap, *pyr, dedup, batch, rois, key, grp, first, index, inv, urois, ubox, Uptr);
+    else
+        rois_dedup(s, B, Pptr, cap, scale, dedup, batch, rois, key, grp, first, index, inv, urois, ubox, Uptr);
+}
+
+void azk_rois_dedup(hipStream_t s, const double *B, const AzDetSeg *seg, int n, int cap, float dedup, int batch,
                     float *rois, long long *key, int *grp, unsigned char *first, int *index, int *inv, float *urois,
-                    double *ubox, int *Uptr)
+                    double *ubox, int *Uptr, int *row_hw)
 {
-    const int g = grid_for(cap, TB / 64);      // one wave per element
-    hipLaunchKernelGGL(k_first_rois, dim3(g), dim3(TB), 0, s, B, Pptr, scale, dedup, batch, rois, key, grp, first);
-    hipLaunchKernelGGL(k_dedup_rois, dim3(g), dim3(TB), 0, s, key, grp, Pptr, first, rois, B, index, inv,
-                       urois, ubox, Uptr);
-}
-
-void azk_rois_dedup_seg(hipStream_t s, const double *B, const AzDetSeg *seg, int n, int cap, float dedup, int batch,
-                        float *rois, long long *key, int *grp, unsigned char *first, int *index, int *inv, float *urois,
-                        double *ubox, int *Uptr, int *row_hw)
-{
-    const int g = grid_for(cap, TB / 64);      // one wave per element
     const int *Pptr = seg->off + n;            // (device address: the boxes of the pass)
-    hipLaunchKernelGGL(k_first_rois_seg, dim3(g), dim3(TB), 0, s, B, seg, dedup, batch, rois, key, grp, first);
-    hipLaunchKernelGGL(k_dedup_rois, dim3(g), dim3(TB), 0, s, key, grp, Pptr, first, rois, B, index, inv,
-                       urois, ubox, Uptr);
+    rois_dedup(s, B, Pptr, cap, seg, dedup, batch, rois, key, grp, first, index, inv, urois, ubox, Uptr);
     hipLaunchKernelGGL(k_seg_row_hw, dim3(grid_for(cap, TB)), dim3(TB), 0, s, seg, urois, Uptr, row_hw);
-}
-void azk_dedup_slots(hipStream_t s, const long long *key, const int *grp, const int *Pptr, int cap,
-                     const unsigned char *first, const float *rois, const double *B, int *index, int *inv, float *urois,
-                     double *ubox, int *Uptr)
-{
-    hipLaunchKernelGGL(k_dedup_rois, dim3(grid_for(cap, TB / 64)), dim3(TB), 0, s, key, grp, Pptr, first, rois, B, index,
-                       inv, urois, ubox, Uptr);
-}
-void azk_dedup_rois(hipStream_t s, const long long *key, const int *grp, const int *Nptr, int cap,
-                    unsigned char *first, const float *rois, const double *B, int *index, int *inv,
-                    float *urois, double *ubox, int *Uptr)
-{
-    const int g = grid_for(cap, TB / 64);      // one wave per element
-    hipLaunchKernelGGL(k_first, dim3(g), dim3(TB), 0, s, key, grp, Nptr, first);
-    hipLaunchKernelGGL(k_dedup_rois, dim3(g), dim3(TB), 0, s, key, grp, Nptr, first, rois, B, index, inv,
-                       urois, ubox, Uptr);
 }
 
 void azk_flags_compact(hipStream_t s, AzCounts *cnt, int level, int capR, int capCand, const double *B,

@@ -97,6 +97,39 @@ static __device__ __forceinline__ long long roi_and_key(const double *box, doubl
     return dedup > 0.0f ? h : (long long)r;
 }
 
+// _project_im_rois (test.py:73-97) + _get_rois_blob (:61-71) + the dedup hash (:212-214) of one box.  Level: the first
+// minimum over s of |w * h * s^2 - 224^2| (np.argmin), in f64; roi = f32(box * s[level]), column 0 = f32(level); the key
+// of np.round(roi * DEDUP_BOXES) . [1, 1e3, 1e6, 1e9, 1e12] -- roi_and_key's plus rint(level * dedup) with weight 1
+// (0 for every level at 1/16 up to level 7).  S == 1 (the reference's else branch, level 0): roi_and_key's bits.
+static __device__ __forceinline__ long long pyramid_roi_and_key(const double *box, const AzPyrScales &sc, float dedup,
+                                                                float *roi5, int r)
+{
+    int lv = 0;
+    double s = sc.s[0];
+    if (sc.S > 1) {
+        const double w = box[2] - box[0] + 1.0, h = box[3] - box[1] + 1.0;
+        const double area = w * h;
+        double best = 0.0;
+#pragma unroll
+        for (int i = 0; i < AZ_PYRAMID_MAX; ++i) {
+            if (i >= sc.S) break;
+            const double d = fabs(area * (sc.s[i] * sc.s[i]) - 224.0 * 224.0);
+            if (i == 0 || d < best) { best = d; lv = i; s = sc.s[i]; }
+        }
+    }
+    const float L = (float)lv;
+    roi5[0] = L;
+    long long h = (long long)rintf(L * dedup), mult = 1000;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const float x = (float)(box[c] * s);
+        roi5[1 + c] = x;
+        h += (long long)rintf(x * dedup) * mult;
+        mult *= 1000;
+    }
+    return dedup > 0.0f ? h : (long long)r;
+}
+
 // divide_region, lib/utils/div.pyx:15-76.
 struct DivPlan { int min_ind; unsigned num_long; double l_short, l_long; };
 

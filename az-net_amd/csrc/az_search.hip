@@ -360,8 +360,8 @@ static int ensure_static_plan(az_ctx *c, const az_params *p, int nlev)
         roff = 0;
         for (int l = 0; l < nlev; ++l) {
             const int cur = l & 1;
-            azk_rois_dedup(s, c->B[cur], &c->cnt->P[l], c->maxR, p->scale, (float)p->dedup, p->batch_size, c->rois,
-                           c->key, c->grp, c->first, c->index, c->inv, c->urois, c->ubox, &c->cnt->U[l]);
+            azk_rois_dedup(s, c->B[cur], &c->cnt->P[l], c->maxR, p->scale, nullptr, (float)p->dedup, p->batch_size,
+                           c->rois, c->key, c->grp, c->first, c->index, c->inv, c->urois, c->ubox, &c->cnt->U[l]);
             if (l + 1 < nlev) {
                 azk_divide(s, &c->cnt->P[l], &c->cnt->CH[l], &c->cnt->err, c->maxR, c->maxCh, c->B[cur], p->min_side,
                            c->choff, c->child, c->ckey, nullptr, nullptr, nullptr, 0, nullptr);
@@ -818,12 +818,9 @@ static int enqueue_search(az_ctx *c, const az_params *p, int K, int nlev, int k,
         }
         if (!fused_lv || l > plan.lv_limit) {   // (otherwise the fused predecessor -- spec_levels or level_geom -- has done this already)
           Timed t(c, "rois_dedup", l);
-          if (c->pyr_now)          // (a pyramid search, az_propose_pyramid: always this plain level loop)
-              azk_pyramid_rois_dedup(s, c->B[cur], Pptr, c->maxR, c->pyr_sc, (float)p->dedup, p->batch_size, c->rois, c->key,
-                                     c->grp, c->first, c->index, INV(l), c->urois, c->ubox, Uptr);
-          else
-              azk_rois_dedup(s, c->B[cur], Pptr, c->maxR, p->scale, (float)p->dedup, p->batch_size, c->rois, c->key,
-                             c->grp, c->first, c->index, INV(l), c->urois, c->ubox, Uptr); }
+          // (a pyramid search, az_propose_pyramid, always takes this plain level loop)
+          azk_rois_dedup(s, c->B[cur], Pptr, c->maxR, p->scale, c->pyr_now ? &c->pyr_sc : nullptr, (float)p->dedup,
+                         p->batch_size, c->rois, c->key, c->grp, c->first, c->index, INV(l), c->urois, c->ubox, Uptr); }
         // The last level of a default search with a fixed proposal count: its candidates, its counters and the final
         // top-k come from ONE launch (az_static.hip: k_final_select) instead of k_flags, k_compact, k_rank_count and
         // k_rank_scatter; the tail kernel emits the selection keys.  (params.reserved bits 1 / 3 keep the separate

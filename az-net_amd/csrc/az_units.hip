@@ -61,19 +61,24 @@ int az_divide_region(az_ctx *c, const double *regions, int P, double min_side, d
     return AZ_OK;
 }
 
-int az_roi_dedup(az_ctx *c, const double *boxes, int P, double scale, double dedup, int batch_size,
-                 float *rois_out, int32_t *index_out, int32_t *inv_index_out, int *n_unique)
+// the box-upload prologue of the entries that take P boxes: counters cleared, the boxes in B[0], P[0] = P
+static int upload_boxes(az_ctx *c, const double *boxes, int P)
 {
-    int rc = check_geom(c);
-    if (rc) return rc;
-    if (P < 0 || (P && !boxes) || !n_unique || batch_size <= 0) return fail(c, AZ_ERR_INVALID, "az_roi_dedup: bad arguments");
-    if (P > c->maxR) return fail(c, AZ_ERR_CAPACITY, "az_roi_dedup: too many regions");
-    HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     HIPCHK(c, hipMemsetAsync(c->cnt, 0, sizeof(AzCounts), s));
     if (P) HIPCHK(c, hipMemcpyAsync(c->B[0], boxes, (size_t)P * 4 * sizeof(double), hipMemcpyHostToDevice, s));
-    if ((rc = set_count(c, &c->cnt->P[0], P)) != AZ_OK) return rc;
-    azk_rois_dedup(s, c->B[0], &c->cnt->P[0], c->maxR, scale, (float)dedup, batch_size, c->rois, c->key, c->grp,
+    return set_count(c, &c->cnt->P[0], P);
+}
+
+// az_roi_dedup / az_roi_dedup_pyramid past their argument checks: one scale, or the pyramid `pyr`
+static int roi_dedup(az_ctx *c, const double *boxes, int P, double scale, const AzPyrScales *pyr, double dedup,
+                     int batch_size, float *rois_out, int32_t *index_out, int32_t *inv_index_out, int *n_unique)
+{
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    int rc = upload_boxes(c, boxes, P);
+    if (rc) return rc;
+    azk_rois_dedup(s, c->B[0], &c->cnt->P[0], c->maxR, scale, pyr, (float)dedup, batch_size, c->rois, c->key, c->grp,
                    c->first, c->index, c->inv, c->urois, c->ubox, &c->cnt->U[0]);
     HIPCHK(c, hipMemcpyAsync(c->h_cnt, c->cnt, sizeof(AzCounts), hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
@@ -83,6 +88,16 @@ int az_roi_dedup(az_ctx *c, const double *boxes, int P, double scale, double ded
     if (U && index_out) HIPCHK(c, hipMemcpy(index_out, c->index, (size_t)U * 4, hipMemcpyDeviceToHost));
     if (P && inv_index_out) HIPCHK(c, hipMemcpy(inv_index_out, c->inv, (size_t)P * 4, hipMemcpyDeviceToHost));
     return AZ_OK;
+}
+
+int az_roi_dedup(az_ctx *c, const double *boxes, int P, double scale, double dedup, int batch_size,
+                 float *rois_out, int32_t *index_out, int32_t *inv_index_out, int *n_unique)
+{
+    int rc = check_geom(c);
+    if (rc) return rc;
+    if (P < 0 || (P && !boxes) || !n_unique || batch_size <= 0) return fail(c, AZ_ERR_INVALID, "az_roi_dedup: bad arguments");
+    if (P > c->maxR) return fail(c, AZ_ERR_CAPACITY, "az_roi_dedup: too many regions");
+    return roi_dedup(c, boxes, P, scale, nullptr, dedup, batch_size, rois_out, index_out, inv_index_out, n_unique);
 }
 
 int az_roi_dedup_pyramid(az_ctx *c, const double *boxes, int P, const double *scales, int S, double dedup, int batch_size,
@@ -95,21 +110,7 @@ int az_roi_dedup_pyramid(az_ctx *c, const double *boxes, int P, const double *sc
     if (P < 0 || (P && !boxes) || !n_unique || batch_size <= 0)
         return fail(c, AZ_ERR_INVALID, "az_roi_dedup_pyramid: bad arguments");
     if (P > c->maxR) return fail(c, AZ_ERR_CAPACITY, "az_roi_dedup_pyramid: too many regions");
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    HIPCHK(c, hipMemsetAsync(c->cnt, 0, sizeof(AzCounts), s));
-    if (P) HIPCHK(c, hipMemcpyAsync(c->B[0], boxes, (size_t)P * 4 * sizeof(double), hipMemcpyHostToDevice, s));
-    if ((rc = set_count(c, &c->cnt->P[0], P)) != AZ_OK) return rc;
-    azk_pyramid_rois_dedup(s, c->B[0], &c->cnt->P[0], c->maxR, sc, (float)dedup, batch_size, c->rois, c->key, c->grp,
-                           c->first, c->index, c->inv, c->urois, c->ubox, &c->cnt->U[0]);
-    HIPCHK(c, hipMemcpyAsync(c->h_cnt, c->cnt, sizeof(AzCounts), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    const int U = c->h_cnt->U[0];
-    *n_unique = U;
-    if (P && rois_out) HIPCHK(c, hipMemcpy(rois_out, c->rois, (size_t)P * 5 * 4, hipMemcpyDeviceToHost));
-    if (U && index_out) HIPCHK(c, hipMemcpy(index_out, c->index, (size_t)U * 4, hipMemcpyDeviceToHost));
-    if (P && inv_index_out) HIPCHK(c, hipMemcpy(inv_index_out, c->inv, (size_t)P * 4, hipMemcpyDeviceToHost));
-    return AZ_OK;
+    return roi_dedup(c, boxes, P, 0.0, &sc, dedup, batch_size, rois_out, index_out, inv_index_out, n_unique);
 }
 
 static int stage_rois(az_ctx *c, const float *rois, int R)
@@ -123,19 +124,26 @@ static int stage_rois(az_ctx *c, const float *rois, int R)
     return set_count(c, &c->cnt->U[0], R);
 }
 
+// az_roi_pool / az_roi_pool_pyramid past their argument checks: RoIPool of the staged rois from the context's map, or
+// through the map table feats / feat_hw (roi column 0 indexes it)
+static int roi_pool(az_ctx *c, int R, float *out, const float *const *feats, const int *feat_hw)
+{
+    azk_roi_pool(c->stream, c->feat, c->d, c->spatial_scale, c->urois, &c->cnt->U[0], c->maxR, c->pool5, nullptr, 0, 0,
+                 0, 0, nullptr, feats, feat_hw);
+    // the ABI returns Caffe's [R, C, 7, 7] flattening; HBM holds [R, 49, C]
+    if (R) azk_permute_k(c->stream, c->pool5, c->part, R, c->d.C, 0);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (R) HIPCHK(c, hipMemcpy(out, c->part, (size_t)R * c->d.K6 * 4, hipMemcpyDeviceToHost));
+    return AZ_OK;
+}
+
 int az_roi_pool(az_ctx *c, const float *rois, int R, float *out)
 {
     int rc = check_ready(c, true);
     if (rc) return rc;
     if ((rc = stage_rois(c, rois, R)) != AZ_OK) return rc;
     if (!out) return fail(c, AZ_ERR_INVALID, "az_roi_pool: null output");
-    azk_roi_pool(c->stream, c->feat, c->d, c->spatial_scale, c->urois, &c->cnt->U[0], c->maxR, c->pool5, nullptr, 0, 0,
-                 0);
-    // the ABI returns Caffe's [R, C, 7, 7] flattening; HBM holds [R, 49, C]
-    if (R) azk_permute_k(c->stream, c->pool5, c->part, R, c->d.C, 0);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (R) HIPCHK(c, hipMemcpy(out, c->part, (size_t)R * c->d.K6 * 4, hipMemcpyDeviceToHost));
-    return AZ_OK;
+    return roi_pool(c, R, out, nullptr, nullptr);
 }
 
 int az_roi_pool_pyramid(az_ctx *c, const float *rois, int R, float *out)
@@ -150,12 +158,7 @@ int az_roi_pool_pyramid(az_ctx *c, const float *rois, int R, float *out)
             return fail(c, AZ_ERR_INVALID, "az_roi_pool_pyramid: roi column 0 must be a level of the pyramid set");
     }
     if ((rc = stage_rois(c, rois, R)) != AZ_OK) return rc;
-    azk_roi_pool(c->stream, c->feat, c->d, c->spatial_scale, c->urois, &c->cnt->U[0], c->maxR, c->pool5, nullptr, 0, 0,
-                 0, 0, nullptr, c->pyr_feats, c->pyr_hw);
-    if (R) azk_permute_k(c->stream, c->pool5, c->part, R, c->d.C, 0);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (R) HIPCHK(c, hipMemcpy(out, c->part, (size_t)R * c->d.K6 * 4, hipMemcpyDeviceToHost));
-    return AZ_OK;
+    return roi_pool(c, R, out, c->pyr_feats, c->pyr_hw);
 }
 
 int az_head_forward(az_ctx *c, const float *rois, int R, float *zoom_prob, float *adj_prob, float *adj_bbox)
@@ -489,6 +492,36 @@ int az_det_forward(az_ctx *c, const float *rois, int R, float *cls_prob, float *
     return AZ_OK;
 }
 
+// the stream's detections of P boxes (dprob / dpred: every box's row, after the un-dedup gather) to the host
+static int fetch_dets(az_ctx *c, int P, float *scores_out, double *boxes_out)
+{
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    const size_t nc = (size_t)c->det_ncls;
+    if (scores_out) HIPCHK(c, hipMemcpy(scores_out, c->dprob, (size_t)P * nc * 4, hipMemcpyDeviceToHost));
+    if (boxes_out) HIPCHK(c, hipMemcpy(boxes_out, c->dpred, (size_t)P * nc * 4 * sizeof(double), hipMemcpyDeviceToHost));
+    return AZ_OK;
+}
+
+// az_detect / az_detect_pyramid past their argument checks: projection + dedup (one scale, or the pyramid `pyr`), the
+// head with RoIPool from the context's map or through the map table feats / feat_hw, the un-dedup gather, the download
+static int detect(az_ctx *c, const double *boxes, int P, double scale, const AzPyrScales *pyr, double dedup,
+                  int batch_size, int im_h, int im_w, double eps, const float *const *feats, const int *feat_hw,
+                  float *scores_out, double *boxes_out)
+{
+    if (P == 0) return AZ_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    if (!(c->profiling & 4)) clear_events(c);
+    int rc = upload_boxes(c, boxes, P);
+    if (rc) return rc;
+    azk_rois_dedup(s, c->B[0], &c->cnt->P[0], c->maxR, scale, pyr, (float)dedup, batch_size, c->rois, c->key, c->grp,
+                   c->first, c->index, c->inv, c->urois, c->ubox, &c->cnt->U[0]);
+    launch_det_head(c, &c->cnt->U[0], im_h, im_w, eps, P, feats, feat_hw);
+    azk_det_gather(s, &c->cnt->P[0], c->inv, c->det_ncls, c->dprob_u, c->dpred_u, c->dprob, c->dpred);
+    return fetch_dets(c, P, scores_out, boxes_out);
+}
+
 int az_detect(az_ctx *c, const double *boxes, int P, double scale, double dedup, int batch_size, int im_h,
               int im_w, double eps, float *scores_out, double *boxes_out)
 {
@@ -496,23 +529,7 @@ int az_detect(az_ctx *c, const double *boxes, int P, double scale, double dedup,
     if (rc) return rc;
     if (P < 0 || (P && !boxes) || batch_size <= 0 || !(scale > 0)) return fail(c, AZ_ERR_INVALID, "az_detect: bad arguments");
     if (P > c->maxR) return fail(c, AZ_ERR_CAPACITY, "az_detect: too many boxes");
-    if (P == 0) return AZ_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    if (!(c->profiling & 4)) clear_events(c);
-    HIPCHK(c, hipMemsetAsync(c->cnt, 0, sizeof(AzCounts), s));
-    HIPCHK(c, hipMemcpyAsync(c->B[0], boxes, (size_t)P * 4 * sizeof(double), hipMemcpyHostToDevice, s));
-    if ((rc = set_count(c, &c->cnt->P[0], P)) != AZ_OK) return rc;
-    azk_rois_dedup(s, c->B[0], &c->cnt->P[0], c->maxR, scale, (float)dedup, batch_size, c->rois, c->key, c->grp,
-                   c->first, c->index, c->inv, c->urois, c->ubox, &c->cnt->U[0]);
-    launch_det_head(c, &c->cnt->U[0], im_h, im_w, eps, P);
-    azk_det_gather(s, &c->cnt->P[0], c->inv, c->det_ncls, c->dprob_u, c->dpred_u, c->dprob, c->dpred);
-    HIPCHK(c, hipStreamSynchronize(s));
-    HIPCHK(c, hipGetLastError());
-    const size_t nc = (size_t)c->det_ncls;
-    if (scores_out) HIPCHK(c, hipMemcpy(scores_out, c->dprob, (size_t)P * nc * 4, hipMemcpyDeviceToHost));
-    if (boxes_out) HIPCHK(c, hipMemcpy(boxes_out, c->dpred, (size_t)P * nc * 4 * sizeof(double), hipMemcpyDeviceToHost));
-    return AZ_OK;
+    return detect(c, boxes, P, scale, nullptr, dedup, batch_size, im_h, im_w, eps, nullptr, nullptr, scores_out, boxes_out);
 }
 
 // _frcnn_forward over an image pyramid: az_detect with the pyramid projection and RoIPool through the map table (each
@@ -528,23 +545,8 @@ int az_detect_pyramid(az_ctx *c, const double *boxes, int P, const double *scale
     if (c->pyr_S != S)
         return fail(c, AZ_ERR_STATE, "az_detect_pyramid: no pyramid of that many maps set (az_set_feature_pyramid_dev_nhwc)");
     if (P > c->maxR) return fail(c, AZ_ERR_CAPACITY, "az_detect_pyramid: too many boxes");
-    if (P == 0) return AZ_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    if (!(c->profiling & 4)) clear_events(c);
-    HIPCHK(c, hipMemsetAsync(c->cnt, 0, sizeof(AzCounts), s));
-    HIPCHK(c, hipMemcpyAsync(c->B[0], boxes, (size_t)P * 4 * sizeof(double), hipMemcpyHostToDevice, s));
-    if ((rc = set_count(c, &c->cnt->P[0], P)) != AZ_OK) return rc;
-    azk_pyramid_rois_dedup(s, c->B[0], &c->cnt->P[0], c->maxR, sc, (float)dedup, batch_size, c->rois, c->key, c->grp,
-                           c->first, c->index, c->inv, c->urois, c->ubox, &c->cnt->U[0]);
-    launch_det_head(c, &c->cnt->U[0], im_h, im_w, eps, P, c->pyr_feats, c->pyr_hw);
-    azk_det_gather(s, &c->cnt->P[0], c->inv, c->det_ncls, c->dprob_u, c->dpred_u, c->dprob, c->dpred);
-    HIPCHK(c, hipStreamSynchronize(s));
-    HIPCHK(c, hipGetLastError());
-    const size_t nc = (size_t)c->det_ncls;
-    if (scores_out) HIPCHK(c, hipMemcpy(scores_out, c->dprob, (size_t)P * nc * 4, hipMemcpyDeviceToHost));
-    if (boxes_out) HIPCHK(c, hipMemcpy(boxes_out, c->dpred, (size_t)P * nc * 4 * sizeof(double), hipMemcpyDeviceToHost));
-    return AZ_OK;
+    return detect(c, boxes, P, 0.0, &sc, dedup, batch_size, im_h, im_w, eps, c->pyr_feats, c->pyr_hw, scores_out,
+                  boxes_out);
 }
 
 // test_net (lib/detect/test.py:541-668) over saved proposals: _frcnn_forward (:259-318) of n images in one pass per
@@ -608,15 +610,12 @@ int az_detect_batch(az_ctx *c, int n, const float *const *maps, int C, const int
                                  hipMemcpyHostToDevice, s));
         HIPCHK(c, hipMemsetAsync(c->cnt, 0, sizeof(AzCounts), s));
         { Timed t(c, "det_rois_dedup", 0);
-          azk_rois_dedup_seg(s, dB, ds, hs->n, c->maxR, (float)dedup, batch_size, c->rois, c->key, c->grp, c->first,
-                             c->index, c->inv, c->urois, c->ubox, &c->cnt->U[0], c->drow_hw); }
+          azk_rois_dedup(s, dB, ds, hs->n, c->maxR, (float)dedup, batch_size, c->rois, c->key, c->grp, c->first, c->index,
+                         c->inv, c->urois, c->ubox, &c->cnt->U[0], c->drow_hw); }
         launch_det_head(c, &c->cnt->U[0], 1, 1, eps, P, d_feats, d_feat_hw, c->drow_hw);
         azk_det_gather(s, d_off + hs->n, c->inv, c->det_ncls, c->dprob_u, c->dpred_u, c->dprob, c->dpred);
-        HIPCHK(c, hipStreamSynchronize(s));
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpy(scores_out + (size_t)box_off[i0] * nc, c->dprob, (size_t)P * nc * 4, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(boxes_out + (size_t)box_off[i0] * nc * 4, c->dpred, (size_t)P * nc * 4 * sizeof(double),
-                            hipMemcpyDeviceToHost));
+        const int rc = fetch_dets(c, P, scores_out + (size_t)box_off[i0] * nc, boxes_out + (size_t)box_off[i0] * nc * 4);
+        if (rc) return rc;
         i0 = i1;
     }
     return AZ_OK;

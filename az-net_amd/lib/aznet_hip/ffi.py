@@ -213,6 +213,11 @@ def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
+def _scales(scales):
+    """The scales of an image pyramid as the ABI takes them: contiguous f64."""
+    return _f64(np.asarray(scales, dtype=np.float64).reshape(-1))
+
+
 def _p(a, ct):
     return a.ctypes.data_as(ctypes.POINTER(ct))
 
@@ -357,20 +362,25 @@ class AzContext(object):
                         (0 if full_spec is None else ((512 | 1024) if full_spec == "closure" else (512 if full_spec else 256))) |
                         (0 if early_end else 4096))
 
-    def propose(self, params, want_scores=False, want_stats=False):
-        cap = params.num_proposals if params.fixed_num else self.max_candidates
-        boxes = np.empty((cap, 4), dtype=np.float64)
-        scores = np.empty((cap,), dtype=np.float32)
+    def _search_result(self, call, cap, want_scores, want_stats):
+        """One search's result: call(boxes, scores, cap, n, stats) fills the buffers allocated here (ctypes arguments);
+        returns boxes [n,4] f64, with scores [n] f32 and / or the AzStats when asked."""
+        boxes = np.empty((max(cap, 1), 4), dtype=np.float64)
+        scores = np.empty((max(cap, 1),), dtype=np.float32)
         n = ctypes.c_int(0)
         st = AzStats()
-        self._chk(self.L.az_propose(self.h, ctypes.byref(params), _p(boxes, ctypes.c_double),
-                                    _p(scores, ctypes.c_float), cap, ctypes.byref(n), ctypes.byref(st)))
-        out = [boxes[:n.value].copy() if n.value < cap else boxes]
+        self._chk(call(_p(boxes, ctypes.c_double), _p(scores, ctypes.c_float), cap, ctypes.byref(n), ctypes.byref(st)))
+        out = [boxes[:n.value].copy()]
         if want_scores:
             out.append(scores[:n.value].copy())
         if want_stats:
             out.append(st)
         return out[0] if len(out) == 1 else tuple(out)
+
+    def propose(self, params, want_scores=False, want_stats=False):
+        cap = params.num_proposals if params.fixed_num else self.max_candidates
+        return self._search_result(lambda *out: self.L.az_propose(self.h, ctypes.byref(params), *out), cap, want_scores,
+                                   want_stats)
 
     # ---- multi-scale test pyramids (cfg.TEST.SCALES with several entries) --------------------------------------------
     def set_feature_pyramid(self, maps, producer_done=False):
@@ -402,55 +412,25 @@ class AzContext(object):
     def roi_dedup_pyramid(self, boxes, scales, dedup=1. / 16., batch_size=10000):
         """_get_rois_blob over a pyramid + np.unique per batch_size chunk: (rois [P,5] f32 with the level in column 0,
         index [U], inverse [P])."""
-        boxes = _f64(boxes).reshape(-1, 4)
-        sc = _f64(np.asarray(scales, dtype=np.float64).reshape(-1))
-        P = boxes.shape[0]
-        rois = np.empty((max(P, 1), 5), dtype=np.float32)
-        index = np.empty((max(P, 1),), dtype=np.int32)
-        inv = np.empty((max(P, 1),), dtype=np.int32)
-        n = ctypes.c_int(0)
-        self._chk(self.L.az_roi_dedup_pyramid(self.h, _p(boxes, ctypes.c_double), P, _p(sc, ctypes.c_double), sc.size,
-                                              float(dedup), int(batch_size), _p(rois, ctypes.c_float),
-                                              _p(index, ctypes.c_int32), _p(inv, ctypes.c_int32), ctypes.byref(n)))
-        return rois[:P].copy(), index[:n.value].copy(), inv[:P].copy()
+        sc = _scales(scales)
+        return self._roi_dedup(self.L.az_roi_dedup_pyramid, (_p(sc, ctypes.c_double), sc.size), boxes, dedup, batch_size)
 
     def roi_pool_pyramid(self, rois):
-        rois = _f32(rois).reshape(-1, 5)
-        R = rois.shape[0]
-        out = np.empty((max(R, 1), self.dims["K6"]), dtype=np.float32)
-        self._chk(self.L.az_roi_pool_pyramid(self.h, _p(rois, ctypes.c_float), R, _p(out, ctypes.c_float)))
-        return out[:R]
+        return self._roi_pool(self.L.az_roi_pool_pyramid, rois)
 
     def propose_pyramid(self, params, scales, want_scores=False, want_stats=False):
         """propose() over the pyramid set (az_propose_pyramid: the plain level loop); params.scale is ignored."""
-        sc = _f64(np.asarray(scales, dtype=np.float64).reshape(-1))
+        sc = _scales(scales)
         cap = params.num_proposals if params.fixed_num else self.max_candidates
-        boxes = np.empty((max(cap, 1), 4), dtype=np.float64)
-        scores = np.empty((max(cap, 1),), dtype=np.float32)
-        n = ctypes.c_int(0)
-        st = AzStats()
-        self._chk(self.L.az_propose_pyramid(self.h, ctypes.byref(params), _p(sc, ctypes.c_double), sc.size,
-                                            _p(boxes, ctypes.c_double), _p(scores, ctypes.c_float), cap,
-                                            ctypes.byref(n), ctypes.byref(st)))
-        out = [boxes[:n.value].copy()]
-        if want_scores:
-            out.append(scores[:n.value].copy())
-        if want_stats:
-            out.append(st)
-        return out[0] if len(out) == 1 else tuple(out)
+        return self._search_result(
+            lambda *out: self.L.az_propose_pyramid(self.h, ctypes.byref(params), _p(sc, ctypes.c_double), sc.size, *out),
+            cap, want_scores, want_stats)
 
     def detect_pyramid(self, boxes, scales, im_h, im_w, dedup=1. / 16., batch_size=10000, eps=1e-14):
         """detect() over the pyramid set (az_detect_pyramid)."""
-        boxes = _f64(boxes).reshape(-1, 4)
-        sc = _f64(np.asarray(scales, dtype=np.float64).reshape(-1))
-        P = boxes.shape[0]
-        nc = self.det_dims["ncls"]
-        s = np.empty((max(P, 1), nc), dtype=np.float32)
-        b = np.empty((max(P, 1), 4 * nc), dtype=np.float64)
-        self._chk(self.L.az_detect_pyramid(self.h, _p(boxes, ctypes.c_double), P, _p(sc, ctypes.c_double), sc.size,
-                                           float(dedup), int(batch_size), int(im_h), int(im_w), float(eps),
-                                           _p(s, ctypes.c_float), _p(b, ctypes.c_double)))
-        return s[:P], b[:P]
+        sc = _scales(scales)
+        return self._detect(self.L.az_detect_pyramid, (_p(sc, ctypes.c_double), sc.size), boxes, im_h, im_w, dedup,
+                            batch_size, eps)
 
     def _ext(self, handle):
         """torch view of one of the context's HIP streams (by raw handle)."""
@@ -637,39 +617,17 @@ class AzContext(object):
         if not getattr(self, "_batches", None):
             raise AzError(-4, "batch_fetch without batch_launch")
         params, maps = self._batches[0]
-        cap = params.num_proposals
-        boxes = np.empty((cap, 4), dtype=np.float64)
-        scores = np.empty((cap,), dtype=np.float32)
-        n = ctypes.c_int(0)
-        st = AzStats()
         try:
-            self._chk(self.L.az_batch_fetch(self.h, int(i), _p(boxes, ctypes.c_double), _p(scores, ctypes.c_float),
-                                            cap, ctypes.byref(n), ctypes.byref(st)))
+            return self._search_result(lambda *out: self.L.az_batch_fetch(self.h, int(i), *out), params.num_proposals,
+                                       want_scores, want_stats)
         finally:
             if i == len(maps) - 1:
                 self._batches.popleft()
-        out = [boxes[:n.value].copy()]
-        if want_scores:
-            out.append(scores[:n.value].copy())
-        if want_stats:
-            out.append(st)
-        return out[0] if len(out) == 1 else tuple(out)
 
     def propose_fetch(self, want_scores=False, want_stats=False):
         params = self._queued.pop(0) if getattr(self, "_queued", None) else self._last_params
         cap = params.num_proposals if params.fixed_num else self.max_candidates
-        boxes = np.empty((cap, 4), dtype=np.float64)
-        scores = np.empty((cap,), dtype=np.float32)
-        n = ctypes.c_int(0)
-        st = AzStats()
-        self._chk(self.L.az_propose_fetch(self.h, _p(boxes, ctypes.c_double), _p(scores, ctypes.c_float),
-                                          cap, ctypes.byref(n), ctypes.byref(st)))
-        out = [boxes[:n.value].copy()]
-        if want_scores:
-            out.append(scores[:n.value].copy())
-        if want_stats:
-            out.append(st)
-        return out[0] if len(out) == 1 else tuple(out)
+        return self._search_result(lambda *out: self.L.az_propose_fetch(self.h, *out), cap, want_scores, want_stats)
 
     @staticmethod
     def result_record_layout(num_proposals):
@@ -749,22 +707,28 @@ class AzContext(object):
         return out[:n.value].copy()
 
     def roi_dedup(self, boxes, scale, dedup=1. / 16., batch_size=10000):
+        return self._roi_dedup(self.L.az_roi_dedup, (float(scale),), boxes, dedup, batch_size)
+
+    def _roi_dedup(self, fn, proj, boxes, dedup, batch_size):
+        """az_roi_dedup / az_roi_dedup_pyramid (fn), proj: the arguments that name the scale or the pyramid."""
         boxes = _f64(boxes).reshape(-1, 4)
         P = boxes.shape[0]
         rois = np.empty((max(P, 1), 5), dtype=np.float32)
         index = np.empty((max(P, 1),), dtype=np.int32)
         inv = np.empty((max(P, 1),), dtype=np.int32)
         n = ctypes.c_int(0)
-        self._chk(self.L.az_roi_dedup(self.h, _p(boxes, ctypes.c_double), P, float(scale), float(dedup),
-                                      int(batch_size), _p(rois, ctypes.c_float), _p(index, ctypes.c_int32),
-                                      _p(inv, ctypes.c_int32), ctypes.byref(n)))
+        self._chk(fn(self.h, _p(boxes, ctypes.c_double), P, *proj, float(dedup), int(batch_size), _p(rois, ctypes.c_float),
+                     _p(index, ctypes.c_int32), _p(inv, ctypes.c_int32), ctypes.byref(n)))
         return rois[:P].copy(), index[:n.value].copy(), inv[:P].copy()
 
     def roi_pool(self, rois):
+        return self._roi_pool(self.L.az_roi_pool, rois)
+
+    def _roi_pool(self, fn, rois):
         rois = _f32(rois).reshape(-1, 5)
         R = rois.shape[0]
         out = np.empty((max(R, 1), self.dims["K6"]), dtype=np.float32)
-        self._chk(self.L.az_roi_pool(self.h, _p(rois, ctypes.c_float), R, _p(out, ctypes.c_float)))
+        self._chk(fn(self.h, _p(rois, ctypes.c_float), R, _p(out, ctypes.c_float)))
         return out[:R]
 
     def head_forward(self, rois):
@@ -850,14 +814,17 @@ class AzContext(object):
         return p[:R], b[:R]
 
     def detect(self, boxes, scale, im_h, im_w, dedup=1. / 16., batch_size=10000, eps=1e-14):
+        return self._detect(self.L.az_detect, (float(scale),), boxes, im_h, im_w, dedup, batch_size, eps)
+
+    def _detect(self, fn, proj, boxes, im_h, im_w, dedup, batch_size, eps):
+        """az_detect / az_detect_pyramid (fn), proj: the arguments that name the scale or the pyramid."""
         boxes = _f64(boxes).reshape(-1, 4)
         P = boxes.shape[0]
         nc = self.det_dims["ncls"]
         s = np.empty((max(P, 1), nc), dtype=np.float32)
         b = np.empty((max(P, 1), 4 * nc), dtype=np.float64)
-        self._chk(self.L.az_detect(self.h, _p(boxes, ctypes.c_double), P, float(scale), float(dedup),
-                                   int(batch_size), int(im_h), int(im_w), float(eps), _p(s, ctypes.c_float),
-                                   _p(b, ctypes.c_double)))
+        self._chk(fn(self.h, _p(boxes, ctypes.c_double), P, *proj, float(dedup), int(batch_size), int(im_h), int(im_w),
+                     float(eps), _p(s, ctypes.c_float), _p(b, ctypes.c_double)))
         return s[:P], b[:P]
 
     def detect_batch(self, maps, boxes_list, scales, im_shapes, dedup=1. / 16., batch_size=10000, eps=1e-14):

@@ -54,7 +54,26 @@ class _Blob(object):
         self.shape = tuple(shape)
 
 
-class HipAZNet(object):
+class _NetDict(object):
+    """The reference's test loops take a dict of caffe.Nets ({'full': ..., 'fc': ...}); a net answers net[k], k in net and
+    net.keys() with itself for each name in NAMES."""
+    NAMES = ()
+
+    def __getitem__(self, k):
+        if k in self.NAMES:
+            return self
+        raise KeyError(k)
+
+    def keys(self):
+        return list(self.NAMES)
+
+    def __contains__(self, k):
+        return k in self.NAMES
+
+
+class HipAZNet(_NetDict):
+    NAMES = ("full", "fc")
+
     def __init__(self, head, backbone=None, device=0, name="vgg16_az_net_hip", ctx=None,
                  max_regions=None, gemm_mode=None):
         self.ctx = ctx or ffi.AzContext(device, max_regions=max_regions, gemm_mode=gemm_mode)
@@ -65,18 +84,6 @@ class HipAZNet(object):
         self.name = name
         self.blobs = {k: _Blob() for k in ("data", "rois", "conv5_3")}
         self._conv = None          # what the last forward/set_image left in HBM
-
-    # dict-of-two compatibility: net['full'] / net['fc'] / 'fc' in net.keys()
-    def __getitem__(self, k):
-        if k in ("full", "fc"):
-            return self
-        raise KeyError(k)
-
-    def keys(self):
-        return ["full", "fc"]
-
-    def __contains__(self, k):
-        return k in ("full", "fc")
 
     # ---- feature map -----------------------------------------------------------------
     def set_conv(self, conv, wait=True):
@@ -169,11 +176,12 @@ class HipAZNet(object):
         return out
 
 
-class HipDetNet(object):
+class HipDetNet(_NetDict):
     """Fast R-CNN detection net on the shared conv map: stands where the reference's
     `frcnn_nets = {'fc': caffe.Net(frcnn/test_fc.prototxt, ...)}` stood (tools/test_shared.py).
     It shares the AZ net's az_ctx, so both heads read the same channel-last map in HBM.
     Also pycaffe-shaped (`forward(rois=, conv5_3=)` -> cls_prob, bbox_pred; test.py:302-307)."""
+    NAMES = ("fc",)
 
     def __init__(self, det_head, az_net, name="vgg16_frcnn_hip"):
         self.ctx = az_net.ctx
@@ -182,17 +190,6 @@ class HipDetNet(object):
         self.num_classes = self.ctx.det_dims["ncls"]
         self.name = name
         self.blobs = {k: _Blob() for k in ("data", "rois", "conv5_3")}
-
-    def __getitem__(self, k):
-        if k == "fc":
-            return self
-        raise KeyError(k)
-
-    def keys(self):
-        return ["fc"]
-
-    def __contains__(self, k):
-        return k == "fc"
 
     def detect(self, boxes, scale, im_shape, dedup, batch_size, eps):
         return self.ctx.detect(boxes, scale, im_shape[0], im_shape[1], dedup=dedup, batch_size=batch_size, eps=eps)
@@ -210,13 +207,14 @@ class HipDetNet(object):
         return {"cls_prob": p, "bbox_pred": b}
 
 
-class HipFrcnnNet(object):
+class HipFrcnnNet(_NetDict):
     """Fast R-CNN detection net with its OWN conv layers, for detection over saved proposals: stands where the
     reference's `nets = {'full': caffe.Net(frcnn/test.prototxt, caffemodel)}` stood (tools/test_det_net.py, used by
     test_net, lib/detect/test.py:541-668).  It owns an az_ctx with only the detection head loaded (fp32) and a backbone:
     any callable that maps the [1,3,H,W] data blob (a CUDA tensor) to conv5_3 -- normally a VGG16Conv5 with the
     detection net's conv weights (caffemodel.backbone_from_layers).
     `detect` / `detect_batch` run az_detect_batch."""
+    NAMES = ("full",)
 
     def __init__(self, det_head, backbone, device=0, name="vgg16_frcnn_hip", max_regions=None):
         self.ctx = ffi.AzContext(device, max_regions=max_regions, gemm_mode=0)
@@ -228,17 +226,6 @@ class HipFrcnnNet(object):
         self.num_classes = self.ctx.det_dims["ncls"]
         self.name = name
         self.blobs = {k: _Blob() for k in ("data", "rois", "conv5_3")}
-
-    def __getitem__(self, k):
-        if k == "full":
-            return self
-        raise KeyError(k)
-
-    def keys(self):
-        return ["full"]
-
-    def __contains__(self, k):
-        return k == "full"
 
     def _torch_device(self):
         import torch

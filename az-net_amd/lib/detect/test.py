@@ -109,6 +109,21 @@ def _append_boxes(boxes):
     return div._sift_dup(subs, 1 / cfg.DEDUP_BOXES)
 
 
+def _append_clipped(Y, im_shape):
+    """cfg.SEAR.APPEND_BOXES (test.py:408-413): the appended boxes, clipped to the image."""
+    if cfg.SEAR.APPEND_BOXES:
+        Y = _append_boxes(Y)
+        Y[:, 0::4] = np.maximum(Y[:, 0::4], 0)
+        Y[:, 1::4] = np.maximum(Y[:, 1::4], 0)
+        Y[:, 2::4] = np.minimum(Y[:, 2::4], im_shape[1] - 1)
+        Y[:, 3::4] = np.minimum(Y[:, 3::4], im_shape[0] - 1)
+    return Y
+
+
+def _proposal_line(Y, st):
+    return '{0} proposals, evaluate {1} regions, reaches depth {2}.'.format(Y.shape[0], st.num_eval, st.depth)
+
+
 def im_propose(net, im, return_conv=False, num_proposals=None, conv=None, stage=None):
     """Generate object proposals with AZ-Net (test.py:346-414).
 
@@ -122,27 +137,17 @@ def im_propose(net, im, return_conv=False, num_proposals=None, conv=None, stage=
     scales = _im_scale(im.shape)
     if len(scales) > 1:
         Y, st, conv = _pyramid_search(hnet, im, scales, num_proposals, conv, stage)
-        print('{0} proposals, evaluate {1} regions, reaches depth {2}.'
-              .format(Y.shape[0], st.num_eval, st.depth))
-        if return_conv:
-            return Y, conv
-        return Y
-    if conv is None:
-        blob, _ = _get_image_blob(im, hnet)
-        conv_t = hnet.compute_conv(blob)
-        conv = {name: conv_t for name in cfg.SEAR.FRCNN_CONV}
     else:
-        hnet.set_conv(conv[cfg.SEAR.AZ_CONV[0]])
-    params = _params(im.shape, scales[0], num_proposals)
-    Y, st = hnet.propose(params, want_stats=True, stage=stage)
-    if cfg.SEAR.APPEND_BOXES:
-        Y = _append_boxes(Y)
-        Y[:, 0::4] = np.maximum(Y[:, 0::4], 0)
-        Y[:, 1::4] = np.maximum(Y[:, 1::4], 0)
-        Y[:, 2::4] = np.minimum(Y[:, 2::4], im.shape[1] - 1)
-        Y[:, 3::4] = np.minimum(Y[:, 3::4], im.shape[0] - 1)
-    print('{0} proposals, evaluate {1} regions, reaches depth {2}.'
-          .format(Y.shape[0], st.num_eval, st.depth))
+        if conv is None:
+            blob, _ = _get_image_blob(im, hnet)
+            conv_t = hnet.compute_conv(blob)
+            conv = {name: conv_t for name in cfg.SEAR.FRCNN_CONV}
+        else:
+            hnet.set_conv(conv[cfg.SEAR.AZ_CONV[0]])
+        params = _params(im.shape, scales[0], num_proposals)
+        Y, st = hnet.propose(params, want_stats=True, stage=stage)
+    Y = _append_clipped(Y, im.shape)
+    print(_proposal_line(Y, st))
     if return_conv:
         return Y, conv
     return Y
@@ -152,7 +157,7 @@ def _pyramid_search(hnet, im, scales, num_proposals=None, conv=None, stage=None)
     """im_propose over an image pyramid (several cfg.TEST.SCALES; test.py:27-97): the padded blob's S conv5_3 maps (or
     the cached ones in `conv`), then one az_propose_pyramid call -- the plain level loop, each level's regions projected
     to the pyramid level whose scaled area is closest to 224 x 224.  Synchronous.  Returns (Y, stats, conv dict); Y is
-    what im_propose returns (APPEND_BOXES applied)."""
+    the search's boxes (before APPEND_BOXES)."""
     if stage is not None:
         raise NotImplementedError("multi-GPU result staging of a pyramid search (cfg.TEST.SCALES with several entries): "
                                   "run one GPU per process without staging")
@@ -163,12 +168,6 @@ def _pyramid_search(hnet, im, scales, num_proposals=None, conv=None, stage=None)
         hnet.set_pyramid(conv[cfg.SEAR.AZ_CONV[0]])
     params = _params(im.shape, scales[0], num_proposals)
     Y, st = hnet.propose_pyramid(params, scales, want_stats=True)
-    if cfg.SEAR.APPEND_BOXES:
-        Y = _append_boxes(Y)
-        Y[:, 0::4] = np.maximum(Y[:, 0::4], 0)
-        Y[:, 1::4] = np.maximum(Y[:, 1::4], 0)
-        Y[:, 2::4] = np.minimum(Y[:, 2::4], im.shape[1] - 1)
-        Y[:, 3::4] = np.minimum(Y[:, 3::4], im.shape[0] - 1)
     return Y, st, conv
 
 
@@ -211,25 +210,16 @@ def _propose_start(net, im, num_proposals=None, after=None, stage=None):
 
 def _propose_finish(net, h, return_conv=False):
     """Second half of im_propose: wait for the search launched by _propose_start, format as im_propose does."""
-    hnet = net["full"] if isinstance(net, dict) else net
     if "pyramid" in h:
         Y, st = h["pyramid"]
-        print('{0} proposals, evaluate {1} regions, reaches depth {2}.'
-              .format(Y.shape[0], st.num_eval, st.depth))
-        return (Y, h["conv"]) if return_conv else Y
-    Y, st = hnet.ctx.propose_fetch(want_stats=True)
-    shape = h["shape"]
-    if cfg.SEAR.APPEND_BOXES:
-        Y = _append_boxes(Y)
-        Y[:, 0::4] = np.maximum(Y[:, 0::4], 0)
-        Y[:, 1::4] = np.maximum(Y[:, 1::4], 0)
-        Y[:, 2::4] = np.minimum(Y[:, 2::4], shape[1] - 1)
-        Y[:, 3::4] = np.minimum(Y[:, 3::4], shape[0] - 1)
-    print('{0} proposals, evaluate {1} regions, reaches depth {2}.'
-          .format(Y.shape[0], st.num_eval, st.depth))
-    if return_conv:
-        return Y, {name: h["conv"] for name in cfg.SEAR.FRCNN_CONV}
-    return Y
+        conv = h["conv"]
+    else:
+        hnet = net["full"] if isinstance(net, dict) else net
+        Y, st = hnet.ctx.propose_fetch(want_stats=True)
+        conv = {name: h["conv"] for name in cfg.SEAR.FRCNN_CONV}
+    Y = _append_clipped(Y, h["shape"])
+    print(_proposal_line(Y, st))
+    return (Y, conv) if return_conv else Y
 
 
 def _batch_backbones(net, ims, after=None):
@@ -275,14 +265,8 @@ def _batch_finish(net, h, i, quiet=False):
     if "results" not in h:
         h["results"] = hnet.ctx.batch_fetch_all(want_stats=True)      # (the whole batch in one call)
     Y, st = h["results"][i]
-    shape = h["shapes"][i]
-    if cfg.SEAR.APPEND_BOXES:
-        Y = _append_boxes(Y)
-        Y[:, 0::4] = np.maximum(Y[:, 0::4], 0)
-        Y[:, 1::4] = np.maximum(Y[:, 1::4], 0)
-        Y[:, 2::4] = np.minimum(Y[:, 2::4], shape[1] - 1)
-        Y[:, 3::4] = np.minimum(Y[:, 3::4], shape[0] - 1)
-    line = '{0} proposals, evaluate {1} regions, reaches depth {2}.'.format(Y.shape[0], st.num_eval, st.depth)
+    Y = _append_clipped(Y, h["shapes"][i])
+    line = _proposal_line(Y, st)
     if quiet:
         return Y, line
     print(line)
@@ -420,42 +404,33 @@ def _frcnn_forward(net, im, all_boxes, num_classes, conv=None):
     every class, un-dedup).  Returns scores [R, K] and boxes [R, 4K] as float64, and conv.
     A full net (a HipFrcnnNet, no 'fc' key: test.py:291) runs its own backbone on the image first, then the head
     (az_detect_batch of one image; more proposals than the region capacity go in pieces of whole dedup chunks)."""
+    boxes = np.ascontiguousarray(all_boxes[:, 0:4], dtype=np.float64)
+    scales = _im_scale(im.shape)
+    pyramid = len(scales) > 1
+    args = (cfg.DEDUP_BOXES, cfg.SEAR.BATCH_SIZE, cfg.EPS)
     if _is_full_net(net):
         fnet = net["full"]
-        scale = _im_scale(im.shape)
-        if len(scale) > 1:
-            # an image pyramid: its padded maps, each roi pooled from the level its scaled area is closest to 224^2 at
-            maps = fnet.compute_pyramid(_as_uint8(im), cfg.PIXEL_MEANS, scale)
-            assert num_classes == fnet.num_classes
-            scores, boxes = fnet.detect_pyramid(None, np.ascontiguousarray(all_boxes[:, 0:4], dtype=np.float64), scale,
-                                                im.shape, cfg.DEDUP_BOXES, cfg.SEAR.BATCH_SIZE, cfg.EPS)
-            return scores.astype(np.float64), boxes, {name: maps for name in cfg.SEAR.FRCNN_CONV}
-        conv_t = fnet.compute_conv(fnet.image_blob_enqueue(_as_uint8(im), cfg.PIXEL_MEANS, scale[0]))
         assert num_classes == fnet.num_classes
-        scores, boxes = fnet.detect(conv_t, np.ascontiguousarray(all_boxes[:, 0:4], dtype=np.float64), scale[0],
-                                    im.shape, cfg.DEDUP_BOXES, cfg.SEAR.BATCH_SIZE, cfg.EPS)
-        return scores.astype(np.float64), boxes, {name: conv_t for name in cfg.SEAR.FRCNN_CONV}
+        if pyramid:
+            # an image pyramid: its padded maps, each roi pooled from the level its scaled area is closest to 224^2 at
+            maps = fnet.compute_pyramid(_as_uint8(im), cfg.PIXEL_MEANS, scales)
+            scores, pred = fnet.detect_pyramid(None, boxes, scales, im.shape, *args)
+        else:
+            maps = fnet.compute_conv(fnet.image_blob_enqueue(_as_uint8(im), cfg.PIXEL_MEANS, scales[0]))
+            scores, pred = fnet.detect(maps, boxes, scales[0], im.shape, *args)
+        return scores.astype(np.float64), pred, {name: maps for name in cfg.SEAR.FRCNN_CONV}
+    # shared detection on the map (or pyramid) the AZ search left in the context, or the cached one in `conv`
     dnet = net["fc"] if isinstance(net, dict) else net
-    scales = _im_scale(im.shape)
-    if len(scales) > 1:
-        # shared detection on the pyramid the AZ search left in the context (or the cached one in `conv`)
-        if conv is not None:
-            c = conv[cfg.SEAR.FRCNN_CONV[0]]
-            if c is not dnet.az_net._conv:
-                dnet.az_net.set_pyramid(c)
-        assert num_classes == dnet.num_classes
-        scores, boxes = dnet.detect_pyramid(np.ascontiguousarray(all_boxes[:, 0:4], dtype=np.float64), scales, im.shape,
-                                            cfg.DEDUP_BOXES, cfg.SEAR.BATCH_SIZE, cfg.EPS)
-        return scores.astype(np.float64), boxes, conv
+    assert num_classes == dnet.num_classes
     if conv is not None:
         c = conv[cfg.SEAR.FRCNN_CONV[0]]
         if c is not dnet.az_net._conv:
-            dnet.az_net.set_conv(c)
-    scale = _im_scale(im.shape)[0]
-    assert num_classes == dnet.num_classes
-    scores, boxes = dnet.detect(np.ascontiguousarray(all_boxes[:, 0:4], dtype=np.float64), scale, im.shape,
-                                cfg.DEDUP_BOXES, cfg.SEAR.BATCH_SIZE, cfg.EPS)
-    return scores.astype(np.float64), boxes, conv
+            (dnet.az_net.set_pyramid if pyramid else dnet.az_net.set_conv)(c)
+    if pyramid:
+        scores, pred = dnet.detect_pyramid(boxes, scales, im.shape, *args)
+    else:
+        scores, pred = dnet.detect(boxes, scales[0], im.shape, *args)
+    return scores.astype(np.float64), pred, conv
 
 
 def im_detect(net, im, boxes, num_classes):
@@ -559,19 +534,65 @@ def test_proposals(net, imdb):
     return prop_file
 
 
+class _Detections(object):
+    """The per-class bookkeeping of test_net_shared / test_net (test.py:676-737, 562-647): per class, an image's scores
+    above an adaptive threshold, at most 100 per image and `800 / (K-1)` per image on average over the set (a min-heap of
+    the kept scores); at the end the set's final thresholds, detections.pkl, NMS (cfg.TEST.NMS) and
+    imdb.evaluate_detections when the imdb has one."""
+
+    def __init__(self, num_classes, num_images):
+        self.num_classes = num_classes
+        self.max_per_set = 800 // (num_classes - 1) * num_images       # Python-2 integer division
+        self.max_per_image = 100
+        self.thresh = -np.inf * np.ones(num_classes)
+        self.top_scores = [[] for _ in range(num_classes)]
+        self.all_boxes = [[[] for _ in range(num_images)] for _ in range(num_classes)]
+
+    def add(self, i, scores, boxes):
+        import heapq
+        for j in range(1, self.num_classes):
+            inds = np.where((scores[:, j] > self.thresh[j]))[0]
+            cls_scores = scores[inds, j]
+            cls_boxes = boxes[inds, j * 4:(j + 1) * 4]
+            top_inds = np.argsort(-cls_scores)[:self.max_per_image]
+            cls_scores = cls_scores[top_inds]
+            cls_boxes = cls_boxes[top_inds, :]
+            top = self.top_scores[j]
+            for val in cls_scores:
+                heapq.heappush(top, val)
+            if len(top) > self.max_per_set:
+                while len(top) > self.max_per_set:
+                    heapq.heappop(top)
+                self.thresh[j] = top[0]
+            self.all_boxes[j][i] = np.hstack((cls_boxes, cls_scores[:, np.newaxis])).astype(np.float32, copy=False)
+
+    def finish(self, images, imdb, output_dir):
+        """The final thresholds over `images` (the indices with detections), detections.pkl, NMS and the evaluation:
+        returns the detections after NMS."""
+        all_boxes = self.all_boxes
+        for j in range(1, self.num_classes):
+            for i in images:
+                inds = np.where(all_boxes[j][i][:, -1] > self.thresh[j])[0]
+                all_boxes[j][i] = all_boxes[j][i][inds, :]
+        det_file = os.path.join(output_dir, 'detections.pkl')
+        with open(det_file, 'wb') as f:
+            pickle.dump(all_boxes, f, pickle.HIGHEST_PROTOCOL)
+        print('Applying NMS to all detections')
+        nms_dets = apply_nms(all_boxes, cfg.TEST.NMS)
+        if hasattr(imdb, "evaluate_detections"):
+            print('Evaluating detections')
+            imdb.evaluate_detections(nms_dets, output_dir)
+        return nms_dets
+
+
 def test_net_shared(sc_net, frcnn_net, imdb):
     """Detection over an imdb with shared conv layers (test.py:670-778): per class keep scores
     above an adaptive threshold, at most 100 per image and `800 / (K-1)` per image on average
     over the set (min-heap), write detections.pkl, apply NMS (cfg.TEST.NMS) and hand the result to
     imdb.evaluate_detections when the imdb has one."""
-    import heapq
     num_images = len(imdb.image_index)
     num_classes = imdb.num_classes
-    max_per_set = 800 // (num_classes - 1) * num_images          # Python-2 integer division (test.py:676)
-    max_per_image = 100
-    thresh = -np.inf * np.ones(num_classes)
-    top_scores = [[] for _ in range(num_classes)]
-    all_boxes = [[[] for _ in range(num_images)] for _ in range(num_classes)]
+    dets = _Detections(num_classes, num_images)
     num_boxes = 0.0
     hnet = sc_net["full"] if isinstance(sc_net, dict) else sc_net
     output_dir = get_output_dir(imdb, hnet)
@@ -616,35 +637,11 @@ def test_net_shared(sc_net, frcnn_net, imdb):
         num_boxes += scores.shape[0]
         _t['im_detect'].toc()
         _t['misc'].tic()
-        for j in range(1, num_classes):
-            inds = np.where((scores[:, j] > thresh[j]))[0]
-            cls_scores = scores[inds, j]
-            cls_boxes = boxes[inds, j * 4:(j + 1) * 4]
-            top_inds = np.argsort(-cls_scores)[:max_per_image]
-            cls_scores = cls_scores[top_inds]
-            cls_boxes = cls_boxes[top_inds, :]
-            for val in cls_scores:
-                heapq.heappush(top_scores[j], val)
-            if len(top_scores[j]) > max_per_set:
-                while len(top_scores[j]) > max_per_set:
-                    heapq.heappop(top_scores[j])
-                thresh[j] = top_scores[j][0]
-            all_boxes[j][i] = np.hstack((cls_boxes, cls_scores[:, np.newaxis])).astype(np.float32, copy=False)
+        dets.add(i, scores, boxes)
         _t['misc'].toc()
         print('im_detect: {:d}/{:d} {:.3f}s {:.3f}s'.format(i + 1, num_images, _t['im_detect'].average_time,
                                                           _t['misc'].average_time))
-    for j in range(1, num_classes):
-        for i in range(num_images):
-            inds = np.where(all_boxes[j][i][:, -1] > thresh[j])[0]
-            all_boxes[j][i] = all_boxes[j][i][inds, :]
-    det_file = os.path.join(output_dir, 'detections.pkl')
-    with open(det_file, 'wb') as f:
-        pickle.dump(all_boxes, f, pickle.HIGHEST_PROTOCOL)
-    print('Applying NMS to all detections')
-    nms_dets = apply_nms(all_boxes, cfg.TEST.NMS)
-    if hasattr(imdb, "evaluate_detections"):
-        print('Evaluating detections')
-        imdb.evaluate_detections(nms_dets, output_dir)
+    nms_dets = dets.finish(range(num_images), imdb, output_dir)
     print('The average detection time is {:.3f}s'.format(_t['im_detect'].average_time))
     print('On average, {0} boxes per image are proposed'.format(num_boxes / num_images))
     return nms_dets
@@ -676,17 +673,12 @@ def test_net(net, prop_file, imdb):
     NMS (cfg.TEST.NMS) and imdb.evaluate_detections when the imdb has one.
     cfg.TEST.BATCH_IMAGES > 1 (an extension): up to that many consecutive images with proposals go through one
     az_detect_batch; same detections, same printed lines in the same order."""
-    import heapq
     with open(prop_file, 'rb') as f:
         prop = pickle.load(f)
     prop_boxes = prop['boxes']
     num_images = len(imdb.image_index)
     num_classes = imdb.num_classes
-    max_per_set = 800 // (num_classes - 1) * num_images          # Python-2 integer division (test.py:562)
-    max_per_image = 100
-    thresh = -np.inf * np.ones(num_classes)
-    top_scores = [[] for _ in range(num_classes)]
-    all_boxes = [[[] for _ in range(num_images)] for _ in range(num_classes)]
+    dets = _Detections(num_classes, num_images)
     num_boxes = 0.0
     fnet = net["full"]
     output_dir = get_output_dir(imdb, fnet)
@@ -715,34 +707,10 @@ def test_net(net, prop_file, imdb):
             scores, boxes = results[k]
             num_boxes += scores.shape[0]
             _t['misc'].tic()
-            for j in range(1, num_classes):
-                inds = np.where((scores[:, j] > thresh[j]))[0]
-                cls_scores = scores[inds, j]
-                cls_boxes = boxes[inds, j * 4:(j + 1) * 4]
-                top_inds = np.argsort(-cls_scores)[:max_per_image]
-                cls_scores = cls_scores[top_inds]
-                cls_boxes = cls_boxes[top_inds, :]
-                for val in cls_scores:
-                    heapq.heappush(top_scores[j], val)
-                if len(top_scores[j]) > max_per_set:
-                    while len(top_scores[j]) > max_per_set:
-                        heapq.heappop(top_scores[j])
-                    thresh[j] = top_scores[j][0]
-                all_boxes[j][i] = np.hstack((cls_boxes, cls_scores[:, np.newaxis])).astype(np.float32, copy=False)
+            dets.add(i, scores, boxes)
             _t['misc'].toc()
             print('im_detect: {:d}/{:d} {:.3f}s {:.3f}s'.format(i + 1, num_images, det_avg[k], _t['misc'].average_time))
-    for j in range(1, num_classes):
-        for i in todo:
-            inds = np.where(all_boxes[j][i][:, -1] > thresh[j])[0]
-            all_boxes[j][i] = all_boxes[j][i][inds, :]
-    det_file = os.path.join(output_dir, 'detections.pkl')
-    with open(det_file, 'wb') as f:
-        pickle.dump(all_boxes, f, pickle.HIGHEST_PROTOCOL)
-    print('Applying NMS to all detections')
-    nms_dets = apply_nms(all_boxes, cfg.TEST.NMS)
-    if hasattr(imdb, "evaluate_detections"):
-        print('Evaluating detections')
-        imdb.evaluate_detections(nms_dets, output_dir)
+    nms_dets = dets.finish(todo, imdb, output_dir)
     print('The average time is proposal {:.3f}s, detection {:.3f}s'.format(prop['time'], _t['im_detect'].average_time))
     print('On average, {0} boxes per image are generated'.format(num_boxes / num_images))
     return nms_dets

@@ -2,8 +2,8 @@
 """Multi-scale test pyramids, timed (development tool): a 500x375 image through the full-size synthetic VGG16 and heads
 at SCALES = (480, 576, 688, 864, 1200), MAX_SIZE = 2000 (S = 5) and at (600,), MAX_SIZE = 1000 (S = 1), Tz = 0.5:
   front-end + backbone ms (HipAZNet.compute_pyramid: the padded blob and one backbone pass per level),
-  search ms (az_propose_pyramid) and head rows per level, projection + dedup us per level (k_pyramid_rois +
-  k_dedup_rois, device events), az_detect_pyramid ms at 300 proposals; medians of `reps` runs.
+  search ms (az_propose_pyramid) and head rows per level, projection + dedup us per level (k_first_rois with the
+  pyramid projection + k_dedup_rois, device events), az_detect_pyramid ms at 300 proposals; medians of `reps` runs.
 Usage: perf_pyramid.py [reps]"""
 import os
 import sys
