@@ -962,4 +962,184 @@ int az_last_kernel_times(az_ctx *c, char *names_out, float *ms_out, int32_t *lev
     return AZ_OK;
 }
 
+// --------------------------------------------------------------------------------------
+// Training data layer (lib/az_data_layer/roidb.py; kernels in az_train.hip).
+static_assert(sizeof(az_train_params) == 6 * 8 + 4 * 4 + 2 * AZ_TRAIN_MAX_REGIONS * 4 * 8, "az_train_params layout (ffi.AzTrainParams restates it)");
+
+static int train_params_ok(const az_train_params *p)
+{
+    return p && p->n_addregions >= 1 && p->n_addregions <= AZ_TRAIN_MAX_REGIONS && p->n_subregion >= 1 &&
+           p->n_subregion <= AZ_TRAIN_MAX_REGIONS && p->min_side > 0.0 && p->train_rep >= 0;
+}
+
+// a device arena in scratch slot `slot`: add() hands out 256-byte-aligned pieces, take() allocates
+struct TrainArena {
+    size_t total = 0;
+    size_t add(size_t bytes) { const size_t at = total; total += (bytes + 255) & ~(size_t)255; return at; }
+};
+
+int az_zoom_labels(az_ctx *c, const double *rois, int R, const double *gt, int N, double max_area_ratio, double min_obj,
+                   uint8_t *labels_out)
+{
+    if (!c || R < 0 || N < 0 || (R && (!rois || !labels_out)) || (N && !gt))
+        return fail(c, AZ_ERR_INVALID, "az_zoom_labels: bad arguments");
+    if (R == 0) return AZ_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    TrainArena ar;
+    const size_t o_r = ar.add((size_t)R * 32), o_g = ar.add((size_t)N * 32 + 32), o_l = ar.add((size_t)R);
+    int rc;
+    if ((rc = ev_grow(c, 0, &c->ev_a, ar.total)) != AZ_OK) return rc;
+    char *base = (char *)c->ev_a;
+    hipStream_t s = c->stream;
+    HIPCHK(c, hipMemcpyAsync(base + o_r, rois, (size_t)R * 32, hipMemcpyHostToDevice, s));
+    if (N) HIPCHK(c, hipMemcpyAsync(base + o_g, gt, (size_t)N * 32, hipMemcpyHostToDevice, s));
+    azk_zoom_labels(s, (const double *)(base + o_r), R, (const double *)(base + o_g), N, max_area_ratio, min_obj,
+                    (unsigned char *)(base + o_l));
+    HIPCHK(c, hipMemcpyAsync(labels_out, base + o_l, (size_t)R, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    return AZ_OK;
+}
+
+int az_train_ex_rois(az_ctx *c, const az_train_params *p, int n_images, const int32_t *sizes, const double *gt,
+                     const int32_t *gt_off, const double *noise, long long n_noise, float *ex_boxes_out,
+                     uint8_t *zoom_out, int32_t *ex_off_out, int cap, long long *noise_used_out, long long *needed_out)
+{
+    if (!c || !train_params_ok(p) || n_images < 0 || n_noise < 0 || cap < 0 || !ex_off_out || !needed_out ||
+        (n_images && (!sizes || !gt_off || !noise_used_out)) || (n_noise && !noise) || (cap && (!ex_boxes_out || !zoom_out)))
+        return fail(c, AZ_ERR_INVALID, "az_train_ex_rois: bad arguments");
+    needed_out[0] = needed_out[1] = 0;
+    ex_off_out[0] = 0;
+    if (n_images == 0) return AZ_OK;
+    std::vector<int> sizes3((size_t)n_images * 3);
+    for (int i = 0; i < n_images; ++i) {
+        const int h = sizes[2 * i], w = sizes[2 * i + 1];
+        if (h <= 0 || w <= 0 || gt_off[i + 1] < gt_off[i] || gt_off[0] != 0)
+            return fail(c, AZ_ERR_INVALID, "az_train_ex_rois: image sizes must be positive and gt_off ascend from 0");
+        // K = int(np.log2(side / MIN_SIDE) + 1.0), roidb.py:247-250
+        const double k = std::log2((double)(h < w ? h : w) / p->min_side) + 1.0;
+        sizes3[3 * i] = h; sizes3[3 * i + 1] = w; sizes3[3 * i + 2] = k > 0.0 ? (int)k : 0;
+        if (sizes3[3 * i + 2] > AZ_MAX_LEVELS) return fail(c, AZ_ERR_INVALID, "az_train_ex_rois: too many levels");
+    }
+    const int NG = gt_off[n_images];
+    if (NG && !gt) return fail(c, AZ_ERR_INVALID, "az_train_ex_rois: NULL gt");
+    HIPCHK(c, hipSetDevice(c->device));
+    TrainArena ar;
+    const size_t o_sz = ar.add(sizes3.size() * 4), o_gt = ar.add((size_t)NG * 32 + 32), o_go = ar.add(((size_t)n_images + 1) * 4),
+                 o_no = ar.add((size_t)n_noise * 8 + 8), o_ex = ar.add((size_t)cap * 16 + 16), o_zo = ar.add((size_t)cap + 16),
+                 o_eo = ar.add(((size_t)n_images + 1) * 4), o_us = ar.add((size_t)n_images * 8),
+                 o_B = ar.add((size_t)azk_train_level_cap() * 8 * 8), o_st = ar.add(16);
+    int rc;
+    if ((rc = ev_grow(c, 0, &c->ev_a, ar.total)) != AZ_OK) return rc;
+    char *base = (char *)c->ev_a;
+    hipStream_t s = c->stream;
+    HIPCHK(c, hipMemcpyAsync(base + o_sz, sizes3.data(), sizes3.size() * 4, hipMemcpyHostToDevice, s));
+    if (NG) HIPCHK(c, hipMemcpyAsync(base + o_gt, gt, (size_t)NG * 32, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(base + o_go, gt_off, ((size_t)n_images + 1) * 4, hipMemcpyHostToDevice, s));
+    if (n_noise) HIPCHK(c, hipMemcpyAsync(base + o_no, noise, (size_t)n_noise * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemsetAsync(base + o_eo, 0, ((size_t)n_images + 1) * 4, s));
+    if (azk_train_ex_rois(s, p, n_images, (const int *)(base + o_sz), (const double *)(base + o_gt), (const int *)(base + o_go),
+                          (const double *)(base + o_no), n_noise, (float *)(base + o_ex), (unsigned char *)(base + o_zo),
+                          (int *)(base + o_eo), (long long *)(base + o_us), cap, (double *)(base + o_B),
+                          (long long *)(base + o_st)))
+        return fail(c, AZ_ERR_HIP, "az_train_ex_rois: launch failed");
+    long long status[2] = {0, 0};
+    std::vector<int32_t> eoff((size_t)n_images + 1);
+    HIPCHK(c, hipMemcpyAsync(status, base + o_st, 16, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(eoff.data(), base + o_eo, eoff.size() * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));     // status / eoff live on this frame
+    if (status[0] & 1) {
+        needed_out[0] = status[1];
+        return fail(c, AZ_ERR_CAPACITY, "az_train_ex_rois: the noise ran out; at least " + std::to_string(status[1]) + " doubles are needed");
+    }
+    if (status[0] & 2)
+        return fail(c, AZ_ERR_CAPACITY, "az_train_ex_rois: a level holds more than " + std::to_string(azk_train_level_cap()) +
+                                            " children before the dedup");
+    if (status[0] & 4)
+        return fail(c, AZ_ERR_INVALID, "az_train_ex_rois: a region's coordinate leaves the dedup hash's range (negative, or >= 1000 * min_side)");
+    const int E = eoff[n_images];
+    if (E > cap) {
+        needed_out[1] = E;
+        return fail(c, AZ_ERR_CAPACITY, "az_train_ex_rois: cap too small; " + std::to_string(E) + " example regions");
+    }
+    std::memcpy(ex_off_out, eoff.data(), eoff.size() * 4);
+    HIPCHK(c, hipMemcpyAsync(noise_used_out, base + o_us, (size_t)n_images * 8, hipMemcpyDeviceToHost, s));
+    if (E) {
+        HIPCHK(c, hipMemcpyAsync(ex_boxes_out, base + o_ex, (size_t)E * 16, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(zoom_out, base + o_zo, (size_t)E, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(c, hipStreamSynchronize(s));
+    return AZ_OK;
+}
+
+int az_train_adj_targets(az_ctx *c, const az_train_params *p, int n_images, const float *ex_boxes, const int32_t *ex_off,
+                         const float *gt, const int32_t *gt_off, double *targets_out, int32_t *tgt_off_out, int cap)
+{
+    if (!c || !train_params_ok(p) || n_images < 0 || cap < 0 || !tgt_off_out || (n_images && (!ex_off || !gt_off)) ||
+        (cap && !targets_out))
+        return fail(c, AZ_ERR_INVALID, "az_train_adj_targets: bad arguments");
+    tgt_off_out[0] = 0;
+    if (n_images == 0) return AZ_OK;
+    int max_gt = 0;
+    for (int i = 0; i < n_images; ++i) {
+        if (ex_off[i + 1] < ex_off[i] || gt_off[i + 1] < gt_off[i] || ex_off[0] != 0 || gt_off[0] != 0)
+            return fail(c, AZ_ERR_INVALID, "az_train_adj_targets: offsets must ascend from 0");
+        max_gt = std::max(max_gt, gt_off[i + 1] - gt_off[i]);
+    }
+    const int E = ex_off[n_images], NG = gt_off[n_images];
+    if ((E && !ex_boxes) || (NG && !gt)) return fail(c, AZ_ERR_INVALID, "az_train_adj_targets: NULL array");
+    if ((size_t)max_gt * p->n_subregion * sizeof(double) > azk_adj_lds_max())
+        return fail(c, AZ_ERR_CAPACITY, "az_train_adj_targets: an image has more objects than the match matrix's LDS holds");
+    HIPCHK(c, hipSetDevice(c->device));
+    TrainArena ar;
+    const size_t o_ex = ar.add((size_t)E * 16 + 16), o_eo = ar.add(((size_t)n_images + 1) * 4), o_gt = ar.add((size_t)NG * 16 + 16),
+                 o_go = ar.add(((size_t)n_images + 1) * 4), o_cn = ar.add(((size_t)E + 1) * 4), o_to = ar.add(((size_t)n_images + 1) * 4);
+    int rc;
+    if ((rc = ev_grow(c, 0, &c->ev_a, ar.total)) != AZ_OK) return rc;
+    if ((rc = ev_grow(c, 1, &c->ev_b, (size_t)cap * 56 + 56)) != AZ_OK) return rc;
+    char *base = (char *)c->ev_a;
+    hipStream_t s = c->stream;
+    if (E) HIPCHK(c, hipMemcpyAsync(base + o_ex, ex_boxes, (size_t)E * 16, hipMemcpyHostToDevice, s));
+    if (NG) HIPCHK(c, hipMemcpyAsync(base + o_gt, gt, (size_t)NG * 16, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(base + o_eo, ex_off, ((size_t)n_images + 1) * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(base + o_go, gt_off, ((size_t)n_images + 1) * 4, hipMemcpyHostToDevice, s));
+    if (azk_train_adj_count(s, p, n_images, E, (const float *)(base + o_ex), (const int *)(base + o_eo), (const float *)(base + o_gt),
+                            (const int *)(base + o_go), (int *)(base + o_cn), (int *)(base + o_to)))
+        return fail(c, AZ_ERR_HIP, "az_train_adj_targets: launch failed");
+    // (the rows are written behind the counts without a host wait; a `cap` that turns out too small makes the kernel
+    //  write nothing for the rows past it, and the call fails below)
+    if (azk_train_adj_write(s, p, n_images, E, max_gt, (const float *)(base + o_ex), (const int *)(base + o_eo),
+                            (const float *)(base + o_gt), (const int *)(base + o_go), (int *)(base + o_cn), (double *)c->ev_b, cap))
+        return fail(c, AZ_ERR_HIP, "az_train_adj_targets: launch failed");
+    HIPCHK(c, hipMemcpyAsync(tgt_off_out, base + o_to, ((size_t)n_images + 1) * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    const int T = tgt_off_out[n_images];
+    if (T > cap) return fail(c, AZ_ERR_CAPACITY, "az_train_adj_targets: cap too small; " + std::to_string(T) + " targets");
+    if (T) HIPCHK(c, hipMemcpy(targets_out, c->ev_b, (size_t)T * 56, hipMemcpyDeviceToHost));
+    return AZ_OK;
+}
+
+int az_train_target_stats(az_ctx *c, int n_sub, double eps, double *targets, long long T, double *means_out,
+                          double *stds_out, int normalise_in_place)
+{
+    if (!c || n_sub < 1 || n_sub > AZ_TRAIN_MAX_REGIONS || T < 0 || (T && !targets) || !means_out || !stds_out)
+        return fail(c, AZ_ERR_INVALID, "az_train_target_stats: bad arguments");
+    HIPCHK(c, hipSetDevice(c->device));
+    TrainArena ar;
+    const size_t o_pt = ar.add(azk_stats_part_doubles(T, n_sub) * 8), o_m = ar.add((size_t)n_sub * 32), o_s = ar.add((size_t)n_sub * 32);
+    int rc;
+    if ((rc = ev_grow(c, 0, &c->ev_a, ar.total)) != AZ_OK) return rc;
+    if ((rc = ev_grow(c, 1, &c->ev_b, (size_t)T * 56 + 56)) != AZ_OK) return rc;
+    char *base = (char *)c->ev_a;
+    hipStream_t s = c->stream;
+    if (T) HIPCHK(c, hipMemcpyAsync(c->ev_b, targets, (size_t)T * 56, hipMemcpyHostToDevice, s));
+    if (azk_train_target_stats(s, n_sub, eps, (double *)c->ev_b, T, (double *)(base + o_pt), (double *)(base + o_m),
+                               (double *)(base + o_s), normalise_in_place))
+        return fail(c, AZ_ERR_HIP, "az_train_target_stats: launch failed");
+    HIPCHK(c, hipMemcpyAsync(means_out, base + o_m, (size_t)n_sub * 32, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(stds_out, base + o_s, (size_t)n_sub * 32, hipMemcpyDeviceToHost, s));
+    if (T && normalise_in_place) HIPCHK(c, hipMemcpyAsync(targets, c->ev_b, (size_t)T * 56, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    return AZ_OK;
+}
+
 }  // extern "C"

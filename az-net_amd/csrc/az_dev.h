@@ -442,6 +442,34 @@ void azk_pool_hist(hipStream_t s, const float *pool, long long n, unsigned int p
 void azk_pool_keep(hipStream_t s, const float *pool, long long n, unsigned int kmin, float *dst,
                    unsigned long long *ndst);
 
+// utils.cython_bbox.bbox_overlaps of one pair (lib/utils/bbox.pyx:150-171), f64
+static __device__ __forceinline__ double az_iou_f64(const double *b, const double *q)
+{
+    const double box_area = (q[2] - q[0] + 1.0) * (q[3] - q[1] + 1.0);
+    const double iw = (b[2] < q[2] ? b[2] : q[2]) - (b[0] > q[0] ? b[0] : q[0]) + 1.0;
+    if (!(iw > 0.0)) return 0.0;
+    const double ih = (b[3] < q[3] ? b[3] : q[3]) - (b[1] > q[1] ? b[1] : q[1]) + 1.0;
+    if (!(ih > 0.0)) return 0.0;
+    const double ua = (b[2] - b[0] + 1.0) * (b[3] - b[1] + 1.0) + box_area - iw * ih;
+    return iw * ih / ua;
+}
+
+// ---- launchers (az_train.hip): the training data layer -----------------------------------------------------------------
+void azk_zoom_labels(hipStream_t s, const double *rois, int R, const double *gt, int N, double max_ratio, double min_obj,
+                     unsigned char *out);
+int azk_train_level_cap();
+int azk_train_ex_rois(hipStream_t s, const az_train_params *p, int n_images, const int *sizes3, const double *gt,
+                      const int *gt_off, const double *noise, long long n_noise, float *ex, unsigned char *zoom,
+                      int *ex_off, long long *used, int cap, double *B, long long *status);
+size_t azk_adj_lds_max();
+int azk_train_adj_count(hipStream_t s, const az_train_params *p, int n_images, int E, const float *ex, const int *ex_off,
+                        const float *gt, const int *gt_off, int *cnt, int *tgt_off);
+int azk_train_adj_write(hipStream_t s, const az_train_params *p, int n_images, int E, int max_gt, const float *ex,
+                        const int *ex_off, const float *gt, const int *gt_off, int *cnt, double *targets, int cap);
+size_t azk_stats_part_doubles(long long T, int n_sub);
+int azk_train_target_stats(hipStream_t s, int n_sub, double eps, double *targets, long long T, double *part, double *means,
+                           double *stds, int normalise);
+
 // ---- launcher (az_box.hip): what this box sustains (register-only fp32 MFMA loop on all SIMDs; float4 copy) ----------
 int azk_measure_box(hipStream_t s, double *mfma_tflops, double *copy_tbps, size_t copy_bytes);
 

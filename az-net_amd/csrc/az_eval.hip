@@ -56,16 +56,7 @@ __global__ void __launch_bounds__(256) k_image_blob(const unsigned char *__restr
 }
 
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ double iou_f64(const double *b, const double *q)
-{
-    const double box_area = (q[2] - q[0] + 1.0) * (q[3] - q[1] + 1.0);
-    const double iw = (b[2] < q[2] ? b[2] : q[2]) - (b[0] > q[0] ? b[0] : q[0]) + 1.0;
-    if (!(iw > 0.0)) return 0.0;
-    const double ih = (b[3] < q[3] ? b[3] : q[3]) - (b[1] > q[1] ? b[1] : q[1]) + 1.0;
-    if (!(ih > 0.0)) return 0.0;
-    const double ua = (b[2] - b[0] + 1.0) * (b[3] - b[1] + 1.0) + box_area - iw * ih;
-    return iw * ih / ua;
-}
+__device__ __forceinline__ double iou_f64(const double *b, const double *q) { return az_iou_f64(b, q); }
 
 __global__ void __launch_bounds__(256) k_bbox_overlaps(const double *__restrict__ boxes, int N,
                                                         const double *__restrict__ query, int K,

@@ -42,6 +42,7 @@ SYMBOLS = [
     "az_detect_batch", "az_voc_eval", "az_coco_eval",
     "az_set_feature_pyramid_dev_nhwc", "az_roi_dedup_pyramid", "az_roi_pool_pyramid", "az_propose_pyramid",
     "az_detect_pyramid",
+    "az_zoom_labels", "az_train_ex_rois", "az_train_adj_targets", "az_train_target_stats",
 ]
 
 
@@ -65,6 +66,37 @@ class AzStats(ctypes.Structure):
                 ("pass_rows", ctypes.c_int32 * AZ_MAX_LEVELS),
                 ("search_form", ctypes.c_int32), ("n_reruns", ctypes.c_int32),
                 ("pass_levels", ctypes.c_int32 * AZ_MAX_LEVELS)]
+
+
+AZ_TRAIN_MAX_REGIONS = 16    # include/aznet_hip.h
+
+
+class AzTrainParams(ctypes.Structure):
+    _fields_ = [("min_side", ctypes.c_double), ("zoom_err_prob", ctypes.c_double), ("emb_obj_thresh", ctypes.c_double),
+                ("emb_reg_thresh", ctypes.c_double), ("adj_thresh", ctypes.c_double), ("eps", ctypes.c_double),
+                ("train_rep", ctypes.c_int32), ("n_addregions", ctypes.c_int32), ("n_subregion", ctypes.c_int32),
+                ("reserved", ctypes.c_int32),
+                ("addregions", (ctypes.c_double * 4) * AZ_TRAIN_MAX_REGIONS),
+                ("subregion", (ctypes.c_double * 4) * AZ_TRAIN_MAX_REGIONS)]
+
+
+def make_train_params(tp):
+    """az_train_params from a dict (az_data_layer.roidb.train_params) or an AzTrainParams."""
+    if isinstance(tp, AzTrainParams):
+        return tp
+    p = AzTrainParams()
+    for k in ("min_side", "zoom_err_prob", "emb_obj_thresh", "emb_reg_thresh", "adj_thresh", "eps"):
+        setattr(p, k, float(tp[k]))
+    p.train_rep = int(tp["train_rep"])
+    for name, cnt in (("addregions", "n_addregions"), ("subregion", "n_subregion")):
+        rows = tp[name]
+        if not 1 <= len(rows) <= AZ_TRAIN_MAX_REGIONS:
+            raise AzError(AZ_ERR_INVALID, "%s: 1..%d rows" % (name, AZ_TRAIN_MAX_REGIONS))
+        setattr(p, cnt, len(rows))
+        for i, r in enumerate(rows):
+            for q in range(4):
+                getattr(p, name)[i][q] = float(r[q])
+    return p
 
 
 SEARCH_FORMS = {0: "level_loop", 1: "pair_speculation", 2: "whole_tree_pass", 3: "closure_pass", 4: "one_pass_plan",
@@ -182,6 +214,11 @@ def load_library(path=None):
     L.az_voc_eval.argtypes = [vp, ci, ci, dp, dp, ip, dp, u8p, ip, cd, ci, ctypes.POINTER(ctypes.c_int8), dp, dp,
                               ctypes.POINTER(ctypes.c_int64), dp, dp]
     L.az_coco_eval.argtypes = [vp, ci, ci, dp, dp, ip, dp, dp, u8p, ip, dp, dp, dp, ip, ctypes.POINTER(ctypes.c_int8)]
+    tpp = ctypes.POINTER(AzTrainParams)
+    L.az_zoom_labels.argtypes = [vp, dp, ci, dp, ci, cd, cd, u8p]
+    L.az_train_ex_rois.argtypes = [vp, tpp, ci, ip, dp, ip, dp, ll, fp, u8p, ip, ci, llp, llp]
+    L.az_train_adj_targets.argtypes = [vp, tpp, ci, fp, ip, fp, ip, dp, ip, ci]
+    L.az_train_target_stats.argtypes = [vp, ci, cd, dp, ll, dp, dp, ci]
     L.az_image_blob_size.argtypes = [ci, ci, cd, cip, cip]
     L.az_image_blob_host.argtypes = [vp, u8p, ci, ci, fp, cd, fp, ci, ci]
     L.az_image_blob_dev.argtypes = [vp, u8p, ci, ci, fp, cd, vp, ci, ci]
@@ -965,6 +1002,103 @@ class AzContext(object):
         self._chk(self.L.az_recall_match(self.h, n, _p(b, ctypes.c_double), _p(boff, ctypes.c_int32),
                                          _p(g, ctypes.c_double), _p(goff, ctypes.c_int32), _p(out, ctypes.c_double)))
         return out
+
+    # ---- training data layer (lib/az_data_layer/roidb.py) ------------------------------------
+    def zoom_labels(self, rois, gt, max_area_ratio, min_obj):
+        """_compute_zoom_labels (roidb.py:313-341): bool [R]."""
+        r = _f64(rois).reshape(-1, 4)
+        g = _f64(gt).reshape(-1, 4)
+        out = np.zeros((r.shape[0],), dtype=np.uint8)
+        self._chk(self.L.az_zoom_labels(self.h, _p(r, ctypes.c_double), r.shape[0], _p(g, ctypes.c_double), g.shape[0],
+                                        float(max_area_ratio), float(min_obj), _p(out, ctypes.c_uint8)))
+        return out.astype(bool)
+
+    @staticmethod
+    def _offsets(arrays):
+        off = np.zeros(len(arrays) + 1, dtype=np.int32)
+        if len(arrays):
+            off[1:] = np.cumsum([a.shape[0] for a in arrays])
+        return off
+
+    def train_ex_rois(self, tp, sizes, gt_list, noise, cap=None):
+        """az_train_ex_rois: example regions and zoom labels of len(sizes) images, consuming `noise` (uniform doubles)
+        as one stream.  Returns (ex_boxes f32 [E,4], zoom u8 [E], ex_off int32 [n+1], noise_used int64 [n]).
+        Raises AzError(AZ_ERR_CAPACITY) with `.needed` = the doubles needed where the noise ran out; with an explicit
+        `cap` that is too small, the same with `.needed_cap` (cap=None grows the buffer and calls again)."""
+        p = make_train_params(tp)
+        n = len(sizes)
+        sz = np.ascontiguousarray(np.asarray(sizes, dtype=np.int32).reshape(-1, 2))
+        gts = [_f64(g).reshape(-1, 4) for g in gt_list]
+        assert len(gts) == n
+        goff = self._offsets(gts)
+        g = _f64(np.vstack([np.zeros((0, 4))] + gts))
+        nz = _f64(noise).ravel()
+        grow = cap is None
+        cap = int(cap) if cap is not None else max(1024, 8192 * n)
+        while True:
+            ex = np.zeros((cap, 4), dtype=np.float32)
+            zoom = np.zeros((cap,), dtype=np.uint8)
+            eoff = np.zeros(n + 1, dtype=np.int32)
+            used = np.zeros(max(n, 1), dtype=np.int64)
+            need = np.zeros(2, dtype=np.int64)
+            rc = self.L.az_train_ex_rois(self.h, ctypes.byref(p), n, _p(sz, ctypes.c_int32), _p(g, ctypes.c_double),
+                                         _p(goff, ctypes.c_int32), _p(nz, ctypes.c_double), nz.size,
+                                         _p(ex, ctypes.c_float), _p(zoom, ctypes.c_uint8), _p(eoff, ctypes.c_int32), cap,
+                                         _p(used, ctypes.c_longlong), _p(need, ctypes.c_longlong))
+            if rc == AZ_ERR_CAPACITY and (need[0] or need[1]):
+                if need[1] and grow:
+                    cap = int(need[1])
+                    continue
+                e = AzError(rc, self.L.az_last_error(self.h).decode())
+                if need[0]:
+                    e.needed = int(need[0])
+                else:
+                    e.needed_cap = int(need[1])
+                raise e
+            self._chk(rc)
+            E = int(eoff[n])
+            return ex[:E], zoom[:E], eoff, used[:n]
+
+    def train_adj_targets(self, tp, ex_boxes, ex_off, gt_list, cap=None):
+        """az_train_adj_targets: ex_boxes f32 [E,4] with ex_off [n+1], gt_list of n f32 [.,4] arrays ->
+        (targets f64 [T,7] un-normalised, tgt_off int32 [n+1]).  An explicit `cap` that is too small raises
+        AzError(AZ_ERR_CAPACITY) with `.needed_cap`."""
+        p = make_train_params(tp)
+        ex = _f32(ex_boxes).reshape(-1, 4)
+        eoff = np.ascontiguousarray(ex_off, dtype=np.int32).ravel()
+        n = eoff.size - 1
+        gts = [_f32(g).reshape(-1, 4) for g in gt_list]
+        assert len(gts) == n and int(eoff[n]) == ex.shape[0]
+        goff = self._offsets(gts)
+        g = _f32(np.vstack([np.zeros((0, 4), np.float32)] + gts))
+        grow = cap is None
+        cap = int(cap) if cap is not None else max(1024, ex.shape[0])
+        while True:
+            t = np.zeros((cap, 7), dtype=np.float64)
+            toff = np.zeros(n + 1, dtype=np.int32)
+            rc = self.L.az_train_adj_targets(self.h, ctypes.byref(p), n, _p(ex, ctypes.c_float), _p(eoff, ctypes.c_int32),
+                                             _p(g, ctypes.c_float), _p(goff, ctypes.c_int32), _p(t, ctypes.c_double),
+                                             _p(toff, ctypes.c_int32), cap)
+            if rc == AZ_ERR_CAPACITY and int(toff[n]) > cap:
+                if grow:
+                    cap = int(toff[n])
+                    continue
+                e = AzError(rc, self.L.az_last_error(self.h).decode())
+                e.needed_cap = int(toff[n])
+                raise e
+            self._chk(rc)
+            return t[:int(toff[n])], toff
+
+    def train_target_stats(self, n_sub, eps, targets, normalise=True):
+        """az_train_target_stats over targets f64 [T,7] (C-contiguous; normalised IN PLACE when asked) ->
+        (means [n_sub,4], stds [n_sub,4])."""
+        assert targets.dtype == np.float64 and targets.flags["C_CONTIGUOUS"] and (targets.ndim == 2 and targets.shape[1] == 7)
+        means = np.zeros((int(n_sub), 4), dtype=np.float64)
+        stds = np.zeros((int(n_sub), 4), dtype=np.float64)
+        self._chk(self.L.az_train_target_stats(self.h, int(n_sub), float(eps), _p(targets, ctypes.c_double),
+                                               targets.shape[0], _p(means, ctypes.c_double), _p(stds, ctypes.c_double),
+                                               1 if normalise else 0))
+        return means, stds
 
     # ---- detection evaluation (imdb.evaluate_detections, VOC) -------------------------------
     def voc_eval(self, n_classes, n_images, det_box, det_conf, det_off, gt_box, gt_difficult, gt_off,

@@ -1,5 +1,7 @@
 """Base image database (reference: lib/datasets/imdb.py): identity, image list, ground truth,
 and `evaluate_recall` -- whose box matching runs on the GPU (az_recall_match)."""
+import os
+
 import numpy as np
 
 from aznet_hip import ffi
@@ -48,6 +50,40 @@ class imdb(object):
 
     def image_path_at(self, i):
         raise NotImplementedError
+
+    def image_size(self, i):
+        """(height, width) of image i (imdb.py:83-85): PIL reads the file's header, no pixels are decoded."""
+        from PIL import Image
+        with Image.open(self.image_path_at(i)) as im:
+            size = im.size
+        return (size[1], size[0])
+
+    @property
+    def cache_path(self):
+        """<ROOT>/data/cache (imdb.py:69-74), where the training caches go."""
+        import datasets
+        p = os.path.abspath(os.path.join(datasets.ROOT_DIR, "data", "cache"))
+        if not os.path.isdir(p):
+            os.makedirs(p)
+        return p
+
+    def append_flipped_images(self):
+        """imdb.append_flipped_images (imdb.py:101-118): every entry once more with its boxes mirrored and
+        'flipped' set; the image list doubles.  Widths come from image_size (the reference opens every file)."""
+        num_images = self.num_images
+        widths = [self.image_size(i)[1] for i in range(num_images)]
+        for i in range(num_images):
+            boxes = self.roidb[i]["boxes"].copy()
+            oldx1 = boxes[:, 0].copy()
+            oldx2 = boxes[:, 2].copy()
+            boxes[:, 0] = widths[i] - oldx2 - 1.0
+            boxes[:, 2] = widths[i] - oldx1 - 1.0
+            assert (boxes[:, 2] >= boxes[:, 0]).all()
+            entry = {"boxes": boxes, "gt_classes": self.roidb[i]["gt_classes"], "flipped": True}
+            if "gt_overlaps" in self.roidb[i]:
+                entry["gt_overlaps"] = self.roidb[i]["gt_overlaps"]
+            self.roidb.append(entry)
+        self._image_index = self._image_index * 2
 
     def image_at(self, i):
         """BGR uint8 HxWx3 array of image i (cv2.imread's convention, which is not available

@@ -32,6 +32,9 @@ class SyntheticImdb(imdb):
     def image_path_at(self, i):
         return "synthetic://%d" % self.image_index[i]
 
+    def image_size(self, i):
+        return (self.height, self.width)
+
     def gt_roidb(self):
         out = []
         for idx in self.image_index:
@@ -61,6 +64,10 @@ class NpyDirImdb(imdb):
 
     def image_at(self, i):
         return np.load(self.image_path_at(i))
+
+    def image_size(self, i):
+        shape = np.load(self.image_path_at(i), mmap_mode="r").shape      # (the .npy header only)
+        return (int(shape[0]), int(shape[1]))
 
     def gt_roidb(self):
         out = []

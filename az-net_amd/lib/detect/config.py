@@ -39,8 +39,8 @@ class edict(dict):
 
 def _defaults():
     """Default option tree.  Values are the reference's (lib/detect/config.py:39-219)."""
-    train = dict(        # config.py:39-104 -- unused by the proposal path; present so the
-        SCALES=(600,),   # reference's YAML files (experiments/cfgs/*.yml) merge cleanly
+    train = dict(        # config.py:39-104 -- unused by the proposal path; read by the training data layer
+        SCALES=(600,),   # (az_data_layer) and present so the reference's YAML files (experiments/cfgs/*.yml) merge
         MAX_SIZE=1000, IMS_PER_BATCH=2, BATCH_SIZE=128, FG_FRACTION=0.25, AZ_POS_FRACTION=0.5,
         FG_THRESH=0.5, BG_THRESH_HI=0.5, BG_THRESH_LO=0.1, USE_FLIPPED=True, BBOX_REG=True,
         BBOX_THRESH=0.5, SNAPSHOT_ITERS=10000, USE_CACHE=False, SNAPSHOT_INFIX='',

@@ -499,6 +499,53 @@ int az_bias_relu(void *stream, float *y, const float *bias, int C, long long hw,
  * is monotonic). */
 int az_bias_relu_pool(void *stream, const float *y, const float *bias, float *out, int C, int H, int W, int channels_last);
 
+/* ---- training data layer (lib/az_data_layer/roidb.py) -------------------------------------------- */
+#define AZ_TRAIN_MAX_REGIONS 16   /* rows of cfg.TRAIN.ADDREGIONS / cfg.SEAR.SUBREGION a call may carry */
+/* The cfg keys the training kernels read: SEAR.MIN_SIDE, SEAR.TRAIN_REP, SEAR.ZOOM_ERR_PROB, SEAR.EMB_OBJ_THRESH,
+ * SEAR.EMB_REG_THRESH, SEAR.ADJ_THRESH, EPS, TRAIN.ADDREGIONS, SEAR.SUBREGION (lib/detect/config.py:91-195). */
+typedef struct {
+    double min_side, zoom_err_prob, emb_obj_thresh, emb_reg_thresh, adj_thresh, eps;
+    int32_t train_rep, n_addregions, n_subregion, reserved;
+    double addregions[AZ_TRAIN_MAX_REGIONS][4];
+    double subregion[AZ_TRAIN_MAX_REGIONS][4];
+} az_train_params;
+
+/* _compute_zoom_labels (roidb.py:313-341 over bbox_zoom_labels, lib/utils/bbox.pyx:20-60): labels_out[r] = 1 when
+ * some object n has area(gt_n) / (area(roi_r) + 1e-14) <= max_area_ratio and intersection / (area(gt_n) + 1e-14)
+ * >= min_obj.  rois f64 [R,4], gt f64 [N,4] (N = 0: all 0). */
+int az_zoom_labels(az_ctx *ctx, const double *rois, int R, const double *gt, int N, double max_area_ratio,
+                   double min_obj, uint8_t *labels_out);
+/* _compute_ex_rois (roidb.py:230-299) for n_images images in ONE launch: image i has sizes[i] = (h, w) and the objects
+ * gt[gt_off[i]:gt_off[i+1]] (f64 [.,4]).  Per image, train_rep zoom searches from the addregions roots over
+ * int(log2(min(h, w) / min_side) + 1) levels -- zoom labels, `err = noise <= zoom_err_prob` on the next |B| doubles of
+ * `noise`, divide_region of the regions with label XOR err -- then every object's n_subregion super-regions
+ * (roidb.py:270-289), clipped to the image, sides >= min_side kept, in the reference's order.  The images consume ONE
+ * stream: image i + 1 starts where image i stopped (the position lives on the device).
+ * ex_boxes_out f32 [cap,4] (the f64 box rounded once, roidb.py:65), zoom_out [cap], ex_off_out [n_images + 1],
+ * noise_used_out [n_images].  AZ_ERR_CAPACITY, and nothing in the outputs, when `noise` runs out (needed_out[0] = the
+ * doubles needed at the level that ran out; how many more the rest needs depends on the noise itself) or the regions
+ * outgrow `cap` (needed_out[1] = their exact number), or a level holds more than 4096 children before the dedup;
+ * needed_out [2] is zero otherwise. */
+int az_train_ex_rois(az_ctx *ctx, const az_train_params *p, int n_images, const int32_t *sizes, const double *gt,
+                     const int32_t *gt_off, const double *noise, long long n_noise, float *ex_boxes_out,
+                     uint8_t *zoom_out, int32_t *ex_off_out, int cap, long long *noise_used_out, long long *needed_out);
+/* _compute_targets (roidb.py:146-227) for n_images images: image i owns ex_boxes[ex_off[i]:ex_off[i+1]] and
+ * gt[gt_off[i]:gt_off[i+1]], both the roidb's f32, widened to f64.  Per example region k with max IoU >= adj_thresh:
+ * the sub-regions (x2 - x1, y2 - y1) * subregion + (x1, y1), their IoU with every object, the objects whose IoU with
+ * sub-region 0 is below adj_thresh retired, then min(n_subregion, objects left) rounds of: the first maximum in
+ * row-major order (a maximum of 0 still matches), one row (dx, dy, dw, dh, k within its image, sub-region,
+ * IoU(region, object)), that sub-region and object retired.  targets_out f64 [cap,7] ordered by image, k, round;
+ * tgt_off_out [n_images + 1].  AZ_ERR_CAPACITY with tgt_off_out filled (tgt_off_out[n_images] = rows needed) and no
+ * rows written when cap is too small, or when an image has more objects than the matrix's LDS holds. */
+int az_train_adj_targets(az_ctx *ctx, const az_train_params *p, int n_images, const float *ex_boxes,
+                         const int32_t *ex_off, const float *gt, const int32_t *gt_off, double *targets_out,
+                         int32_t *tgt_off_out, int cap);
+/* roidb.py:110-134 over T target rows: per sub-region (column 5) counts + eps, sums and squared sums of columns 0-3
+ * in a fixed two-level order (the same bits on every run), means = sums / counts, stds = sqrt(sq / counts - means^2)
+ * -> means_out / stds_out [n_sub * 4]; normalise_in_place != 0: every row's columns 0-3 -> (x - mean) / std. */
+int az_train_target_stats(az_ctx *ctx, int n_sub, double eps, double *targets, long long T, double *means_out,
+                          double *stds_out, int normalise_in_place);
+
 /* ---- measurement ------------------------------------------------------------------ */
 /* HIP-event timing (events on the ctx stream) of the launches made by az_propose /
  * az_head_forward.  mode bits: 1 = time only the fc GEMM launches, 2 = time every launch
