@@ -1,6 +1,6 @@
 // az_capi.hip -- the C ABI of libaznet_hip.so (include/aznet_hip.h): context lifecycle, head and feature maps, the two
 // lanes and the public launch / fetch entry points, measurement switches, the native exchange.  The forms of a search live
-// in az_search.hip, the unit entry points in az_units.hip.  There is no CPU fallback anywhere in this library: without a
+// in az_plan.hip / az_shape.hip / az_search.hip / az_batch.hip, the unit entry points in az_units.hip.  There is no CPU fallback anywhere in this library: without a
 // gfx950 device az_create fails with AZ_ERR_NO_DEVICE.
 #include "az_ctx.h"
 
@@ -21,6 +21,8 @@ int az_create(int device, az_ctx **out)
     if (hipSetDevice(device) != hipSuccess) return AZ_ERR_NO_DEVICE;
     az_ctx *c = new az_ctx();
     c->device = device;
+    c->env = az_read_env();
+    c->use_graphs = c->env.graph ? 1 : 0; c->plan_cache_max = c->env.plan_cache; c->gemm12_min_rows = c->env.gemm12_min;
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return AZ_ERR_HIP; }
     if (hipHostMalloc((void **)&c->h_cnt, RES_HDR + (size_t)AZ_TOPK_MAX * 36) != hipSuccess) { delete c; return AZ_ERR_HIP; }
     for (int i = 0; i < 3; ++i)
@@ -218,7 +220,7 @@ int az_load_head(az_ctx *c, int C, int n6, int n71, int n72, const float *W6, co
     HIPCHK(c, hipMemcpy(c->bt + 55, bz, 4, hipMemcpyHostToDevice));
     HIPCHK(c, hipDeviceSynchronize());
     // the many-row GEMM's LDS opt-in is per device; without it every launch stays on k_fc_splitk
-    if (azk_fc_gemm12_prepare() != 0) { (void)hipGetLastError(); c->gemm12_min_rows = 0x7fffffff; c->gemm12_env = 1; }
+    if (azk_fc_gemm12_prepare() != 0) { (void)hipGetLastError(); c->gemm12_min_rows = 0x7fffffff; }
     if (c->gemm_parts && azk_fc_terms_prepare(c->gemm_parts) != 0) {
         (void)hipGetLastError();
         return fail(c, AZ_ERR_HIP, "az_load_head: the 16-bit-term GEMM's LDS opt-in failed on this device (az_set_gemm_mode)");
@@ -409,7 +411,7 @@ static int make_lane(az_ctx *c, az_ctx **out, bool with_head, const char *what)
     t->W6 = c->W6; t->b6 = c->b6; t->W7 = c->W7; t->b7 = c->b7; t->Wt = c->Wt; t->bt = c->bt; t->W6p = c->W6p;
     t->head_bufs = false;
     if (with_head && (rc = ensure_lane_head(t)) != AZ_OK) return bail(rc, "head buffers");
-    t->gemm12_env = c->gemm12_env; t->gemm12_min_rows = c->gemm12_min_rows; t->gemm12_dual_rows = c->gemm12_dual_rows;
+    t->env = c->env; t->plan_cache_max = c->plan_cache_max; t->gemm12_min_rows = c->gemm12_min_rows; t->gemm12_dual_rows = c->gemm12_dual_rows;
     t->head_loaded = true;
     t->profiling = c->profiling; t->use_graphs = c->use_graphs; t->cal = c->cal;
     *out = t;
@@ -536,7 +538,7 @@ int az_propose_fetch(az_ctx *c, double *boxes_out, float *scores_out, int cap, i
     return rc;
 }
 
-// ---- a batch of images in lockstep (az_search.hip: batch_launch_impl) --------------------------------------------------
+// ---- a batch of images in lockstep (az_batch.hip: batch_launch_impl) --------------------------------------------------
 static az_ctx *batch_lane(az_ctx *c, int *lane_out, int *rc_out)
 {
     *lane_out = 0; *rc_out = AZ_OK;

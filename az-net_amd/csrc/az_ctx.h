@@ -1,6 +1,7 @@
 // az_ctx.h -- the context behind the C ABI (include/aznet_hip.h) and the host-side helpers its translation units share:
-// az_capi.hip (lifecycle, head, maps, lanes, public launch / fetch, measurement, exchange), az_search.hip (the forms of a
-// search: plans, caches, cost model, launch sequence, collecting a result), az_units.hip (unit entry points, detection head,
+// az_capi.hip (lifecycle, head, maps, lanes, public launch / fetch, measurement, exchange), az_plan.hip / az_shape.hip /
+// az_search.hip / az_batch.hip (the forms of a search: cost model and planner, per-shape caches, launch sequence and collecting
+// a result, lockstep batches; az_search.h), az_units.hip (unit entry points, detection head,
 // NMS, tuner, recall, front-end).  Helpers are internal (anonymous namespace: one copy per translation unit).
 #pragma once
 #include "az_dev.h"
@@ -8,6 +9,7 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <deque>
 #include <map>
@@ -21,8 +23,36 @@ struct AzEventRec { std::string name; int level; hipEvent_t a, b; int slot; /* >
 constexpr size_t RES_HDR = 1024;    // AzCounts, padded, at the head of the result block
 static_assert(sizeof(AzCounts) <= RES_HDR, "AzCounts outgrew its slot");
 
+// The environment switches (measurements and A/B tests only; none changes a result): read once per context by
+// az_create (az_read_env, the library's one getenv site), lanes and batch slots take their owner's table.
+struct AzEnv {
+    bool graph = false;        // AZ_GRAPH=1: hipGraph replay (the default az_set_graphs starts from)
+    bool trace = false;        // AZ_TRACE=1: announce and wait for every launch group (debugging; process-wide, Timed::trace)
+    bool full_debug = false;   // AZ_FULL_DEBUG (set): says on stderr when the whole-tree pass is taken or repeated, what the head-pass calibration measured, and when a batch is not taken in lockstep
+    bool pass_cal = true;      // AZ_PASS_CAL=0: built-in head-pass costs instead of the first-launch measurement
+    int plan_cache = 64;       // AZ_PLAN_CACHE=<n>: shapes kept in the plan cache (64)
+    int gemm12_min = 161;      // AZ_GEMM12_MIN=<rows>: row count from which host-known launches take k_fc_splitk12 (161; 0 = never, held as INT_MAX)
+    bool static_tree = true;   // AZ_STATIC_TREE=0: level loop also for Tz <= 0
+    int pair_spec = 1;         // AZ_PAIR_SPEC=0|2: pair speculation never / whenever possible (1: by the context's history)
+    int full_spec = 1;         // AZ_FULL_SPEC=0|2|3: whole-tree speculation never / whenever possible / the closure whenever possible (1: by history)
+    int two_stage = 1;         // AZ_TWO_STAGE=0|2|4: one-pass searches never staged / staged on two lanes as well / two stages, never three
+};
+
+inline AzEnv az_read_env()
+{
+    AzEnv v;
+    auto num = [](const char *name, int unset) { const char *e = getenv(name); return e ? atoi(e) : unset; };
+    v.graph = num("AZ_GRAPH", 0) != 0; v.trace = num("AZ_TRACE", 0) != 0; v.full_debug = getenv("AZ_FULL_DEBUG") != nullptr;
+    v.pass_cal = num("AZ_PASS_CAL", 1) != 0; v.static_tree = num("AZ_STATIC_TREE", 1) != 0;
+    if (num("AZ_PLAN_CACHE", 0) > 0) v.plan_cache = num("AZ_PLAN_CACHE", 0);
+    if (getenv("AZ_GEMM12_MIN")) v.gemm12_min = num("AZ_GEMM12_MIN", 0) > 0 ? num("AZ_GEMM12_MIN", 0) : 0x7fffffff;
+    v.pair_spec = num("AZ_PAIR_SPEC", 1); v.full_spec = num("AZ_FULL_SPEC", 1); v.two_stage = num("AZ_TWO_STAGE", 1);
+    return v;
+}
+
 struct az_ctx {
     int device = 0;
+    AzEnv env;
     hipStream_t stream = nullptr;
     std::string err;
     int maxR = 16384, maxCand = 16384 * AZ_NSUB, maxCh = 65536;
@@ -122,9 +152,7 @@ struct az_ctx {
     int plan_cache_max = 64;
     unsigned *key_u = nullptr;                // selection keys of the decoded boxes (tail kernel), [row][11]
     std::vector<std::pair<int, int>> nostatic; // image shapes whose trees outgrew the plan buffers (a few; oldest dropped)
-    int static_env = -1;                      // AZ_STATIC_TREE=0: always run the level loop (measurements)
     int last_static = 0;
-    int final_env = 1;                        // AZ_FINAL_FUSED=0: separate candidate / selection kernels at the last level
     int hint_rows[AZ_MAX_LEVELS] = {0};       // rows of the head pass launched at each level in the last fetched level-loop search (kernel choice)
     // the last fetched level-loop search, per level: regions, zoomed regions, unique rois, pair-speculation rows (-1: none)
     int hint_P[AZ_MAX_LEVELS] = {0}, hint_PZ[AZ_MAX_LEVELS] = {0}, hint_U[AZ_MAX_LEVELS] = {0}, hint_SPN[AZ_MAX_LEVELS] = {0};
@@ -146,9 +174,7 @@ struct az_ctx {
                        unsigned long long use; };
     std::vector<ShapeHint> hints;
     unsigned long long hint_clock = 0;
-    int pair_env = -1;                        // AZ_PAIR_SPEC: 0 never, 1 by history (default), 2 always
     std::vector<std::pair<int, int>> nopair;  // image shapes whose pair-speculation rows outgrew the tables
-    int full_env = -1;                        // AZ_FULL_SPEC: 0 never, 1 by history (default), 2 always
     int full_now = 0;                         // the search being launched takes the whole-tree pass: 1 = tree rows, 2 = closure
     int last_full = 0;
     // the closure's rows of the shape last looked at by the cost model (0: not built): what the one pass would cost
@@ -180,17 +206,19 @@ struct az_ctx {
     hipStream_t last_s = nullptr;             // the stream the search launched last ends on
     hipEvent_t ev_h6 = nullptr, ev_i7 = nullptr, ev_s2 = nullptr;
     bool i7_live = false, s2_live = false;
-    int split_env = -1, split_now = 0, async_err = 0;
+    int split_now = 0, async_err = 0;
+    bool no_stage_streams = false;            // this device / runtime did not give the extra streams: every search in one stage
     float *part7 = nullptr;                   // int7's split-K slabs [S7][maxR][n7]
     // Staged searches write int7's slabs into THREE buffers in turn (ring[0] = part7): the heads of search i - 3 -- the last
     // reader of the buffer search i writes -- ran before that search was fetched, and a lane never holds more than
     // AZ_QUEUE_MAX = 3 unfetched searches, so int7 needs no event wait for the previous search's heads any more (each wait on
-    // the main stream is a ~6 us bubble between two chip-wide kernels).  AZ_P7_RING=0: one buffer + the wait (measurements).
+    // the main stream is a ~6 us bubble between two chip-wide kernels).  No room for the two extra buffers: one buffer + the wait.
     static_assert(AZ_QUEUE_MAX <= 3, "the int7 slab ring has one buffer per search a lane may hold unfetched");
     float *part7_ring[3] = {nullptr, nullptr, nullptr};
-    int part7_turn = 0, part7_ring_env = -1;
+    int part7_turn = 0;
+    bool part7_no_room = false, part7_wait = false;   // no memory for the two extra buffers; a launch failed after taking one: the next staged search waits for ev_s2
     az_ctx *twin = nullptr, *owner = nullptr;
-    // A batch of images searched in lockstep (az_batch_launch; az_search.hip: batch_launch_impl, az_batch.hip).  Held by the
+    // A batch of images searched in lockstep (az_batch_launch; az_batch.hip: batch_launch_impl).  Held by the
     // lane whose head buffers the batch's passes run in (the context, or its twin for every other batch when two lanes are
     // on); every image of the batch has a SLOT: an az_ctx of its own for the tree (regions, counters, candidates, result
     // slots, history), created without head buffers -- it gets them if one of its searches ever has to be run again alone.
@@ -206,7 +234,6 @@ struct az_ctx {
         // the images' result blocks (counters + selected boxes and scores) lie side by side, on the device and in pinned host
         // memory: ONE device-to-host copy per batch (eight copies of 12 KB cost 75 us of stream time, one of 95 KB ~10)
         unsigned char *res_dev = nullptr, *res_host = nullptr;
-        int gemm12_rows = -1;                 // rows of a pass from which int6 takes the many-row kernel (AZ_BATCH_GEMM12_ROWS)
         int n_live = 0, next_fetch = 0;       // images of the batch in flight; the one az_batch_fetch returns next
         bool lockstep = false;                // false: the batch's images were launched one after the other on their slots
         int rows_hint[AZ_MAX_LEVELS] = {0};   // rows of the passes of the last fetched batch (which int6 kernel takes a level)
@@ -258,8 +285,7 @@ struct az_ctx {
     float *score_v = nullptr, *zoom_v = nullptr;
     unsigned char *keep_v = nullptr;
     unsigned *key_v = nullptr;
-    int gemm12_env = -1;
-    int gemm12_min_rows = 161;                // rows from which a host-known launch takes az_head12.hip (AZ_GEMM12_MIN;
+    int gemm12_min_rows = 161;                // rows from which a host-known launch takes az_head12.hip (AzEnv::gemm12_min;
                                               // measured crossover with k_fc_splitk: 160 rows)
     int gemm12_dual_rows = 161;               // ... and from which a launch whose row count only the device knows takes it, going by the previous search
     // Fast R-CNN head on the shared map (az_load_det_head)
@@ -348,19 +374,17 @@ struct az_ctx {
     // on it, the step from level `limit` on runs on the multi-launch kernels
     struct LvLimit { int h, w, limit; };
     std::vector<LvLimit> lv_limits;
-    int defer_root_env = -1;            // AZ_DEFER_ROOT=0: keep the root's row in the speculative pass (measurements)
-    int level_fused_env = -1;           // AZ_LEVEL_FUSED=0: keep levels >= 4 as separate launches (measurements)
     struct GraphEntry { hipGraphExec_t exec; int npass; int pass_src[AZ_MAX_LEVELS + 2]; int pass_lv[AZ_MAX_LEVELS + 2]; };
     std::map<std::string, GraphEntry> graphs;        // captured launch sequences (az_set_graphs)
-    int use_graphs = -1;                             // -1: take the AZ_GRAPH environment variable
+    int use_graphs = 0;                              // az_set_graphs (az_create: AzEnv::graph)
     int last_defer = 0;
     // Early end: a tree whose previous search of the shape had no regions from some level on is enqueued only up to that
     // level (the passes and geometry kernels of an empty level cost ~35 us each, a fifth of a sparse search); the last
     // geometry kernel checks -- regions after all set err bit 1024 and az_propose_fetch runs the search again in full
-    // (params.reserved bit 12 / AZ_EARLY_END=0: never).  A miss costs more than a hit saves (a second search against two
+    // (params.reserved bit 12: never).  A miss costs more than a hit saves (a second search against two
     // empty levels), so the cut is taken only when the context's last FOUR level-loop searches all ended at or before the
     // level in question: early_hist holds the first empty level of the last eight (4 bits each, 15 = none).
-    int last_cut = 0, cut_env = -1;
+    int last_cut = 0;
     unsigned early_hist = 0xFFFFFFFFu;
     int n_hist = 0;                     // level-loop searches this context has recorded in early_hist (saturating)
     // head passes of the search being enqueued / last launched: where each one's row count lives
@@ -485,7 +509,7 @@ struct Timed {
     }
     // AZ_TRACE=1 (debugging): every launch group is announced on stderr and waited for, so a faulting kernel is the one
     // named last
-    static bool trace() { static const bool t = getenv("AZ_TRACE") && atoi(getenv("AZ_TRACE")); return t; }
+    static bool trace() { static const bool t = az_read_env().trace; return t; }
     Timed(az_ctx *c_, const char *n, int l, int cls = 2) : c(c_), name(n), level(l)
     {
         if (trace()) { fprintf(stderr, "az[%p]: %s L%d ...", (void *)c_, n, l); fflush(stderr); }
@@ -564,21 +588,17 @@ void launch_head(az_ctx *c, const int *Uptr, int level, int im_h, int im_w, doub
         c->pass_lv[c->npass] = level;
         c->pass_src[c->npass++] = in_cnt ? (int)(Uptr - c0) : -(rows_hint > 0 ? rows_hint : 0) - 1;
     }
-    if (c->gemm12_env < 0) {            // AZ_GEMM12_MIN=<rows> (0: never): measurements
-        const char *f = getenv("AZ_GEMM12_MIN");
-        if (f) c->gemm12_min_rows = atoi(f) > 0 ? atoi(f) : 0x7fffffff;
-        c->gemm12_env = 1;
-    }
     const bool split = c->split_now && c->stream2 && c->ev_h6 && c->ev_i7;
     hipStream_t s2 = split ? c->stream2 : c->stream;
     // Stage 1 of a staged search waits for the int7 of the previous one (ev_i7) -- RoIPool included: beside int7 the
     // HBM-bound RoIPool of the next image costs that int7 40 us (70 -> 110) to hide 27 of its own, and the int6 behind it
     // starts later for it.  Measured on one lane, three searches queued: 1.181 -> 1.128 ms per image (two queued: 1.135 ->
-    // 1.141: there the host's launch latency did the same by accident).  AZ_ROI_AFTER_I7=0: RoIPool does not wait (the
-    // round-5 first version; measurements).  The same order across the two lanes of a context (a lane's many-row RoIPool
-    // behind the OTHER lane's int7, an event both ways) was measured too: 1.114 -> 1.138 ms, not kept.
-    static const int roi_after_i7 = getenv("AZ_ROI_AFTER_I7") ? atoi(getenv("AZ_ROI_AFTER_I7")) : 1;
-    if (roi_after_i7 && c->i7_live) { if (hipStreamWaitEvent(c->stream, c->ev_i7, 0) != hipSuccess) c->async_err = 1; c->i7_live = false; }
+    // 1.141: there the host's launch latency did the same by accident).  The same order across the two lanes of a context
+    // (a lane's many-row RoIPool behind the OTHER lane's int7, an event both ways) was measured too: 1.114 -> 1.138 ms, not kept.
+    // int6 has to wait for that int7 in any case: h6, which this pass's slab sum writes, is that int7's operand -- and an
+    // int6 that starts while int7's workgroups still hold CUs runs with stragglers to its end (one persistent workgroup per
+    // CU, work dealt statically: measured 1.13 -> 1.24 ms per image when the two overlapped)
+    if (c->i7_live) { if (hipStreamWaitEvent(c->stream, c->ev_i7, 0) != hipSuccess) c->async_err = 1; c->i7_live = false; }
     { Timed t(c, "roi_pool", level);
       azk_roi_pool(c->stream, c->feat, d, c->spatial_scale, urois ? urois : c->urois, Uptr, c->maxR, c->pool5, c->pool5p,
                    azk_act_plane_elems(c->maxR, d.K6), c->gemm_parts, 0, coop_tail, c->gemm_parts == 2 ? c->gscale : nullptr,
@@ -590,11 +610,6 @@ void launch_head(az_ctx *c, const int *Uptr, int level, int im_h, int im_w, doub
         c->events.push_back({name, level, nullptr, nullptr, sl});
         return c->span_ring + 2 * (size_t)sl;
     };
-    // int6 waits for the int7 of the previous two-stage search of this context (as the RoIPool above by default): h6, which this
-    // pass's slab sum writes, is that int7's operand -- and an int6 that starts while int7's workgroups still hold CUs runs
-    // with stragglers to its end (one persistent workgroup per CU, work dealt statically: measured 1.13 -> 1.24 ms per image
-    // when the two overlapped)
-    if (c->i7_live) { if (hipStreamWaitEvent(c->stream, c->ev_i7, 0) != hipSuccess) c->async_err = 1; c->i7_live = false; }
     const int prof_keep = c->profiling;
     unsigned long long *ts6 = c->gemm_parts ? nullptr : span_slot("fc6_gemm");
     if (ts6) c->profiling &= ~(1 | 2);                     // (no event pair around a launch that times itself)
@@ -626,9 +641,8 @@ void launch_head(az_ctx *c, const int *Uptr, int level, int im_h, int im_w, doub
     // images follow each other without an event hop (each ~13 us on the critical path: slab sum -> int7 on the second
     // stream, int7 -> the next image's RoIPool back on the first); stage 2 = the heads (+ geometry, or stage 3).  int7 writes
     // its slabs where the previous search's heads read theirs: it waits for that search's stage 2, which ended ~1000 us
-    // before.  One lane, three queued: 1.130-1.135 -> 1.116 ms per image.  AZ_I7_STAGE1=0: int7 in stage 2 (measurements).
-    static const int i7s1 = getenv("AZ_I7_STAGE1") ? atoi(getenv("AZ_I7_STAGE1")) : 1;
-    const bool i7_first = split && i7s1 && c->part7;
+    // before.  One lane, three queued: 1.130-1.135 -> 1.116 ms per image.  (A head without slabs of int7's own: int7 in stage 2.)
+    const bool i7_first = split && c->part7;
     if (split && !i7_first) {
         // stage 2 from here on: int7 behind the slab sum, everything the caller enqueues behind this pass behind int7
         if (hipEventRecord(c->ev_h6, c->stream) != hipSuccess || hipStreamWaitEvent(s2, c->ev_h6, 0) != hipSuccess) c->async_err = 1;
@@ -637,17 +651,17 @@ void launch_head(az_ctx *c, const int *Uptr, int level, int im_h, int im_w, doub
     float *p7 = c->part7 ? c->part7 : c->part;
     bool ring = false;
     if (i7_first) {
-        if (c->part7_ring_env < 0) { const char *e = getenv("AZ_P7_RING"); c->part7_ring_env = (e && !atoi(e)) ? 0 : 1; }
-        if (c->part7_ring_env && !c->part7_ring[1]) {
+        if (!c->part7_no_room && !c->part7_ring[1]) {
             c->part7_ring[0] = c->part7;
-            for (int q = 1; q < 3 && c->part7_ring_env; ++q)
-                if (dalloc(c, &c->part7_ring[q], (size_t)c->S7 * c->maxR * d.n7) != AZ_OK) { c->err.clear(); (void)hipGetLastError(); c->part7_ring_env = 0; }
-            if (!c->part7_ring_env) c->part7_ring[1] = c->part7_ring[2] = nullptr;     // (no room: one buffer + the wait)
+            for (int q = 1; q < 3 && !c->part7_no_room; ++q)
+                if (dalloc(c, &c->part7_ring[q], (size_t)c->S7 * c->maxR * d.n7) != AZ_OK) { c->err.clear(); (void)hipGetLastError(); c->part7_no_room = true; }
+            if (c->part7_no_room) c->part7_ring[1] = c->part7_ring[2] = nullptr;     // (no room: one buffer + the wait)
         }
-        if (c->part7_ring_env && c->part7_ring[2] && c->part7_ring[0] == c->part7) {
+        if (!c->part7_no_room && c->part7_ring[2] && c->part7_ring[0] == c->part7) {
             p7 = c->part7_ring[c->part7_turn];
             c->part7_turn = (c->part7_turn + 1) % 3;
-            ring = true;
+            ring = !c->part7_wait;           // (a failed launch's buffer is not among the three unfetched searches': wait once)
+            c->part7_wait = false;
         }
     }
     unsigned long long *ts7 = span_slot("fc7_gemm");
@@ -762,6 +776,7 @@ int stage_impl(az_ctx *c, void *dst_dev, size_t cap_bytes);
 // the scales of a pyramid entry checked (S in [1, AZ_PYRAMID_MAX], every scale positive and finite, fp32 GEMM mode) and
 // packed; the context's error set on failure (`who`: the entry's name)
 int pyramid_args(az_ctx *c, const double *scales, int S, AzPyrScales *sc, const char *who);
+// ---- az_batch.hip --------------------------------------------------------------------------------------------------------
 // n images (one shape or several, the same number of levels) in lockstep on lane L (whose head buffers the passes use), image b
 // on slots[b] with parameters params[b] and map maps[b] of Hs[b] x Ws[b] cells;
 // AZ_ERR_STATE + *not_taken = 1: this shape / these settings do not take the lockstep form (nothing enqueued)

@@ -343,7 +343,6 @@ void azk_fc_gemm12(hipStream_t s, const float *x, int ldx, const float *W, int l
 void azk_fc_gemm(hipStream_t s, const float *x, int ldx, const float *W, int ldw, const int *Mptr, int capM,
                  int N, int K, int S, float *part, int max_strips = 1 << 30, unsigned long long *ts = nullptr);
 int azk_fc_chunk(int K, int S);
-int azk_gemm_grid();
 // ---- int6 on the 16-bit matrix cores (az_head_terms.hip): operands as `parts` planes of 16-bit terms ----
 // Activation (pool5) planes: tile-major -- block (row / 32, k / 32) holds 32 rows x 32 terms (2 KB), K padded to a
 // multiple of 32 (the padding is zeroed once, at allocation) -- so that a wave's tile load is 1 KB contiguous.

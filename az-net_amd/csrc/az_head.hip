@@ -285,12 +285,6 @@ constexpr int GEMM_GRID = 512;       // 2 workgroups per CU, multiple of 8 XCDs
 #ifndef DENSE_MIN_NRT
 #define DENSE_MIN_NRT 1     /* (1 vs 2: 130 rows = 3 strips | 1 strip + half: 241 -> 234 us; neutral elsewhere) */
 #endif
-static int gemm_grid()
-{
-    static int g = -1;
-    if (g < 0) { const char *e = getenv("AZ_GEMM_GRID"); g = e ? atoi(e) : GEMM_GRID; }
-    return g;
-}
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef float floatx4 __attribute__((ext_vector_type(4)));
@@ -674,7 +668,7 @@ __device__ __forceinline__ void fc_tile(const float *__restrict__ X, int ldx, co
 __global__ void __launch_bounds__(256, 2)
 k_fc_splitk(const float *__restrict__ X, int ldx, const float *__restrict__ Wt, int ldw,
             const int *Mptr, int capM, int N, int K, int S, int Kc, float *__restrict__ part, int max_strips,
-            int half_enabled, unsigned long long *ts)
+            unsigned long long *ts)
 {
     __shared__ __attribute__((aligned(16))) float sA[2][BM * LDT];
     __shared__ __attribute__((aligned(16))) float sB[2][BN * LDT];
@@ -722,28 +716,27 @@ k_fc_splitk(const float *__restrict__ X, int ldx, const float *__restrict__ Wt, 
     // If the balanced split would end in a 1- or 2-strip tile (the weight-streaming code path), the
     // strips are dealt front-loaded instead -- e.g. 4 strips + half as (3, 1+half), not (2, 2+half).
     bool half_last = false, front = false;
-    if ((half_enabled & 1) && mloop && (M & 31) && (M & 31) <= 16 && (M >> 5) >= 1) {
+    if (mloop && (M & 31) && (M & 31) <= 16 && (M >> 5) >= 1) {
         const int st2 = M >> 5;
         int mt2 = tiles_for(st2), s0, nrt_last;
         mtile_rows(st2, mt2, mt2 - 1, s0, nrt_last);
         if (nrt_last == 4) {
             ++mt2;
             mtile_rows(st2, mt2, mt2 - 1, s0, nrt_last);
-            front = nrt_last < 3 && !(half_enabled & 4);
+            front = nrt_last < 3;
         }
         strips = st2; mt = mt2; half_last = true;
     }
     // spread items (fewer groups than workgroups) with <= 16 rows past the last full strip: those rows are a half strip in
     // the LAST tile, the tiles counted as if it were a strip -- 48 rows = (1 strip | half strip), 144 = (2 | 2 + half)
-    if ((half_enabled & 1) && !mloop && (M & 31) && (M & 31) <= 16 && (M >> 5) >= 1) {
+    if (!mloop && (M & 31) && (M & 31) <= 16 && (M >> 5) >= 1) {
         const int st2 = M >> 5;
         const int mt2 = tiles_for(st2 + 1);
         int s0, nrt_last;
         mtile_rows(st2, mt2, mt2 - 1, s0, nrt_last);
         if (mt2 >= 2 && nrt_last <= 3) { strips = st2; mt = mt2; half_last = true; }
     }
-    // (half_enabled bit 4: no quarter strips -- AZ_GEMM_QUART=0, measurements)
-    const bool quart_last = half_last && (M & 31) <= 8 && !(half_enabled & 16);
+    const bool quart_last = half_last && (M & 31) <= 8;
     const int nitems = mloop ? G : G * mt;
     // Two tiles per group on a full grid: workgroups b and b + 8 -- the same XCD, hence the same L2 -- take the two tiles
     // of ONE group at the same time (the group's weight panel comes from memory once); b and b + 256 tend to share a CU
@@ -751,7 +744,7 @@ k_fc_splitk(const float *__restrict__ X, int ldx, const float *__restrict__ Wt, 
     // fetched twice.)
     const bool xcd_pairs = !mloop && mt == 2 && nitems == (int)gridDim.x && (nitems & 15) == 0 && (((int)gridDim.x / 2) & 15) == 0;
     // (256 % mt != 0 in general: the rotation that makes tile(b + 256) = tile(b) + mt / 2)
-    const int pair_rot = (half_enabled & 8) ? 0 : (((mt >> 1) - (int)(gridDim.x / 2) % mt) % mt + mt) % mt;
+    const int pair_rot = (((mt >> 1) - (int)(gridDim.x / 2) % mt) % mt + mt) % mt;
 
     for (int item = blockIdx.x; item < nitems; item += gridDim.x) {
         int g = mloop ? item : item / mt;
@@ -763,7 +756,7 @@ k_fc_splitk(const float *__restrict__ X, int ldx, const float *__restrict__ Wt, 
         float *slab = part + (size_t)s * capM * N;
         // (spread items: m-tiles differ by one strip -- front ones larger.  Workgroups b and b + gridDim / 2 tend to
         //  share a CU (two resident per CU): the second half of the grid walks the m-tiles rotated by half a turn, so a
-        //  CU gets a larger and a smaller tile rather than two large ones.  AZ_GEMM_PAIR=0: plain order.)
+        //  CU gets a larger and a smaller tile rather than two large ones.)
         int t_sp = xcd_pairs ? (((item >> 3) + (item >= (int)gridDim.x / 2 ? 1 : 0)) & 1) : item - g * mt;
         // (a whole group rotates or not -- decided by where its first item falls --, so every m-tile is still visited once)
         if (!mloop && !xcd_pairs && pair_rot && (((g * mt) / ((int)gridDim.x / 2)) & 1)) t_sp = (t_sp + pair_rot) % mt;
@@ -1123,14 +1116,9 @@ void azk_nchw_to_nhwc(hipStream_t s, const float *in, float *out, int C, int HW)
 // Fixed number of K chunks per layer (independent of M; see the header comment).
 int azk_fc_split(int K)
 {
-    // (AZ_SPLIT_BIG: measurements -- the number of chunks is part of a row's bits, so it is one per process)
-    static int big = -1;
-    if (big < 0) { const char *e = getenv("AZ_SPLIT_BIG"); big = (e && atoi(e) > 0) ? atoi(e) : 16; }
-    if (K >= 16384) return big;
-    // (AZ_SPLIT_MID: measurements, as AZ_SPLIT_BIG -- int7's chunk count)
-    static int mid = -1;
-    if (mid < 0) { const char *e = getenv("AZ_SPLIT_MID"); mid = (e && atoi(e) > 0) ? atoi(e) : 8; }
-    if (K >= 2048) return mid;
+    // (the number of chunks is part of a row's bits)
+    if (K >= 16384) return 16;
+    if (K >= 2048) return 8;
     if (K >= 512) return 2;
     return 1;
 }
@@ -1145,18 +1133,11 @@ static int fc_chunk(int K, int S)
 void azk_fc_gemm(hipStream_t s, const float *x, int ldx, const float *W, int ldw, const int *Mptr, int capM,
                  int N, int K, int S, float *part, int max_strips, unsigned long long *ts)
 {
-    static int half = -1;                  // AZ_GEMM_HALF=0: pad the last rows to a full strip instead (measurements)
-    if (half < 0) {
-        const char *e = getenv("AZ_GEMM_HALF"), *f = getenv("AZ_GEMM_BALANCED"), *g = getenv("AZ_GEMM_PAIR");     // (bit 2: balanced tiles, bit 3: no pair rotation: measurements)
-        const char *q = getenv("AZ_GEMM_QUART");
-        half = ((e ? atoi(e) : 1) ? 1 : 0) | ((f && atoi(f)) ? 4 : 0) | ((g && !atoi(g)) ? 8 : 0) | ((q && !atoi(q)) ? 16 : 0);
-    }
-    hipLaunchKernelGGL(k_fc_splitk, dim3(gemm_grid()), dim3(256), 0, s, x, ldx, W, ldw, Mptr, capM, N, K, S,
-                       fc_chunk(K, S), part, max_strips, half, ts);
+    hipLaunchKernelGGL(k_fc_splitk, dim3(GEMM_GRID), dim3(256), 0, s, x, ldx, W, ldw, Mptr, capM, N, K, S,
+                       fc_chunk(K, S), part, max_strips, ts);
 }
 
 int azk_fc_chunk(int K, int S) { return fc_chunk(K, S); }
-int azk_gemm_grid() { return gemm_grid(); }
 
 void azk_fc_reduce(hipStream_t s, const float *part, const float *bias, const int *Mptr, int capM, int N,
                    int S, float *y, int ldy, int relu)

@@ -331,7 +331,7 @@ __device__ __forceinline__ int tile12(const float *__restrict__ X, int ldx, cons
 
 __global__ void __launch_bounds__(W_NT)
 k_fc_splitk12(const float *__restrict__ X, int ldx, const float *__restrict__ Wt, int ldw, const int *Mptr, int capM,
-              int N, int K, int S, int Kc, float *__restrict__ part, int min_rows, int pair_mode, unsigned long long *ts)
+              int N, int K, int S, int Kc, float *__restrict__ part, int min_rows, unsigned long long *ts)
 {
     extern __shared__ __attribute__((aligned(16))) float lds12[];
     float *sA = lds12, *sB = lds12 + 2 * W_BM * W_LDT;
@@ -355,7 +355,7 @@ k_fc_splitk12(const float *__restrict__ X, int ldx, const float *__restrict__ Wt
     // swapping from group to group so that the 11- and the 10-strip tile do not let one drift ahead): the second read of
     // a weight tile then finds it in L2 instead of going to memory again.  Same items, same bits; only who does which.
     // (every workgroup then has G / (grid / 2) items -- the ngrp * mt it has anyway when the groups divide evenly)
-    const bool paired = pair_mode && mt == 2 && ((int)gridDim.x & 15) == 0 && G % (int)gridDim.x == 0;
+    const bool paired = mt == 2 && ((int)gridDim.x & 15) == 0 && G % (int)gridDim.x == 0;
     const int pq = ((int)blockIdx.x / 16) * 8 + ((int)blockIdx.x & 7), prole = ((int)blockIdx.x >> 3) & 1;
     auto item_at = [&](int idx) {
         int gi = idx / mt, t = idx - gi * mt;
@@ -424,9 +424,6 @@ int azk_fc_gemm12_prepare()
 void azk_fc_gemm12(hipStream_t s, const float *x, int ldx, const float *W, int ldw, const int *Mptr, int capM, int N,
                    int K, int S, int Kc, float *part, int min_rows, unsigned long long *ts)
 {
-    static int grid = -1, pair = -1;    // AZ_GEMM12_GRID, AZ_GEMM12_PAIR=0: environment switches, the same for every device
-    if (grid < 0) { const char *e = getenv("AZ_GEMM12_GRID"); grid = e ? atoi(e) : 256; }
-    if (pair < 0) { const char *e = getenv("AZ_GEMM12_PAIR"); pair = (e && !atoi(e)) ? 0 : 1; }
-    hipLaunchKernelGGL(k_fc_splitk12, dim3(grid), dim3(W_NT), lds12_bytes(), s, x, ldx, W, ldw, Mptr, capM, N, K, S, Kc, part, min_rows,
-                       pair, ts);
+    hipLaunchKernelGGL(k_fc_splitk12, dim3(256), dim3(W_NT), lds12_bytes(), s, x, ldx, W, ldw, Mptr, capM, N, K, S, Kc, part, min_rows,
+                       ts);
 }

@@ -367,7 +367,7 @@ template <int WAVES, int AROWS, int P, bool F16, int CW>
 __global__ void __launch_bounds__(WAVES * 64, 2)
 k_fc_terms(const unsigned short *__restrict__ Xp, int ldx, size_t xplane, const unsigned short *__restrict__ Wp,
            int ldw, size_t wplane, const int *Mptr, int capM, int N, int K, int S, int Kc,
-           float *__restrict__ part, int min_strips, int max_strips, int xcd_order, const float *__restrict__ scales)
+           float *__restrict__ part, int min_strips, int max_strips, const float *__restrict__ scales)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned short lds[];
     const int M = *Mptr;
@@ -401,7 +401,7 @@ k_fc_terms(const unsigned short *__restrict__ Xp, int ldx, size_t xplane, const 
         default: if constexpr (AROWS > 64) fc_tile_terms<4, WAVES, AROWS, P, F16, CW>(Xp, ldx, xplane, Wp, ldw, wplane, M, N, m0, wstrip0, n0, k0, kend, slab, lds, oscale); break;
         }
     };
-    if (xcd_order && mt > 1 && gridDim.x == 256 && (S & 7) == 0) {
+    if (mt > 1 && gridDim.x == 256 && (S & 7) == 0) {
         // What limits this kernel is the operand feed from beyond the L2 (an XCD's 32 workgroups stream 32 different
         // weight panels).  Work items (group, m-tile) are dealt so that, on one XCD (workgroups b = x mod 8), the m-tiles
         // of a group run at the same time on neighbouring workgroups (one fetch of the weight panel serves mt readers
@@ -495,13 +495,13 @@ template <int P, bool F16, int CW> struct TermsShape {
         return 0;
     }
     static void launch(hipStream_t s, const unsigned short *Xp, int ldx, size_t xplane, const unsigned short *Wp, int ldw,
-                       size_t wplane, const int *Mptr, int capM, int N, int K, int S, int Kc, float *part, int xcd_order,
+                       size_t wplane, const int *Mptr, int capM, int N, int K, int S, int Kc, float *part,
                        const float *scales)
     {
         hipLaunchKernelGGL((k_fc_terms<4, 64, P, F16, 1>), dim3(512), dim3(256), shm_n, s, Xp, ldx, xplane, Wp, ldw, wplane,
-                           Mptr, capM, N, K, S, Kc, part, 1, 2, 0, scales);
+                           Mptr, capM, N, K, S, Kc, part, 1, 2, scales);
         hipLaunchKernelGGL((k_fc_terms<8, 256, P, F16, CW>), dim3(256), dim3(512), shm_w, s, Xp, ldx, xplane, Wp, ldw, wplane,
-                           Mptr, capM, N, K, S, Kc, part, 3, 1 << 30, xcd_order, scales);
+                           Mptr, capM, N, K, S, Kc, part, 3, 1 << 30, scales);
     }
 };
 typedef TermsShape<2, true, 2> Terms2;       // two fp16 terms: 256 x 256 tiles
@@ -519,9 +519,8 @@ int azk_fc_gemm_terms(hipStream_t s, const unsigned short *Xp, int ldx, size_t x
                       int ldw, size_t wplane, const int *Mptr, int capM, int N, int K, int S, int Kc, float *part,
                       int parts, const float *scales)
 {
-    static const int xcd_order = getenv("AZ_X3_ORDER") ? atoi(getenv("AZ_X3_ORDER")) : 1;      // experiment knob
-    if (parts == 3) Terms3::launch(s, Xp, ldx, xplane, Wp, ldw, wplane, Mptr, capM, N, K, S, Kc, part, xcd_order, scales);
-    else if (parts == 2) Terms2::launch(s, Xp, ldx, xplane, Wp, ldw, wplane, Mptr, capM, N, K, S, Kc, part, xcd_order, scales);
+    if (parts == 3) Terms3::launch(s, Xp, ldx, xplane, Wp, ldw, wplane, Mptr, capM, N, K, S, Kc, part, scales);
+    else if (parts == 2) Terms2::launch(s, Xp, ldx, xplane, Wp, ldw, wplane, Mptr, capM, N, K, S, Kc, part, scales);
     else return -1;
     return 0;
 }

@@ -70,7 +70,7 @@ static __device__ __forceinline__ void level_geom_body(const AzLevelArgs &a)
     // Both read the same inputs.  The chain writes the NEXT level's index / inv_index / rois / counters; the only one of
     // those that shares a name with an input is inv_index, which is why a.inv (this level's) and a.inv_next are two
     // buffers: the copier may be dispatched late (CUs held by another context's GEMM) and read a.inv at any time.
-    const bool copier = gridDim.x == 1 || blockIdx.x == 1, chain = blockIdx.x == 0;
+    const bool copier = blockIdx.x == 1, chain = blockIdx.x == 0;
     const int P = cnt->P[l];
     const int U = *a.Uptr;
     const int ybase = cnt->ytot[l];
@@ -385,9 +385,7 @@ __global__ void __launch_bounds__(NT) k_level_geom_b(const AzLevelArgs *args) { 
 
 void azk_level_geom(hipStream_t s, const AzLevelArgs &a)
 {
-    static int two = -1;                 // AZ_LEVEL_WGS=1: one workgroup does both roles (measurements)
-    if (two < 0) { const char *e = getenv("AZ_LEVEL_WGS"); two = (e && atoi(e) == 1) ? 0 : 1; }
-    hipLaunchKernelGGL(k_level_geom, dim3(two ? 2 : 1), dim3(NT), 0, s, a);
+    hipLaunchKernelGGL(k_level_geom, dim3(2), dim3(NT), 0, s, a);
 }
 
 void azk_level_geom_batch(hipStream_t s, const AzLevelArgs *args_dev, int n)

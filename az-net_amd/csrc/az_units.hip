@@ -258,12 +258,11 @@ int az_nms(az_ctx *c, const float *dets, int n, double thresh, int64_t *keep, in
           azk_nms_one_small(s, hd, n, thresh, hk, hn, tag); }
         // Poll the result in the mapped block -- a stream synchronisation costs an interrupt round trip (~10-15 us) on top of
         // a kernel of about that length.  Count and keep entries carry the call's tag (words may land out of order); the
-        // stream's own completion is picked up by whatever uses it next (same stream: ordered).  (AZ_NMS_POLL=0, profiling,
-        // or no answer within a millisecond: the plain wait, after which everything is visible.)
-        static const bool poll = !(getenv("AZ_NMS_POLL") && !atoi(getenv("AZ_NMS_POLL")));
+        // stream's own completion is picked up by whatever uses it next (same stream: ordered).  (Profiling, or no answer
+        // within a millisecond: the plain wait, after which everything is visible.)
         const unsigned want = tag & 0x3FFFFFu;
         bool got = false;
-        if (poll && !c->profiling) {
+        if (!c->profiling) {
             const volatile int *vn = hn;
             for (int spin = 0; spin < 200000 && !got; ++spin) got = ((unsigned)*vn >> 9) == want;
             if (got) got = nms_keep_tagged(hk, (int)((unsigned)*vn & 0x1FFu), tag, 200000);
@@ -298,8 +297,7 @@ int az_nms(az_ctx *c, const float *dets, int n, double thresh, int64_t *keep, in
     int *nk = c->nms_order + c->nms_cap;      // spare int after the order array
     HIPCHK(c, hipMemcpyAsync(c->nms_dets, dets, (size_t)n * 5 * 4, hipMemcpyHostToDevice, s));
     if (!(c->profiling & 4)) clear_events(c);
-    static const bool poll_g = !(getenv("AZ_NMS_POLL") && !atoi(getenv("AZ_NMS_POLL")));
-    if (poll_g && !c->profiling) {
+    if (!c->profiling) {
         // keep list and count straight into host-mapped memory, the count last (k_nms_scan): no copy-back commands, no
         // stream synchronisation -- the host polls the count
         const size_t need = (size_t)n * 8 + 64;
@@ -643,8 +641,7 @@ int az_nms_batched(az_ctx *c, const float *dets, const int32_t *offsets, int n_g
     if (total > 0 && (!dets || !keep)) return fail(c, AZ_ERR_INVALID, "az_nms_batched: NULL array");
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    static const bool poll = !(getenv("AZ_NMS_POLL") && !atoi(getenv("AZ_NMS_POLL")));
-    if (!small.empty() && poll && !c->profiling && total <= 16384) {
+    if (!small.empty() && !c->profiling && total <= 16384) {
         // The reference's call site (apply_nms: 20 classes x <= 100 boxes per image): everything -- boxes, offsets, group
         // list, keep lists, counts -- lives in ONE host-mapped block; one launch, no copy commands, and the host polls a
         // flag that the last workgroup to finish raises (a stream synchronisation plus five copies cost 70 of 96 us).

@@ -1,6 +1,6 @@
 """Stress of az_nms / az_nms_batched against a NumPy restatement of nms.pyx with this library's tie rule
 (descending score, HIGHER index first): which path, if any, ever returns a wrong keep list?
-    python tests/dev/nms_flaky.py [rounds]         (AZ_NMS_POLL=0 for the stream-wait form)"""
+    python tests/dev/nms_flaky.py [rounds]"""
 import os, sys
 import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "..", "az-net_amd", "lib"))
@@ -57,7 +57,7 @@ def main():
                 if list(k1) != refs[t][gi]:
                     bad["single"] += 1
                     detail.append(("single", r, t, gi, len(d), len(k1), len(refs[t][gi])))
-    print("rounds", rounds, "AZ_NMS_POLL", os.environ.get("AZ_NMS_POLL"), "mismatches", bad)
+    print("rounds", rounds, "mismatches", bad)
     for x in detail[:40]:
         print("  ", x)
 

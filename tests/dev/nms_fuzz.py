@@ -1,6 +1,6 @@
 """Longer runs of tests/test_gpu_nms_fuzz.py's adversarial cases (ties, duplicates, clusters, grid boxes, degenerate boxes,
 thresholds 0 / 1 / > 1, sizes around the kernel and chunk boundaries) against the oracle's walk in the kernel's documented
-tie order.  usage: nms_fuzz.py [cases] [seed]   (AZ_NMS_POLL=0: the copy-back path instead of the polled one)"""
+tie order.  usage: nms_fuzz.py [cases] [seed]"""
 import sys
 sys.path.insert(0, "az-net_amd/lib"); sys.path.insert(0, "."); sys.path.insert(0, "tests")
 import numpy as np

@@ -1,4 +1,4 @@
-"""int6 / int7 launch times by row count through az_head_forward (HIP events per launch group): AZ_GEMM_QUART=0|1 A/B."""
+"""int6 / int7 launch times by row count through az_head_forward (HIP events per launch group)."""
 import sys
 sys.path.insert(0, "az-net_amd/lib"); sys.path.insert(0, ".")
 import numpy as np, torch

@@ -1,4 +1,4 @@
-"""A batch of images of one shape searched in lockstep (az_batch_launch; az-net_amd/csrc/az_batch.hip, az_search.hip:
+"""A batch of images of one shape searched in lockstep (az_batch_launch; az-net_amd/csrc/az_batch.hip:
 batch_launch_impl) -- the images of consecutive iterations of the reference's dataset loop (lib/detect/test.py:508-513), each
 with its own tree, every level's rois of all of them in ONE head pass.  Whatever shares a pass with an image, its result is
 what the plain level loop (and the CPU oracle) give for that image alone: boxes, scores, every counter, bit for bit."""
