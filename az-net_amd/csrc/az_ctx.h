@@ -407,6 +407,7 @@ struct az_ctx {
     std::vector<hipEvent_t> event_pool;   // recycled events
     std::vector<void *> allocs;        // head-sized buffers (az_load_head)
     std::vector<void *> allocs_geom;   // geometry buffers (first use)
+    std::vector<az_solver *> solvers;  // trainers created on this context (az_solver.hip), freed with it
     bool geom_ready = false;
 };
 
@@ -793,6 +794,8 @@ struct RankScratch {
 void rank_scratch_sizes(int D, size_t *hist_n, size_t *sums_n);
 void rank_by_score(hipStream_t s, int D, long long S, int n_images, int n_classes, const double *score, const int *det_off,
                    const RankScratch &r, const unsigned **by_seg, const unsigned **by_class);
+// ---- az_solver.hip -------------------------------------------------------------------------------------------------------
+void az_solver_free_all(az_ctx *c);       // az_destroy: the trainers still alive
 // ---- az_capi.hip --------------------------------------------------------------------------------------------------------
 int set_feature_map_common(az_ctx *c, const float *src, bool src_is_host, int C, int H, int W, bool wait = true);
 int ensure_lane_head(az_ctx *t);          // the head buffers of a lane / batch slot created without them

@@ -98,6 +98,36 @@ class VGG16Conv5(object):
 
     __call__ = forward
 
+    def set_trainable(self, names):
+        """The convolutions whose parameters take gradients in forward_train (train.prototxt: lr_mult > 0); every other
+        layer is frozen.  Returns [(name, weight, bias)] of the trainable ones: leaf tensors whose .grad backward fills."""
+        out = []
+        for layer in self.layers:
+            if layer is None:
+                continue
+            on = layer[0] in names
+            layer[1].requires_grad_(on)
+            layer[2].requires_grad_(on)
+            if on:
+                out.append(layer)
+        return out
+
+    def forward_train(self, blob):
+        """conv5_3 [N,C,h,w] of a training blob [N,3,H,W] with autograd through the layers set_trainable named: plain torch
+        ops (the fused in-place bias / ReLU kernels of `forward` are not differentiable); the frozen layers in front of
+        the first trainable one run under no_grad.  The solver calls conv5_3.backward(d conv5_3)."""
+        x = torch.as_tensor(blob, dtype=torch.float32, device=self.device)
+        if self.cl_compute:
+            x = x.contiguous(memory_format=torch.channels_last)
+        for layer in self.layers:
+            if layer is None:
+                x = F.max_pool2d(x, kernel_size=2, stride=2, ceil_mode=True)
+                continue
+            _, w, b = layer
+            with torch.set_grad_enabled(bool(x.requires_grad or w.requires_grad)):
+                x = F.relu(F.conv2d(x, w, b, padding=1))
+        return x if (x.is_contiguous() or x.is_contiguous(memory_format=torch.channels_last)) else x.contiguous()
+
     @torch.no_grad()
     def normalize_output(self, blob):
         """Synthetic (random-init) weights only: rescale conv5_3's filters so the map has

@@ -43,6 +43,8 @@ SYMBOLS = [
     "az_set_feature_pyramid_dev_nhwc", "az_roi_dedup_pyramid", "az_roi_pool_pyramid", "az_propose_pyramid",
     "az_detect_pyramid",
     "az_zoom_labels", "az_train_ex_rois", "az_train_adj_targets", "az_train_target_stats",
+    "az_solver_create", "az_solver_destroy", "az_solver_load", "az_solver_read", "az_solver_set_hyper", "az_solver_step",
+    "az_solver_update", "az_sgd_update", "az_solver_forward_test", "az_solver_fetch", "az_solver_gemm_unit",
 ]
 
 
@@ -219,6 +221,18 @@ def load_library(path=None):
     L.az_train_ex_rois.argtypes = [vp, tpp, ci, ip, dp, ip, dp, ll, fp, u8p, ip, ci, llp, llp]
     L.az_train_adj_targets.argtypes = [vp, tpp, ci, fp, ip, fp, ip, dp, ip, ci]
     L.az_train_target_stats.argtypes = [vp, ci, cd, dp, ll, dp, dp, ci]
+    u64 = ctypes.c_uint64
+    L.az_solver_create.argtypes = [vp, ci, ci, ci, ci, ci, u64, ctypes.POINTER(vp)]
+    L.az_solver_destroy.argtypes = [vp]
+    L.az_solver_load.argtypes = [vp] + [fp] * 12
+    L.az_solver_read.argtypes = [vp] + [fp] * 12
+    L.az_solver_set_hyper.argtypes = [vp, fp, fp, fp]
+    L.az_solver_step.argtypes = [vp, vp, ci, ci, ci, ci, fp, ci, fp, fp, fp, fp, u64, ll, fp, dp, vp]
+    L.az_solver_update.argtypes = [vp, cd, cd, cd, cd]
+    L.az_sgd_update.argtypes = [vp, vp, vp, vp, ll, cd, cd, cd, cd]
+    L.az_solver_forward_test.argtypes = [vp, vp, ci, ci, ci, ci, fp, ci, fp, fp, fp]
+    L.az_solver_fetch.argtypes = [vp, ctypes.c_char_p, vp, ll, llp]
+    L.az_solver_gemm_unit.argtypes = [vp, ci, fp, fp, fp, ci, ci, ci]
     L.az_image_blob_size.argtypes = [ci, ci, cd, cip, cip]
     L.az_image_blob_host.argtypes = [vp, u8p, ci, ci, fp, cd, fp, ci, ci]
     L.az_image_blob_dev.argtypes = [vp, u8p, ci, ci, fp, cd, vp, ci, ci]
@@ -1261,6 +1275,192 @@ class AzContext(object):
 
 
 _default_ctx = None
+
+
+HEAD_KEYS = ("W6", "b6", "W71", "b71", "W72", "b72", "Was", "bas", "Wab", "bab", "Wz", "bz")
+_SOLVER_U8 = ("mask6", "mask71", "mask72")
+
+
+def dropout_mask(seed, iteration, layer, n, ratio=0.5):
+    """The NumPy form of the trainer's dropout mask (include/aznet_hip.h, az_solver_step): keep flags (uint8) of the elements
+    0 .. n-1 of layer 0 / 1 / 2 (int6, int7_1, int7_2) at (seed, iteration)."""
+    M = (1 << 64) - 1
+
+    def mix(z):
+        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M
+        return z ^ (z >> 31)
+    G = 0x9E3779B97F4A7C15
+    key = mix((mix((mix((int(seed) + G) & M) + int(iteration)) & M) + int(layer)) & M)
+    with np.errstate(over="ignore"):
+        z = np.uint64(key) + np.uint64(G) * (np.arange(n, dtype=np.uint64) + np.uint64(1))
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z = z ^ (z >> np.uint64(31))
+    return ((z >> np.uint64(40)) >= np.uint64(int(float(ratio) * 16777216.0))).astype(np.uint8)
+
+
+def sgd_update_numpy(w, g, hist, rate, momentum, decay, clip_scale):
+    """The NumPy form of az_sgd_update / az_solver_update for one blob (float32, one rounding per operation; rate and decay
+    already carry lr_mult / decay_mult): returns (w, hist) after the step."""
+    f = np.float32
+    gg = g.astype(f) * f(clip_scale)
+    gg = gg + f(decay) * w
+    h = f(momentum) * hist + f(rate) * gg
+    return w - h, h
+
+
+class AzSolver(object):
+    """The AZ-net trainer behind conv5_3 (az_solver_*): fp32 master weights, gradients and momentum history of the head in
+    HBM; one `step` is forward + backward of a minibatch, `update` Caffe's SGD step."""
+
+    def __init__(self, ctx, C, n6, n71, n72, max_rois=256, seed=0, head=None):
+        self.ctx, self.L = ctx, ctx.L
+        h = ctypes.c_void_p()
+        ctx._chk(self.L.az_solver_create(ctx.h, int(C), int(n6), int(n71), int(n72), int(max_rois), int(seed) & ((1 << 64) - 1),
+                                         ctypes.byref(h)))
+        self.h = h
+        self.dims = dict(C=int(C), n6=int(n6), n71=int(n71), n72=int(n72), K6=int(C) * 49)
+        self.max_rois = int(max_rois)
+        self.last_rows = 0
+        if head is not None:
+            self.load(head)
+
+    def _shapes(self):
+        d = self.dims
+        return {"W6": (d["n6"], d["K6"]), "b6": (d["n6"],), "W71": (d["n71"], d["n6"]), "b71": (d["n71"],),
+                "W72": (d["n72"], d["n6"]), "b72": (d["n72"],), "Was": (11, d["n71"]), "bas": (11,),
+                "Wab": (44, d["n71"]), "bab": (44,), "Wz": (1, d["n72"]), "bz": (1,)}
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.L.az_solver_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def load(self, head):
+        """head: {name: Caffe-layout array} for any subset of HEAD_KEYS."""
+        shp = self._shapes()
+        arrs = []
+        for k in HEAD_KEYS:
+            if k in head:
+                a = _f32(head[k]).reshape(shp[k])
+                arrs.append(a)
+            else:
+                arrs.append(None)
+        self.ctx._chk(self.L.az_solver_load(self.h, *[_p(a, ctypes.c_float) if a is not None else None for a in arrs]))
+
+    def read(self):
+        out = {k: np.empty(v, dtype=np.float32) for k, v in self._shapes().items()}
+        self.ctx._chk(self.L.az_solver_read(self.h, *[_p(out[k], ctypes.c_float) for k in HEAD_KEYS]))
+        return out
+
+    def set_hyper(self, lr_mult=None, decay_mult=None, dropout_ratio=None):
+        def arr(v, n):
+            if v is None:
+                return None, None
+            a = _f32(v).reshape(n)
+            return a, _p(a, ctypes.c_float)
+        a, pa = arr(lr_mult, 12)
+        b, pb = arr(decay_mult, 12)
+        c, pc = arr(dropout_ratio, 3)
+        self.ctx._chk(self.L.az_solver_set_hyper(self.h, pa, pb, pc))
+
+    def _map(self, conv):
+        """(pointer, N, H, W, channels_last) of a float32 CUDA tensor [N,C,H,W] in either memory format."""
+        import torch
+        assert conv.is_cuda and conv.dtype == torch.float32 and conv.dim() == 4 and conv.shape[1] == self.dims["C"]
+        N, _, H, W = (int(x) for x in conv.shape)
+        if conv.is_contiguous():
+            cl = 0
+        elif conv.is_contiguous(memory_format=torch.channels_last):
+            cl = 1
+        else:
+            raise AzError(AZ_ERR_INVALID, "conv5_3 must be contiguous or channels_last")
+        return ctypes.c_void_p(conv.data_ptr()), N, H, W, cl
+
+    def step(self, conv, rois, adj_labels, adj_targets, adj_loss_weights, zoom_labels, seed, iteration, dmap=None):
+        """Forward + backward of one minibatch.  conv: CUDA tensor [N,C,H,W]; dmap: None or a CUDA tensor of conv's shape and
+        memory format that receives d loss / d conv5_3.  Returns (losses [zoom, adj, bbox] f32, sum of squares of the head's
+        gradients)."""
+        import torch
+        ptr, N, H, W, cl = self._map(conv)
+        rois = _f32(rois).reshape(-1, 5)
+        R = rois.shape[0]
+        al, at, aw = _f32(adj_labels).reshape(R, 11), _f32(adj_targets).reshape(R, 44), _f32(adj_loss_weights).reshape(R, 44)
+        zl = _f32(zoom_labels).reshape(R)
+        dptr = None
+        if dmap is not None:
+            assert dmap.is_cuda and dmap.dtype == conv.dtype and dmap.shape == conv.shape and dmap.stride() == conv.stride()
+            dptr = ctypes.c_void_p(dmap.data_ptr())
+        torch.cuda.current_stream(conv.device).synchronize()
+        losses = np.zeros(3, dtype=np.float32)
+        sq = ctypes.c_double(0.0)
+        f = ctypes.c_float
+        self.ctx._chk(self.L.az_solver_step(self.h, ptr, N, H, W, cl, _p(rois, f), R, _p(al, f), _p(at, f), _p(aw, f), _p(zl, f),
+                                            int(seed) & ((1 << 64) - 1), int(iteration), _p(losses, f), ctypes.byref(sq), dptr))
+        self.last_rows = R
+        return losses, float(sq.value)
+
+    def update(self, rate, momentum, weight_decay, clip_scale=1.0):
+        self.ctx._chk(self.L.az_solver_update(self.h, float(rate), float(momentum), float(weight_decay), float(clip_scale)))
+
+    def forward_test(self, conv, rois):
+        """TEST-phase forward (dropout off): raw (zoom_score [R], adj_score [R,11], adj_bbox [R,44])."""
+        import torch
+        ptr, N, H, W, cl = self._map(conv)
+        rois = _f32(rois).reshape(-1, 5)
+        R = rois.shape[0]
+        z, a, b = np.empty(R, np.float32), np.empty((R, 11), np.float32), np.empty((R, 44), np.float32)
+        torch.cuda.current_stream(conv.device).synchronize()
+        f = ctypes.c_float
+        self.ctx._chk(self.L.az_solver_forward_test(self.h, ptr, N, H, W, cl, _p(rois, f), R, _p(z, f), _p(a, f), _p(b, f)))
+        self.last_rows = R
+        return z, a, b
+
+    def fetch(self, name):
+        """A saved tensor of the last pass by name (az_solver_fetch), shaped."""
+        n = ctypes.c_longlong(0)
+        self.ctx._chk(self.L.az_solver_fetch(self.h, name.encode(), None, 0, ctypes.byref(n)))
+        dt = np.uint8 if name in _SOLVER_U8 else (np.int32 if name == "argmax" else np.float32)
+        out = np.empty(n.value // np.dtype(dt).itemsize, dtype=dt)
+        self.ctx._chk(self.L.az_solver_fetch(self.h, name.encode(), out.ctypes.data_as(ctypes.c_void_p), n.value, ctypes.byref(n)))
+        if len(name) > 2 and name[1] == "_" and name[2:] in HEAD_KEYS:
+            return out.reshape(self._shapes()[name[2:]])
+        return out.reshape(self.last_rows, -1) if self.last_rows else out
+
+
+def sgd_update(ctx, w, g, hist, rate, momentum, decay, clip_scale=1.0):
+    """az_sgd_update on three contiguous float32 CUDA tensors of one size (w and hist are updated in place)."""
+    import torch
+    for t in (w, g, hist):
+        assert t.is_cuda and t.dtype == torch.float32 and t.numel() == w.numel()
+        assert t.is_contiguous() or t.is_contiguous(memory_format=torch.channels_last)
+    assert g.stride() == w.stride() and hist.stride() == w.stride()
+    torch.cuda.current_stream(w.device).synchronize()
+    ctx._chk(ctx.L.az_sgd_update(ctx.h, ctypes.c_void_p(w.data_ptr()), ctypes.c_void_p(g.data_ptr()),
+                                 ctypes.c_void_p(hist.data_ptr()), int(w.numel()), float(rate), float(momentum), float(decay),
+                                 float(clip_scale)))
+
+
+def gemm_unit(ctx, form, a, b):
+    """One product of the trainer's GEMM kernel (az_solver_gemm_unit): form 0 a[M,K] b[N,K]^T, 1 a[M,K] b[K,N], 2 a[K,M]^T b[K,N]."""
+    a, b = _f32(a), _f32(b)
+    if form == 0:
+        (M, K), N = a.shape, b.shape[0]
+    elif form == 1:
+        (M, K), N = a.shape, b.shape[1]
+    else:
+        (K, M), N = a.shape, b.shape[1]
+    d = np.empty((M, N), dtype=np.float32)
+    f = ctypes.c_float
+    ctx._chk(ctx.L.az_solver_gemm_unit(ctx.h, int(form), _p(a, f), _p(b, f), _p(d, f), M, N, K))
+    return d
 
 
 def bias_relu_(y, bias):

@@ -1,0 +1,191 @@
+"""A small reader for the two protobuf TEXT files the reference hands to caffe.SGDSolver (lib/detect/train_az.py:41-49):
+the solver prototxt (flat `key: value`) and, from the `train_net` it names, per layer only what training on this backend
+needs -- `param { lr_mult decay_mult }`, `dropout_ratio` and the weight filler's `std`.  The layer GRAPH is fixed here
+(VGG16 conv1_1 .. conv5_3, roi_pool5, int6, int7_1 / int7_2, adj_score / adj_bbox / zoom_score): a net whose learnable
+layers are not exactly these is refused.  `write_train_prototxt` / `write_solver_prototxt` emit such files from a layer
+table (the synthetic runs of tools/train_az_net.py and the tests; the reference's own files are not shipped)."""
+import os
+import re
+
+CONV_LAYERS = ("conv1_1", "conv1_2", "conv2_1", "conv2_2", "conv3_1", "conv3_2", "conv3_3", "conv4_1", "conv4_2",
+               "conv4_3", "conv5_1", "conv5_2", "conv5_3")
+HEAD_LAYERS = ("int6", "int7_1", "int7_2", "adj_score", "adj_bbox", "zoom_score")
+DROPOUT_OF = {"int6": 0, "int7_1": 1, "int7_2": 2}
+FILLER_STD = {"int6": 1e-4, "int7_1": 1e-4, "int7_2": 1e-3, "adj_score": 1e-2, "adj_bbox": 1e-3, "zoom_score": 1e-2}
+SOLVER_DEFAULTS = dict(base_lr=0.001, lr_policy="step", gamma=0.1, stepsize=120000, momentum=0.9, weight_decay=0.0005,
+                       clip_gradients=-1.0, display=20, average_loss=1, snapshot_prefix="vgg16_az_net", train_net=None)
+
+_TOKEN = re.compile(r"""\s*(?:(\#[^\n]*)|([{}:])|"((?:[^"\\]|\\.)*)"|'((?:[^'\\]|\\.)*)'|([^\s{}:#"']+))""")
+
+
+def _tokens(text):
+    pos, out = 0, []
+    while pos < len(text):
+        m = _TOKEN.match(text, pos)
+        if not m:
+            if text[pos:].strip() == "":
+                break
+            raise ValueError("prototxt: cannot read %r" % text[pos:pos + 20])
+        pos = m.end()
+        if m.group(1) is not None:
+            continue
+        if m.group(2) is not None:
+            out.append((m.group(2), None))
+        elif m.group(3) is not None or m.group(4) is not None:
+            out.append(("str", m.group(3) if m.group(3) is not None else m.group(4)))
+        else:
+            out.append(("word", m.group(5)))
+    return out
+
+
+def _scalar(kind, v):
+    if kind == "str":
+        return v
+    for cast in (int, float):
+        try:
+            return cast(v)
+        except ValueError:
+            pass
+    return {"true": True, "false": False}.get(v, v)
+
+
+def parse_text(text):
+    """Protobuf text format -> a list of (key, value) pairs; a message value is itself such a list."""
+    toks = _tokens(text)
+
+    def block(i, top):
+        items = []
+        while i < len(toks):
+            kind, v = toks[i]
+            if kind == "}":
+                if top:
+                    raise ValueError("prototxt: unbalanced '}'")
+                return items, i + 1
+            if kind != "word":
+                raise ValueError("prototxt: expected a field name, got %r" % (v or kind))
+            key = v
+            i += 1
+            if i < len(toks) and toks[i][0] == ":":
+                i += 1
+            if i >= len(toks):
+                raise ValueError("prototxt: field %s has no value" % key)
+            if toks[i][0] == "{":
+                val, i = block(i + 1, False)
+            else:
+                val = _scalar(*toks[i])
+                i += 1
+            items.append((key, val))
+        if not top:
+            raise ValueError("prototxt: missing '}'")
+        return items, i
+    return block(0, True)[0]
+
+
+def _get(items, key, default=None):
+    for k, v in items:
+        if k == key:
+            return v
+    return default
+
+
+def read_solver(path):
+    """The solver prototxt as a dict over SOLVER_DEFAULTS' keys (other fields, e.g. `snapshot: 0`, are ignored)."""
+    with open(path) as f:
+        items = parse_text(f.read())
+    out = dict(SOLVER_DEFAULTS)
+    for k, v in items:
+        if isinstance(v, list):
+            raise ValueError("solver prototxt: %s is a message; expected flat `key: value` lines" % k)
+        if k in out:
+            out[k] = v
+    if out["train_net"] is None:
+        raise ValueError("solver prototxt %s names no train_net" % path)
+    if out["lr_policy"] not in ("step", "fixed"):
+        raise ValueError("lr_policy %r: this backend implements \"step\" and \"fixed\"" % (out["lr_policy"],))
+    return out
+
+
+def read_train_net(path):
+    """{layer name: {"lr_mult": [w, b], "decay_mult": [w, b], "dropout_ratio": r or None, "std": s or None}} for the
+    thirteen convolutions and the six InnerProduct layers.  Caffe's defaults (1 / 1) stand where a `param` block is absent."""
+    with open(path) as f:
+        items = parse_text(f.read())
+    layers = [v for k, v in items if k in ("layer", "layers") and isinstance(v, list)]
+    if not layers:
+        raise ValueError("%s: no layers" % path)
+    out, drops = {}, {}
+    for L in layers:
+        name, typ = _get(L, "name"), str(_get(L, "type", ""))
+        if typ in ("Convolution", "InnerProduct"):
+            if name not in CONV_LAYERS + HEAD_LAYERS or (typ == "Convolution") != (name in CONV_LAYERS):
+                raise ValueError("%s: learnable layer %r (%s) is not part of the AZ-net this backend trains "
+                                 "(conv1_1 .. conv5_3, %s)" % (path, name, typ, ", ".join(HEAD_LAYERS)))
+            params = [v for k, v in L if k == "param" and isinstance(v, list)]
+            lr = [float(_get(p, "lr_mult", 1.0)) for p in params] + [1.0, 1.0]
+            dc = [float(_get(p, "decay_mult", 1.0)) for p in params] + [1.0, 1.0]
+            std = None
+            ip = _get(L, "inner_product_param")
+            if isinstance(ip, list) and isinstance(_get(ip, "weight_filler"), list):
+                std = _get(_get(ip, "weight_filler"), "std")
+            out[name] = {"lr_mult": lr[:2], "decay_mult": dc[:2], "dropout_ratio": None,
+                         "std": float(std) if std is not None else None}
+        elif typ == "Dropout":
+            dp = _get(L, "dropout_param")
+            drops[_get(L, "bottom")] = float(_get(dp, "dropout_ratio", 0.5)) if isinstance(dp, list) else 0.5
+    missing = [n for n in CONV_LAYERS + HEAD_LAYERS if n not in out]
+    if missing:
+        raise ValueError("%s: not the AZ-net (missing %s)" % (path, ", ".join(missing)))
+    for bottom, r in drops.items():
+        if bottom not in DROPOUT_OF:
+            raise ValueError("%s: Dropout on %r; this backend has it on int6, int7_1, int7_2" % (path, bottom))
+        out[bottom]["dropout_ratio"] = r
+    return out
+
+
+def resolve_train_net(solver_path, train_net):
+    """Caffe opens train_net relative to the working directory; a file beside the solver is accepted as well."""
+    for p in (train_net, os.path.join(os.path.dirname(os.path.abspath(solver_path)), os.path.basename(train_net))):
+        if os.path.exists(p):
+            return p
+    raise IOError("train_net %s not found (from %s)" % (train_net, solver_path))
+
+
+# ---- writers ------------------------------------------------------------------------------------------------------------
+def layer_table(frozen=("conv1_1", "conv1_2", "conv2_1", "conv2_2"), dropout=0.5):
+    """The AZ-net's learnable layers as rows (name, type, lr_mult w, lr_mult b, decay_mult w, decay_mult b, std, dropout):
+    train.prototxt freezes conv1_1 .. conv2_2, the shared variant all thirteen convolutions."""
+    rows = []
+    for n in CONV_LAYERS:
+        f = n in frozen
+        rows.append((n, "Convolution", 0.0 if f else 1.0, 0.0 if f else 2.0, 0.0 if f else 1.0, 0.0, None, None))
+    for n in HEAD_LAYERS:
+        rows.append((n, "InnerProduct", 1.0, 2.0, 1.0, 0.0, FILLER_STD[n], dropout if n in DROPOUT_OF else None))
+    return rows
+
+
+def write_train_prototxt(path, rows):
+    out = ['name: "az_net_train"']
+    for name, typ, lw, lb, dw, db, std, drop in rows:
+        out.append('layer {\n  name: "%s"\n  type: "%s"\n  param {\n    lr_mult: %g\n    decay_mult: %g\n  }\n  param {\n'
+                   '    lr_mult: %g\n    decay_mult: %g\n  }' % (name, typ, lw, dw, lb, db))
+        if std is not None:
+            out.append('  inner_product_param {\n    weight_filler {\n      type: "gaussian"\n      std: %g\n    }\n'
+                       '    bias_filler {\n      type: "constant"\n      value: 0\n    }\n  }' % std)
+        out.append("}")
+        if drop is not None:
+            out.append('layer {\n  name: "drop_%s"\n  type: "Dropout"\n  bottom: "%s"\n  top: "%s"\n  dropout_param {\n'
+                       '    dropout_ratio: %g\n  }\n}' % (name, name, name, drop))
+    with open(path, "w") as f:
+        f.write("\n".join(out) + "\n")
+
+
+def write_solver_prototxt(path, train_net, **kw):
+    d = dict(SOLVER_DEFAULTS)
+    d.update(kw)
+    d["train_net"] = train_net
+    with open(path, "w") as f:
+        for k in ("train_net", "base_lr", "lr_policy", "gamma", "stepsize", "momentum", "weight_decay", "clip_gradients",
+                  "display", "average_loss", "snapshot_prefix"):
+            v = d[k]
+            f.write('%s: %s\n' % (k, '"%s"' % v if isinstance(v, str) else repr(v)))
+        f.write("# snapshots are written by SolverWrapper.snapshot\nsnapshot: 0\n")

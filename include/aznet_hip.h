@@ -546,6 +546,79 @@ int az_train_adj_targets(az_ctx *ctx, const az_train_params *p, int n_images, co
 int az_train_target_stats(az_ctx *ctx, int n_sub, double eps, double *targets, long long T, double *means_out,
                           double *stds_out, int normalise_in_place);
 
+/* ---- AZ-net training from conv5_3 on (models/Pascal/VGG16/az-net/train.prototxt, lib/detect/train_az.py) ------------------ */
+/* Replaces caffe.SGDSolver(solver_prototxt) and solver.step(1) (train_az.py:41,106) for everything behind conv5_3: the layers
+ * roi_pool5 (ROIPooling 7x7, 1/16) -> int6 -> {int7_1 -> adj_score, adj_bbox; int7_2 -> zoom_score} (InnerProduct, ReLU and
+ * Dropout in place on int6 / int7_1 / int7_2), loss_zoom and loss_adj (SigmoidCrossEntropyLoss), loss_bbox (SmoothL1Loss with
+ * adj_targets and adj_loss_weights), all with loss_weight 1 and normalised by the roi rows R.  The convolutions stay with the
+ * caller (PyTorch-ROCm autograd): the step returns d loss / d conv5_3.  A trainer belongs to its az_ctx (az_destroy frees the
+ * trainers still alive), runs on the ctx stream and is synchronous like every other call.  It holds fp32 master weights in
+ * Caffe layout ([out][in]; roi_pool5 flattened c * 49 + p), one gradient and one momentum history per parameter, and the
+ * activations of one step for up to max_rois rows.  The twelve parameters are always in az_load_head's order:
+ *   W6 b6 W71 b71 W72 b72 Was bas Wab bab Wz bz.
+ * fp32 throughout, GEMMs on v_mfma_f32_32x32x2_f32; no floating-point atomics and no scheduling-dependent order in any
+ * reduction: the same step from the same state gives the same bits. */
+typedef struct az_solver az_solver;
+/* net.params as Caffe's fillers leave them (train.prototxt: gaussian std 1e-4, 1e-4, 1e-3, 1e-2, 1e-3, 1e-2 for int6, int7_1,
+ * int7_2, adj_score, adj_bbox, zoom_score; biases 0), drawn from the generator below with `seed` (Box-Muller on the two 24-bit
+ * halves of element e's word under layer id 16 + parameter index; Caffe's own RNG stream is not reproduced); history zero.
+ * lr_mult / decay_mult start at 1 / 1 for weights and 2 / 0 for biases, the dropout ratios at 0.5.  C, n6 multiples of 4. */
+int az_solver_create(az_ctx *ctx, int C, int n6, int n71, int n72, int max_rois, uint64_t seed, az_solver **out);
+int az_solver_destroy(az_solver *s);
+/* solver.net.copy_from(pretrained_model) (train_az.py:45) / net.params[...].data reads (train_az.py:56-61,71-80): host arrays
+ * in Caffe layout; a NULL array is skipped. */
+int az_solver_load(az_solver *s, const float *W6, const float *b6, const float *W71, const float *b71, const float *W72,
+                   const float *b72, const float *Was, const float *bas, const float *Wab, const float *bab, const float *Wz,
+                   const float *bz);
+int az_solver_read(az_solver *s, float *W6, float *b6, float *W71, float *b71, float *W72, float *b72, float *Was, float *bas,
+                   float *Wab, float *bab, float *Wz, float *bz);
+/* param { lr_mult decay_mult } of the six layers ([12], parameter order) and dropout_ratio of int6, int7_1, int7_2 ([3], each
+ * in [0, 1)) as train.prototxt states them; a NULL array keeps the current values. */
+int az_solver_set_hyper(az_solver *s, const float *lr_mult, const float *decay_mult, const float *dropout_ratio);
+/* net.forward() + net.backward() of one minibatch (Caffe Solver::Step before the update).  conv_dev: conv5_3 of N images on the
+ * device, [N][C][H][W] (channels_last = 0) or [N][H][W][C] (1); rois [R][5] (batch index, x1, y1, x2, y2 in network-input
+ * pixels), adj_labels [R][11], adj_targets [R][44], adj_loss_weights [R][44], zoom_labels [R]: host arrays, the blobs of
+ * lib/az_data_layer/layer.py.  losses_out [3] = loss_zoom, loss_adj, loss_bbox; sumsq_out = the sum of squares of the twelve
+ * parameter gradients (which stay on the device for az_solver_update); dmap_dev (may be NULL): d loss / d conv5_3, written over
+ * a caller-owned device buffer of conv_dev's shape and layout.
+ *   ROIPooling: az_roi_pool's arithmetic per roi on image batch_index, arg-max = first maximum in (h, w) scan order; backward:
+ *     every pooled gradient to its arg-max cell (a gather over the rois in row order), empty bins send nothing.
+ *   InnerProduct: y = x W^T + b; dx = dy W, dW = dy^T x, db = column sums in row order.  ReLU passes where its output is > 0.
+ *   SigmoidCrossEntropyLoss: -1/R sum(x (t - [x >= 0]) - log(1 + exp(x - 2 x [x >= 0]))), dx = (sigmoid(x) - t) / R, t in [0, 1].
+ *   SmoothL1Loss: d = w (x - t), f = 0.5 d^2 if |d| < 1 else |d| - 0.5, sum f / R; dx = w (d if |d| < 1 else sign d) / R.
+ *   Dropout (ratio p, layer id L = 0 / 1 / 2 for int6 / int7_1 / int7_2, element e = row * width + column), all in uint64
+ *   arithmetic modulo 2^64:
+ *       mix(z): z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; return z ^ (z >> 31)
+ *       key = mix(mix(mix(seed + 0x9E3779B97F4A7C15) + iteration) + L)
+ *       keep(e) = (mix(key + 0x9E3779B97F4A7C15 * (e + 1)) >> 40) >= floor(p * 2^24);   y = keep ? x * (1 / (1 - p)) : 0
+ *   (Caffe's own RNG stream is not reproduced.)  The backward uses the same mask and scale.
+ * Bad arguments (NULL arrays, R outside [1, max_rois], a batch index outside [0, N)) return AZ_ERR_INVALID before anything is
+ * written. */
+int az_solver_step(az_solver *s, const float *conv_dev, int N, int H, int W, int channels_last, const float *rois, int R,
+                   const float *adj_labels, const float *adj_targets, const float *adj_loss_weights, const float *zoom_labels,
+                   uint64_t seed, long long iteration, float *losses_out, double *sumsq_out, float *dmap_dev);
+/* SGDSolver::ComputeUpdateValue + Net::Update for the head's parameters with the gradients of the last az_solver_step: per
+ * element, one rounding per operation, g = clip_scale * g; g = g + (weight_decay * decay_mult) * w;
+ * hist = momentum * hist + (rate * lr_mult) * g; w = w - hist.  The caller computes rate (lr_policy) and clip_scale
+ * (clip_gradients / the L2 norm of ALL learnable gradients when that exceeds clip_gradients, else 1). */
+int az_solver_update(az_solver *s, double rate, double momentum, double weight_decay, double clip_scale);
+/* The same arithmetic on raw device pointers (n floats each; rate and decay already multiplied by the blob's lr_mult /
+ * decay_mult): what the convolution parameters PyTorch owns are updated with. */
+int az_sgd_update(az_ctx *ctx, float *w_dev, const float *g_dev, float *hist_dev, long long n, double rate, double momentum,
+                  double decay, double clip_scale);
+/* net.forward() in Caffe's TEST phase (dropout = identity) on the trainer's current weights: the raw zoom_score [R],
+ * adj_score [R][11], adj_bbox [R][44] (host; any may be NULL). */
+int az_solver_forward_test(az_solver *s, const float *conv_dev, int N, int H, int W, int channels_last, const float *rois, int R,
+                           float *zoom_score, float *adj_score, float *adj_bbox);
+/* net.blobs[...].data / .diff and net.params[...].diff of the last pass, for tests: pool5, argmax (int32: h * W + w in the roi's
+ * map, -1 for an empty bin), pre6 / pre71 / pre72 (pre-activations), a6 / a71 / a72, mask6 / mask71 / mask72 (uint8),
+ * adj_score, adj_bbox, zoom_score, d_adj_score, d_adj_bbox, d_zoom_score, d_pre6, d_pre71, d_pre72, d_pool5, and per parameter
+ * P of the twelve: g_P (gradient), h_P (history), w_P (value).  out == NULL: only the size. */
+int az_solver_fetch(az_solver *s, const char *name, void *out, long long cap_bytes, long long *bytes_out);
+/* One product of the trainer's GEMM kernel on host arrays, for tests: d [M][N] = form 0: a [M][K] b[N][K]^T (forward);
+ * 1: a [M][K] b [K][N] (dx); 2: a [K][M]^T b [K][N] (dW). */
+int az_solver_gemm_unit(az_ctx *ctx, int form, const float *a, const float *b, float *d, int M, int N, int K);
+
 /* ---- measurement ------------------------------------------------------------------ */
 /* HIP-event timing (events on the ctx stream) of the launches made by az_propose /
  * az_head_forward.  mode bits: 1 = time only the fc GEMM launches, 2 = time every launch
