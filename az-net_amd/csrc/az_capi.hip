@@ -159,9 +159,11 @@ int az_load_head(az_ctx *c, int C, int n6, int n71, int n72, const float *W6, co
     A(pool5, R * d.K6);
     {
         const size_t p6 = (size_t)c->S6 * R * n6, p7 = (size_t)c->S7 * R * d.n7;
-        const size_t pm = p6 > p7 ? p6 : p7;
+        size_t pm = p6 > p7 ? p6 : p7;
         const size_t pw = (size_t)n6 * d.K6;          // also stages W6 for the column permutation
-        A(part, pm > pw ? pm : pw);
+        const size_t pr = R * d.K6;                   // ... and az_roi_pool's rows in Caffe's order (more than the slabs when S6 n6 < K6)
+        pm = pm > pw ? pm : pw;
+        A(part, pm > pr ? pm : pr);
     }
     A(h6, R * n6); A(h7, R * d.n7);
     A(part7, (size_t)c->S7 * R * d.n7);

@@ -179,7 +179,10 @@ int az_set_gemm_mode(az_ctx *ctx, int parts);
  * blobs, row-major [out, in]; they are copied (and re-tiled) into HBM.
  *   W6 [n6, C*49] b6 [n6] | W71 [n71, n6] b71 | W72 [n72, n6] b72
  *   Was [11, n71] bas | Wab [44, n71] bab | Wz [1, n72] bz
- * C, n6 must be multiples of 4. */
+ * Sizes: C, n6, n71 and n72 are positive multiples of 4, and n71 + n72 <= 3072 (the tail kernel stages four rows of
+ * int7_1 | int7_2, zero-padded to a multiple of 256, in a 64 KB LDS tile).  Anything else is AZ_ERR_INVALID and leaves the
+ * head loaded before in place.  The number of K chunks of a layer is fixed by its K alone (1, 2, 8, 16 from K = 512, 2048,
+ * 16384), never by the row count: a roi's bits do not depend on its batch at any size (tests/test_gpu_head_sizes.py). */
 int az_load_head(az_ctx *ctx, int C, int n6, int n71, int n72,
                  const float *W6, const float *b6, const float *W71, const float *b71,
                  const float *W72, const float *b72, const float *Was, const float *bas,
@@ -335,7 +338,9 @@ int az_nms_batched(az_ctx *ctx, const float *dets, const int32_t *offsets, int n
 /* Replaces caffe.Net(frcnn/test_fc.prototxt, caffemodel) (tools/test_shared.py): the detection
  * head models/Pascal/VGG16/frcnn/test_fc.prototxt:14-145 -- fc6 [n6, C*49], fc7 [n7, n6],
  * cls_score [ncls, n7] (+Softmax), bbox_pred [4*ncls, n7]; Caffe [out, in] layout.  2 <= ncls <= 256 (VOC: 21;
- * COCO, models/COCO/VGG16/frcnn/test_fc.prototxt:97-135: 81). */
+ * COCO, models/COCO/VGG16/frcnn/test_fc.prototxt:97-135: 81).
+ * Sizes: C, n6 and n7 are positive multiples of 4 (n7 has no upper limit: this head's tail is a GEMM); with an AZ head
+ * loaded, C must be that head's.  Anything else is AZ_ERR_INVALID and leaves the detection head loaded before in place. */
 int az_load_det_head(az_ctx *ctx, int C, int n6, int n7, int ncls, const float *W6, const float *b6,
                      const float *W7, const float *b7, const float *Wc, const float *bc,
                      const float *Wb, const float *bb);

@@ -12,6 +12,8 @@ What is checked, at the full head (25088 -> 4096 -> ...):
 import numpy as np
 import pytest
 
+from head_sizes_ref import f64_head as _f64_head
+
 pytestmark = pytest.mark.gpu
 
 
@@ -35,21 +37,6 @@ def _rois(n, seed=3):
     rng = np.random.RandomState(seed)
     x1 = rng.uniform(0, 900, n); y1 = rng.uniform(0, 500, n)
     return np.stack([np.zeros(n), x1, y1, x1 + rng.uniform(16, 300, n), y1 + rng.uniform(16, 300, n)], 1).astype(np.float32)
-
-
-def _f64_head(orc, head, fmap, rois):
-    n = rois.shape[0]
-    p5 = orc.roi_pool(fmap[0], rois).reshape(n, -1).astype(np.float64)
-
-    def f(x, W, b, relu):
-        y = x @ W.astype(np.float64).T + b.astype(np.float64)
-        return np.maximum(y, 0) if relu else y
-    h6 = f(p5, head["W6"], head["b6"], True)
-    h71 = f(h6, head["W71"], head["b71"], True)
-    h72 = f(h6, head["W72"], head["b72"], True)
-    sg = lambda x: 1.0 / (1.0 + np.exp(-x))          # noqa: E731
-    return sg(f(h72, head["Wz"], head["bz"], False)), sg(f(h71, head["Was"], head["bas"], False)), \
-        f(h71, head["Wab"], head["bab"], False)
 
 
 @pytest.mark.parametrize("gain", [1.0, 1e-4, 3e4, -1.0], ids=["as_is", "tiny", "huge", "negated"])

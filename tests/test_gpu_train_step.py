@@ -226,10 +226,12 @@ def test_bad_arguments_write_nothing(ctx):
 
 
 # ---- 2. one step ---------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("rows,channels_last", [(128, False), (130, True), (5, False), (1, True)])
-def test_one_step_reduced_head(ctx, rows, channels_last):
-    head, fmap, blobs = R.small_case(R=rows)
-    print("reduced head, R = %d, %s" % (rows, "channels_last" if channels_last else "NCHW"))
+@pytest.mark.parametrize("rows,channels_last,dims", [(128, False, None), (130, True, None), (5, False, None), (1, True, None),
+                                                     (37, False, (12, 132, 68, 36))],       # (odd sizes: no multiple of a tile)
+                         ids=["128-False", "130-True", "5-False", "1-True", "37-False-12x132x68x36"])
+def test_one_step_reduced_head(ctx, rows, channels_last, dims):
+    head, fmap, blobs = R.small_case(R=rows, dims=dims)
+    print("reduced head%s, R = %d, %s" % ("" if dims is None else " %s" % (dims,), rows, "channels_last" if channels_last else "NCHW"))
     run_and_compare(ctx, head, fmap, blobs, seed=3, it=0, channels_last=channels_last)
 
 

@@ -256,9 +256,10 @@ def full_size_case():
     return filler_head(5, **FULL), fmap, blobs
 
 
-def small_case(R=128, seed=7):
+def small_case(R=128, seed=7, dims=None):
+    """dims: (C, n6, n71, n72), default synth.SMALL_DIMS."""
     from aznet_hip import synth
-    d = synth.SMALL_DIMS
+    d = synth.SMALL_DIMS if dims is None else dict(zip(("C", "n6", "n71", "n72"), dims))
     fmap = np.concatenate([synth.make_feature_map(s, d["C"], 24, 32) for s in (seed, seed + 1)], axis=0)
     return filler_head(seed, **d), fmap, random_blobs(seed, R, 2, 24, 32)
 
