@@ -1283,7 +1283,8 @@ _SOLVER_U8 = ("mask6", "mask71", "mask72")
 
 def dropout_mask(seed, iteration, layer, n, ratio=0.5):
     """The NumPy form of the trainer's dropout mask (include/aznet_hip.h, az_solver_step): keep flags (uint8) of the elements
-    0 .. n-1 of layer 0 / 1 / 2 (int6, int7_1, int7_2) at (seed, iteration)."""
+    0 .. n-1 of layer 0 / 1 / 2 (int6, int7_1, int7_2) at (seed, iteration).  The trainer holds the ratio as a float32
+    and thresholds at (unsigned)((double)ratio_f32 * 2^24): the ratio is rounded to float32 here first (0.3 -> 5033165)."""
     M = (1 << 64) - 1
 
     def mix(z):
@@ -1297,7 +1298,7 @@ def dropout_mask(seed, iteration, layer, n, ratio=0.5):
         z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
         z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
         z = z ^ (z >> np.uint64(31))
-    return ((z >> np.uint64(40)) >= np.uint64(int(float(ratio) * 16777216.0))).astype(np.uint8)
+    return ((z >> np.uint64(40)) >= np.uint64(int(float(np.float32(ratio)) * 16777216.0))).astype(np.uint8)
 
 
 def sgd_update_numpy(w, g, hist, rate, momentum, decay, clip_scale):

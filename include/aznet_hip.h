@@ -596,6 +596,8 @@ int az_solver_set_hyper(az_solver *s, const float *lr_mult, const float *decay_m
  *       mix(z): z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; return z ^ (z >> 31)
  *       key = mix(mix(mix(seed + 0x9E3779B97F4A7C15) + iteration) + L)
  *       keep(e) = (mix(key + 0x9E3779B97F4A7C15 * (e + 1)) >> 40) >= floor(p * 2^24);   y = keep ? x * (1 / (1 - p)) : 0
+ *   with p the float32 of az_solver_set_hyper (0.3 is 0.300000012: floor(p * 2^24) = 5033165, not 5033164), p * 2^24 exact
+ *   in double and 1 / (1 - p) in float32; p = 0: no mask is drawn, written or read.
  *   (Caffe's own RNG stream is not reproduced.)  The backward uses the same mask and scale.
  * Bad arguments (NULL arrays, R outside [1, max_rois], a batch index outside [0, N)) return AZ_ERR_INVALID before anything is
  * written. */

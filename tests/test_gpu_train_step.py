@@ -36,21 +36,27 @@ def check(name, got, r64, r32, rows=None):
     return e_dev <= b
 
 
-def device_masks(sol, seed, it, n):
+DEFAULT_RATIOS = (0.5, 0.5, 0.5)
+
+
+def device_masks(sol, seed, it, n, ratios=DEFAULT_RATIOS):
+    """The fetched masks of the layers that have dropout (ratio > 0), each equal to the NumPy form of the generator."""
     from aznet_hip import ffi
     masks = {}
     for t, l, k in LAYERS:
-        m = sol.fetch("mask%d" % t)
-        assert np.array_equal(m, ffi.dropout_mask(seed, it, l, m.size).reshape(m.shape)), "mask of layer %d" % t
-        masks[t] = m
+        if ratios[l] > 0:
+            m = sol.fetch("mask%d" % t)
+            assert np.array_equal(m, ffi.dropout_mask(seed, it, l, m.size, ratio=ratios[l]).reshape(m.shape)), "mask of layer %d" % t
+            masks[t] = m
     return masks
 
 
-def device_gates(sol, head, pool, blobs, masks):
-    """The device's ReLU gates, checked against float64 as the issue allows, for the restatement to use."""
+def device_gates(sol, head, pool, blobs, masks, ratios=DEFAULT_RATIOS, count=None):
+    """The device's ReLU gates, checked against float64 as the issue allows, for the restatement to use.  count: a list
+    that receives the number of gates that differed."""
     gates = {t: sol.fetch("pre%d" % t) > 0 for t, _, _ in LAYERS}
-    r64 = R.step(head, pool, blobs, masks, gates=gates, want_dpool=False)
-    r32 = R.step(head, pool, blobs, masks, gates=gates, dtype=np.float32, want_dpool=False)
+    r64 = R.step(head, pool, blobs, masks, gates=gates, ratios=ratios, want_dpool=False)
+    r32 = R.step(head, pool, blobs, masks, gates=gates, dtype=np.float32, ratios=ratios, want_dpool=False)
     for t, _, _ in LAYERS:
         pre64 = r64["pre%d" % t]
         fwd = R.bound(R.rel_err(r32["pre%d" % t], pre64)) * np.abs(pre64).max()
@@ -58,10 +64,20 @@ def device_gates(sol, head, pool, blobs, masks):
         print("  gates of layer %d: %d of %d differ from float64" % (t, int(diff.sum()), diff.size))
         assert np.all(np.abs(pre64[diff]) <= fwd), "a gate differs where the pre-activation is not within rounding of zero"
         assert diff.mean() <= 1e-4
+        if count is not None:
+            count.append(int(diff.sum()))
     return gates
 
 
-def run_and_compare(ctx, head, fmap, blobs, seed, it, channels_last=False, max_rois=256, update=True):
+def same_bits(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
+
+
+def run_and_compare(ctx, head, fmap, blobs, seed, it, channels_last=False, max_rois=256, update=True, ratios=None, lr_mult=None,
+                    decay_mult=None):
+    """ratios / lr_mult / decay_mult (dicts by parameter name): hyper-parameters other than az_solver_create's, set after a
+    step at the defaults, so that a layer whose ratio is 0 finds a stale mask in its buffer that it must not look at."""
     import torch
     from aznet_hip import ffi
     N, C, H, W = fmap.shape
@@ -71,17 +87,43 @@ def run_and_compare(ctx, head, fmap, blobs, seed, it, channels_last=False, max_r
     if channels_last:
         conv = conv.contiguous(memory_format=torch.channels_last)
     dmap = torch.empty_like(conv)
-    losses, sumsq = sol.step(conv, blobs["rois"], blobs["adj_labels"], blobs["adj_targets"], blobs["adj_loss_weights"],
-                             blobs["zoom_labels"], seed, it, dmap=dmap)
+    args = (conv, blobs["rois"], blobs["adj_labels"], blobs["adj_targets"], blobs["adj_loss_weights"], blobs["zoom_labels"])
+    other = not (ratios is None and lr_mult is None and decay_mult is None)
+    ratios = DEFAULT_RATIOS if ratios is None else tuple(ratios)
+    lr_mult, decay_mult = lr_mult or R.LR_MULT, decay_mult or R.DECAY_MULT
+    stale = {}
+    if other:
+        sol.step(*args, seed + 1, it, dmap=dmap)
+        stale = {t: sol.fetch("mask%d" % t) for t, _, _ in LAYERS}
+        assert all(0.4 < m.mean() < 0.6 for m in stale.values())
+        sol.set_hyper([lr_mult[k] for k in R.KEYS], [decay_mult[k] for k in R.KEYS], ratios)
+    losses, sumsq = sol.step(*args, seed, it, dmap=dmap)
     pool, arg = R.roi_pool(fmap, blobs["rois"])
     assert np.array_equal(sol.fetch("pool5"), pool), "pool5"
     assert np.array_equal(sol.fetch("argmax"), arg), "argmax"
     n = pool.shape[0]
-    masks = device_masks(sol, seed, it, n)
-    gates = device_gates(sol, head, pool, blobs, masks)
-    r64 = R.step(head, pool, blobs, masks, gates=gates)
-    r32 = R.step(head, pool, blobs, masks, gates=gates, dtype=np.float32)
-    rows, ok = [], True
+    masks = device_masks(sol, seed, it, n, ratios)
+    ngates = []
+    gates = device_gates(sol, head, pool, blobs, masks, ratios, ngates)
+    for t, l, _ in LAYERS:                                            # ReLU + dropout: exact given the pre-activation
+        pre, a, dp = sol.fetch("pre%d" % t), sol.fetch("a%d" % t), sol.fetch("d_pre%d" % t)
+        relu = np.maximum(pre, np.float32(0))
+        if ratios[l] > 0:
+            scale = np.float32(1) / (np.float32(1) - np.float32(ratios[l]))
+            assert same_bits(a, np.where(masks[t] > 0, relu * scale, np.float32(0)).astype(np.float32)), "a%d" % t
+            assert not dp[(pre <= 0) | (masks[t] == 0)].any()
+        else:                                                         # no dropout: the stale mask is neither read nor written
+            assert same_bits(a, relu), "a%d without dropout is not relu(pre%d)" % (t, t)
+            assert not dp[pre <= 0].any()
+            if stale:
+                assert same_bits(sol.fetch("mask%d" % t), stale[t])
+                dropped = (pre > 0) & (stale[t] == 0)
+                print("  layer %d without dropout: %d of %d units with a zero in the stale mask have d_pre != 0"
+                      % (t, int(np.count_nonzero(dp[dropped])), int(dropped.sum())))
+                assert dropped.any() and np.count_nonzero(dp[dropped]) > 0        # gated by pre > 0 alone (values: d_pre below)
+    r64 = R.step(head, pool, blobs, masks, gates=gates, ratios=ratios)
+    r32 = R.step(head, pool, blobs, masks, gates=gates, dtype=np.float32, ratios=ratios)
+    rows, ok = [("gates that differ", float(sum(ngates)), 0.0, 0.0)], True
     for name in ("pre6", "a6", "pre71", "pre72", "adj_score", "adj_bbox", "zoom_score", "d_adj_score", "d_adj_bbox",
                  "d_zoom_score", "d_pre71", "d_pre72", "d_pre6", "d_pool5"):
         ok &= check(name, sol.fetch(name).reshape(np.shape(r64[name])), r64[name], r32[name], rows)
@@ -94,23 +136,28 @@ def run_and_compare(ctx, head, fmap, blobs, seed, it, channels_last=False, max_r
     ok &= check("d_conv5_3", dmap.cpu().numpy(), d64, d32, rows)
     if update:
         rate, mom, wd = 0.001, 0.9, 0.0005
+        mult = dict(lr_mult=lr_mult, decay_mult=decay_mult)
         for rep, clip_at in ((0, 1e-3), (1, None)):                 # a clipped step, then an unclipped one on top of its history
             cs = R.clip_scale(sumsq, clip_at)
             if rep == 0:
-                p64, h64 = R.sgd(head, r64["grads"], {k: np.zeros_like(v) for k, v in head.items()}, rate, mom, wd, R.clip_scale(r64["sumsq"], clip_at))
-                p32, h32 = R.sgd(head, r32["grads"], {k: np.zeros_like(v) for k, v in head.items()}, rate, mom, wd, R.clip_scale(r32["sumsq"], clip_at), dtype=np.float32)
+                p64, h64 = R.sgd(head, r64["grads"], {k: np.zeros_like(v) for k, v in head.items()}, rate, mom, wd, R.clip_scale(r64["sumsq"], clip_at), **mult)
+                p32, h32 = R.sgd(head, r32["grads"], {k: np.zeros_like(v) for k, v in head.items()}, rate, mom, wd, R.clip_scale(r32["sumsq"], clip_at), dtype=np.float32, **mult)
                 assert cs < 1.0
             else:
-                p64, h64 = R.sgd(p64, r64["grads"], h64, rate, mom, wd, 1.0)
-                p32, h32 = R.sgd(p32, r32["grads"], h32, rate, mom, wd, 1.0, dtype=np.float32)
+                p64, h64 = R.sgd(p64, r64["grads"], h64, rate, mom, wd, 1.0, **mult)
+                p32, h32 = R.sgd(p32, r32["grads"], h32, rate, mom, wd, 1.0, dtype=np.float32, **mult)
             sol.update(rate, mom, wd, cs)
             for k in R.KEYS:
                 ok &= check("w_%s/%d" % (k, rep), sol.fetch("w_" + k), p64[k], p32[k], rows)
                 ok &= check("h_%s/%d" % (k, rep), sol.fetch("h_" + k), h64[k], h32[k], rows)
         got = sol.read()
         assert all(np.array_equal(got[k], sol.fetch("w_" + k)) for k in R.KEYS)
+        for k in R.KEYS:                                              # lr_mult 0: after the two updates not a bit has moved
+            if lr_mult[k] == 0:
+                assert np.abs(sol.fetch("g_" + k)).max() > 0, k
+                assert same_bits(sol.fetch("w_" + k), head[k]) and same_bits(sol.fetch("h_" + k), np.zeros_like(head[k])), k
     sol.close()
-    assert ok, "a tensor exceeds 8 x the float32-CPU error: " + ", ".join(r[0] for r in rows if r[1] > r[3])
+    assert ok, "a tensor exceeds 8 x the float32-CPU error: " + ", ".join(r[0] for r in rows[1:] if r[1] > r[3])
     return rows
 
 
@@ -275,7 +322,7 @@ def test_same_step_twice_same_bits(ctx):
 
 
 # ---- 4 / 5. trajectories through SolverWrapper, the snapshot's round trip, the tools ---------------------------------------------
-def _wrapper(ctx, tmp, frozen_all):
+def _wrapper(ctx, tmp, frozen_all, edit_rows=None):
     from aznet_hip import ffi, synth
     from datasets.synthetic import SyntheticImdb
     from detect.train_az import SolverWrapper, get_training_roidb
@@ -285,7 +332,7 @@ def _wrapper(ctx, tmp, frozen_all):
     np.random.seed(T["roidb_seed"])
     get_training_roidb(imdb)
     dims = {k: v for k, v in synth.SMALL_DIMS.items() if k != "C"}
-    return SolverWrapper(R.traj_solver_files(str(tmp), frozen_all), imdb, str(tmp / "out"), backbone=R.traj_backbone("cuda:0"),
+    return SolverWrapper(R.traj_solver_files(str(tmp), frozen_all, edit_rows), imdb, str(tmp / "out"), backbone=R.traj_backbone("cuda:0"),
                          ctx=ctx, dims=dims, seed=T["solver_seed"])
 
 

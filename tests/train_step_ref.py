@@ -82,11 +82,14 @@ def smooth_l1(x, t, w, num):
 def step(params, pool5, blobs, masks, gates=None, dtype=np.float64, ratios=(0.5, 0.5, 0.5), want_dpool=True):
     """Forward + backward of the head on pooled rows.  params: the twelve Caffe-layout arrays; pool5 [R, C*49];
     blobs: adj_labels [R,11], adj_targets [R,44], adj_loss_weights [R,44], zoom_labels [R]; masks: {6, 71, 72: keep
-    flags [R, n]} (None: no dropout); gates: {6, 71, 72: bool [R, n]} to impose on the ReLUs (None: pre > 0).
+    flags [R, n]} (None: no dropout); gates: {6, 71, 72: bool [R, n]} to impose on the ReLUs (None: pre > 0); ratios: the
+    dropout ratios of int6 / int7_1 / int7_2, rounded to float32 first in BOTH dtypes (the trainer holds them as float32, so
+    that is the ratio the step is run at); a layer whose ratio is 0 has no dropout and its mask is not looked at.
     Returns a dict of every tensor by the names az_solver_fetch uses."""
     dt = dtype
     P = {k: np.asarray(params[k], dtype=dt) for k in KEYS}
     R = pool5.shape[0]
+    ratios = [float(np.float32(r)) for r in ratios]
     out = {}
 
     def hidden(x, W, b, tag, ratio):
@@ -295,34 +298,39 @@ def traj_backbone(device):
     return bb
 
 
-def traj_solver_files(dirname, frozen_all):
+def traj_solver_files(dirname, frozen_all, edit_rows=None):
+    """edit_rows: a function on the rows of prototxt.layer_table, applied before the train net is written."""
     from detect import prototxt as P
     net = os.path.join(dirname, "train_%s.prototxt" % ("shared" if frozen_all else "az"))
-    P.write_train_prototxt(net, P.layer_table(frozen=P.CONV_LAYERS if frozen_all else P.CONV_LAYERS[:4]))
+    rows = P.layer_table(frozen=P.CONV_LAYERS if frozen_all else P.CONV_LAYERS[:4])
+    P.write_train_prototxt(net, rows if edit_rows is None else edit_rows(rows))
     sol = os.path.join(dirname, "solver_%s.prototxt" % ("shared" if frozen_all else "az"))
     P.write_solver_prototxt(sol, net, **TRAJ["solver"])
     return sol
 
 
 class RefTrajectory(object):
-    """The restatement stepping beside a device run: same start, same minibatches, same conv5_3 maps, same masks."""
+    """The restatement stepping beside a device run: same start, same minibatches, same conv5_3 maps, same masks (drawn at
+    `ratios`; none for a layer whose ratio is 0), the update with `lr_mult` / `decay_mult`."""
 
-    def __init__(self, params, dtype, solver=None):
+    def __init__(self, params, dtype, solver=None, ratios=(0.5, 0.5, 0.5), lr_mult=LR_MULT, decay_mult=DECAY_MULT):
         self.dt = dtype
         self.p = {k: np.asarray(v, dtype) for k, v in params.items()}
         self.h = {k: np.zeros_like(v) for k, v in self.p.items()}
         self.sp = dict(TRAJ["solver"] if solver is None else solver)
         self.it = 0
+        self.ratios, self.lr_mult, self.decay_mult = tuple(ratios), lr_mult, decay_mult
 
     def step(self, conv, blobs, seed, gates=None):
         from aznet_hip import ffi
         pool, _ = roi_pool(conv, blobs["rois"])
         n = pool.shape[0]
-        masks = {t: ffi.dropout_mask(seed, self.it, l, n * self.p[k].shape[0]).reshape(n, -1)
-                 for t, l, k in ((6, 0, "b6"), (71, 1, "b71"), (72, 2, "b72"))}
-        r = step(self.p, pool, blobs, masks, gates=gates, dtype=self.dt, want_dpool=False)
+        masks = {t: ffi.dropout_mask(seed, self.it, l, n * self.p[k].shape[0], ratio=self.ratios[l]).reshape(n, -1)
+                 for t, l, k in ((6, 0, "b6"), (71, 1, "b71"), (72, 2, "b72")) if self.ratios[l] > 0}
+        r = step(self.p, pool, blobs, masks, gates=gates, dtype=self.dt, ratios=self.ratios, want_dpool=False)
         rate = learning_rate(self.sp["lr_policy"], self.sp["base_lr"], self.it, self.sp["gamma"], self.sp["stepsize"])
         self.p, self.h = sgd(self.p, r["grads"], self.h, rate, self.sp["momentum"], self.sp["weight_decay"],
-                             clip_scale(r["sumsq"], self.sp["clip_gradients"]), dtype=self.dt)
+                             clip_scale(r["sumsq"], self.sp["clip_gradients"]), dtype=self.dt, lr_mult=self.lr_mult,
+                             decay_mult=self.decay_mult)
         self.it += 1
         return r
