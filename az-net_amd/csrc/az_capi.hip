@@ -39,6 +39,7 @@ int az_destroy(az_ctx *c)
 {
     if (!c) return AZ_ERR_INVALID;
     az_solver_free_all(c);
+    az_det_solver_free_all(c);
     destroy_twin(c);
     destroy_batch(c);
     if (c->comm) { if (c->comm_stream) hipStreamSynchronize(c->comm_stream); azk_rccl_destroy(c->comm); c->comm = nullptr; }

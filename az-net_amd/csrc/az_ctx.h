@@ -408,6 +408,7 @@ struct az_ctx {
     std::vector<void *> allocs;        // head-sized buffers (az_load_head)
     std::vector<void *> allocs_geom;   // geometry buffers (first use)
     std::vector<az_solver *> solvers;  // trainers created on this context (az_solver.hip), freed with it
+    std::vector<az_det_solver *> det_solvers;  // the detection net's trainers (az_det_solver.hip), freed with it
     bool geom_ready = false;
 };
 
@@ -796,6 +797,8 @@ void rank_by_score(hipStream_t s, int D, long long S, int n_images, int n_classe
                    const RankScratch &r, const unsigned **by_seg, const unsigned **by_class);
 // ---- az_solver.hip -------------------------------------------------------------------------------------------------------
 void az_solver_free_all(az_ctx *c);       // az_destroy: the trainers still alive
+// ---- az_det_solver.hip ---------------------------------------------------------------------------------------------------
+void az_det_solver_free_all(az_ctx *c);
 // ---- az_capi.hip --------------------------------------------------------------------------------------------------------
 int set_feature_map_common(az_ctx *c, const float *src, bool src_is_host, int C, int H, int W, bool wait = true);
 int ensure_lane_head(az_ctx *t);          // the head buffers of a lane / batch slot created without them

@@ -1,0 +1,393 @@
+// az_det_solver.hip -- detection-net (Fast R-CNN) TRAINING from conv5_3 on (models/*/VGG16/frcnn/train.prototxt): RoIPool with
+// arg-max -> fc6 -> fc7 -> {cls_score, bbox_pred}, SoftmaxWithLoss and SmoothL1Loss, the backward pass, the gradient norm and
+// Caffe's momentum-SGD update.  The kernels are the AZ-net trainer's (az_solver_dev.h) in this graph's order; the one new
+// kernel is the softmax loss.  fp32 master weights in Caffe layout ([out][in], roi_pool5 flattened c*49 + p).
+//
+// Every reduction has a fixed order (no floating-point atomics): see az_solver.hip; the softmax sums a row lane-strided and
+// then over a fixed butterfly, the row losses in row order per wave and then over the LDS tree.  The same step from the same
+// state gives the same bits.
+#include "az_solver_dev.h"
+
+namespace {
+
+__device__ __forceinline__ float wave_max(float v)
+{
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ float wave_sum(float v)
+{
+    for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o, 64);       // both partners add the same two numbers: one value in all lanes
+    return v;
+}
+
+// Caffe SoftmaxWithLoss, normalised by the R rows.  One workgroup of four waves; wave w serves the rows w, w + 4, ...: the row
+// maximum by a wave reduction, e = exp(x - max), the sum lane-strided (columns lane, lane + 64, ...) and then over the
+// butterfly, p = e / sum.  With labels: loss_row = -log(max(p[label], FLT_MIN)), d = (p - onehot) / R, and the row losses
+// summed in f64, per wave in row order and then over block_sum's tree.  Without (TEST phase): only p.  ncls <= 256.
+constexpr int SM_PER_LANE = 4;
+__global__ void __launch_bounds__(256) k_solver_softmax_loss(const float *__restrict__ x, const float *__restrict__ labels, int R, int ncls,
+                                                             float *__restrict__ prob, float *__restrict__ dx, float *__restrict__ loss)
+{
+    __shared__ double sh[256];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float inv = 1.0f / (float)R;
+    double acc = 0.0;
+    for (int r = wave; r < R; r += 4) {
+        const float *xr = x + (size_t)r * ncls;
+        float v[SM_PER_LANE];
+        float m = -FLT_MAX;
+#pragma unroll
+        for (int q = 0; q < SM_PER_LANE; ++q) {
+            const int j = lane + 64 * q;
+            v[q] = j < ncls ? xr[j] : -FLT_MAX;
+            m = fmaxf(m, v[q]);
+        }
+        m = wave_max(m);
+        float s = 0.0f;
+#pragma unroll
+        for (int q = 0; q < SM_PER_LANE; ++q) {
+            const int j = lane + 64 * q;
+            v[q] = j < ncls ? expf(v[q] - m) : 0.0f;
+            s = s + v[q];
+        }
+        s = wave_sum(s);
+        const int lab = labels ? (int)labels[r] : -1;
+#pragma unroll
+        for (int q = 0; q < SM_PER_LANE; ++q) {
+            const int j = lane + 64 * q;
+            if (j >= ncls) continue;
+            const float p = v[q] / s;
+            prob[(size_t)r * ncls + j] = p;
+            if (labels) {
+                dx[(size_t)r * ncls + j] = (p - (j == lab ? 1.0f : 0.0f)) * inv;
+                if (j == lab) acc += (double)(-logf(fmaxf(p, FLT_MIN)));
+            }
+        }
+    }
+    if (!labels) return;
+    const double tot = block_sum(acc, sh);
+    if (threadIdx.x == 0) *loss = (float)(tot / (double)R);
+}
+
+}  // namespace
+
+// parameter order of the ABI: W6 b6 W7 b7 Wc bc Wb bb (fc6, fc7, cls_score, bbox_pred)
+enum { D_W6, D_B6, D_W7, D_B7, D_WC, D_BC, D_WB, D_BB, DNPARAM };
+static const char *const DPNAME[DNPARAM] = {"W6", "b6", "W7", "b7", "Wc", "bc", "Wb", "bb"};
+static const float DET_FILLER_STD[4] = {5e-3f, 5e-3f, 1e-2f, 1e-3f};      // fc6 fc7 (without a pretrained model) cls_score bbox_pred
+
+struct az_det_solver {
+    az_ctx *c = nullptr;
+    int C = 0, n6 = 0, n7 = 0, ncls = 0, K6 = 0, maxR = 0;
+    size_t pn[DNPARAM] = {0};
+    float *w[DNPARAM] = {nullptr}, *g[DNPARAM] = {nullptr}, *h[DNPARAM] = {nullptr};
+    float lr_mult[DNPARAM], decay_mult[DNPARAM];
+    float drop[2] = {0.5f, 0.5f};
+    // one step's activations and gradients (rows: maxR)
+    float *rois = nullptr, *labels = nullptr, *tgt = nullptr, *wgt = nullptr;
+    int *geo = nullptr, *argmax = nullptr;
+    float *pool5 = nullptr, *pre6 = nullptr, *a6 = nullptr, *pre7 = nullptr, *a7 = nullptr;
+    unsigned char *m6 = nullptr, *m7 = nullptr;
+    float *s_cls = nullptr, *prob = nullptr, *s_bb = nullptr;                  // raw cls_score, cls_prob, bbox_pred
+    float *d_cls = nullptr, *d_bb = nullptr, *d7 = nullptr, *d6 = nullptr, *dpool = nullptr;
+    float *part = nullptr, *loss = nullptr;
+    double *sq_part = nullptr, *sq = nullptr;
+    size_t part_elems = 0;
+    std::vector<void *> allocs;
+    int R = 0, N = 0, H = 0, W = 0, trained = 0, has_prob = 0;
+};
+
+namespace {
+
+template <typename T>
+int dsalloc(az_det_solver *s, T **p, size_t n)
+{
+    void *q = nullptr;
+    if (hipMalloc(&q, n * sizeof(T) + 256) != hipSuccess) return fail(s->c, AZ_ERR_HIP, "az_det_solver: hipMalloc(" + std::to_string(n * sizeof(T)) + " B) failed");
+    s->allocs.push_back(q);
+    *p = (T *)q;
+    return AZ_OK;
+}
+
+int det_check_args(az_det_solver *s, const float *conv, int N, int H, int W, const float *rois, int R, const std::string &who)
+{
+    if (!s) return AZ_ERR_INVALID;
+    if (!conv || !rois) return fail(s->c, AZ_ERR_INVALID, who + ": null conv5_3 or rois");
+    if (N < 1 || H < 1 || W < 1 || (long long)H * W > 0x3fffffff) return fail(s->c, AZ_ERR_INVALID, who + ": bad map shape");
+    if (R < 1 || R > s->maxR) return fail(s->c, AZ_ERR_INVALID, who + ": R must be in [1, max_rois = " + std::to_string(s->maxR) + "]");
+    for (int r = 0; r < R; ++r) {
+        const float *roi = rois + 5 * (size_t)r;
+        if (!(roi[0] >= 0.0f && roi[0] < (float)N) || roi[0] != std::floor(roi[0]))
+            return fail(s->c, AZ_ERR_INVALID, who + ": roi " + std::to_string(r) + " names image " + std::to_string(roi[0]) + " of " + std::to_string(N));
+        for (int q = 1; q < 5; ++q)
+            if (!std::isfinite(roi[q]) || std::fabs(roi[q]) > 1e8f) return fail(s->c, AZ_ERR_INVALID, who + ": roi coordinate not finite");
+    }
+    return AZ_OK;
+}
+
+// RoIPool -> fc6 -> fc7 -> {cls_score, bbox_pred}; train: dropout on fc6 / fc7 with the step's masks (layer ids 0 / 1)
+int det_forward(az_det_solver *s, const float *conv, int N, int H, int W, int cl, const float *rois, int R, bool train,
+                unsigned long long seed, unsigned long long iter)
+{
+    az_ctx *c = s->c;
+    HIPCHK(c, hipMemcpyAsync(s->rois, rois, (size_t)R * 5 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    const MapView m{N, s->C, H, W, cl ? 1 : 0};
+    { Timed t(c, "roi_pool_argmax", 0);
+      hipLaunchKernelGGL(k_solver_roi_geo, dim3((R + 255) / 256), dim3(256), 0, c->stream, s->rois, R, c->spatial_scale, s->geo);
+      hipLaunchKernelGGL(k_solver_roi_pool, dim3(grid_for((long long)R * s->K6, 16384)), dim3(256), 0, c->stream, conv, m, s->geo, R,
+                         s->pool5, s->argmax); }
+    const bool m6 = train && s->drop[0] > 0.f, m7 = train && s->drop[1] > 0.f;
+    fc_forward(s, "fc6_fwd", s->pool5, D_W6, R, s->n6, s->K6, s->pre6, s->a6, m6 ? s->m6 : nullptr, az_layer_key(seed, iter, 0), train ? s->drop[0] : 0.f);
+    fc_forward(s, "fc7_fwd", s->a6, D_W7, R, s->n7, s->n6, s->pre7, s->a7, m7 ? s->m7 : nullptr, az_layer_key(seed, iter, 1), train ? s->drop[1] : 0.f);
+    fc_forward(s, "cls_score_fwd", s->a7, D_WC, R, s->ncls, s->n7, s->s_cls, nullptr, nullptr, 0, 0.f);
+    fc_forward(s, "bbox_pred_fwd", s->a7, D_WB, R, 4 * s->ncls, s->n7, s->s_bb, nullptr, nullptr, 0, 0.f);
+    s->R = R; s->N = N; s->H = H; s->W = W;
+    return AZ_OK;
+}
+
+}  // namespace
+
+void az_det_solver_free_all(az_ctx *c)
+{
+    while (!c->det_solvers.empty()) az_det_solver_destroy(c->det_solvers.back());
+}
+
+extern "C" {
+
+int az_det_solver_create(az_ctx *c, int C, int n6, int n7, int num_classes, int max_rois, uint64_t seed, az_det_solver **out)
+{
+    if (!c || !out) return AZ_ERR_INVALID;
+    *out = nullptr;
+    if (C < 4 || C % 4 || n6 < 4 || n6 % 4 || n7 < 4 || n7 % 4 || num_classes < 2 || num_classes > 64 * SM_PER_LANE || max_rois < 1 ||
+        max_rois > 4096 || (long long)C * 49 * n6 > (1LL << 33) || (long long)n6 * n7 > (1LL << 33))
+        return fail(c, AZ_ERR_INVALID, "az_det_solver_create: C, n6, n7 must be positive multiples of 4, 2 <= num_classes <= 256, 1 <= max_rois <= 4096");
+    HIPCHK(c, hipSetDevice(c->device));
+    az_det_solver *s = new az_det_solver();
+    s->c = c; s->C = C; s->n6 = n6; s->n7 = n7; s->ncls = num_classes; s->K6 = C * 49; s->maxR = max_rois;
+    const size_t K6 = (size_t)s->K6, nc = (size_t)num_classes, nb = 4 * nc;
+    const size_t pn[DNPARAM] = {n6 * K6, (size_t)n6, (size_t)n7 * n6, (size_t)n7, nc * n7, nc, nb * n7, nb};
+    int rc = AZ_OK;
+    for (int p = 0; p < DNPARAM && rc == AZ_OK; ++p) {
+        s->pn[p] = pn[p];
+        s->lr_mult[p] = (p & 1) ? 2.0f : 1.0f;
+        s->decay_mult[p] = (p & 1) ? 0.0f : 1.0f;
+        if ((rc = dsalloc(s, &s->w[p], pn[p])) == AZ_OK && (rc = dsalloc(s, &s->g[p], pn[p])) == AZ_OK) rc = dsalloc(s, &s->h[p], pn[p]);
+    }
+    const size_t R = (size_t)max_rois;
+    // the slabs of a split-K product hold at most 256 tiles of 128 x 128 (pick_split); an unsplit forward layer R x its width
+    size_t nmax = (size_t)(n6 > n7 ? n6 : n7); nmax = nmax > nb ? nmax : nb; nmax = nmax > K6 ? nmax : K6;
+    s->part_elems = R * nmax > (size_t)4 << 20 ? R * nmax : (size_t)4 << 20;
+#define SA(p, n) if (rc == AZ_OK) rc = dsalloc(s, &s->p, (n))
+    SA(rois, R * 5); SA(labels, R); SA(tgt, R * nb); SA(wgt, R * nb); SA(geo, R * 8);
+    SA(argmax, R * K6); SA(pool5, R * K6); SA(dpool, R * K6);
+    SA(pre6, R * n6); SA(a6, R * n6); SA(d6, R * n6); SA(m6, R * n6);
+    SA(pre7, R * n7); SA(a7, R * n7); SA(d7, R * n7); SA(m7, R * n7);
+    SA(s_cls, R * nc); SA(prob, R * nc); SA(d_cls, R * nc); SA(s_bb, R * nb); SA(d_bb, R * nb);
+    SA(part, s->part_elems); SA(loss, 4); SA(sq_part, (size_t)DNPARAM * SQ_BLOCKS); SA(sq, 2);
+#undef SA
+    if (rc != AZ_OK) { for (void *q : s->allocs) hipFree(q); delete s; return rc; }
+    for (int p = 0; p < DNPARAM; ++p) {
+        hipMemsetAsync(s->h[p], 0, pn[p] * sizeof(float), c->stream);
+        hipMemsetAsync(s->g[p], 0, pn[p] * sizeof(float), c->stream);
+        if (p & 1) hipMemsetAsync(s->w[p], 0, pn[p] * sizeof(float), c->stream);
+        else hipLaunchKernelGGL(k_solver_fill_gauss, dim3(grid_for((long long)pn[p], 8192)), dim3(256), 0, c->stream, s->w[p], (long long)pn[p],
+                                DET_FILLER_STD[p / 2], az_layer_key(seed, 0, 16 + p));
+    }
+    if (hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess) {
+        for (void *q : s->allocs) hipFree(q);
+        delete s;
+        return fail(c, AZ_ERR_HIP, "az_det_solver_create: initialising the parameters failed");
+    }
+    c->det_solvers.push_back(s);
+    *out = s;
+    return AZ_OK;
+}
+
+int az_det_solver_destroy(az_det_solver *s)
+{
+    if (!s) return AZ_ERR_INVALID;
+    az_ctx *c = s->c;
+    hipSetDevice(c->device);
+    hipStreamSynchronize(c->stream);
+    for (void *q : s->allocs) hipFree(q);
+    for (size_t i = 0; i < c->det_solvers.size(); ++i) if (c->det_solvers[i] == s) { c->det_solvers.erase(c->det_solvers.begin() + i); break; }
+    delete s;
+    return AZ_OK;
+}
+
+int az_det_solver_load(az_det_solver *s, const float *W6, const float *b6, const float *W7, const float *b7, const float *Wc,
+                       const float *bc, const float *Wb, const float *bb)
+{
+    if (!s) return AZ_ERR_INVALID;
+    az_ctx *c = s->c;
+    const float *src[DNPARAM] = {W6, b6, W7, b7, Wc, bc, Wb, bb};
+    HIPCHK(c, hipSetDevice(c->device));
+    for (int p = 0; p < DNPARAM; ++p)       // a null array keeps what the trainer holds
+        if (src[p]) HIPCHK(c, hipMemcpyAsync(s->w[p], src[p], s->pn[p] * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return AZ_OK;
+}
+
+int az_det_solver_read(az_det_solver *s, float *W6, float *b6, float *W7, float *b7, float *Wc, float *bc, float *Wb, float *bb)
+{
+    if (!s) return AZ_ERR_INVALID;
+    az_ctx *c = s->c;
+    float *dst[DNPARAM] = {W6, b6, W7, b7, Wc, bc, Wb, bb};
+    HIPCHK(c, hipSetDevice(c->device));
+    for (int p = 0; p < DNPARAM; ++p)
+        if (dst[p]) HIPCHK(c, hipMemcpyAsync(dst[p], s->w[p], s->pn[p] * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return AZ_OK;
+}
+
+int az_det_solver_set_hyper(az_det_solver *s, const float *lr_mult, const float *decay_mult, const float *dropout_ratio)
+{
+    if (!s) return AZ_ERR_INVALID;
+    if (dropout_ratio) for (int i = 0; i < 2; ++i) if (!(dropout_ratio[i] >= 0.0f && dropout_ratio[i] < 1.0f)) return fail(s->c, AZ_ERR_INVALID, "az_det_solver_set_hyper: dropout ratio outside [0, 1)");
+    if (lr_mult) for (int p = 0; p < DNPARAM; ++p) if (!(lr_mult[p] >= 0.0f)) return fail(s->c, AZ_ERR_INVALID, "az_det_solver_set_hyper: negative lr_mult");
+    if (decay_mult) for (int p = 0; p < DNPARAM; ++p) if (!(decay_mult[p] >= 0.0f)) return fail(s->c, AZ_ERR_INVALID, "az_det_solver_set_hyper: negative decay_mult");
+    if (lr_mult) for (int p = 0; p < DNPARAM; ++p) s->lr_mult[p] = lr_mult[p];
+    if (decay_mult) for (int p = 0; p < DNPARAM; ++p) s->decay_mult[p] = decay_mult[p];
+    if (dropout_ratio) for (int i = 0; i < 2; ++i) s->drop[i] = dropout_ratio[i];
+    return AZ_OK;
+}
+
+int az_det_solver_step(az_det_solver *s, const float *conv_dev, int N, int H, int W, int channels_last, const float *rois, int R,
+                       const float *labels, const float *bbox_targets, const float *bbox_loss_weights, uint64_t seed,
+                       long long iteration, float *losses_out, double *sumsq_out, float *dmap_dev)
+{
+    int rc = det_check_args(s, conv_dev, N, H, W, rois, R, "az_det_solver_step");
+    if (rc != AZ_OK) return rc;
+    az_ctx *c = s->c;
+    if (!labels || !bbox_targets || !bbox_loss_weights || iteration < 0)
+        return fail(c, AZ_ERR_INVALID, "az_det_solver_step: null label / target array or negative iteration");
+    const int nc = s->ncls, nb = 4 * s->ncls;
+    for (int r = 0; r < R; ++r)            // before anything is enqueued
+        if (!(labels[r] >= 0.0f && labels[r] < (float)nc) || labels[r] != std::floor(labels[r]))
+            return fail(c, AZ_ERR_INVALID, "az_det_solver_step: label " + std::to_string(labels[r]) + " of row " + std::to_string(r) + " is no class in [0, " + std::to_string(nc) + ")");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!(c->profiling & 4)) clear_events(c);
+    hipStream_t st = c->stream;
+    HIPCHK(c, hipMemcpyAsync(s->labels, labels, (size_t)R * sizeof(float), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(s->tgt, bbox_targets, (size_t)R * nb * sizeof(float), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(s->wgt, bbox_loss_weights, (size_t)R * nb * sizeof(float), hipMemcpyHostToDevice, st));
+    if ((rc = det_forward(s, conv_dev, N, H, W, channels_last, rois, R, true, seed, (unsigned long long)iteration)) != AZ_OK) return rc;
+    const int n6 = s->n6, n7 = s->n7, K6 = s->K6;
+    { Timed t(c, "losses", 0);
+      hipLaunchKernelGGL(k_solver_softmax_loss, dim3(1), dim3(256), 0, st, s->s_cls, s->labels, R, nc, s->prob, s->d_cls, s->loss + 0);
+      hipLaunchKernelGGL(k_solver_smooth_l1, dim3(1), dim3(256), 0, st, s->s_bb, s->tgt, s->wgt, R * nb, R, s->d_bb, s->loss + 1); }
+    s->has_prob = 1;
+    auto colsum = [&](const float *dy, int Nc, float *db) {
+        hipLaunchKernelGGL(k_solver_colsum, dim3((Nc + 255) / 256), dim3(256), 0, st, dy, R, Nc, db);
+    };
+    auto act_bwd = [&](float *d, const float *pre, const unsigned char *mask, float ratio, int Nc) {
+        Timed t(c, "act_bwd", 0);
+        hipLaunchKernelGGL(k_solver_act_bwd, dim3(grid_for((long long)R * Nc)), dim3(256), 0, st, d, pre, ratio > 0.f ? mask : nullptr,
+                           1.0f / (1.0f - ratio), (long long)R * Nc);
+    };
+    // the two output layers: dW = dy^T x, db, and their two dx, which add into d7
+    gemm_any(s, "cls_score_dw", 2, s->d_cls, s->a7, s->g[D_WC], nc, n7, R, 0);
+    gemm_any(s, "bbox_pred_dw", 2, s->d_bb, s->a7, s->g[D_WB], nb, n7, R, 0);
+    { Timed t(c, "bias_grads", 0); colsum(s->d_cls, nc, s->g[D_BC]); colsum(s->d_bb, nb, s->g[D_BB]); }
+    gemm_any(s, "cls_score_dx", 1, s->d_cls, s->w[D_WC], s->d7, R, n7, nc, 0);
+    gemm_any(s, "bbox_pred_dx", 1, s->d_bb, s->w[D_WB], s->d7, R, n7, nb, 1);
+    act_bwd(s->d7, s->pre7, s->m7, s->drop[1], n7);
+    gemm_any(s, "fc7_dw", 2, s->d7, s->a6, s->g[D_W7], n7, n6, R, 0);
+    { Timed t(c, "bias_grads", 0); colsum(s->d7, n7, s->g[D_B7]); }
+    gemm_any(s, "fc7_dx", 1, s->d7, s->w[D_W7], s->d6, R, n6, n7, 0);
+    act_bwd(s->d6, s->pre6, s->m6, s->drop[0], n6);
+    gemm_any(s, "fc6_dw", 2, s->d6, s->pool5, s->g[D_W6], n6, K6, R, 0);
+    { Timed t(c, "bias_grads", 0); colsum(s->d6, n6, s->g[D_B6]); }
+    if (dmap_dev) {
+        gemm_any(s, "fc6_dx", 1, s->d6, s->w[D_W6], s->dpool, R, K6, n6, 0);
+        const MapView m{N, s->C, H, W, channels_last ? 1 : 0};
+        Timed t(c, "roi_pool_bwd", 0);
+        hipLaunchKernelGGL(k_solver_roi_pool_bwd, dim3(grid_for((long long)N * s->C * H * W, 1 << 30)), dim3(256), 0, st, s->dpool,
+                           s->argmax, s->geo, R, m, dmap_dev);
+    }
+    { Timed t(c, "grad_sumsq", 0);
+      for (int p = 0; p < DNPARAM; ++p)
+          hipLaunchKernelGGL(k_solver_sumsq, dim3(SQ_BLOCKS), dim3(256), 0, st, s->g[p], (long long)s->pn[p], s->sq_part + (size_t)p * SQ_BLOCKS);
+      hipLaunchKernelGGL(k_solver_sumsq_final, dim3(1), dim3(256), 0, st, s->sq_part, DNPARAM * SQ_BLOCKS, s->sq); }
+    float hl[2]; double hs = 0.0;
+    HIPCHK(c, hipMemcpyAsync(hl, s->loss, sizeof(hl), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(&hs, s->sq, sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    HIPCHK(c, hipGetLastError());
+    s->trained = dmap_dev ? 2 : 1;
+    if (losses_out) { losses_out[0] = hl[0]; losses_out[1] = hl[1]; }
+    if (sumsq_out) *sumsq_out = hs;
+    return AZ_OK;
+}
+
+int az_det_solver_update(az_det_solver *s, double rate, double momentum, double weight_decay, double clip_scale)
+{
+    if (!s) return AZ_ERR_INVALID;
+    az_ctx *c = s->c;
+    if (!(rate >= 0.0) || !(momentum >= 0.0) || !(weight_decay >= 0.0) || !(clip_scale > 0.0) || !std::isfinite(rate + momentum + weight_decay + clip_scale))
+        return fail(c, AZ_ERR_INVALID, "az_det_solver_update: rate, momentum, weight_decay >= 0 and clip_scale > 0, all finite");
+    if (!s->trained) return fail(c, AZ_ERR_STATE, "az_det_solver_update: no az_det_solver_step has produced gradients");
+    HIPCHK(c, hipSetDevice(c->device));
+    { Timed t(c, "sgd_update", 0);
+      for (int p = 0; p < DNPARAM; ++p)
+          hipLaunchKernelGGL(k_solver_sgd, dim3(grid_for((long long)s->pn[p], 16384)), dim3(256), 0, c->stream, s->w[p], s->g[p], s->h[p],
+                             (long long)s->pn[p], (float)(rate * (double)s->lr_mult[p]), (float)momentum,
+                             (float)(weight_decay * (double)s->decay_mult[p]), (float)clip_scale); }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    return AZ_OK;
+}
+
+int az_det_solver_forward_test(az_det_solver *s, const float *conv_dev, int N, int H, int W, int channels_last, const float *rois,
+                               int R, float *cls_prob, float *bbox_pred)
+{
+    int rc = det_check_args(s, conv_dev, N, H, W, rois, R, "az_det_solver_forward_test");
+    if (rc != AZ_OK) return rc;
+    az_ctx *c = s->c;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!(c->profiling & 4)) clear_events(c);
+    if ((rc = det_forward(s, conv_dev, N, H, W, channels_last, rois, R, false, 0, 0)) != AZ_OK) return rc;
+    s->trained = 0;
+    hipLaunchKernelGGL(k_solver_softmax_loss, dim3(1), dim3(256), 0, c->stream, s->s_cls, (const float *)nullptr, R, s->ncls, s->prob,
+                       (float *)nullptr, (float *)nullptr);
+    s->has_prob = 1;
+    if (cls_prob) HIPCHK(c, hipMemcpyAsync(cls_prob, s->prob, (size_t)R * s->ncls * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (bbox_pred) HIPCHK(c, hipMemcpyAsync(bbox_pred, s->s_bb, (size_t)R * 4 * s->ncls * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    return AZ_OK;
+}
+
+int az_det_solver_fetch(az_det_solver *s, const char *name, void *out, long long cap_bytes, long long *bytes_out)
+{
+    if (!s || !name || !bytes_out) return AZ_ERR_INVALID;
+    az_ctx *c = s->c;
+    const std::string nm(name);
+    const size_t R = (size_t)s->R, nc = (size_t)s->ncls;
+    const void *src = nullptr;
+    size_t bytes = 0;
+    struct Ent { const char *n; const void *p; size_t b; };
+    const Ent tab[] = {
+        {"pool5", s->pool5, R * s->K6 * 4}, {"argmax", s->argmax, R * s->K6 * 4}, {"d_pool5", s->dpool, R * s->K6 * 4},
+        {"pre6", s->pre6, R * s->n6 * 4}, {"a6", s->a6, R * s->n6 * 4}, {"d_pre6", s->d6, R * s->n6 * 4}, {"mask6", s->m6, R * s->n6},
+        {"pre7", s->pre7, R * s->n7 * 4}, {"a7", s->a7, R * s->n7 * 4}, {"d_pre7", s->d7, R * s->n7 * 4}, {"mask7", s->m7, R * s->n7},
+        {"cls_score", s->s_cls, R * nc * 4}, {"cls_prob", s->prob, R * nc * 4}, {"bbox_pred", s->s_bb, R * nc * 16},
+        {"d_cls_score", s->d_cls, R * nc * 4}, {"d_bbox_pred", s->d_bb, R * nc * 16},
+    };
+    bool is_param = false;
+    for (const Ent &e : tab) if (nm == e.n) { src = e.p; bytes = e.b; }
+    if (!src && nm.size() > 2 && nm[1] == '_' && (nm[0] == 'g' || nm[0] == 'h' || nm[0] == 'w'))
+        for (int p = 0; p < DNPARAM; ++p)
+            if (nm.substr(2) == DPNAME[p]) { src = nm[0] == 'g' ? s->g[p] : (nm[0] == 'h' ? s->h[p] : s->w[p]); bytes = s->pn[p] * 4; is_param = true; }
+    if (!src) return fail(c, AZ_ERR_INVALID, "az_det_solver_fetch: no saved tensor named '" + nm + "'");
+    if (!is_param && s->R == 0) return fail(c, AZ_ERR_STATE, "az_det_solver_fetch: no forward pass has run");
+    *bytes_out = (long long)bytes;
+    if (!out) return AZ_OK;
+    if (cap_bytes < (long long)bytes) return fail(c, AZ_ERR_CAPACITY, "az_det_solver_fetch: '" + nm + "' needs " + std::to_string(bytes) + " bytes");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
+    return AZ_OK;
+}
+
+}  // extern "C"

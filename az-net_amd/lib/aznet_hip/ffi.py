@@ -45,6 +45,9 @@ SYMBOLS = [
     "az_zoom_labels", "az_train_ex_rois", "az_train_adj_targets", "az_train_target_stats",
     "az_solver_create", "az_solver_destroy", "az_solver_load", "az_solver_read", "az_solver_set_hyper", "az_solver_step",
     "az_solver_update", "az_sgd_update", "az_solver_forward_test", "az_solver_fetch", "az_solver_gemm_unit",
+    "az_det_targets", "az_det_target_stats",
+    "az_det_solver_create", "az_det_solver_destroy", "az_det_solver_load", "az_det_solver_read", "az_det_solver_set_hyper",
+    "az_det_solver_step", "az_det_solver_update", "az_det_solver_forward_test", "az_det_solver_fetch",
 ]
 
 
@@ -233,6 +236,17 @@ def load_library(path=None):
     L.az_solver_forward_test.argtypes = [vp, vp, ci, ci, ci, ci, fp, ci, fp, fp, fp]
     L.az_solver_fetch.argtypes = [vp, ctypes.c_char_p, vp, ll, llp]
     L.az_solver_gemm_unit.argtypes = [vp, ci, fp, fp, fp, ci, ci, ci]
+    L.az_det_targets.argtypes = [vp, ci, fp, ip, fp, ip, ip, cd, cd, cd, fp, dp]
+    L.az_det_target_stats.argtypes = [vp, ci, fp, ip, ci, cd, ci, dp, dp, dp]
+    L.az_det_solver_create.argtypes = [vp, ci, ci, ci, ci, ci, u64, ctypes.POINTER(vp)]
+    L.az_det_solver_destroy.argtypes = [vp]
+    L.az_det_solver_load.argtypes = [vp] + [fp] * 8
+    L.az_det_solver_read.argtypes = [vp] + [fp] * 8
+    L.az_det_solver_set_hyper.argtypes = [vp, fp, fp, fp]
+    L.az_det_solver_step.argtypes = [vp, vp, ci, ci, ci, ci, fp, ci, fp, fp, fp, u64, ll, fp, dp, vp]
+    L.az_det_solver_update.argtypes = [vp, cd, cd, cd, cd]
+    L.az_det_solver_forward_test.argtypes = [vp, vp, ci, ci, ci, ci, fp, ci, fp, fp]
+    L.az_det_solver_fetch.argtypes = [vp, ctypes.c_char_p, vp, ll, llp]
     L.az_image_blob_size.argtypes = [ci, ci, cd, cip, cip]
     L.az_image_blob_host.argtypes = [vp, u8p, ci, ci, fp, cd, fp, ci, ci]
     L.az_image_blob_dev.argtypes = [vp, u8p, ci, ci, fp, cd, vp, ci, ci]
@@ -1114,6 +1128,41 @@ class AzContext(object):
                                                1 if normalise else 0))
         return means, stds
 
+    def det_targets(self, ex_boxes, ex_off, gt_list, label_list, bbox_thresh, bg_thresh_lo, eps):
+        """az_det_targets: ex_boxes f32 [E,4] with ex_off [n+1], gt_list of n f32 [.,4] arrays and label_list of n integer
+        arrays -> (targets f32 [E,5] un-normalised, max_overlaps f64 [E])."""
+        ex = _f32(ex_boxes).reshape(-1, 4)
+        eoff = np.ascontiguousarray(ex_off, dtype=np.int32).ravel()
+        n = eoff.size - 1
+        gts = [_f32(g).reshape(-1, 4) for g in gt_list]
+        labs = [np.asarray(l).astype(np.int32).ravel() for l in label_list]
+        assert len(gts) == n and len(labs) == n and int(eoff[n]) == ex.shape[0]
+        assert all(g.shape[0] == l.size for g, l in zip(gts, labs))
+        goff = self._offsets(gts)
+        g = _f32(np.vstack([np.zeros((0, 4), np.float32)] + gts))
+        lab = np.ascontiguousarray(np.concatenate([np.zeros(0, np.int32)] + labs), dtype=np.int32)
+        t = np.zeros((ex.shape[0], 5), dtype=np.float32)
+        mo = np.zeros(ex.shape[0], dtype=np.float64)
+        self._chk(self.L.az_det_targets(self.h, n, _p(ex, ctypes.c_float), _p(eoff, ctypes.c_int32), _p(g, ctypes.c_float),
+                                        _p(lab, ctypes.c_int32), _p(goff, ctypes.c_int32), float(bbox_thresh), float(bg_thresh_lo),
+                                        float(eps), _p(t, ctypes.c_float), _p(mo, ctypes.c_double)))
+        return t, mo
+
+    def det_target_stats(self, targets, ex_off, num_classes, eps, normalise=True):
+        """az_det_target_stats over targets f32 [E,5] (C-contiguous; normalised IN PLACE when asked) with ex_off [n+1] ->
+        (counts [num_classes], means [num_classes,4], stds [num_classes,4])."""
+        assert targets.dtype == np.float32 and targets.flags["C_CONTIGUOUS"] and (targets.ndim == 2 and targets.shape[1] == 5)
+        eoff = np.ascontiguousarray(ex_off, dtype=np.int32).ravel()
+        assert int(eoff[-1]) == targets.shape[0]
+        K = int(num_classes)
+        counts = np.zeros(K, dtype=np.float64)
+        means = np.zeros((K, 4), dtype=np.float64)
+        stds = np.zeros((K, 4), dtype=np.float64)
+        self._chk(self.L.az_det_target_stats(self.h, eoff.size - 1, _p(targets, ctypes.c_float), _p(eoff, ctypes.c_int32), K, float(eps),
+                                             1 if normalise else 0, _p(counts, ctypes.c_double), _p(means, ctypes.c_double),
+                                             _p(stds, ctypes.c_double)))
+        return counts, means, stds
+
     # ---- detection evaluation (imdb.evaluate_detections, VOC) -------------------------------
     def voc_eval(self, n_classes, n_images, det_box, det_conf, det_off, gt_box, gt_difficult, gt_off,
                  min_overlap=0.5, metric_07=True, want_curves=True):
@@ -1432,6 +1481,116 @@ class AzSolver(object):
         out = np.empty(n.value // np.dtype(dt).itemsize, dtype=dt)
         self.ctx._chk(self.L.az_solver_fetch(self.h, name.encode(), out.ctypes.data_as(ctypes.c_void_p), n.value, ctypes.byref(n)))
         if len(name) > 2 and name[1] == "_" and name[2:] in HEAD_KEYS:
+            return out.reshape(self._shapes()[name[2:]])
+        return out.reshape(self.last_rows, -1) if self.last_rows else out
+
+
+DET_HEAD_KEYS = ("W6", "b6", "W7", "b7", "Wc", "bc", "Wb", "bb")
+_DET_SOLVER_U8 = ("mask6", "mask7")
+
+
+class AzDetSolver(object):
+    """The detection-net trainer behind conv5_3 (az_det_solver_*): fc6 -> fc7 -> {cls_score, bbox_pred} with fp32 master
+    weights, gradients and momentum history in HBM; `step` is forward + backward of a minibatch, `update` Caffe's SGD step."""
+
+    def __init__(self, ctx, C, n6, n7, num_classes, max_rois=256, seed=0, head=None):
+        self.ctx, self.L = ctx, ctx.L
+        h = ctypes.c_void_p()
+        ctx._chk(self.L.az_det_solver_create(ctx.h, int(C), int(n6), int(n7), int(num_classes), int(max_rois),
+                                             int(seed) & ((1 << 64) - 1), ctypes.byref(h)))
+        self.h = h
+        self.dims = dict(C=int(C), n6=int(n6), n7=int(n7), ncls=int(num_classes), K6=int(C) * 49)
+        self.max_rois = int(max_rois)
+        self.last_rows = 0
+        if head is not None:
+            self.load(head)
+
+    def _shapes(self):
+        d = self.dims
+        return {"W6": (d["n6"], d["K6"]), "b6": (d["n6"],), "W7": (d["n7"], d["n6"]), "b7": (d["n7"],),
+                "Wc": (d["ncls"], d["n7"]), "bc": (d["ncls"],), "Wb": (4 * d["ncls"], d["n7"]), "bb": (4 * d["ncls"],)}
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.L.az_det_solver_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def load(self, head):
+        """head: {name: Caffe-layout array} for any subset of DET_HEAD_KEYS."""
+        shp = self._shapes()
+        arrs = [_f32(head[k]).reshape(shp[k]) if k in head else None for k in DET_HEAD_KEYS]
+        self.ctx._chk(self.L.az_det_solver_load(self.h, *[_p(a, ctypes.c_float) if a is not None else None for a in arrs]))
+
+    def read(self):
+        out = {k: np.empty(v, dtype=np.float32) for k, v in self._shapes().items()}
+        self.ctx._chk(self.L.az_det_solver_read(self.h, *[_p(out[k], ctypes.c_float) for k in DET_HEAD_KEYS]))
+        return out
+
+    def set_hyper(self, lr_mult=None, decay_mult=None, dropout_ratio=None):
+        def arr(v, n):
+            if v is None:
+                return None, None
+            a = _f32(v).reshape(n)
+            return a, _p(a, ctypes.c_float)
+        a, pa = arr(lr_mult, 8)
+        b, pb = arr(decay_mult, 8)
+        c, pc = arr(dropout_ratio, 2)
+        self.ctx._chk(self.L.az_det_solver_set_hyper(self.h, pa, pb, pc))
+
+    _map = AzSolver._map
+
+    def step(self, conv, rois, labels, bbox_targets, bbox_loss_weights, seed, iteration, dmap=None):
+        """Forward + backward of one minibatch.  conv: CUDA tensor [N,C,H,W]; dmap: None or a CUDA tensor of conv's shape and
+        memory format that receives d loss / d conv5_3.  Returns (losses [cls, bbox] f32, sum of squares of the head's
+        gradients)."""
+        import torch
+        ptr, N, H, W, cl = self._map(conv)
+        rois = _f32(rois).reshape(-1, 5)
+        R, nb = rois.shape[0], 4 * self.dims["ncls"]
+        lab, bt, bw = _f32(labels).reshape(R), _f32(bbox_targets).reshape(R, nb), _f32(bbox_loss_weights).reshape(R, nb)
+        dptr = None
+        if dmap is not None:
+            assert dmap.is_cuda and dmap.dtype == conv.dtype and dmap.shape == conv.shape and dmap.stride() == conv.stride()
+            dptr = ctypes.c_void_p(dmap.data_ptr())
+        torch.cuda.current_stream(conv.device).synchronize()
+        losses = np.zeros(2, dtype=np.float32)
+        sq = ctypes.c_double(0.0)
+        f = ctypes.c_float
+        self.ctx._chk(self.L.az_det_solver_step(self.h, ptr, N, H, W, cl, _p(rois, f), R, _p(lab, f), _p(bt, f), _p(bw, f),
+                                                int(seed) & ((1 << 64) - 1), int(iteration), _p(losses, f), ctypes.byref(sq), dptr))
+        self.last_rows = R
+        return losses, float(sq.value)
+
+    def update(self, rate, momentum, weight_decay, clip_scale=1.0):
+        self.ctx._chk(self.L.az_det_solver_update(self.h, float(rate), float(momentum), float(weight_decay), float(clip_scale)))
+
+    def forward_test(self, conv, rois):
+        """TEST-phase forward (dropout off): (cls_prob [R, ncls], raw bbox_pred [R, 4 ncls])."""
+        import torch
+        ptr, N, H, W, cl = self._map(conv)
+        rois = _f32(rois).reshape(-1, 5)
+        R, K = rois.shape[0], self.dims["ncls"]
+        p, b = np.empty((R, K), np.float32), np.empty((R, 4 * K), np.float32)
+        torch.cuda.current_stream(conv.device).synchronize()
+        f = ctypes.c_float
+        self.ctx._chk(self.L.az_det_solver_forward_test(self.h, ptr, N, H, W, cl, _p(rois, f), R, _p(p, f), _p(b, f)))
+        self.last_rows = R
+        return p, b
+
+    def fetch(self, name):
+        """A saved tensor of the last pass by name (az_det_solver_fetch), shaped."""
+        n = ctypes.c_longlong(0)
+        self.ctx._chk(self.L.az_det_solver_fetch(self.h, name.encode(), None, 0, ctypes.byref(n)))
+        dt = np.uint8 if name in _DET_SOLVER_U8 else (np.int32 if name == "argmax" else np.float32)
+        out = np.empty(n.value // np.dtype(dt).itemsize, dtype=dt)
+        self.ctx._chk(self.L.az_det_solver_fetch(self.h, name.encode(), out.ctypes.data_as(ctypes.c_void_p), n.value, ctypes.byref(n)))
+        if len(name) > 2 and name[1] == "_" and name[2:] in DET_HEAD_KEYS:
             return out.reshape(self._shapes()[name[2:]])
         return out.reshape(self.last_rows, -1) if self.last_rows else out
 

@@ -12,6 +12,11 @@ CONV_LAYERS = ("conv1_1", "conv1_2", "conv2_1", "conv2_2", "conv3_1", "conv3_2",
 HEAD_LAYERS = ("int6", "int7_1", "int7_2", "adj_score", "adj_bbox", "zoom_score")
 DROPOUT_OF = {"int6": 0, "int7_1": 1, "int7_2": 2}
 FILLER_STD = {"int6": 1e-4, "int7_1": 1e-4, "int7_2": 1e-3, "adj_score": 1e-2, "adj_bbox": 1e-3, "zoom_score": 1e-2}
+# the detection net (models/*/VGG16/frcnn/train.prototxt): fc6 / fc7 carry no filler (they come from the pretrained model)
+DET_HEAD_LAYERS = ("fc6", "fc7", "cls_score", "bbox_pred")
+DET_DROPOUT_OF = {"fc6": 0, "fc7": 1}
+DET_FILLER_STD = {"fc6": None, "fc7": None, "cls_score": 1e-2, "bbox_pred": 1e-3}
+DET_FILLER_DEFAULT = 5e-3          # fc6 / fc7 without a pretrained model
 SOLVER_DEFAULTS = dict(base_lr=0.001, lr_policy="step", gamma=0.1, stepsize=120000, momentum=0.9, weight_decay=0.0005,
                        clip_gradients=-1.0, display=20, average_loss=1, snapshot_prefix="vgg16_az_net", train_net=None)
 
@@ -108,6 +113,16 @@ def read_solver(path):
 def read_train_net(path):
     """{layer name: {"lr_mult": [w, b], "decay_mult": [w, b], "dropout_ratio": r or None, "std": s or None}} for the
     thirteen convolutions and the six InnerProduct layers.  Caffe's defaults (1 / 1) stand where a `param` block is absent."""
+    return _read_net(path, HEAD_LAYERS, DROPOUT_OF, "AZ-net")
+
+
+def read_det_train_net(path):
+    """The same table for the detection net (frcnn/train.prototxt): the thirteen convolutions, fc6, fc7, cls_score,
+    bbox_pred, with Dropout on fc6 / fc7."""
+    return _read_net(path, DET_HEAD_LAYERS, DET_DROPOUT_OF, "detection net")
+
+
+def _read_net(path, HEAD_LAYERS, DROPOUT_OF, what):
     with open(path) as f:
         items = parse_text(f.read())
     layers = [v for k, v in items if k in ("layer", "layers") and isinstance(v, list)]
@@ -118,8 +133,8 @@ def read_train_net(path):
         name, typ = _get(L, "name"), str(_get(L, "type", ""))
         if typ in ("Convolution", "InnerProduct"):
             if name not in CONV_LAYERS + HEAD_LAYERS or (typ == "Convolution") != (name in CONV_LAYERS):
-                raise ValueError("%s: learnable layer %r (%s) is not part of the AZ-net this backend trains "
-                                 "(conv1_1 .. conv5_3, %s)" % (path, name, typ, ", ".join(HEAD_LAYERS)))
+                raise ValueError("%s: learnable layer %r (%s) is not part of the %s this backend trains "
+                                 "(conv1_1 .. conv5_3, %s)" % (path, name, typ, what, ", ".join(HEAD_LAYERS)))
             params = [v for k, v in L if k == "param" and isinstance(v, list)]
             lr = [float(_get(p, "lr_mult", 1.0)) for p in params] + [1.0, 1.0]
             dc = [float(_get(p, "decay_mult", 1.0)) for p in params] + [1.0, 1.0]
@@ -134,10 +149,10 @@ def read_train_net(path):
             drops[_get(L, "bottom")] = float(_get(dp, "dropout_ratio", 0.5)) if isinstance(dp, list) else 0.5
     missing = [n for n in CONV_LAYERS + HEAD_LAYERS if n not in out]
     if missing:
-        raise ValueError("%s: not the AZ-net (missing %s)" % (path, ", ".join(missing)))
+        raise ValueError("%s: not the %s (missing %s)" % (path, what, ", ".join(missing)))
     for bottom, r in drops.items():
         if bottom not in DROPOUT_OF:
-            raise ValueError("%s: Dropout on %r; this backend has it on int6, int7_1, int7_2" % (path, bottom))
+            raise ValueError("%s: Dropout on %r; this backend has it on %s" % (path, bottom, ", ".join(sorted(DROPOUT_OF, key=DROPOUT_OF.get))))
         out[bottom]["dropout_ratio"] = r
     return out
 
@@ -163,8 +178,19 @@ def layer_table(frozen=("conv1_1", "conv1_2", "conv2_1", "conv2_2"), dropout=0.5
     return rows
 
 
-def write_train_prototxt(path, rows):
-    out = ['name: "az_net_train"']
+def det_layer_table(frozen=("conv1_1", "conv1_2", "conv2_1", "conv2_2"), dropout=0.5):
+    """The detection net's learnable layers as layer_table's rows: frcnn/train.prototxt freezes conv1_1 .. conv2_2."""
+    rows = []
+    for n in CONV_LAYERS:
+        f = n in frozen
+        rows.append((n, "Convolution", 0.0 if f else 1.0, 0.0 if f else 2.0, 0.0 if f else 1.0, 0.0, None, None))
+    for n in DET_HEAD_LAYERS:
+        rows.append((n, "InnerProduct", 1.0, 2.0, 1.0, 0.0, DET_FILLER_STD[n], dropout if n in DET_DROPOUT_OF else None))
+    return rows
+
+
+def write_train_prototxt(path, rows, name="az_net_train"):
+    out = ['name: "%s"' % name]
     for name, typ, lw, lb, dw, db, std, drop in rows:
         out.append('layer {\n  name: "%s"\n  type: "%s"\n  param {\n    lr_mult: %g\n    decay_mult: %g\n  }\n  param {\n'
                    '    lr_mult: %g\n    decay_mult: %g\n  }' % (name, typ, lw, dw, lb, db))

@@ -626,6 +626,72 @@ int az_solver_fetch(az_solver *s, const char *name, void *out, long long cap_byt
  * 1: a [M][K] b [K][N] (dx); 2: a [K][M]^T b [K][N] (dW). */
 int az_solver_gemm_unit(az_ctx *ctx, int form, const float *a, const float *b, float *d, int M, int N, int K);
 
+/* ---- detection-net training: the box-regression targets (lib/roi_data_layer/roidb.py) ------------------------------------ */
+/* _compute_targets (roidb.py:149-207) for n_images images in ONE launch (a thread per example box, no host wait inside):
+ * image i owns ex_boxes[ex_off[i]:ex_off[i+1]] (f32 [.,4] as the roidb stores them, widened to f64 as the reference's
+ * astype(float) does) and the objects gt[gt_off[i]:gt_off[i+1]] (f32 [.,4]) with gt_labels (int32).  Per example box: the
+ * maximum IoU over the image's objects (bbox_overlaps' arithmetic, f64) and the FIRST maximum's object.  Where the maximum is
+ * >= bbox_thresh the row is [label, dx, dy, dw, dh] rounded to f32, in the reference's order: widths and heights + eps, the
+ * centres from those, max(1, .) afterwards, dx = (tcx - pcx) / pw, dw = log(tw / pw); elsewhere the row is zero.
+ * targets_out f32 [E][5], max_overlaps_out f64 [E].  An image without objects: zero rows and max_overlaps = the float32 of
+ * bg_thresh_lo (roidb.py:160-163). */
+int az_det_targets(az_ctx *ctx, int n_images, const float *ex_boxes, const int32_t *ex_off, const float *gt,
+                   const int32_t *gt_labels, const int32_t *gt_off, double bbox_thresh, double bg_thresh_lo, double eps,
+                   float *targets_out, double *max_overlaps_out);
+/* roidb.py:119-145 over the set: targets f32 [E][5] (rows of image i: ex_off[i]:ex_off[i+1]).  Per image and class
+ * 1 .. num_classes - 1 the float32 sums of t and of t * t (the square rounded to float32) over the rows with that label, in
+ * row order (NumPy's axis-0 sum of a float32 array); those added into float64 across the images in image order, counts
+ * starting at eps; means = sums / counts, stds = sqrt(squared sums / counts - means^2); class 0 keeps mean 0, std 0.
+ * normalise_in_place != 0: every labelled row t = f32(f64(t) - mean), then t = f32(f64(t) / std); a std of 0 divides by 0 as
+ * the reference does.  counts_out f64 [num_classes] (may be NULL), means_out / stds_out f64 [num_classes][4].  No atomics:
+ * two runs give the same bits. */
+int az_det_target_stats(az_ctx *ctx, int n_images, float *targets, const int32_t *ex_off, int num_classes, double eps,
+                        int normalise_in_place, double *counts_out, double *means_out, double *stds_out);
+
+/* ---- detection-net training from conv5_3 on (models/Pascal/VGG16/frcnn/train.prototxt, lib/detect/train_det.py) ----------- */
+/* Replaces caffe.SGDSolver(solver_prototxt) and solver.step(1) (train_det.py:40,105) for everything behind conv5_3: roi_pool5
+ * (ROIPooling 7x7, 1/16) -> fc6 -> fc7 (InnerProduct, ReLU, Dropout in place) -> {cls_score [num_classes], bbox_pred
+ * [4 num_classes]}, loss_cls (SoftmaxWithLoss on labels) and loss_bbox (SmoothL1Loss with bbox_targets and bbox_loss_weights),
+ * both with loss_weight 1 and normalised by the roi rows R.  Everything else is as az_solver states it: the convolutions stay
+ * with the caller, fp32 master weights in Caffe layout, one gradient and one history per parameter, the same kernels, the same
+ * fixed orders (the same step from the same state gives the same bits), synchronous calls on the ctx stream, freed with the
+ * ctx.  The eight parameters are always in this order:  W6 b6 W7 b7 Wc bc Wb bb  (fc6, fc7, cls_score, bbox_pred). */
+typedef struct az_det_solver az_det_solver;
+/* The fillers of train.prototxt: gaussian std 0.01 for cls_score, 0.001 for bbox_pred; fc6 / fc7 come from the pretrained
+ * model (az_det_solver_load) and start at gaussian std 0.005 without one; biases 0; history 0; drawn as az_solver_create
+ * draws.  lr_mult / decay_mult start at 1 / 1 (weights) and 2 / 0 (biases), the two dropout ratios at 0.5.
+ * C, n6, n7 positive multiples of 4 (what az_load_det_head accepts), 2 <= num_classes <= 256, 1 <= max_rois <= 4096. */
+int az_det_solver_create(az_ctx *ctx, int C, int n6, int n7, int num_classes, int max_rois, uint64_t seed, az_det_solver **out);
+int az_det_solver_destroy(az_det_solver *s);
+/* solver.net.copy_from(pretrained_model) (train_det.py:44) / net.params[...].data reads and writes (train_det.py:49-54,70-96):
+ * host arrays in Caffe layout; a NULL array is skipped. */
+int az_det_solver_load(az_det_solver *s, const float *W6, const float *b6, const float *W7, const float *b7, const float *Wc,
+                       const float *bc, const float *Wb, const float *bb);
+int az_det_solver_read(az_det_solver *s, float *W6, float *b6, float *W7, float *b7, float *Wc, float *bc, float *Wb, float *bb);
+/* param { lr_mult decay_mult } of the four layers ([8], parameter order) and dropout_ratio of fc6, fc7 ([2], each in [0, 1));
+ * a NULL array keeps the current values. */
+int az_det_solver_set_hyper(az_det_solver *s, const float *lr_mult, const float *decay_mult, const float *dropout_ratio);
+/* net.forward() + net.backward() of one minibatch.  conv_dev, N, H, W, channels_last, rois [R][5], seed, iteration, sumsq_out
+ * and dmap_dev as in az_solver_step (dropout layer ids: 0 = fc6, 1 = fc7); labels [R] (float, whole numbers in
+ * [0, num_classes)), bbox_targets [R][4 num_classes], bbox_loss_weights [R][4 num_classes]: host arrays, the blobs of
+ * lib/roi_data_layer/layer.py.  losses_out [2] = loss_cls, loss_bbox.
+ *   SoftmaxWithLoss: p = exp(x - max x) / sum exp(x - max x) per row; loss = -1/R sum log(max(p[label], FLT_MIN));
+ *     dx = (p - onehot(label)) / R.
+ * A label outside [0, num_classes) (or any other bad argument) returns AZ_ERR_INVALID before anything is enqueued. */
+int az_det_solver_step(az_det_solver *s, const float *conv_dev, int N, int H, int W, int channels_last, const float *rois, int R,
+                       const float *labels, const float *bbox_targets, const float *bbox_loss_weights, uint64_t seed,
+                       long long iteration, float *losses_out, double *sumsq_out, float *dmap_dev);
+/* az_solver_update's arithmetic on the eight parameters with the gradients of the last az_det_solver_step. */
+int az_det_solver_update(az_det_solver *s, double rate, double momentum, double weight_decay, double clip_scale);
+/* net.forward() in the TEST phase (dropout = identity; models/Pascal/VGG16/frcnn/test.prototxt) on the trainer's current
+ * weights: cls_prob [R][num_classes] (softmax) and the raw bbox_pred [R][4 num_classes] (host; either may be NULL). */
+int az_det_solver_forward_test(az_det_solver *s, const float *conv_dev, int N, int H, int W, int channels_last, const float *rois,
+                               int R, float *cls_prob, float *bbox_pred);
+/* Saved tensors of the last pass, for tests: pool5, argmax, pre6, a6, mask6, pre7, a7, mask7 (uint8), cls_score, cls_prob,
+ * bbox_pred, d_cls_score, d_bbox_pred, d_pre7, d_pre6, d_pool5, and per parameter P of the eight g_P, h_P, w_P.
+ * out == NULL: only the size. */
+int az_det_solver_fetch(az_det_solver *s, const char *name, void *out, long long cap_bytes, long long *bytes_out);
+
 /* ---- measurement ------------------------------------------------------------------ */
 /* HIP-event timing (events on the ctx stream) of the launches made by az_propose /
  * az_head_forward.  mode bits: 1 = time only the fc GEMM launches, 2 = time every launch
