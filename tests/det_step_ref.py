@@ -161,11 +161,13 @@ traj_backbone = R.traj_backbone                  # (the AZ trajectory's frozen w
 TorchBlobCtx = R.TorchBlobCtx
 
 
-def traj_solver_files(dirname, frozen_all=True):
+def traj_solver_files(dirname, frozen_all=True, edit_rows=None):
+    """edit_rows: a function on the rows of prototxt.det_layer_table, applied before the train net is written."""
     import os
     from detect import prototxt as P
     net = os.path.join(dirname, "train_det.prototxt")
-    P.write_train_prototxt(net, P.det_layer_table(frozen=P.CONV_LAYERS if frozen_all else P.CONV_LAYERS[:4]), name="frcnn_train")
+    rows = P.det_layer_table(frozen=P.CONV_LAYERS if frozen_all else P.CONV_LAYERS[:4])
+    P.write_train_prototxt(net, rows if edit_rows is None else edit_rows(rows), name="frcnn_train")
     sol = os.path.join(dirname, "solver_det.prototxt")
     P.write_solver_prototxt(sol, net, **TRAJ["solver"])
     return sol

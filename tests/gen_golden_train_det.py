@@ -17,7 +17,17 @@ compact targets, which this NumPy refuses too: it is handed the same table with 
 The generator asserts what keeps the reference itself inside the tests' caps: every class that occurs has at least two
 distinct positive targets (stds > 0), and there is no nan or inf anywhere.
 
-Run:  python tests/gen_golden_train_det.py     (needs the reference tree; not collected by pytest)
+With --edges it records tests/golden/g22_train_det_edges.npz instead and leaves g21 alone: the cases of
+tests/det_edges_ref.py (built there from seeds, so only what the reference answers is stored):
+
+  t<s><i>_{targets,max_overlaps}   _compute_targets on image i of offsets_case under TARGET_SETTINGS[s] (cfg.EPS,
+                                   TRAIN.BBOX_THRESH and TRAIN.BG_THRESH_LO set to it), images without example boxes included
+  s<K>_{means,stds,norm}           add_bbox_regression_targets over stats_case(K) with K classes: its _compute_targets is
+                                   answered with the case's un-normalised targets, so that the reference's own statistics
+                                   and normalisation run on rows that no box geometry would give (one row, identical rows,
+                                   labels past K).  nan and inf are recorded as the reference gives them.
+
+Run:  python tests/gen_golden_train_det.py [--edges]     (needs the reference tree; not collected by pytest)
 """
 import importlib
 import os
@@ -152,7 +162,48 @@ def synthetic_proposals(gt_roidb, w, h):
     return props
 
 
-def main():
+class Width(object):
+    """What add_bbox_regression_targets reads of gt_overlaps: the number of classes."""
+
+    def __init__(self, num_classes):
+        self.shape = (1, num_classes)
+
+
+def record_edges(R, cfg):
+    import det_edges_ref as E
+    g = {}
+    ex, gt, lab = E.offsets_case()
+    keep = (cfg.EPS, cfg.TRAIN.BBOX_THRESH, cfg.TRAIN.BG_THRESH_LO)
+    for key in sorted(E.TARGET_SETTINGS):
+        s = E.TARGET_SETTINGS[key]
+        cfg.EPS, cfg.TRAIN.BBOX_THRESH, cfg.TRAIN.BG_THRESH_LO = s["eps"], s["bbox_thresh"], s["bg_lo"]
+        for i in range(len(ex)):
+            t, mo = R._compute_targets(ex[i], gt[i], lab[i])
+            assert t.dtype == np.float32 and t.shape == (ex[i].shape[0], 5)
+            g["t%s%d_targets" % (key, i)], g["t%s%d_max_overlaps" % (key, i)] = t.copy(), np.asarray(mo).copy()
+        print("setting %s: positives per image %s" % (key, [int((g["t%s%d_targets" % (key, i)][:, 0] > 0).sum()) for i in range(len(ex))]))
+    cfg.EPS, cfg.TRAIN.BBOX_THRESH, cfg.TRAIN.BG_THRESH_LO = keep
+    ref_targets = R._compute_targets
+    try:
+        for K in E.STATS_NCLS:
+            ts = E.stats_case(K)
+            R._compute_targets = lambda ex_rois, gt_rois, labels: (ts[int(ex_rois[0])].copy(), np.zeros(0))
+            roidb = [{"ex_boxes": np.array([i]), "gt_boxes": None, "gt_labels": None, "gt_overlaps": Width(K)} for i in range(len(ts))]
+            with np.errstate(all="ignore"):
+                means, stds = R.add_bbox_regression_targets(roidb)
+            g["s%d_means" % K], g["s%d_stds" % K] = means, stds
+            g["s%d_norm" % K] = np.vstack([e["bbox_targets"] for e in roidb])
+            assert g["s%d_norm" % K].dtype == np.float32
+            print("%d classes, %d images, %d rows: %d nan stds, %d stds below 1e-6" % (K, len(ts), g["s%d_norm" % K].shape[0],
+                  int(np.isnan(stds).sum()), int((stds < 1e-6).sum())))
+    finally:
+        R._compute_targets = ref_targets
+    path = os.path.join(GOLD, "g22_train_det_edges.npz")
+    np.savez_compressed(path, **g)
+    print("wrote %s: %d KB" % (path, os.path.getsize(path) // 1024))
+
+
+def main(edges=False):
     tmp = tempfile.mkdtemp(prefix="azref_")
     try:
         _, _, _, T, C = gg.build_reference(tmp)
@@ -174,6 +225,8 @@ def main():
         cfg = C.cfg
         assert cfg.EPS == 1e-14 and cfg.TRAIN.BBOX_THRESH == cfg.TRAIN.FG_THRESH == cfg.TRAIN.BG_THRESH_HI == 0.5
         assert cfg.TRAIN.BG_THRESH_LO == 0.1 and cfg.TRAIN.BATCH_SIZE == 128 and cfg.TRAIN.FG_FRACTION == 0.25
+        if edges:
+            return record_edges(R, cfg)
         g = {}
 
         def check_stats(roidb, stds, what):
@@ -290,4 +343,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    main(edges="--edges" in sys.argv[1:])

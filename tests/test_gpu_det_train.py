@@ -65,10 +65,10 @@ def device_masks(sol, seed, it, ratios=(0.5, 0.5)):
     return masks
 
 
-def device_gates(sol, head, pool, blobs, masks, count=None):
+def device_gates(sol, head, pool, blobs, masks, count=None, ratios=(0.5, 0.5)):
     gates = {t: sol.fetch("pre%d" % t) > 0 for t, _, _ in D.LAYERS}
-    r64 = D.step(head, pool, blobs, masks, gates=gates, want_dpool=False)
-    r32 = D.step(head, pool, blobs, masks, gates=gates, dtype=np.float32, want_dpool=False)
+    r64 = D.step(head, pool, blobs, masks, gates=gates, ratios=ratios, want_dpool=False)
+    r32 = D.step(head, pool, blobs, masks, gates=gates, dtype=np.float32, ratios=ratios, want_dpool=False)
     for t, _, _ in D.LAYERS:
         pre64 = r64["pre%d" % t]
         fwd = D.bound(D.rel_err(r32["pre%d" % t], pre64)) * np.abs(pre64).max()
