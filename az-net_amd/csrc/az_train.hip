@@ -388,8 +388,11 @@ __global__ void __launch_bounds__(256) k_normalise(double *t, long long T, int n
 {
     const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
     if (r >= T) return;
-    const int cls = (int)t[7 * r + 5];
-    if (cls < 0 || cls >= n_sub) return;
+    // the rows k_stats_partial counted: t[:, -2] == cls (roidb.py:132); a class like 2.5 or -0.5 belongs to none
+    const double c = t[7 * r + 5];
+    if (!(c >= 0.0 && c < (double)n_sub)) return;
+    const int cls = (int)c;
+    if ((double)cls != c) return;
     for (int q = 0; q < 4; ++q) t[7 * r + q] = (t[7 * r + q] - means[4 * cls + q]) / stds[4 * cls + q];
 }
 

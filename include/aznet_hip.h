@@ -529,8 +529,10 @@ int az_zoom_labels(az_ctx *ctx, const double *rois, int R, const double *gt, int
  * ex_boxes_out f32 [cap,4] (the f64 box rounded once, roidb.py:65), zoom_out [cap], ex_off_out [n_images + 1],
  * noise_used_out [n_images].  AZ_ERR_CAPACITY, and nothing in the outputs, when `noise` runs out (needed_out[0] = the
  * doubles needed at the level that ran out; how many more the rest needs depends on the noise itself) or the regions
- * outgrow `cap` (needed_out[1] = their exact number), or a level holds more than 4096 children before the dedup;
- * needed_out [2] is zero otherwise. */
+ * outgrow `cap` (needed_out[1] = their exact number), or a level holds more than 4096 children before the dedup
+ * (needed_out both zero: no larger buffer helps); AZ_ERR_INVALID when a child's _sift_dup hash
+ * round(box / min_side) . [1, 1e3, 1e6, 1e9] leaves [0, 2^40), i.e. y2 / min_side reaches 1100 or the sum is negative.
+ * needed_out [2] is zero otherwise.  After either error the context is usable as before. */
 int az_train_ex_rois(az_ctx *ctx, const az_train_params *p, int n_images, const int32_t *sizes, const double *gt,
                      const int32_t *gt_off, const double *noise, long long n_noise, float *ex_boxes_out,
                      uint8_t *zoom_out, int32_t *ex_off_out, int cap, long long *noise_used_out, long long *needed_out);
@@ -541,13 +543,18 @@ int az_train_ex_rois(az_ctx *ctx, const az_train_params *p, int n_images, const 
  * row-major order (a maximum of 0 still matches), one row (dx, dy, dw, dh, k within its image, sub-region,
  * IoU(region, object)), that sub-region and object retired.  targets_out f64 [cap,7] ordered by image, k, round;
  * tgt_off_out [n_images + 1].  AZ_ERR_CAPACITY with tgt_off_out filled (tgt_off_out[n_images] = rows needed) and no
- * rows written when cap is too small, or when an image has more objects than the matrix's LDS holds. */
+ * rows written when cap is too small; AZ_ERR_CAPACITY before any launch (tgt_off_out[n_images] left 0) when an image's
+ * n_subregion x objects f64 matrix exceeds 128 KB of LDS: 1489 objects at 11 sub-regions, 1024 at 16. */
 int az_train_adj_targets(az_ctx *ctx, const az_train_params *p, int n_images, const float *ex_boxes,
                          const int32_t *ex_off, const float *gt, const int32_t *gt_off, double *targets_out,
                          int32_t *tgt_off_out, int cap);
 /* roidb.py:110-134 over T target rows: per sub-region (column 5) counts + eps, sums and squared sums of columns 0-3
  * in a fixed two-level order (the same bits on every run), means = sums / counts, stds = sqrt(sq / counts - means^2)
- * -> means_out / stds_out [n_sub * 4]; normalise_in_place != 0: every row's columns 0-3 -> (x - mean) / std. */
+ * -> means_out / stds_out [n_sub * 4]; normalise_in_place != 0: every row's columns 0-3 -> (x - mean) / std.  A row
+ * belongs to sub-region c when column 5 == c exactly (roidb.py:119, 132): rows with any other value there (negative,
+ * >= n_sub, not an integer) enter no statistic and are not normalised.  1 <= n_sub <= AZ_TRAIN_MAX_REGIONS, else
+ * AZ_ERR_INVALID.  An absent sub-region has nan statistics at eps 0, a sub-region of identical rows std 0 and nan rows,
+ * as NumPy has them. */
 int az_train_target_stats(az_ctx *ctx, int n_sub, double eps, double *targets, long long T, double *means_out,
                           double *stds_out, int normalise_in_place);
 

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import train_ref as tr
+from train_edges_ref import check_stats, check_targets, stat_bounds, ulp_diff      # noqa: F401  (derived above)
 
 pytestmark = pytest.mark.gpu
 
@@ -31,23 +32,6 @@ def ctx():
     c = ffi.AzContext(0)
     yield c
     c.close()
-
-
-def ulp_diff(a, b):
-    """Distance in units of the last place of b (f64), elementwise."""
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return np.abs(a - b) / np.spacing(np.maximum(np.abs(b), np.finfo(np.float64).tiny))
-
-
-def check_targets(got, ref, what):
-    assert got.shape == ref.shape, (what, got.shape, ref.shape)
-    if ref.shape[0] == 0:
-        return 0.0
-    for col in (4, 5, 0, 1, 6):
-        assert np.array_equal(got[:, col], ref[:, col]), (what, "column", col)
-    u = float(ulp_diff(got[:, 2:4], ref[:, 2:4]).max())
-    assert u <= 4.0, (what, "dw/dh ulp", u)
-    return u
 
 
 def case_noise(g, i, extra=0):
@@ -79,35 +63,6 @@ def test_adj_targets_golden(ctx, g):
         assert toff.tolist() == [0, int(g["c%d_ntargets" % i])]
         worst = max(worst, check_targets(t, g["c%d_targets" % i], "case %d" % i))
     print("max |dw, dh| difference to the reference: %.2f ulp" % worst)
-
-
-def stat_bounds(means, stds):
-    """Per-entry absolute bounds of means and stds from the golden's own values."""
-    dm = 1e-12 * np.maximum(1.0, np.abs(means))
-    var = stds ** 2
-    amp = np.where(var > 0, (var + means ** 2) / np.where(var > 0, var, 1.0), 1.0)
-    ds = 1e-12 * np.maximum(1.0, amp) * np.maximum(1.0, np.abs(stds))
-    return dm, ds
-
-
-def check_stats(m, s, t, means, stds, t_raw, t_norm, in_err=0.0):
-    """Device means / stds / normalised rows against the golden's, within the bounds the module docstring derives.
-    in_err: absolute error bound of the raw dw / dh the device summed (0 when it was handed the golden's own rows; 4 ulp of
-    the largest |x| when it computed them with its own log).  It moves a mean by <= in_err, E[x^2] - mean^2 by
-    <= 4 max|x| in_err, hence a std by <= 2 max|x| in_err / std, and a normalised value by the usual quotient rule."""
-    dm, ds = stat_bounds(means, stds)
-    xmax = float(np.abs(t_raw[:, :4]).max()) if t_raw.shape[0] else 0.0
-    dm = dm + in_err
-    ds = ds + np.where(stds > 0, 2.0 * xmax * in_err / np.where(stds > 0, stds, 1.0), 0.0)
-    print("max |dmean| %.3e (bound %.1e), max |dstd| / bound %.3e" % (np.abs(m - means).max(), dm.min(),
-                                                                     (np.abs(s - stds) / ds).max()))
-    assert np.all(np.abs(m - means) <= dm)
-    assert np.all(np.abs(s - stds) <= ds)
-    cls = t_raw[:, 5].astype(int)
-    tol = (dm[cls] + in_err + np.abs(t_raw[:, :4] - means[cls]) * ds[cls] / stds[cls]) / stds[cls] \
-        + 8 * np.spacing(np.abs(t_norm[:, :4]))
-    assert np.all(np.abs(t[:, :4] - t_norm[:, :4]) <= tol)
-    assert np.array_equal(t[:, 4:], t_norm[:, 4:])
 
 
 def test_target_stats_golden(ctx, g):

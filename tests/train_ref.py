@@ -64,7 +64,20 @@ def super_regions(ri, subregion):
     return np.hstack((ts, ts[:, [0]] + ls[:, [0]] - 1, ts[:, [1]] + ls[:, [1]] - 1))
 
 
+def children_per_parent(Z):
+    """3 * num_long - 1 of every parent (div.pyx:32-45), 0 where divide_region makes none."""
+    Z = np.asarray(Z, dtype=np.float64).reshape(-1, 4)
+    L0, L1 = Z[:, 2] - Z[:, 0] + 1.0, Z[:, 3] - Z[:, 1] + 1.0
+    short = np.minimum(L0, L1) / 2
+    with np.errstate(divide="ignore", invalid="ignore"):
+        q = np.maximum(L0, L1) / short
+    nl = np.where((short > 0) & (q < 1.0e6), np.floor(q), 0).astype(np.int64)
+    return np.where(nl > 0, 3 * nl - 1, 0)
+
+
 def compute_ex_rois(size, gt, noise, c, stats=None):
+    """stats (a dict), when given, receives per zoomed level (P, PZ, CH) in `levels` and the parents' indices in `zoomed`,
+    the largest CH in `max_children` and the largest child count of one parent in `max_parent`."""
     gt = np.asarray(gt, dtype=np.float64).reshape(-1, 4)
     noise = np.asarray(noise, dtype=np.float64)
     sel, labs, used = [np.zeros((0, 4))], [np.zeros((0,), dtype=bool)], 0
@@ -85,7 +98,11 @@ def compute_ex_rois(size, gt, noise, c, stats=None):
             if Z.shape[0] == 0:
                 break
             if stats is not None:
-                stats["max_children"] = max(stats.get("max_children", 0), orc.divide_children(Z).shape[0])
+                ch = orc.divide_children(Z).shape[0]
+                stats["max_children"] = max(stats.get("max_children", 0), ch)
+                stats.setdefault("levels", []).append((int(B.shape[0]), int(Z.shape[0]), int(ch)))   # P, PZ, CH
+                stats["max_parent"] = max(stats.get("max_parent", 0), int(children_per_parent(Z).max()))
+                stats.setdefault("zoomed", []).append(np.where(np.logical_xor(z, err))[0])
             B = orc.divide_region(Z, float(c.min_side))
     for n in range(gt.shape[0]):
         rs = super_regions(gt[n], c.subregion)
@@ -137,7 +154,8 @@ def compute_targets(gt, ex, c, trace=None):
             trace["bound"] = trace.get("bound", 0) + 1
         for _ in range(min(S, int(adj.sum()))):
             s, n = np.unravel_index(ov.argmax(), ov.shape)
-            if trace is not None:      # (what the golden generator asserts its cases reach)
+            if trace is not None:      # (what the golden generators assert their cases reach)
+                trace.setdefault("argmax", []).append(int(ov.argmax()))
                 trace["zero_rounds"] = trace.get("zero_rounds", 0) + int(ov[s, n] == 0)
                 trace["ties"] = trace.get("ties", 0) + int(ov[s, n] > 0 and (ov == ov[s, n]).sum() > 1)
             out.append(bbox_deltas(ex[k], gt[n], c.eps) + [float(k), float(s), overlaps[k, n]])
@@ -209,7 +227,6 @@ class RefBackend(object):
         return np.vstack(out + [np.zeros((0, 7))]), np.array(off, dtype=np.int32)
 
     def train_target_stats(self, n_sub, eps, targets, normalise=True):
-        c = TrainCfg(eps=eps)
-        assert n_sub == len(c.subregion)
+        c = TrainCfg(eps=eps, subregion=[[0, 0, 1, 1]] * int(n_sub))      # (target_stats reads only its length)
         m, s = target_stats([targets], c, normalise)
         return m, s
