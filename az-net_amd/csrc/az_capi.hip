@@ -66,7 +66,7 @@ int az_destroy(az_ctx *c)
     c->spec_store.clear();
     c->plans.clear();
     if (c->feat_owned[0]) { for (float *f : c->feat_owned) hipFree(f); hipFree(c->feat_stage); }
-    for (void *p : {c->ev_a, c->ev_b, c->ev_c, c->ev_d, c->ev_e, c->ev_f, c->ev_g, c->ev_h, c->ev_voc, c->ev_coco,
+    for (void *p : {c->ev_a, c->ev_b, c->ev_c, c->ev_d, c->ev_e, c->ev_f, c->ev_g, c->ev_h, c->ev_voc, c->ev_coco, c->ev_diag,
                     (void *)c->pyr_feats, (void *)c->pyr_hw, (void *)c->hisB,
                     (void *)c->hisZ, (void *)c->pool, (void *)c->pool_tmp, (void *)c->pool_n, (void *)c->pool_hist})
         if (p) hipFree(p);

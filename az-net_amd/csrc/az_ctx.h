@@ -324,7 +324,8 @@ struct az_ctx {
          *ev_g = nullptr, *ev_h = nullptr;
     void *ev_voc = nullptr;             // slot 8: the arena of az_voc_eval
     void *ev_coco = nullptr;            // slot 9: the arena of az_coco_eval
-    size_t ev_sz[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    void *ev_diag = nullptr;            // slot 10: the arena of az_diag_eval
+    size_t ev_sz[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     // front-end on a caller's stream (az_image_blob_dev_on): two pinned host slots and two device slots for the uint8 image,
     // used in turn; a slot's event says its last upload + kernel are done
     // upload slots of az_image_blob_dev_on (pinned host + device staging + "slot free" event).  Two to start with; a slot

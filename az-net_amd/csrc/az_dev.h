@@ -453,6 +453,28 @@ static __device__ __forceinline__ double az_iou_f64(const double *b, const doubl
     return iw * ih / ua;
 }
 
+// bbox_zoom_labels + the any() over objects (bbox.pyx:20-60, roidb.py:335-339)
+static __device__ __forceinline__ bool az_zoom_label(const double *r, const double *gt, int N, double max_ratio, double min_obj)
+{
+    const double rois_area = (r[2] - r[0] + 1.0) * (r[3] - r[1] + 1.0);
+    bool z = false;
+    for (int n = 0; n < N; ++n) {
+        const double *q = gt + 4 * (size_t)n;
+        const double gt_area = (q[2] - q[0] + 1.0) * (q[3] - q[1] + 1.0);
+        const double ratio = gt_area / (rois_area + 1e-14);
+        if (ratio <= max_ratio) {
+            double ov = 0.0;
+            const double iw = (r[2] < q[2] ? r[2] : q[2]) - (r[0] > q[0] ? r[0] : q[0]) + 1.0;
+            if (iw > 0.0) {
+                const double ih = (r[3] < q[3] ? r[3] : q[3]) - (r[1] > q[1] ? r[1] : q[1]) + 1.0;
+                if (ih > 0.0) ov = iw * ih / (gt_area + 1e-14);
+            }
+            z = z || (ov >= min_obj);
+        }
+    }
+    return z;
+}
+
 // ---- launchers (az_train.hip): the training data layer -----------------------------------------------------------------
 void azk_zoom_labels(hipStream_t s, const double *rois, int R, const double *gt, int N, double max_ratio, double min_obj,
                      unsigned char *out);

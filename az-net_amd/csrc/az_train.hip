@@ -18,26 +18,10 @@ constexpr int LV_C = 4096;         // children per level before _sift_dup (measu
 constexpr int W_SORT = 0, W_TMP = LV_C, W_BINS = 2 * LV_C, W_SCZI = W_BINS + (SORT_NB + 2) / 2 + 7,
               W_SZR = W_SCZI + LV_C / 2, W_WSUM = W_SZR + LV_C / 2, W_MM = W_WSUM + 9, W_END = W_MM + 1;
 
-// bbox_zoom_labels + the any() over objects (bbox.pyx:20-60, roidb.py:335-339)
+// zoom_label: az_zoom_label of az_dev.h (az_diag.hip shares it)
 __device__ __forceinline__ bool zoom_label(const double *r, const double *gt, int N, double max_ratio, double min_obj)
 {
-    const double rois_area = (r[2] - r[0] + 1.0) * (r[3] - r[1] + 1.0);
-    bool z = false;
-    for (int n = 0; n < N; ++n) {
-        const double *q = gt + 4 * (size_t)n;
-        const double gt_area = (q[2] - q[0] + 1.0) * (q[3] - q[1] + 1.0);
-        const double ratio = gt_area / (rois_area + 1e-14);
-        if (ratio <= max_ratio) {
-            double ov = 0.0;
-            const double iw = (r[2] < q[2] ? r[2] : q[2]) - (r[0] > q[0] ? r[0] : q[0]) + 1.0;
-            if (iw > 0.0) {
-                const double ih = (r[3] < q[3] ? r[3] : q[3]) - (r[1] > q[1] ? r[1] : q[1]) + 1.0;
-                if (ih > 0.0) ov = iw * ih / (gt_area + 1e-14);
-            }
-            z = z || (ov >= min_obj);
-        }
-    }
-    return z;
+    return az_zoom_label(r, gt, N, max_ratio, min_obj);
 }
 
 __global__ void __launch_bounds__(256) k_zoom_labels(const double *__restrict__ rois, int R, const double *__restrict__ gt,

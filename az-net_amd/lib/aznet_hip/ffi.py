@@ -39,7 +39,7 @@ SYMBOLS = [
     "az_rccl_unique_id", "az_rccl_init", "az_gather_records", "az_rccl_destroy", "az_comm_stream",
     "az_bias_relu", "az_bias_relu_pool", "az_batch_launch", "az_batch_fetch", "az_batch_next_stream",
     "az_batch_stage_results_dev", "az_batch_fetch_all", "az_batch_launch_shapes", "az_abi_sizes",
-    "az_detect_batch", "az_voc_eval", "az_coco_eval",
+    "az_detect_batch", "az_voc_eval", "az_coco_eval", "az_diag_eval",
     "az_set_feature_pyramid_dev_nhwc", "az_roi_dedup_pyramid", "az_roi_pool_pyramid", "az_propose_pyramid",
     "az_detect_pyramid",
     "az_zoom_labels", "az_train_ex_rois", "az_train_adj_targets", "az_train_target_stats",
@@ -220,6 +220,9 @@ def load_library(path=None):
                               ctypes.POINTER(ctypes.c_int64), dp, dp]
     L.az_coco_eval.argtypes = [vp, ci, ci, dp, dp, ip, dp, dp, u8p, ip, dp, dp, dp, ip, ctypes.POINTER(ctypes.c_int8)]
     tpp = ctypes.POINTER(AzTrainParams)
+    L.az_diag_eval.argtypes = [vp, ci, dp, fp, ip, ip, ctypes.c_longlong, dp, ip, ctypes.c_longlong, dp, ip,
+                               ctypes.c_longlong, cd, cd, cd, cd, ip, ci, dp, u8p, ctypes.POINTER(ctypes.c_int64), dp, ip, ip,
+                               ip, ctypes.POINTER(ctypes.c_int64), fp]
     L.az_zoom_labels.argtypes = [vp, dp, ci, dp, ci, cd, cd, u8p]
     L.az_train_ex_rois.argtypes = [vp, tpp, ci, ip, dp, ip, dp, ll, fp, u8p, ip, ci, llp, llp]
     L.az_train_adj_targets.argtypes = [vp, tpp, ci, fp, ip, fp, ip, dp, ip, ci]
@@ -1231,6 +1234,63 @@ class AzContext(object):
                                       _p(gc, ctypes.c_uint8), _p(goff, ctypes.c_int32),
                                       _p(out["precision"], ctypes.c_double), _p(out["recall"], ctypes.c_double),
                                       _p(out["stats"], ctypes.c_double), mp, ip_))
+        return out
+
+    # ---- proposal diagnosis (what tune.py:368-419 records AZ_results.mat for) ----------------
+    def diag_eval(self, anchors_list, zoom_list, level_list, gt_list, props_list, tz, emb_reg_thresh, emb_obj_thresh,
+                  iou_thresh=0.5, cuts=(10, 50, 100, 300, 1000, 2000), area_edges=(32 ** 2, 96 ** 2), want_kernel_ms=False):
+        """az_diag_eval ("Proposal diagnosis") for a whole image set at once: per image [m_i,4] anchors with their zoom scores
+        (f32) and search levels, [k_i,4] objects and [n_i,4] proposals in rank order.  Returns a dict: anchor_label [A]
+        u8, level_table [AZ_MAX_LEVELS,4] int64 (anchors, zoomed, labelled, both), best_iou [G] f64, best_rank /
+        first_hit / deepest_level [G] int32, recall_table [len(cuts)+1,4] int64 (all / small / medium / large; the
+        last row counts every object), the three offset arrays, and with want_kernel_ms the kernels' device time."""
+        n = len(anchors_list)
+        assert len(zoom_list) == n and len(level_list) == n and len(gt_list) == n and len(props_list) == n
+        aoff, goff, poff = self._offsets(anchors_list), self._offsets(gt_list), self._offsets(props_list)
+        a = _f64(np.vstack([np.zeros((0, 4))] + [np.asarray(x).reshape(-1, 4) for x in anchors_list]))
+        g = _f64(np.vstack([np.zeros((0, 4))] + [np.asarray(x).reshape(-1, 4) for x in gt_list]))
+        p = _f64(np.vstack([np.zeros((0, 4))] + [np.asarray(x).reshape(-1, 4) for x in props_list]))
+        z = _f32(np.concatenate([np.zeros(0, np.float32)] + [np.asarray(x, dtype=np.float32).ravel() for x in zoom_list]))
+        lv = np.ascontiguousarray(np.concatenate([np.zeros(0, np.int32)] + [np.asarray(x).ravel() for x in level_list]),
+                                  dtype=np.int32)
+        if z.size != a.shape[0] or lv.size != a.shape[0]:
+            raise AzError(AZ_ERR_INVALID, "diag_eval: zoom scores / levels disagree with the anchors")
+        return self.diag_eval_packed(a, z, lv, aoff, g, goff, p, poff, tz, emb_reg_thresh, emb_obj_thresh, iou_thresh, cuts,
+                                     area_edges, want_kernel_ms=want_kernel_ms)
+
+    def diag_eval_packed(self, anchors, zoom, level, anc_off, gt, gt_off, props, prop_off, tz, emb_reg_thresh,
+                         emb_obj_thresh, iou_thresh, cuts, area_edges, want_kernel_ms=False, counts=None, out=None):
+        """az_diag_eval on arrays that are packed already (what diag_eval builds).  counts: (n_anchors, n_gt, n_props)
+        when they are not to be taken from the arrays; out: a dict of preallocated outputs to fill instead of new ones."""
+        a, g, p = _f64(anchors).reshape(-1, 4), _f64(gt).reshape(-1, 4), _f64(props).reshape(-1, 4)
+        z = _f32(zoom).ravel()
+        lv = np.ascontiguousarray(level, dtype=np.int32).ravel()
+        aoff, goff, poff = (np.ascontiguousarray(o, dtype=np.int32).ravel() for o in (anc_off, gt_off, prop_off))
+        n = aoff.size - 1
+        if n < 0 or goff.size != n + 1 or poff.size != n + 1:
+            raise AzError(AZ_ERR_INVALID, "diag_eval: the three offset arrays need n_images+1 entries each")
+        A, G, P = counts if counts is not None else (a.shape[0], g.shape[0], p.shape[0])
+        ct = np.ascontiguousarray(cuts, dtype=np.int32).ravel()
+        ed = _f64(area_edges).ravel()
+        if ed.size != 2:
+            raise AzError(AZ_ERR_INVALID, "diag_eval: area_edges needs two entries")
+        if out is None:
+            out = {"anchor_label": np.zeros(a.shape[0], np.uint8), "level_table": np.zeros((AZ_MAX_LEVELS, 4), np.int64),
+                   "best_iou": np.zeros(g.shape[0], np.float64), "best_rank": np.zeros(g.shape[0], np.int32),
+                   "first_hit": np.zeros(g.shape[0], np.int32), "deepest_level": np.zeros(g.shape[0], np.int32),
+                   "recall_table": np.zeros((ct.size + 1, 4), np.int64)}
+        ms = ctypes.c_float(0.0)
+        self._chk(self.L.az_diag_eval(
+            self.h, n, _p(a, ctypes.c_double), _p(z, ctypes.c_float), _p(lv, ctypes.c_int32), _p(aoff, ctypes.c_int32), int(A),
+            _p(g, ctypes.c_double), _p(goff, ctypes.c_int32), int(G), _p(p, ctypes.c_double), _p(poff, ctypes.c_int32), int(P),
+            float(tz), float(emb_reg_thresh), float(emb_obj_thresh), float(iou_thresh), _p(ct, ctypes.c_int32), ct.size,
+            _p(ed, ctypes.c_double), _p(out["anchor_label"], ctypes.c_uint8), _p(out["level_table"], ctypes.c_int64),
+            _p(out["best_iou"], ctypes.c_double), _p(out["best_rank"], ctypes.c_int32), _p(out["first_hit"], ctypes.c_int32),
+            _p(out["deepest_level"], ctypes.c_int32), _p(out["recall_table"], ctypes.c_int64),
+            ctypes.byref(ms) if want_kernel_ms else None))
+        out.update(anc_off=aoff, gt_off=goff, prop_off=poff, cuts=ct.copy())
+        if want_kernel_ms:
+            out["kernel_ms"] = float(ms.value)
         return out
 
     # ---- image front-end ---------------------------------------------------------------

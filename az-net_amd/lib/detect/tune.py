@@ -2,6 +2,7 @@
 
     im_propose(net, im)       tune.py:256-316   -> ([Y | score] [n,5], Bhis [m,5])
     tune_thresh(net, imdb)    tune.py:318-366   -> writes thresh.pkl, returns the threshold
+    test_proposals(net, imdb) tune.py:368-419   -> writes AZ_results.mat, returns what it holds (detect.diagnose reads it)
 
 The tuner's search differs from lib/detect/test.py's: it walks K levels (not K-1), compares the
 zoom scores of the first level against 0 and of later levels against cfg.SEAR.Tz (0 in 'Train'
@@ -48,11 +49,18 @@ def _search(hnet, im, conv=None):
 def im_propose(net, im, conv=None):
     """tune.py:256-316.  Returns (hstack(Y, scores) [n,5] float64, Bhis [m,5] float64 =
     anchor regions with their zoom scores, level-major)."""
+    Y5, Bhis, _ = _im_propose_stats(net, im, conv)
+    return Y5, Bhis
+
+
+def _im_propose_stats(net, im, conv=None):
+    """im_propose plus the search's statistics (level_regions: the anchors of each level, Bhis being level-major)."""
     hnet = net["full"] if isinstance(net, dict) else net
     Y, S, st = _search(hnet, im, conv)
     regions, zoom = hnet.ctx.last_anchors()
     print('{0} proposals, evaluate {1} regions, reaches depth {2}.'.format(Y.shape[0], st.num_eval, st.depth))
-    return np.hstack((Y, S.astype(np.float64)[:, np.newaxis])), np.hstack((regions, zoom.astype(np.float64)[:, np.newaxis]))
+    return (np.hstack((Y, S.astype(np.float64)[:, np.newaxis])),
+            np.hstack((regions, zoom.astype(np.float64)[:, np.newaxis])), st)
 
 
 def tune_thresh(net, imdb, gather=None):
@@ -93,3 +101,55 @@ def tune_thresh(net, imdb, gather=None):
     with open(os.path.join(output_dir, 'thresh.pkl'), 'wb') as f:
         pickle.dump(thresh, f, pickle.HIGHEST_PROTOCOL)
     return thresh
+
+
+AZ_RESULTS_KEYS = ("prop_boxes", "anchor_boxes", "gt_boxes", "fn", "Tz", "num_proposals", "im_shapes")
+
+
+def write_az_results(path, results):
+    """AZ_results.mat as tune.py:412-419 writes it: the seven keys, the per-image ones as object arrays of
+    num_images cells built as tune.py:375-379 builds them."""
+    import scipy.io as sio
+    n = len(results["fn"])
+    out = {}
+    for key in ("prop_boxes", "anchor_boxes", "gt_boxes", "fn", "im_shapes"):
+        cells = np.zeros((n,), dtype=object)
+        for i in range(n):
+            cells[i] = results[key][i]
+        out[key] = cells
+    sio.savemat(path, dict(prop_boxes=out["prop_boxes"], anchor_boxes=out["anchor_boxes"], gt_boxes=out["gt_boxes"],
+                           fn=out["fn"], Tz=results["Tz"], num_proposals=results["num_proposals"],
+                           im_shapes=out["im_shapes"]))
+
+
+def test_proposals(net, imdb):
+    """Record everything a fine-grained analysis of a proposal run needs -- proposals, every anchor region with its
+    zoom score, ground truth, file names, image shapes (tune.py:368-419) -- with the tuner-variant search in whatever
+    mode cfg is in.  Writes <output_dir>/AZ_results.mat and returns its contents as a dict, plus `level_regions` (the
+    anchors of each search level per image: anchor_boxes is level-major) for detect.diagnose."""
+    hnet = net["full"] if isinstance(net, dict) else net
+    num_images = len(imdb.image_index)
+    prop_boxes, anchor_boxes, gt_boxes = [None] * num_images, [None] * num_images, [None] * num_images
+    fn, im_shapes, level_regions = [None] * num_images, [None] * num_images, [None] * num_images
+    output_dir = get_output_dir(imdb, hnet)
+    if not os.path.exists(output_dir):
+        os.makedirs(output_dir)
+    _t = {'im_prop': Timer()}
+    gt_roidb = imdb.gt_roidb()
+    from detect.test import _prefetched
+    images = _prefetched(imdb, list(range(num_images)), depth=int(cfg.TEST.get("PREFETCH", 2)))
+    for i in range(num_images):
+        im = next(images)
+        im_shapes[i] = tuple(int(d) for d in im.shape)
+        _t['im_prop'].tic()
+        prop_boxes[i], anchor_boxes[i], st = _im_propose_stats(net, im)
+        _t['im_prop'].toc()
+        level_regions[i] = np.array(st.level_regions[:st.n_levels], dtype=np.int32)
+        gt_boxes[i] = gt_roidb[i]['boxes']
+        fn[i] = os.path.basename(imdb.image_path_at(i))
+        print('im_prop: {:d}/{:d} {:.3f}s'.format(i + 1, num_images, _t['im_prop'].average_time))
+    results = dict(prop_boxes=prop_boxes, anchor_boxes=anchor_boxes, gt_boxes=gt_boxes, fn=fn, Tz=cfg.SEAR.Tz,
+                   num_proposals=cfg.SEAR.NUM_PROPOSALS, im_shapes=im_shapes)
+    write_az_results(os.path.join(output_dir, 'AZ_results.mat'), results)
+    results["level_regions"] = level_regions
+    return results

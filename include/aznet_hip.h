@@ -471,6 +471,38 @@ int az_coco_eval(az_ctx *ctx, int n_classes, int n_images,
                  double *precision_out, double *recall_out, double *stats_out,
                  int32_t *dt_match_out, int8_t *dt_ignore_out);
 
+/* ---- proposal diagnosis (what lib/detect/tune.py:368-419 records AZ_results.mat for) --------------------------- */
+/* The offline analysis of a proposal run, restated in DESIGN §4, "Proposal diagnosis", for n_images images in one call.  Image i owns
+ * anchors[anc_off[i]:anc_off[i+1]] (f64 [.,4]: the search's anchor history `Bhis`, tune.py:299) with the zoom score
+ * (f32) and the search level (int32, 0 = the root level) of each, gt[gt_off[i]:gt_off[i+1]] (f64 [.,4]) and
+ * props[prop_off[i]:prop_off[i+1]] (f64 [.,4], in rank order as the search returns them, tune.py:309-311); n_anchors,
+ * n_gt, n_props are the row counts the offsets must end at.  cuts[n_cuts] (n_cuts <= 16): ascending proposal budgets;
+ * area_edges[2]: an object is small below area_edges[0], medium below area_edges[1], else large, by
+ * area = (x2-x1+1)*(y2-y1+1).  Every output may be NULL:
+ *   anchor_label_out [A] u8      _compute_zoom_labels of the anchor against its image's objects (roidb.py:313-341,
+ *                                lib/utils/bbox.pyx:20-60) at max_area_ratio = emb_reg_thresh, min_obj = emb_obj_thresh
+ *   level_table_out [AZ_MAX_LEVELS][4] i64   per level: anchors, zoomed, labelled, zoomed and labelled; zoomed is
+ *                                (double)zoom >= (level == 0 ? 0.0 : tz) (tune.py:282, 296, 306)
+ *   gt_best_iou_out [G] f64 / gt_best_rank_out [G] i32   the largest bbox_overlaps IoU (bbox.pyx:132-172) of the object
+ *                                with its image's proposals and the rank of its first maximum; 0.0 / -1 without proposals
+ *   gt_first_hit_out [G] i32     the smallest rank with IoU >= iou_thresh, or -1
+ *   gt_deepest_level_out [G] i32 the largest level of an anchor of the image that holds the object (iw > 0, ih > 0,
+ *                                iw*ih / (gt_area + 1e-14) >= emb_obj_thresh: bbox.pyx:48-58 without the area-ratio gate), or -1
+ *   recall_table_out [n_cuts + 1][4] i64   row c: objects with 0 <= first_hit < cuts[c]; the last row: all objects;
+ *                                columns all / small / medium / large
+ *   kernel_ms_out [1] f32        device time of the two launches (two events around them)
+ * Malformed offsets (negative, descending, or not ending at the row counts), a level outside [0, AZ_MAX_LEVELS),
+ * descending cuts or n_cuts > 16 are AZ_ERR_INVALID and row counts past int32 AZ_ERR_CAPACITY, both before any device
+ * work and with the outputs untouched.  Device scratch is kept in the context. */
+int az_diag_eval(az_ctx *ctx, int n_images,
+                 const double *anchors, const float *zoom, const int32_t *level, const int32_t *anc_off, long long n_anchors,
+                 const double *gt, const int32_t *gt_off, long long n_gt,
+                 const double *props, const int32_t *prop_off, long long n_props,
+                 double tz, double emb_reg_thresh, double emb_obj_thresh, double iou_thresh,
+                 const int32_t *cuts, int n_cuts, const double *area_edges,
+                 uint8_t *anchor_label_out, int64_t *level_table_out, double *gt_best_iou_out, int32_t *gt_best_rank_out,
+                 int32_t *gt_first_hit_out, int32_t *gt_deepest_level_out, int64_t *recall_table_out, float *kernel_ms_out);
+
 /* ---- image front-end (_get_image_blob, lib/detect/test.py:27-59) ------------------------- */
 /* uint8 BGR HWC image (host) -> float32 [3, oh, ow] blob: subtract cfg.PIXEL_MEANS, then
  * cv2.resize(fx=fy=scale, INTER_LINEAR) semantics on f32 (half-pixel centres, edge clamp,
