@@ -61,6 +61,7 @@ int az_destroy(az_ctx *c)
     c->allocs_geom.clear();
     for (void *p : c->allocs_det) hipFree(p);
     c->allocs_det.clear();
+    skip_free(c);
     for (auto *q : c->plans) { free_plan(q); delete q; }
     for (auto &e : c->spec_store) for (void *q2 : {(void *)e.urois, (void *)e.B1, (void *)e.choff, (void *)e.Udev}) if (q2) hipFree(q2);
     c->spec_store.clear();

@@ -298,6 +298,18 @@ struct az_ctx {
     unsigned short *dW6p = nullptr; float *dgscale = nullptr; float det_w6_scale = 0.f;
     float *dh6 = nullptr, *dh7 = nullptr, *dpart = nullptr, *dprob_u = nullptr, *ddelta_u = nullptr, *dprob = nullptr;
     double *dpred_u = nullptr, *dpred = nullptr;
+    // the skip-connection front of the detection head (az_skip.hip: az_load_skip_front): up to AZ_SKIP_MAX_SRC borrowed
+    // channel-last maps, each pooled 7x7 and normalised across its channels, concatenated [rows][sumC] in `cat`
+    // (AZ_SKIP_CHUNK rois at a time) and folded to the head's C channels by a 1x1 convolution straight into pool5
+    struct SkipFront {
+        bool loaded = false, maps_set = false;
+        int n = 0, C[AZ_SKIP_MAX_SRC] = {0, 0, 0}, sumC = 0, Cout = 0;
+        float scale[AZ_SKIP_MAX_SRC] = {0.f, 0.f, 0.f};
+        double gain = 1000.0, eps = 1e-10;       // scale5 (test_fc.prototxt of the skip model); the GRN layers' eps
+        float *Wp = nullptr, *bp = nullptr, *cat = nullptr;
+        const float *maps[AZ_SKIP_MAX_SRC] = {nullptr, nullptr, nullptr};
+        int H[AZ_SKIP_MAX_SRC] = {0, 0, 0}, W[AZ_SKIP_MAX_SRC] = {0, 0, 0};
+    } skip;
     // az_detect_batch: one pass's AzDetSeg + boxes (pinned staging and its device copy), per-row image sizes
     unsigned char *dseg_host = nullptr, *dseg_dev = nullptr;
     int *drow_hw = nullptr;
@@ -800,6 +812,13 @@ void rank_by_score(hipStream_t s, int D, long long S, int n_images, int n_classe
 void az_solver_free_all(az_ctx *c);       // az_destroy: the trainers still alive
 // ---- az_det_solver.hip ---------------------------------------------------------------------------------------------------
 void az_det_solver_free_all(az_ctx *c);
+// ---- az_skip.hip --------------------------------------------------------------------------------------------------------
+// what every skip entry refuses before it enqueues anything (`who`: the entry's name); need_maps: the maps must be set
+int skip_check(az_ctx *c, const char *who, bool need_maps);
+// the front on the rois in c->urois (row count *Uptr, at most rows_bound): pool5 [U][49][Cout] as the head's fc6 reads it
+void skip_front_launch(az_ctx *c, const int *Uptr, int rows_bound);
+void skip_free(az_ctx *c);                // az_destroy
+int skip_pool_unit(az_ctx *c, int R, int normalise, float *out);      // az_skip_pool past its checks, the rois staged
 // ---- az_capi.hip --------------------------------------------------------------------------------------------------------
 int set_feature_map_common(az_ctx *c, const float *src, bool src_is_host, int C, int H, int W, bool wait = true);
 int ensure_lane_head(az_ctx *t);          // the head buffers of a lane / batch slot created without them

@@ -420,14 +420,17 @@ int az_load_det_head(az_ctx *c, int C, int n6, int n7, int ncls, const float *W6
     HIPCHK(c, hipMemcpy(c->dbt + ncls, bb, (size_t)4 * ncls * 4, hipMemcpyHostToDevice));
     HIPCHK(c, hipDeviceSynchronize());
     c->det_loaded = true;
+    if (c->skip.loaded && c->skip.Cout != C) skip_free(c);     // (a skip front folds to the head's C)
     return AZ_OK;
 }
 
 // the detection head on the `U` rois in ctx->urois / ctx->ubox
 // (rows_bound: what the host knows about the row count -- the number of boxes before the 1/16 dedup)
 // (feats / feat_hw / row_hw: the rows of several images, az_detect_batch -- RoIPool's map table, per-row image sizes)
+// (skip: pool5 comes from the skip-connection front, az_skip.hip, instead of RoIPool of the context's map)
 static void launch_det_head(az_ctx *c, const int *Uptr, int im_h, int im_w, double eps, int rows_bound,
-                            const float *const *feats = nullptr, const int *feat_hw = nullptr, const int *row_hw = nullptr)
+                            const float *const *feats = nullptr, const int *feat_hw = nullptr, const int *row_hw = nullptr,
+                            bool skip = false)
 {
     AzHeadDims d = c->d;
     const int K6 = d.C * 49, NO = 5 * c->det_ncls;
@@ -442,6 +445,8 @@ static void launch_det_head(az_ctx *c, const int *Uptr, int im_h, int im_w, doub
     const bool terms = c->gemm_parts && c->dW6p;             // (16-bit-term modes: fc6, 86 % of this head's FLOPs, as int6)
     if (terms && c->gemm_parts == 2)
         azk_feat_scale(c->stream, c->feat, (long long)d.C * d.H * d.W, c->dgscale, c->det_w6_scale);
+    if (skip) skip_front_launch(c, Uptr, rows_bound);
+    else
     { Timed t(c, "det_roi_pool", 0);
       azk_roi_pool(c->stream, c->feat, d, c->spatial_scale, c->urois, Uptr, c->maxR, c->pool5, terms ? c->pool5p : nullptr,
                    terms ? azk_act_plane_elems(c->maxR, K6) : 0, terms ? c->gemm_parts : 0, 0, 0,
@@ -505,7 +510,7 @@ static int fetch_dets(az_ctx *c, int P, float *scores_out, double *boxes_out)
 // head with RoIPool from the context's map or through the map table feats / feat_hw, the un-dedup gather, the download
 static int detect(az_ctx *c, const double *boxes, int P, double scale, const AzPyrScales *pyr, double dedup,
                   int batch_size, int im_h, int im_w, double eps, const float *const *feats, const int *feat_hw,
-                  float *scores_out, double *boxes_out)
+                  float *scores_out, double *boxes_out, bool skip = false)
 {
     if (P == 0) return AZ_OK;
     HIPCHK(c, hipSetDevice(c->device));
@@ -515,7 +520,7 @@ static int detect(az_ctx *c, const double *boxes, int P, double scale, const AzP
     if (rc) return rc;
     azk_rois_dedup(s, c->B[0], &c->cnt->P[0], c->maxR, scale, pyr, (float)dedup, batch_size, c->rois, c->key, c->grp,
                    c->first, c->index, c->inv, c->urois, c->ubox, &c->cnt->U[0]);
-    launch_det_head(c, &c->cnt->U[0], im_h, im_w, eps, P, feats, feat_hw);
+    launch_det_head(c, &c->cnt->U[0], im_h, im_w, eps, P, feats, feat_hw, nullptr, skip);
     azk_det_gather(s, &c->cnt->P[0], c->inv, c->det_ncls, c->dprob_u, c->dpred_u, c->dprob, c->dpred);
     return fetch_dets(c, P, scores_out, boxes_out);
 }
@@ -528,6 +533,43 @@ int az_detect(az_ctx *c, const double *boxes, int P, double scale, double dedup,
     if (P < 0 || (P && !boxes) || batch_size <= 0 || !(scale > 0)) return fail(c, AZ_ERR_INVALID, "az_detect: bad arguments");
     if (P > c->maxR) return fail(c, AZ_ERR_CAPACITY, "az_detect: too many boxes");
     return detect(c, boxes, P, scale, nullptr, dedup, batch_size, im_h, im_w, eps, nullptr, nullptr, scores_out, boxes_out);
+}
+
+// The skip-connection detector (az_skip.hip): az_detect / az_det_forward / az_roi_pool with the front in RoIPool's place.
+int az_detect_skip(az_ctx *c, const double *boxes, int P, double scale, double dedup, int batch_size, int im_h,
+                   int im_w, double eps, float *scores_out, double *boxes_out)
+{
+    int rc = skip_check(c, "az_detect_skip", true);
+    if (rc) return rc;
+    if (P < 0 || (P && !boxes) || batch_size <= 0 || !(scale > 0)) return fail(c, AZ_ERR_INVALID, "az_detect_skip: bad arguments");
+    if (P > c->maxR) return fail(c, AZ_ERR_CAPACITY, "az_detect_skip: too many boxes");
+    return detect(c, boxes, P, scale, nullptr, dedup, batch_size, im_h, im_w, eps, nullptr, nullptr, scores_out, boxes_out, true);
+}
+
+int az_det_forward_skip(az_ctx *c, const float *rois, int R, float *cls_prob, float *bbox_pred)
+{
+    int rc = skip_check(c, "az_det_forward_skip", true);
+    if (rc) return rc;
+    if (R > c->maxR) return fail(c, AZ_ERR_CAPACITY, "az_det_forward_skip: too many rois");
+    if ((rc = stage_rois(c, rois, R)) != AZ_OK) return rc;
+    if (!(c->profiling & 4)) clear_events(c);
+    launch_det_head(c, &c->cnt->U[0], 1, 1, 0.0, R, nullptr, nullptr, nullptr, true);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    const size_t nc = (size_t)c->det_ncls;
+    if (R && cls_prob) HIPCHK(c, hipMemcpy(cls_prob, c->dprob_u, (size_t)R * nc * 4, hipMemcpyDeviceToHost));
+    if (R && bbox_pred) HIPCHK(c, hipMemcpy(bbox_pred, c->ddelta_u, (size_t)R * 4 * nc * 4, hipMemcpyDeviceToHost));
+    return AZ_OK;
+}
+
+int az_skip_pool(az_ctx *c, const float *rois, int R, int normalise, float *out)
+{
+    int rc = skip_check(c, "az_skip_pool", true);
+    if (rc) return rc;
+    if (R > c->maxR) return fail(c, AZ_ERR_CAPACITY, "az_skip_pool: too many rois");
+    if (R < 0 || (R && (!rois || !out))) return fail(c, AZ_ERR_INVALID, "az_skip_pool: bad arguments");
+    if ((rc = stage_rois(c, rois, R)) != AZ_OK) return rc;
+    return skip_pool_unit(c, R, normalise ? 1 : 0, out);
 }
 
 // _frcnn_forward over an image pyramid: az_detect with the pyramid projection and RoIPool through the map table (each

@@ -55,9 +55,29 @@ class VGG16Conv5(object):
         self.out_channels = cin
 
     @torch.no_grad()
-    def forward(self, blob):
+    def forward(self, blob, taps=None):
         """blob: [1,3,H,W] float32 (BGR, mean-subtracted), NumPy or torch -> conv5_3 [1,C,h,w]
-        contiguous fp32 tensor on the device."""
+        contiguous fp32 tensor on the device.
+        taps (the skip-connection detector: cfg.SEAR.FRCNN_CONV with several names), e.g. ("conv3_3", "conv4_3"): a dict
+        {name: [1,C,h,w] map in torch.channels_last memory} of the named layers' post-ReLU outputs and of conv5_3."""
+        taps = tuple(taps or ())
+        x, kept = self._layers(blob, taps)
+        if taps:
+            kept[[layer[0] for layer in self.layers if layer is not None][-1]] = x.contiguous(memory_format=torch.channels_last)
+            return kept
+        if self.channels_last_out:
+            return x.contiguous(memory_format=torch.channels_last)
+        return x.contiguous()
+
+    def _layers(self, blob, taps):
+        """The layer stack on `blob`: (conv5_3 as the last layer left it, {name: channels_last copy} of the layers named in
+        `taps`).  A tapped layer in front of a pool cannot take the fused bias + ReLU + pool epilogue (its pre-pool output
+        must exist): bias + ReLU in place (az_bias_relu), then the pool -- the same fp32 operations, the same bits."""
+        names = [layer[0] for layer in self.layers if layer is not None]
+        for t in taps:
+            if t not in names:
+                raise ValueError("no layer %r to tap (layers: %s)" % (t, ", ".join(names)))
+        kept = {}
         x = torch.as_tensor(blob, dtype=torch.float32, device=self.device)
         if self.cl_compute:
             x = x.contiguous(memory_format=torch.channels_last)
@@ -72,29 +92,28 @@ class VGG16Conv5(object):
                     x = F.max_pool2d(x, kernel_size=2, stride=2, ceil_mode=True)
                 skip_pool = False
                 continue
-            if fused and (layer[1].shape[0] % 4 == 0 or not self.cl_compute):
-                y = F.conv2d(x, layer[1], None, padding=1)
-                if (y.is_contiguous(memory_format=torch.channels_last) if self.cl_compute else y.is_contiguous()) \
-                        and y.data_ptr() % 16 == 0 and layer[2].data_ptr() % 16 == 0 and layer[2].is_contiguous():
-                    from . import ffi
-                    try:
-                        if li + 1 < len(self.layers) and self.layers[li + 1] is None:
-                            x = ffi.bias_relu_pool(y, layer[2])
-                            skip_pool = True
-                        else:
-                            x = ffi.bias_relu_(y, layer[2])
-                        continue
-                    except ffi.AzError as e:
-                        # (a layout the fused kernels decline -- AZ_ERR_INVALID, nothing was written: PyTorch's own ops)
-                        if e.code != ffi.AZ_ERR_INVALID:
-                            raise
-                        skip_pool = False
-                x = F.relu_(y + layer[2].view(1, -1, 1, 1))
-                continue
-            x = F.relu_(F.conv2d(x, layer[1], layer[2], padding=1))
-        if self.channels_last_out:
-            return x.contiguous(memory_format=torch.channels_last)
-        return x.contiguous()
+            x, skip_pool = self._conv_relu(x, li, layer, fused, layer[0] in taps)
+            if layer[0] in taps:
+                kept[layer[0]] = x.contiguous(memory_format=torch.channels_last)
+        return x, kept
+
+    def _conv_relu(self, x, li, layer, fused, tapped):
+        """One convolution + bias + ReLU (+ the pool behind it when the fused epilogue takes it: second result True)."""
+        if fused and (layer[1].shape[0] % 4 == 0 or not self.cl_compute):
+            y = F.conv2d(x, layer[1], None, padding=1)
+            if (y.is_contiguous(memory_format=torch.channels_last) if self.cl_compute else y.is_contiguous()) \
+                    and y.data_ptr() % 16 == 0 and layer[2].data_ptr() % 16 == 0 and layer[2].is_contiguous():
+                from . import ffi
+                try:
+                    if not tapped and li + 1 < len(self.layers) and self.layers[li + 1] is None:
+                        return ffi.bias_relu_pool(y, layer[2]), True
+                    return ffi.bias_relu_(y, layer[2]), False
+                except ffi.AzError as e:
+                    # (a layout the fused kernels decline -- AZ_ERR_INVALID, nothing was written: PyTorch's own ops)
+                    if e.code != ffi.AZ_ERR_INVALID:
+                        raise
+            return F.relu_(y + layer[2].view(1, -1, 1, 1)), False
+        return F.relu_(F.conv2d(x, layer[1], layer[2], padding=1)), False
 
     __call__ = forward
 

@@ -154,14 +154,45 @@ def det_head_from_layers(layers):
     W7, b7 = _fc(layers, "fc7")
     Wc, bc = _fc(layers, "cls_score")
     Wb, bb = _fc(layers, "bbox_pred")
-    return {"W6": W6, "b6": b6, "W7": W7, "b7": b7, "Wc": Wc, "bc": bc, "Wb": Wb, "bb": bb}
+    head = {"W6": W6, "b6": b6, "W7": W7, "b7": b7, "Wc": Wc, "bc": bc, "Wb": Wb, "bb": bb}
+    # the skip-connection detector (models/COCO/VGG16_skip): its front travels with the head it feeds, so that whatever
+    # builds a HipDetNet / HipFrcnnNet from this dict gets the model the file holds
+    front = skip_front_from_layers(layers)
+    if front is not None:
+        head["skip_front"] = front
+    return head
+
+
+def skip_front_from_layers(layers, Cs=None, scales=(0.25, 0.125, 0.0625), names=("conv3_3", "conv4_3", "conv5_3"),
+                           gain=1000.0, eps=1e-10):
+    """The skip-connection front of models/COCO/VGG16_skip/frcnn/test_fc.prototxt: conv_pool5, the 1x1 convolution
+    [512, 1280, 1, 1] + bias behind roi_pool3/4/5 -> roi_norm3/4/5 (GRN: no blobs) -> concat5 -> scale5 (a constant:
+    `gain`) -> the dict AzContext.load_skip_front / synth.make_skip_front use.  None when the layer is absent (the plain
+    Fast R-CNN net).  scales / names: the sources in concat5's order, as the prototxt fixes them; Cs: their channel
+    counts (default: the output channels of the file's own conv layers of those names, else VGG16's 256, 512, 512)."""
+    if "conv_pool5" not in layers:
+        return None
+    if Cs is None:
+        own = [layers[n][0].shape[0] for n in names if n in layers and layers[n] and np.ndim(layers[n][0]) == 4]
+        Cs = tuple(int(c) for c in own) if len(own) == len(names) else (256, 512, 512)
+    blobs = layers["conv_pool5"]
+    if len(blobs) < 2:
+        raise ValueError("conv_pool5 needs a weight and a bias blob, found %d blob(s)" % len(blobs))
+    bp = np.ascontiguousarray(blobs[1].ravel(), dtype=np.float32)
+    w = np.asarray(blobs[0], dtype=np.float32)
+    if w.size != bp.size * sum(Cs) or (w.ndim == 4 and w.shape[2:] != (1, 1)):
+        raise ValueError("conv_pool5 is %s with %d biases: not a 1x1 convolution over %d = sum%s channels"
+                         % (w.shape, bp.size, sum(Cs), tuple(Cs)))
+    Wp = np.ascontiguousarray(w.reshape(bp.size, sum(Cs)), dtype=np.float32)
+    return {"Cs": tuple(int(c) for c in Cs), "scales": tuple(float(x) for x in scales), "names": tuple(names),
+            "gain": float(gain), "eps": float(eps), "Wp": Wp, "bp": bp}
 
 
 def backbone_from_layers(layers):
     """{conv name: (W [out, in, 3, 3], b [out])} for conv1_1 .. conv5_3 (VGG16Conv5(weights=...))."""
     out = {}
     for name, blobs in layers.items():
-        if name.startswith("conv") and len(blobs) >= 2 and blobs[0].ndim == 4:
+        if name.startswith("conv") and name != "conv_pool5" and len(blobs) >= 2 and blobs[0].ndim == 4:
             out[name] = (np.ascontiguousarray(blobs[0], dtype=np.float32),
                          np.ascontiguousarray(blobs[1].ravel(), dtype=np.float32))
     return out
@@ -209,5 +240,5 @@ def write_caffemodel(path, layers, v1=False, legacy_shapes=False):
         f.write(bytes(out))
 
 
-__all__ = ["load_caffemodel", "az_head_from_layers", "det_head_from_layers", "backbone_from_layers",
+__all__ = ["load_caffemodel", "az_head_from_layers", "det_head_from_layers", "backbone_from_layers", "skip_front_from_layers",
            "write_caffemodel"]

@@ -19,6 +19,8 @@ AZ_NUM_SUBREG = 11
 AZ_OK = 0
 AZ_BATCH_MAX = 32          # include/aznet_hip.h
 AZ_PYRAMID_MAX = 8         # include/aznet_hip.h
+AZ_SKIP_MAX_SRC = 3        # include/aznet_hip.h
+AZ_SKIP_CHUNK = 128        # include/aznet_hip.h
 AZ_ERR_INVALID, AZ_ERR_HIP, AZ_ERR_CAPACITY, AZ_ERR_STATE, AZ_ERR_NO_DEVICE = -1, -2, -3, -4, -5
 _ERR_NAMES = {-1: "AZ_ERR_INVALID", -2: "AZ_ERR_HIP", -3: "AZ_ERR_CAPACITY", -4: "AZ_ERR_STATE",
               -5: "AZ_ERR_NO_DEVICE"}
@@ -42,6 +44,8 @@ SYMBOLS = [
     "az_detect_batch", "az_voc_eval", "az_coco_eval", "az_diag_eval",
     "az_set_feature_pyramid_dev_nhwc", "az_roi_dedup_pyramid", "az_roi_pool_pyramid", "az_propose_pyramid",
     "az_detect_pyramid",
+    "az_load_skip_front", "az_set_skip_maps_dev_nhwc", "az_detect_skip", "az_det_forward_skip", "az_skip_pool",
+    "az_skip_conv",
     "az_zoom_labels", "az_train_ex_rois", "az_train_adj_targets", "az_train_target_stats",
     "az_solver_create", "az_solver_destroy", "az_solver_load", "az_solver_read", "az_solver_set_hyper", "az_solver_step",
     "az_solver_update", "az_sgd_update", "az_solver_forward_test", "az_solver_fetch", "az_solver_gemm_unit",
@@ -179,6 +183,12 @@ def load_library(path=None):
     L.az_roi_pool_pyramid.argtypes = [vp, fp, ci, fp]
     L.az_propose_pyramid.argtypes = [vp, ctypes.POINTER(AzParams), dp, ci, dp, fp, ci, cip, ctypes.POINTER(AzStats)]
     L.az_detect_pyramid.argtypes = [vp, dp, ci, dp, ci, cd, ci, ci, ci, cd, fp, dp]
+    L.az_load_skip_front.argtypes = [vp, ci, cip, fp, cd, cd, ci, fp, fp]
+    L.az_set_skip_maps_dev_nhwc.argtypes = [vp, ci, ctypes.POINTER(ctypes.c_void_p), cip, cip, cip]
+    L.az_detect_skip.argtypes = [vp, dp, ci, cd, cd, ci, ci, ci, cd, fp, dp]
+    L.az_det_forward_skip.argtypes = [vp, fp, ci, fp, fp]
+    L.az_skip_pool.argtypes = [vp, fp, ci, ci, fp]
+    L.az_skip_conv.argtypes = [vp, fp, ci, fp]
     L.az_detect_batch.argtypes = [vp, ci, ctypes.POINTER(vp), ci, ip, ip, dp, ip, dp, ip, cd, ci, cd, fp, dp]
     L.az_set_profiling.argtypes = [vp, ci]
     L.az_set_graphs.argtypes = [vp, ci]
@@ -306,6 +316,7 @@ class AzContext(object):
         self.h = h
         self.device = int(device)
         self.dims = None
+        self.skip_dims = None          # the loaded skip front's sizes (load_skip_front)
         self.feat_shape = None
         self._feat_keepalive = None
         if max_regions is not None:
@@ -870,6 +881,8 @@ class AzContext(object):
         arrs = [W6] + [_f32(head[k]) for k in ("b6", "W7", "b7", "Wc", "bc", "Wb", "bb")]
         self._chk(self.L.az_load_det_head(self.h, C, n6, n7, ncls, *[_p(a, ctypes.c_float) for a in arrs]))
         self.det_dims = dict(C=C, n6=n6, n7=n7, ncls=ncls)
+        if self.skip_dims is not None and self.skip_dims["Cout"] != C:
+            self.skip_dims = None      # (az_load_det_head dropped the front: it folds to the head's C)
 
     def det_forward(self, rois):
         rois = _f32(rois).reshape(-1, 5)
@@ -894,6 +907,90 @@ class AzContext(object):
         self._chk(fn(self.h, _p(boxes, ctypes.c_double), P, *proj, float(dedup), int(batch_size), int(im_h), int(im_w),
                      float(eps), _p(s, ctypes.c_float), _p(b, ctypes.c_double)))
         return s[:P], b[:P]
+
+    # ---- the skip-connection detector (az_skip.hip) -------------------------------------------
+    def load_skip_front(self, front):
+        """front: dict with Cs (channels of each source), scales (their ROIPooling spatial_scale), Wp [Cout, sum Cs] or
+        Caffe's [Cout, sum Cs, 1, 1] and bp [Cout] (conv_pool5), and optionally gain (scale5: 1000) and eps (the GRN
+        layers': 1e-10), as synth.make_skip_front / caffemodel.skip_front_from_layers return it.  Needs load_det_head."""
+        Cs = np.ascontiguousarray(front["Cs"], dtype=np.intc).reshape(-1)
+        sc = _f32(front["scales"]).reshape(-1)
+        assert Cs.shape[0] == sc.shape[0]
+        Wp = _f32(front["Wp"])
+        Wp = Wp.reshape(Wp.shape[0], -1)
+        bp = _f32(front["bp"]).reshape(-1)
+        Cout = Wp.shape[0]
+        assert Wp.shape == (Cout, int(Cs.sum())) and bp.shape == (Cout,), (Wp.shape, bp.shape, Cs)
+        self._chk(self.L.az_load_skip_front(self.h, int(Cs.shape[0]), _p(Cs, ctypes.c_int), _p(sc, ctypes.c_float),
+                                            float(front.get("gain", 1000.0)), float(front.get("eps", 1e-10)), int(Cout),
+                                            _p(Wp, ctypes.c_float), _p(bp, ctypes.c_float)))
+        self.skip_dims = dict(Cs=[int(x) for x in Cs], sumC=int(Cs.sum()), Cout=int(Cout))
+
+    def _need_front(self, who):
+        """The entries that size their buffers by the front: without one, the ABI's own refusal."""
+        if self.skip_dims is None:
+            raise AzError(AZ_ERR_STATE, "%s: az_load_skip_front has not been called" % who)
+
+    def set_skip_maps(self, maps, producer_done=False):
+        """maps: one float32 CUDA tensor per source of the loaded front, in its order ([1,C,H,W] or [C,H,W]); borrowed
+        (kept alive here).  A map that is not torch.channels_last is copied into that layout first.  torch's current
+        stream is synchronised unless producer_done."""
+        import torch
+        self._need_front("set_skip_maps")
+        ts = []
+        for m in maps:
+            assert m.is_cuda and m.dtype == torch.float32 and m.device.index == self.device, \
+                "skip maps must be float32 CUDA tensors on this context's GPU"
+            if m.dim() == 3:
+                m = m[None]
+            assert m.dim() == 4 and m.shape[0] == 1
+            # (NHWC memory whatever the strides of size-1 dimensions say)
+            ts.append(m.permute(0, 2, 3, 1).contiguous())
+        if not producer_done:
+            torch.cuda.current_stream(ts[0].device).synchronize()
+        n = len(ts)
+        ptrs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])
+        Hs = np.array([t.shape[1] for t in ts], dtype=np.intc)
+        Ws = np.array([t.shape[2] for t in ts], dtype=np.intc)
+        Cs = np.array([t.shape[3] for t in ts], dtype=np.intc)
+        self._chk(self.L.az_set_skip_maps_dev_nhwc(self.h, n, ptrs, _p(Cs, ctypes.c_int), _p(Hs, ctypes.c_int),
+                                                   _p(Ws, ctypes.c_int)))
+        self._skip_keepalive = ts
+        if int(Cs[-1]) == self.skip_dims["Cout"]:          # (the context's ordinary map as well: az_set_skip_maps_dev_nhwc)
+            self._feat_keepalive = ts[-1]
+            self.feat_shape = (int(Cs[-1]), int(Hs[-1]), int(Ws[-1]))
+
+    def detect_skip(self, boxes, scale, im_h, im_w, dedup=1. / 16., batch_size=10000, eps=1e-14):
+        return self._detect(self.L.az_detect_skip, (float(scale),), boxes, im_h, im_w, dedup, batch_size, eps)
+
+    def det_forward_skip(self, rois):
+        rois = _f32(rois).reshape(-1, 5)
+        R = rois.shape[0]
+        nc = self.det_dims["ncls"]
+        p = np.empty((max(R, 1), nc), dtype=np.float32)
+        b = np.empty((max(R, 1), 4 * nc), dtype=np.float32)
+        self._chk(self.L.az_det_forward_skip(self.h, _p(rois, ctypes.c_float), R, _p(p, ctypes.c_float),
+                                             _p(b, ctypes.c_float)))
+        return p[:R], b[:R]
+
+    def skip_pool(self, rois, normalise=True):
+        """concat5 of the rois, [R*49, sum Cs] (row = roi * 49 + bin): the raw ROIPooling maxima (normalise=False) or
+        the normalised, scaled rows the 1x1 convolution reads."""
+        self._need_front("skip_pool")
+        rois = _f32(rois).reshape(-1, 5)
+        R = rois.shape[0]
+        out = np.empty((max(R, 1) * 49, self.skip_dims["sumC"]), dtype=np.float32)
+        self._chk(self.L.az_skip_pool(self.h, _p(rois, ctypes.c_float), R, 1 if normalise else 0, _p(out, ctypes.c_float)))
+        return out[:R * 49]
+
+    def skip_conv(self, cat):
+        """conv_pool5 + relu_pool of host rows [rows, sum Cs] -> [rows, Cout]."""
+        self._need_front("skip_conv")
+        cat = _f32(cat).reshape(-1, self.skip_dims["sumC"])
+        rows = cat.shape[0]
+        out = np.empty((max(rows, 1), self.skip_dims["Cout"]), dtype=np.float32)
+        self._chk(self.L.az_skip_conv(self.h, _p(cat, ctypes.c_float), rows, _p(out, ctypes.c_float)))
+        return out[:rows]
 
     def detect_batch(self, maps, boxes_list, scales, im_shapes, dedup=1. / 16., batch_size=10000, eps=1e-14):
         """detect() for several images at once (az_detect_batch): maps[i] is image i's conv5_3, a float32 CUDA tensor on

@@ -46,6 +46,16 @@ def pyramid_maps(backbone, blob):
     return maps
 
 
+def _skip_names(front):
+    """The blob names of a skip front's sources, in concat5's order (default: the last ones of conv3_3, conv4_3, conv5_3)."""
+    from aznet_hip import synth
+    n = len(front["Cs"])
+    names = tuple(front.get("names") or synth.SKIP_NAMES[len(synth.SKIP_NAMES) - n:])
+    if len(names) != n:
+        raise ValueError("skip front: %d names for %d sources" % (len(names), n))
+    return names
+
+
 class _Blob(object):
     def __init__(self):
         self.shape = None
@@ -84,6 +94,7 @@ class HipAZNet(_NetDict):
         self.name = name
         self.blobs = {k: _Blob() for k in ("data", "rois", "conv5_3")}
         self._conv = None          # what the last forward/set_image left in HBM
+        self.taps = None           # layers compute_conv returns besides conv5_3 (set by a HipDetNet with a skip front)
 
     # ---- feature map -----------------------------------------------------------------
     def set_conv(self, conv, wait=True):
@@ -119,6 +130,12 @@ class HipAZNet(_NetDict):
         if self.backbone is None:
             raise RuntimeError("HipAZNet has no backbone: supply conv5_3 with set_conv()")
         import torch
+        if self.taps:
+            # the skip-connection detector on this context (HipDetNet with a skip front): the tapped maps as well, a dict
+            # {name: channels_last map}; the AZ head reads the last one (conv5_3)
+            maps = self.backbone(data_blob, taps=self.taps)
+            self.set_conv(maps[list(maps)[-1]])
+            return maps
         conv = self.backbone(data_blob)
         self.set_conv(conv)                                    # (synchronises torch's stream first)
         return conv
@@ -183,15 +200,42 @@ class HipDetNet(_NetDict):
     Also pycaffe-shaped (`forward(rois=, conv5_3=)` -> cls_prob, bbox_pred; test.py:302-307)."""
     NAMES = ("fc",)
 
-    def __init__(self, det_head, az_net, name="vgg16_frcnn_hip"):
+    def __init__(self, det_head, az_net, name="vgg16_frcnn_hip", skip_front=None):
+        """skip_front: the skip-connection detector's front (synth.make_skip_front / caffemodel.skip_front_from_layers;
+        default: det_head["skip_front"], which caffemodel.det_head_from_layers sets for a file with conv_pool5):
+        the head then pools every roi from the maps the front names (cfg.SEAR.FRCNN_CONV) instead of conv5_3 alone, and
+        the shared AZ net's compute_conv returns those maps."""
         self.ctx = az_net.ctx
         self.az_net = az_net
         self.ctx.load_det_head(det_head)
+        if skip_front is None:
+            skip_front = det_head.get("skip_front") if isinstance(det_head, dict) else None   # (caffemodel.det_head_from_layers of a skip model)
         self.num_classes = self.ctx.det_dims["ncls"]
         self.name = name
-        self.blobs = {k: _Blob() for k in ("data", "rois", "conv5_3")}
+        self.skip_front, self.skip_names, self._skip_maps = None, None, None
+        if skip_front is not None:
+            self.attach_skip_front(skip_front)
+        self.blobs = {k: _Blob() for k in ("data", "rois") + (self.skip_names or ("conv5_3",))}
+
+    def attach_skip_front(self, front):
+        """Load `front` into the shared context and make the AZ net's compute_conv return the maps it names."""
+        self.ctx.load_skip_front(front)
+        self.skip_front, self.skip_names, self._skip_maps = front, _skip_names(front), None
+        self.az_net.taps = self.skip_names[:-1]
+        self.blobs = {k: _Blob() for k in ("data", "rois") + self.skip_names}
+
+    def set_skip_conv(self, conv):
+        """conv: {name: map} with every map the front names; handed to the context (borrowed) unless it already holds
+        these very tensors."""
+        maps = [conv[n] for n in self.skip_names]
+        if self._skip_maps is None or len(maps) != len(self._skip_maps) or any(a is not b for a, b in zip(maps, self._skip_maps)):
+            self.ctx.set_skip_maps(maps)
+            self._skip_maps = maps
+            self.az_net._conv = maps[-1]
 
     def detect(self, boxes, scale, im_shape, dedup, batch_size, eps):
+        if self.skip_front is not None:
+            return self.ctx.detect_skip(boxes, scale, im_shape[0], im_shape[1], dedup=dedup, batch_size=batch_size, eps=eps)
         return self.ctx.detect(boxes, scale, im_shape[0], im_shape[1], dedup=dedup, batch_size=batch_size, eps=eps)
 
     def detect_pyramid(self, boxes, scales, im_shape, dedup, batch_size, eps):
@@ -201,6 +245,11 @@ class HipDetNet(_NetDict):
 
     def forward(self, blobs=None, **kw):
         rois = np.ascontiguousarray(kw["rois"], dtype=np.float32)
+        if self.skip_front is not None:
+            if all(n in kw for n in self.skip_names):
+                self.set_skip_conv(kw)
+            p, b = self.ctx.det_forward_skip(rois)
+            return {"cls_prob": p, "bbox_pred": b}
         if "conv5_3" in kw and kw["conv5_3"] is not self.az_net._conv:
             self.az_net.set_conv(kw["conv5_3"])
         p, b = self.ctx.det_forward(rois)
@@ -216,9 +265,16 @@ class HipFrcnnNet(_NetDict):
     `detect` / `detect_batch` run az_detect_batch."""
     NAMES = ("full",)
 
-    def __init__(self, det_head, backbone, device=0, name="vgg16_frcnn_hip", max_regions=None):
+    def __init__(self, det_head, backbone, device=0, name="vgg16_frcnn_hip", max_regions=None, skip_front=None):
+        """skip_front: the skip-connection detector's front (see HipDetNet); the backbone must then take `taps`
+        (VGG16Conv5.forward), compute_conv returns the dict of maps and detect goes through az_detect_skip."""
         self.ctx = ffi.AzContext(device, max_regions=max_regions, gemm_mode=0)
         self.ctx.load_det_head(det_head)
+        if skip_front is None:
+            skip_front = det_head.get("skip_front") if isinstance(det_head, dict) else None   # (caffemodel.det_head_from_layers of a skip model)
+        self.skip_front, self.skip_names = None, None
+        if skip_front is not None:
+            self.attach_skip_front(skip_front)
         if ffi._default_ctx is None or getattr(ffi._default_ctx, "h", None) is None:
             ffi.set_default_context(self.ctx)      # apply_nms and the other drop-in helpers use this GPU
         self.backbone = backbone
@@ -226,6 +282,11 @@ class HipFrcnnNet(_NetDict):
         self.num_classes = self.ctx.det_dims["ncls"]
         self.name = name
         self.blobs = {k: _Blob() for k in ("data", "rois", "conv5_3")}
+
+    def attach_skip_front(self, front):
+        """Load `front` into this net's context; compute_conv then returns the maps it names."""
+        self.ctx.load_skip_front(front)
+        self.skip_front, self.skip_names = front, _skip_names(front)
 
     def _torch_device(self):
         import torch
@@ -244,6 +305,9 @@ class HipFrcnnNet(_NetDict):
     def compute_conv(self, data_blob):
         """conv5_3 of one data blob, enqueued on torch's current stream (channels_last: the layout RoIPool reads)."""
         import torch
+        if self.skip_front is not None:
+            maps = self.backbone(data_blob, taps=self.skip_names[:-1])
+            return {n: maps[n] for n in self.skip_names}
         conv = self.backbone(data_blob)
         if not conv.is_contiguous(memory_format=torch.channels_last):
             conv = conv.contiguous(memory_format=torch.channels_last)
@@ -265,7 +329,13 @@ class HipFrcnnNet(_NetDict):
                                        eps=eps)
 
     def detect_batch(self, convs, boxes_list, scales, im_shapes, dedup, batch_size, eps):
+        if self.skip_front is not None:
+            raise ValueError("the skip-connection detector runs one image per call (az_detect_skip): no az_detect_batch")
         return self.ctx.detect_batch(convs, boxes_list, scales, im_shapes, dedup=dedup, batch_size=batch_size, eps=eps)
 
     def detect(self, conv, boxes, scale, im_shape, dedup, batch_size, eps):
+        if self.skip_front is not None:
+            # (the region capacity bounds the proposals of one call: AZ_ERR_CAPACITY beyond it)
+            self.ctx.set_skip_maps([conv[n] for n in self.skip_names])
+            return self.ctx.detect_skip(boxes, scale, im_shape[0], im_shape[1], dedup=dedup, batch_size=batch_size, eps=eps)
         return self.detect_batch([conv], [boxes], [scale], [im_shape], dedup, batch_size, eps)[0]

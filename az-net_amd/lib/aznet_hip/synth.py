@@ -171,3 +171,23 @@ def make_det_head(seed=4242, C=512, n6=4096, n7=4096, ncls=21, pooled=7):
         "Wb": w(4 * ncls, n7, 0.3), "bb": np.zeros(4 * ncls, dtype=np.float32),
     }
     return {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in head.items()}
+
+
+# The skip-connection detector's front (models/COCO/VGG16_skip/frcnn/test_fc.prototxt): roi_pool3/4/5 of conv3_3 /
+# conv4_3 / conv5_3 -> GRN each -> concat5 -> scale5 (x1000) -> conv_pool5 (1x1, 1280 -> 512) + ReLU.
+SKIP_CS = (256, 512, 512)
+SKIP_SCALES = (0.25, 0.125, 0.0625)
+SKIP_NAMES = ("conv3_3", "conv4_3", "conv5_3")
+
+
+def make_skip_front(seed=2468, Cs=SKIP_CS, Cout=512, scales=None, gain=1000.0, eps=1e-10):
+    """Random conv_pool5 weights (Caffe [Cout, sum Cs, 1, 1] squeezed to [Cout, sum Cs]) for AzContext.load_skip_front.
+    Every normalised block has L2 norm `gain`, so weights of standard deviation 1 / (gain sqrt(sources)) give
+    pre-activations of unit variance: about half of pool5 survives the ReLU, as after a trained layer."""
+    Cs = tuple(int(c) for c in Cs)
+    rng = np.random.Generator(np.random.PCG64(30_000 + seed))
+    Wp = rng.standard_normal((Cout, sum(Cs)), dtype=np.float32) * np.float32(1.0 / (gain * np.sqrt(len(Cs))))
+    bp = 0.1 * rng.standard_normal(Cout, dtype=np.float32)
+    return {"Cs": Cs, "scales": tuple(scales if scales is not None else SKIP_SCALES[len(SKIP_SCALES) - len(Cs):]),
+            "names": SKIP_NAMES[len(SKIP_NAMES) - len(Cs):], "gain": float(gain), "eps": float(eps), "Wp": np.ascontiguousarray(Wp, dtype=np.float32),
+            "bp": np.ascontiguousarray(bp, dtype=np.float32)}

@@ -86,6 +86,63 @@ def divide_region(regions):
     return div.divide_region(regions, float(cfg.SEAR.MIN_SIDE))
 
 
+def _skip_mode(net=None):
+    """Whether the detection net is the skip-connection model: exactly when cfg.SEAR.FRCNN_CONV names more than one map
+    (experiments/cfgs/voc_skip.yml: [conv3_3, conv4_3, conv5_3]; the reference's _frcnn_forward, test.py:300-304, hands the
+    net one blob per name).  net: the detection net object (HipDetNet / HipFrcnnNet) -- the configuration and the net must
+    agree, a skip configuration never runs on conv5_3 alone.  The skip model has one test scale."""
+    skip = len(cfg.SEAR.FRCNN_CONV) > 1
+    if net is not None:
+        has = getattr(net, "skip_front", None) is not None
+        if skip and not has:
+            raise ValueError("cfg.SEAR.FRCNN_CONV = %s names the skip-connection detector's maps, but the detection net %r has "
+                             "no skip front (conv_pool5): it would detect on conv5_3 alone"
+                             % (list(cfg.SEAR.FRCNN_CONV), getattr(net, "name", net)))
+        if has and not skip:
+            raise ValueError("the detection net %r has a skip front over %s, but cfg.SEAR.FRCNN_CONV = %s names one map: "
+                             "use the skip configuration (voc_skip.yml)"
+                             % (getattr(net, "name", net), list(net.skip_names), list(cfg.SEAR.FRCNN_CONV)))
+        if has and tuple(net.skip_names) != tuple(cfg.SEAR.FRCNN_CONV):
+            raise ValueError("the skip front reads %s, cfg.SEAR.FRCNN_CONV names %s" % (list(net.skip_names), list(cfg.SEAR.FRCNN_CONV)))
+    if skip and len(cfg.TEST.SCALES) > 1:
+        raise ValueError("the skip-connection detector takes one test scale (cfg.TEST.SCALES = %s): no image pyramids"
+                         % (list(cfg.TEST.SCALES),))
+    return skip
+
+
+def _synthetic_skip_front(net):
+    """The tools' `--net synthetic[:seed]` detection nets (seeded random weights, named vgg16_frcnn_synthetic_<seed> by
+    tools/test_det_net.py and tools/test_shared.py) under a skip configuration: the seeded synthetic front of that seed
+    is attached, so the one command runs the skip model without weights.  Any other net is left as it is -- a net
+    of real weights without conv_pool5 stays without a front, and _skip_mode refuses it."""
+    import re
+    m = re.match(r"^vgg16_frcnn_synthetic_(\d+)$", str(getattr(net, "name", "")))
+    if m and len(cfg.SEAR.FRCNN_CONV) > 1 and getattr(net, "skip_front", 0) is None and hasattr(net, "attach_skip_front"):
+        from aznet_hip import synth
+        Cout = net.ctx.det_dims["C"]
+        Cs = synth.SKIP_CS if Cout == synth.SKIP_CS[-1] else None
+        if Cs is not None and tuple(cfg.SEAR.FRCNN_CONV) == synth.SKIP_NAMES:
+            net.attach_skip_front(synth.make_skip_front(seed=int(m.group(1)) + 2, Cs=Cs, Cout=Cout))
+
+
+def _conv_dict(out):
+    """{name: map} for every name in cfg.SEAR.FRCNN_CONV from what compute_conv returned: a dict of tapped maps (the skip
+    model) or the one conv5_3 tensor."""
+    if isinstance(out, dict):
+        missing = [n for n in cfg.SEAR.FRCNN_CONV if n not in out]
+        if missing:
+            raise ValueError("the backbone returned %s, cfg.SEAR.FRCNN_CONV also names %s" % (sorted(out), missing))
+        return {name: out[name] for name in cfg.SEAR.FRCNN_CONV}
+    return {name: out for name in cfg.SEAR.FRCNN_CONV}
+
+
+def _skip_note(what):
+    """AZ_FULL_DEBUG: one line when cfg.TEST.BATCH_IMAGES > 1 meets the skip model."""
+    if int(cfg.TEST.get("BATCH_IMAGES", 1)) > 1 and os.environ.get("AZ_FULL_DEBUG") is not None:
+        print("%s: the skip-connection detector runs image by image (cfg.TEST.BATCH_IMAGES = %d is not taken)"
+              % (what, int(cfg.TEST.get("BATCH_IMAGES", 1))))
+
+
 def _params(im_shape, scale, num_proposals):
     fixed = not ((cfg.SEAR.FIXED_PROPOSAL_NUM is False) and (num_proposals is None))
     if num_proposals is None:
@@ -140,8 +197,7 @@ def im_propose(net, im, return_conv=False, num_proposals=None, conv=None, stage=
     else:
         if conv is None:
             blob, _ = _get_image_blob(im, hnet)
-            conv_t = hnet.compute_conv(blob)
-            conv = {name: conv_t for name in cfg.SEAR.FRCNN_CONV}
+            conv = _conv_dict(hnet.compute_conv(blob))
         else:
             hnet.set_conv(conv[cfg.SEAR.AZ_CONV[0]])
         params = _params(im.shape, scales[0], num_proposals)
@@ -411,6 +467,12 @@ def _frcnn_forward(net, im, all_boxes, num_classes, conv=None):
     if _is_full_net(net):
         fnet = net["full"]
         assert num_classes == fnet.num_classes
+        if _skip_mode(fnet):
+            # the skip-connection detector (test.py:300-304: one blob per name in cfg.SEAR.FRCNN_CONV): the tapped maps of
+            # its own backbone, then az_detect_skip
+            maps = _conv_dict(fnet.compute_conv(fnet.image_blob_enqueue(_as_uint8(im), cfg.PIXEL_MEANS, scales[0])))
+            scores, pred = fnet.detect(maps, boxes, scales[0], im.shape, *args)
+            return scores.astype(np.float64), pred, maps
         if pyramid:
             # an image pyramid: its padded maps, each roi pooled from the level its scaled area is closest to 224^2 at
             maps = fnet.compute_pyramid(_as_uint8(im), cfg.PIXEL_MEANS, scales)
@@ -422,6 +484,11 @@ def _frcnn_forward(net, im, all_boxes, num_classes, conv=None):
     # shared detection on the map (or pyramid) the AZ search left in the context, or the cached one in `conv`
     dnet = net["fc"] if isinstance(net, dict) else net
     assert num_classes == dnet.num_classes
+    if _skip_mode(dnet):
+        if conv is not None:
+            dnet.set_skip_conv(_conv_dict(conv))
+        scores, pred = dnet.detect(boxes, scales[0], im.shape, *args)
+        return scores.astype(np.float64), pred, conv
     if conv is not None:
         c = conv[cfg.SEAR.FRCNN_CONV[0]]
         if c is not dnet.az_net._conv:
@@ -604,7 +671,13 @@ def test_net_shared(sc_net, frcnn_net, imdb):
     # i+1 while Python does image i's per-class bookkeeping below.  Same calls per image, same printed lines in the same
     # order; the reference's loop (test.py:690-737) waits for each image before it reads the next.
     images = _prefetched(imdb, list(range(num_images)), depth=_prefetch_depth())
-    queued = _can_queue(hnet) and num_images > 0
+    # (the skip-connection detector: image by image through im_detect_shared, whose backbone pass keeps the tapped maps)
+    dnet = frcnn_net["fc"] if isinstance(frcnn_net, dict) else frcnn_net
+    _synthetic_skip_front(dnet)
+    skip = _skip_mode(dnet)
+    if skip:
+        _skip_note("test_net_shared")
+    queued = _can_queue(hnet) and num_images > 0 and not skip
     # cfg.TEST.BATCH_IMAGES > 1 (an extension): the proposals of consecutive images of one shape in lockstep batches
     # (az_batch_launch), the detection head image by image as before; same detections, same printed lines
     nb = int(cfg.TEST.get("BATCH_IMAGES", 1))
@@ -688,6 +761,10 @@ def test_net(net, prop_file, imdb):
     todo = [i for i in range(num_images) if prop_boxes[i].shape[0] != 0]       # test.py:588-589
     images = _prefetched(imdb, todo, depth=_prefetch_depth())
     nb = max(1, int(cfg.TEST.get("BATCH_IMAGES", 1)))
+    _synthetic_skip_front(fnet)
+    if _skip_mode(fnet):
+        _skip_note("test_net")
+        nb = 1                     # (az_detect_skip takes one image per call)
     for g0 in range(0, len(todo), nb):
         idx = todo[g0:g0 + nb]
         ims = [next(images) for _ in idx]

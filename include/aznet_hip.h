@@ -396,6 +396,45 @@ int az_propose_pyramid(az_ctx *ctx, const az_params *p, const double *scales, in
 int az_detect_pyramid(az_ctx *ctx, const double *boxes, int P, const double *scales, int S, double dedup,
                       int batch_size, int im_h, int im_w, double eps, float *scores_out, double *boxes_out);
 
+/* ---- the skip-connection detector (models/COCO/VGG16_skip/frcnn/test_fc.prototxt, experiments/cfgs/voc_skip.yml) ---- */
+/* A front in place of the detection head's RoIPool: every roi is pooled 7x7 from up to three maps (conv3_3, conv4_3,
+ * conv5_3: cfg.SEAR.FRCNN_CONV), each block normalised across its channels, the blocks concatenated, scaled and folded
+ * to the head's C channels by a 1x1 convolution + ReLU; fc6 ... cls_prob / bbox_pred run unchanged on the result.
+ * Inference, one image per call, fp32 only.  Every entry below refuses, before any device work: the 16-bit-term GEMM
+ * modes and a context whose pyramid was set after the skip maps (AZ_ERR_STATE), more rois than the region capacity (AZ_ERR_CAPACITY), a missing
+ * detection head / front / map set (AZ_ERR_STATE). */
+#define AZ_SKIP_MAX_SRC 3
+#define AZ_SKIP_MAX_SUMC 4096   /* channels of all sources together */
+#define AZ_SKIP_CHUNK 128       /* rois per pass of the front: the concatenated rows are held for this many at a time */
+/* roi_pool3/4/5 + roi_norm3/4/5 + concat5 + scale5 + conv_pool5 + relu_pool (test_fc.prototxt of the skip model):
+ * source i has Cs[i] channels (a positive multiple of 4) and ROIPooling spatial_scale spatial_scales[i]; the GRN layers
+ * compute y[c] = x[c] / sqrt(sum_c x[c]^2 + eps) per roi, bin and source (their eps: 1e-10 by default; an all-zero
+ * vector gives zeros); `gain` is scale5's factor (1000); Wp [Cout][sum Cs] and bp [Cout] are conv_pool5's blobs.  Cout
+ * must be the loaded detection head's C (AZ_ERR_INVALID); without a detection head: AZ_ERR_STATE.  On any error the
+ * front loaded before stays in place. */
+int az_load_skip_front(az_ctx *ctx, int n_src, const int *Cs, const float *spatial_scales, double gain, double eps,
+                       int Cout, const float *Wp, const float *bp);
+/* The blobs _frcnn_forward hands the skip net, forward_kwargs[name] = conv[name] for name in cfg.SEAR.FRCNN_CONV
+ * (lib/detect/test.py:300-304): n_src channel-last maps [Hs[i]][Ws[i]][Cs[i]] (device memory), borrowed as
+ * az_set_feature_map_dev_nhwc borrows one.  Channel counts must be the loaded front's (AZ_ERR_INVALID).  The last map
+ * also becomes the context's ordinary map when it has the heads' channel count.  A pyramid set the context held
+ * (az_set_feature_pyramid_dev_nhwc) is dropped: set it again before the next pyramid entry; a pyramid set AFTER these
+ * maps makes the skip entries refuse (AZ_ERR_STATE) until the maps are set again. */
+int az_set_skip_maps_dev_nhwc(az_ctx *ctx, int n_src, const float *const *maps_nhwc_dev, const int *Cs, const int *Hs,
+                              const int *Ws);
+/* _frcnn_forward (lib/detect/test.py:259-318) with the skip net: az_detect's contract and outputs, the head's RoIPool
+ * replaced by the front on the maps of az_set_skip_maps_dev_nhwc. */
+int az_detect_skip(az_ctx *ctx, const double *boxes, int P, double scale, double dedup, int batch_size, int im_h,
+                   int im_w, double eps, float *scores_out, double *boxes_out);
+/* frcnn_net['fc'].forward(rois=..., conv3_3=..., conv4_3=..., conv5_3=...) (lib/detect/test.py:302-307) of the skip
+ * net: az_det_forward's twin. */
+int az_det_forward_skip(az_ctx *ctx, const float *rois, int R, float *cls_prob, float *bbox_pred);
+/* Unit entries.  az_skip_pool: the blobs concat5 (normalise = 0: before roi_norm*, the raw ROIPooling maxima;
+ * normalise = 1: after scale5) as rows [R*49][sum Cs], row = roi * 49 + ph * 7 + pw.  az_skip_conv: conv_pool5 +
+ * relu_pool of `rows` such rows given by the host, out [rows][Cout]. */
+int az_skip_pool(az_ctx *ctx, const float *rois, int R, int normalise, float *out);
+int az_skip_conv(az_ctx *ctx, const float *cat_host, int rows, float *out);
+
 /* ---- zoom-threshold tuner (lib/detect/tune.py, tools/set_thresh.py) ------------------- */
 /* `Bhis` of the tuner's im_propose (tune.py:303, returned at :316) for the last az_propose run
  * with params.reserved bit 2: every region evaluated, level-major, with its zoom score.
