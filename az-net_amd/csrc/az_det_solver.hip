@@ -6,7 +6,7 @@
 // Every reduction has a fixed order (no floating-point atomics): see az_solver.hip; the softmax sums a row lane-strided and
 // then over a fixed butterfly, the row losses in row order per wave and then over the LDS tree.  The same step from the same
 // state gives the same bits.
-#include "az_solver_dev.h"
+#include "az_det_solver.h"
 
 namespace {
 
@@ -72,32 +72,6 @@ __global__ void __launch_bounds__(256) k_solver_softmax_loss(const float *__rest
 
 }  // namespace
 
-// parameter order of the ABI: W6 b6 W7 b7 Wc bc Wb bb (fc6, fc7, cls_score, bbox_pred)
-enum { D_W6, D_B6, D_W7, D_B7, D_WC, D_BC, D_WB, D_BB, DNPARAM };
-static const char *const DPNAME[DNPARAM] = {"W6", "b6", "W7", "b7", "Wc", "bc", "Wb", "bb"};
-static const float DET_FILLER_STD[4] = {5e-3f, 5e-3f, 1e-2f, 1e-3f};      // fc6 fc7 (without a pretrained model) cls_score bbox_pred
-
-struct az_det_solver {
-    az_ctx *c = nullptr;
-    int C = 0, n6 = 0, n7 = 0, ncls = 0, K6 = 0, maxR = 0;
-    size_t pn[DNPARAM] = {0};
-    float *w[DNPARAM] = {nullptr}, *g[DNPARAM] = {nullptr}, *h[DNPARAM] = {nullptr};
-    float lr_mult[DNPARAM], decay_mult[DNPARAM];
-    float drop[2] = {0.5f, 0.5f};
-    // one step's activations and gradients (rows: maxR)
-    float *rois = nullptr, *labels = nullptr, *tgt = nullptr, *wgt = nullptr;
-    int *geo = nullptr, *argmax = nullptr;
-    float *pool5 = nullptr, *pre6 = nullptr, *a6 = nullptr, *pre7 = nullptr, *a7 = nullptr;
-    unsigned char *m6 = nullptr, *m7 = nullptr;
-    float *s_cls = nullptr, *prob = nullptr, *s_bb = nullptr;                  // raw cls_score, cls_prob, bbox_pred
-    float *d_cls = nullptr, *d_bb = nullptr, *d7 = nullptr, *d6 = nullptr, *dpool = nullptr;
-    float *part = nullptr, *loss = nullptr;
-    double *sq_part = nullptr, *sq = nullptr;
-    size_t part_elems = 0;
-    std::vector<void *> allocs;
-    int R = 0, N = 0, H = 0, W = 0, trained = 0, has_prob = 0;
-};
-
 namespace {
 
 template <typename T>
@@ -115,6 +89,13 @@ int det_check_args(az_det_solver *s, const float *conv, int N, int H, int W, con
     if (!s) return AZ_ERR_INVALID;
     if (!conv || !rois) return fail(s->c, AZ_ERR_INVALID, who + ": null conv5_3 or rois");
     if (N < 1 || H < 1 || W < 1 || (long long)H * W > 0x3fffffff) return fail(s->c, AZ_ERR_INVALID, who + ": bad map shape");
+    return det_check_rois(s, N, rois, R, who);
+}
+
+}  // namespace
+
+int det_check_rois(az_det_solver *s, int N, const float *rois, int R, const std::string &who)
+{
     if (R < 1 || R > s->maxR) return fail(s->c, AZ_ERR_INVALID, who + ": R must be in [1, max_rois = " + std::to_string(s->maxR) + "]");
     for (int r = 0; r < R; ++r) {
         const float *roi = rois + 5 * (size_t)r;
@@ -126,7 +107,80 @@ int det_check_args(az_det_solver *s, const float *conv, int N, int H, int W, con
     return AZ_OK;
 }
 
-// RoIPool -> fc6 -> fc7 -> {cls_score, bbox_pred}; train: dropout on fc6 / fc7 with the step's masks (layer ids 0 / 1)
+// fc6 -> fc7 -> {cls_score, bbox_pred}; train: dropout on fc6 / fc7 with the step's masks (layer ids 0 / 1)
+void det_head_forward(az_det_solver *s, int R, bool train, unsigned long long seed, unsigned long long iter)
+{
+    const bool m6 = train && s->drop[0] > 0.f, m7 = train && s->drop[1] > 0.f;
+    fc_forward(s, "fc6_fwd", s->pool5, D_W6, R, s->n6, s->K6, s->pre6, s->a6, m6 ? s->m6 : nullptr, az_layer_key(seed, iter, 0), train ? s->drop[0] : 0.f);
+    fc_forward(s, "fc7_fwd", s->a6, D_W7, R, s->n7, s->n6, s->pre7, s->a7, m7 ? s->m7 : nullptr, az_layer_key(seed, iter, 1), train ? s->drop[1] : 0.f);
+    fc_forward(s, "cls_score_fwd", s->a7, D_WC, R, s->ncls, s->n7, s->s_cls, nullptr, nullptr, 0, 0.f);
+    fc_forward(s, "bbox_pred_fwd", s->a7, D_WB, R, 4 * s->ncls, s->n7, s->s_bb, nullptr, nullptr, 0, 0.f);
+}
+
+int det_stage_targets(az_det_solver *s, int R, const float *labels, const float *bbox_targets, const float *bbox_loss_weights,
+                      long long iteration, const std::string &who)
+{
+    az_ctx *c = s->c;
+    if (!labels || !bbox_targets || !bbox_loss_weights || iteration < 0)
+        return fail(c, AZ_ERR_INVALID, who + ": null label / target array or negative iteration");
+    const int nc = s->ncls, nb = 4 * s->ncls;
+    for (int r = 0; r < R; ++r)            // before anything is enqueued
+        if (!(labels[r] >= 0.0f && labels[r] < (float)nc) || labels[r] != std::floor(labels[r]))
+            return fail(c, AZ_ERR_INVALID, who + ": label " + std::to_string(labels[r]) + " of row " + std::to_string(r) + " is no class in [0, " + std::to_string(nc) + ")");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!(c->profiling & 4)) clear_events(c);
+    hipStream_t st = c->stream;
+    HIPCHK(c, hipMemcpyAsync(s->labels, labels, (size_t)R * sizeof(float), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(s->tgt, bbox_targets, (size_t)R * nb * sizeof(float), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(s->wgt, bbox_loss_weights, (size_t)R * nb * sizeof(float), hipMemcpyHostToDevice, st));
+    return AZ_OK;
+}
+
+// SoftmaxWithLoss, SmoothL1Loss and the backward pass down to d_pre6 (want_dpool: and d_pool5)
+void det_head_backward(az_det_solver *s, int R, bool want_dpool)
+{
+    az_ctx *c = s->c;
+    hipStream_t st = c->stream;
+    const int nc = s->ncls, nb = 4 * s->ncls, n6 = s->n6, n7 = s->n7, K6 = s->K6;
+    { Timed t(c, "losses", 0);
+      hipLaunchKernelGGL(k_solver_softmax_loss, dim3(1), dim3(256), 0, st, s->s_cls, s->labels, R, nc, s->prob, s->d_cls, s->loss + 0);
+      hipLaunchKernelGGL(k_solver_smooth_l1, dim3(1), dim3(256), 0, st, s->s_bb, s->tgt, s->wgt, R * nb, R, s->d_bb, s->loss + 1); }
+    s->has_prob = 1;
+    auto colsum = [&](const float *dy, int Nc, float *db) {
+        hipLaunchKernelGGL(k_solver_colsum, dim3((Nc + 255) / 256), dim3(256), 0, st, dy, R, Nc, db);
+    };
+    auto act_bwd = [&](float *d, const float *pre, const unsigned char *mask, float ratio, int Nc) {
+        Timed t(c, "act_bwd", 0);
+        hipLaunchKernelGGL(k_solver_act_bwd, dim3(grid_for((long long)R * Nc)), dim3(256), 0, st, d, pre, ratio > 0.f ? mask : nullptr,
+                           1.0f / (1.0f - ratio), (long long)R * Nc);
+    };
+    // the two output layers: dW = dy^T x, db, and their two dx, which add into d7
+    gemm_any(s, "cls_score_dw", 2, s->d_cls, s->a7, s->g[D_WC], nc, n7, R, 0);
+    gemm_any(s, "bbox_pred_dw", 2, s->d_bb, s->a7, s->g[D_WB], nb, n7, R, 0);
+    { Timed t(c, "bias_grads", 0); colsum(s->d_cls, nc, s->g[D_BC]); colsum(s->d_bb, nb, s->g[D_BB]); }
+    gemm_any(s, "cls_score_dx", 1, s->d_cls, s->w[D_WC], s->d7, R, n7, nc, 0);
+    gemm_any(s, "bbox_pred_dx", 1, s->d_bb, s->w[D_WB], s->d7, R, n7, nb, 1);
+    act_bwd(s->d7, s->pre7, s->m7, s->drop[1], n7);
+    gemm_any(s, "fc7_dw", 2, s->d7, s->a6, s->g[D_W7], n7, n6, R, 0);
+    { Timed t(c, "bias_grads", 0); colsum(s->d7, n7, s->g[D_B7]); }
+    gemm_any(s, "fc7_dx", 1, s->d7, s->w[D_W7], s->d6, R, n6, n7, 0);
+    act_bwd(s->d6, s->pre6, s->m6, s->drop[0], n6);
+    gemm_any(s, "fc6_dw", 2, s->d6, s->pool5, s->g[D_W6], n6, K6, R, 0);
+    { Timed t(c, "bias_grads", 0); colsum(s->d6, n6, s->g[D_B6]); }
+    if (want_dpool) gemm_any(s, "fc6_dx", 1, s->d6, s->w[D_W6], s->dpool, R, K6, n6, 0);
+}
+
+// TEST phase: cls_prob of the raw scores
+void det_softmax_test(az_det_solver *s, int R)
+{
+    hipLaunchKernelGGL(k_solver_softmax_loss, dim3(1), dim3(256), 0, s->c->stream, s->s_cls, (const float *)nullptr, R, s->ncls, s->prob,
+                       (float *)nullptr, (float *)nullptr);
+    s->has_prob = 1;
+}
+
+namespace {
+
+// RoIPool -> the head
 int det_forward(az_det_solver *s, const float *conv, int N, int H, int W, int cl, const float *rois, int R, bool train,
                 unsigned long long seed, unsigned long long iter)
 {
@@ -137,11 +191,7 @@ int det_forward(az_det_solver *s, const float *conv, int N, int H, int W, int cl
       hipLaunchKernelGGL(k_solver_roi_geo, dim3((R + 255) / 256), dim3(256), 0, c->stream, s->rois, R, c->spatial_scale, s->geo);
       hipLaunchKernelGGL(k_solver_roi_pool, dim3(grid_for((long long)R * s->K6, 16384)), dim3(256), 0, c->stream, conv, m, s->geo, R,
                          s->pool5, s->argmax); }
-    const bool m6 = train && s->drop[0] > 0.f, m7 = train && s->drop[1] > 0.f;
-    fc_forward(s, "fc6_fwd", s->pool5, D_W6, R, s->n6, s->K6, s->pre6, s->a6, m6 ? s->m6 : nullptr, az_layer_key(seed, iter, 0), train ? s->drop[0] : 0.f);
-    fc_forward(s, "fc7_fwd", s->a6, D_W7, R, s->n7, s->n6, s->pre7, s->a7, m7 ? s->m7 : nullptr, az_layer_key(seed, iter, 1), train ? s->drop[1] : 0.f);
-    fc_forward(s, "cls_score_fwd", s->a7, D_WC, R, s->ncls, s->n7, s->s_cls, nullptr, nullptr, 0, 0.f);
-    fc_forward(s, "bbox_pred_fwd", s->a7, D_WB, R, 4 * s->ncls, s->n7, s->s_bb, nullptr, nullptr, 0, 0.f);
+    det_head_forward(s, R, train, seed, iter);
     s->R = R; s->N = N; s->H = H; s->W = W;
     return AZ_OK;
 }
@@ -176,6 +226,7 @@ int az_det_solver_create(az_ctx *c, int C, int n6, int n7, int num_classes, int 
     }
     const size_t R = (size_t)max_rois;
     // the slabs of a split-K product hold at most 256 tiles of 128 x 128 (pick_split); an unsplit forward layer R x its width
+    // (az_det_solver_attach_skip relies on this 4M-float floor for the front's split products)
     size_t nmax = (size_t)(n6 > n7 ? n6 : n7); nmax = nmax > nb ? nmax : nb; nmax = nmax > K6 ? nmax : K6;
     s->part_elems = R * nmax > (size_t)4 << 20 ? R * nmax : (size_t)4 << 20;
 #define SA(p, n) if (rc == AZ_OK) rc = dsalloc(s, &s->p, (n))
@@ -260,47 +311,12 @@ int az_det_solver_step(az_det_solver *s, const float *conv_dev, int N, int H, in
     int rc = det_check_args(s, conv_dev, N, H, W, rois, R, "az_det_solver_step");
     if (rc != AZ_OK) return rc;
     az_ctx *c = s->c;
-    if (!labels || !bbox_targets || !bbox_loss_weights || iteration < 0)
-        return fail(c, AZ_ERR_INVALID, "az_det_solver_step: null label / target array or negative iteration");
-    const int nc = s->ncls, nb = 4 * s->ncls;
-    for (int r = 0; r < R; ++r)            // before anything is enqueued
-        if (!(labels[r] >= 0.0f && labels[r] < (float)nc) || labels[r] != std::floor(labels[r]))
-            return fail(c, AZ_ERR_INVALID, "az_det_solver_step: label " + std::to_string(labels[r]) + " of row " + std::to_string(r) + " is no class in [0, " + std::to_string(nc) + ")");
-    HIPCHK(c, hipSetDevice(c->device));
-    if (!(c->profiling & 4)) clear_events(c);
+    if ((rc = det_stage_targets(s, R, labels, bbox_targets, bbox_loss_weights, iteration, "az_det_solver_step")) != AZ_OK) return rc;
     hipStream_t st = c->stream;
-    HIPCHK(c, hipMemcpyAsync(s->labels, labels, (size_t)R * sizeof(float), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(s->tgt, bbox_targets, (size_t)R * nb * sizeof(float), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(s->wgt, bbox_loss_weights, (size_t)R * nb * sizeof(float), hipMemcpyHostToDevice, st));
     if ((rc = det_forward(s, conv_dev, N, H, W, channels_last, rois, R, true, seed, (unsigned long long)iteration)) != AZ_OK) return rc;
-    const int n6 = s->n6, n7 = s->n7, K6 = s->K6;
-    { Timed t(c, "losses", 0);
-      hipLaunchKernelGGL(k_solver_softmax_loss, dim3(1), dim3(256), 0, st, s->s_cls, s->labels, R, nc, s->prob, s->d_cls, s->loss + 0);
-      hipLaunchKernelGGL(k_solver_smooth_l1, dim3(1), dim3(256), 0, st, s->s_bb, s->tgt, s->wgt, R * nb, R, s->d_bb, s->loss + 1); }
-    s->has_prob = 1;
-    auto colsum = [&](const float *dy, int Nc, float *db) {
-        hipLaunchKernelGGL(k_solver_colsum, dim3((Nc + 255) / 256), dim3(256), 0, st, dy, R, Nc, db);
-    };
-    auto act_bwd = [&](float *d, const float *pre, const unsigned char *mask, float ratio, int Nc) {
-        Timed t(c, "act_bwd", 0);
-        hipLaunchKernelGGL(k_solver_act_bwd, dim3(grid_for((long long)R * Nc)), dim3(256), 0, st, d, pre, ratio > 0.f ? mask : nullptr,
-                           1.0f / (1.0f - ratio), (long long)R * Nc);
-    };
-    // the two output layers: dW = dy^T x, db, and their two dx, which add into d7
-    gemm_any(s, "cls_score_dw", 2, s->d_cls, s->a7, s->g[D_WC], nc, n7, R, 0);
-    gemm_any(s, "bbox_pred_dw", 2, s->d_bb, s->a7, s->g[D_WB], nb, n7, R, 0);
-    { Timed t(c, "bias_grads", 0); colsum(s->d_cls, nc, s->g[D_BC]); colsum(s->d_bb, nb, s->g[D_BB]); }
-    gemm_any(s, "cls_score_dx", 1, s->d_cls, s->w[D_WC], s->d7, R, n7, nc, 0);
-    gemm_any(s, "bbox_pred_dx", 1, s->d_bb, s->w[D_WB], s->d7, R, n7, nb, 1);
-    act_bwd(s->d7, s->pre7, s->m7, s->drop[1], n7);
-    gemm_any(s, "fc7_dw", 2, s->d7, s->a6, s->g[D_W7], n7, n6, R, 0);
-    { Timed t(c, "bias_grads", 0); colsum(s->d7, n7, s->g[D_B7]); }
-    gemm_any(s, "fc7_dx", 1, s->d7, s->w[D_W7], s->d6, R, n6, n7, 0);
-    act_bwd(s->d6, s->pre6, s->m6, s->drop[0], n6);
-    gemm_any(s, "fc6_dw", 2, s->d6, s->pool5, s->g[D_W6], n6, K6, R, 0);
-    { Timed t(c, "bias_grads", 0); colsum(s->d6, n6, s->g[D_B6]); }
+    det_head_backward(s, R, dmap_dev != nullptr);
+    s->sk.trained = 0;
     if (dmap_dev) {
-        gemm_any(s, "fc6_dx", 1, s->d6, s->w[D_W6], s->dpool, R, K6, n6, 0);
         const MapView m{N, s->C, H, W, channels_last ? 1 : 0};
         Timed t(c, "roi_pool_bwd", 0);
         hipLaunchKernelGGL(k_solver_roi_pool_bwd, dim3(grid_for((long long)N * s->C * H * W, 1 << 30)), dim3(256), 0, st, s->dpool,
@@ -330,7 +346,7 @@ int az_det_solver_update(az_det_solver *s, double rate, double momentum, double 
     if (!s->trained) return fail(c, AZ_ERR_STATE, "az_det_solver_update: no az_det_solver_step has produced gradients");
     HIPCHK(c, hipSetDevice(c->device));
     { Timed t(c, "sgd_update", 0);
-      for (int p = 0; p < DNPARAM; ++p)
+      for (int p = 0; p < (s->sk.trained ? DNALL : DNPARAM); ++p)       // conv_pool5 too, behind a skip step
           hipLaunchKernelGGL(k_solver_sgd, dim3(grid_for((long long)s->pn[p], 16384)), dim3(256), 0, c->stream, s->w[p], s->g[p], s->h[p],
                              (long long)s->pn[p], (float)(rate * (double)s->lr_mult[p]), (float)momentum,
                              (float)(weight_decay * (double)s->decay_mult[p]), (float)clip_scale); }
@@ -348,10 +364,8 @@ int az_det_solver_forward_test(az_det_solver *s, const float *conv_dev, int N, i
     HIPCHK(c, hipSetDevice(c->device));
     if (!(c->profiling & 4)) clear_events(c);
     if ((rc = det_forward(s, conv_dev, N, H, W, channels_last, rois, R, false, 0, 0)) != AZ_OK) return rc;
-    s->trained = 0;
-    hipLaunchKernelGGL(k_solver_softmax_loss, dim3(1), dim3(256), 0, c->stream, s->s_cls, (const float *)nullptr, R, s->ncls, s->prob,
-                       (float *)nullptr, (float *)nullptr);
-    s->has_prob = 1;
+    s->trained = 0; s->sk.trained = 0;
+    det_softmax_test(s, R);
     if (cls_prob) HIPCHK(c, hipMemcpyAsync(cls_prob, s->prob, (size_t)R * s->ncls * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     if (bbox_pred) HIPCHK(c, hipMemcpyAsync(bbox_pred, s->s_bb, (size_t)R * 4 * s->ncls * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -377,10 +391,13 @@ int az_det_solver_fetch(az_det_solver *s, const char *name, void *out, long long
     };
     bool is_param = false;
     for (const Ent &e : tab) if (nm == e.n) { src = e.p; bytes = e.b; }
-    if (!src && nm.size() > 2 && nm[1] == '_' && (nm[0] == 'g' || nm[0] == 'h' || nm[0] == 'w'))
+    if (!src && skip_train_fetch(s, nm, &src, &bytes, &is_param)) {}
+    else if (!src && nm.size() > 2 && nm[1] == '_' && (nm[0] == 'g' || nm[0] == 'h' || nm[0] == 'w'))
         for (int p = 0; p < DNPARAM; ++p)
             if (nm.substr(2) == DPNAME[p]) { src = nm[0] == 'g' ? s->g[p] : (nm[0] == 'h' ? s->h[p] : s->w[p]); bytes = s->pn[p] * 4; is_param = true; }
     if (!src) return fail(c, AZ_ERR_INVALID, "az_det_solver_fetch: no saved tensor named '" + nm + "'");
+    if ((nm == "d_cat" || nm == "d_raw") && !s->sk.has_dcat)
+        return fail(c, AZ_ERR_STATE, "az_det_solver_fetch: the last skip pass asked for no map gradient, so it computed no '" + nm + "'");
     if (!is_param && s->R == 0) return fail(c, AZ_ERR_STATE, "az_det_solver_fetch: no forward pass has run");
     *bytes_out = (long long)bytes;
     if (!out) return AZ_OK;

@@ -131,10 +131,14 @@ class VGG16Conv5(object):
                 out.append(layer)
         return out
 
-    def forward_train(self, blob):
+    def forward_train(self, blob, taps=()):
         """conv5_3 [N,C,h,w] of a training blob [N,3,H,W] with autograd through the layers set_trainable named: plain torch
         ops (the fused in-place bias / ReLU kernels of `forward` are not differentiable); the frozen layers in front of
-        the first trainable one run under no_grad.  The solver calls conv5_3.backward(d conv5_3)."""
+        the first trainable one run under no_grad.  The solver calls conv5_3.backward(d conv5_3).
+        taps: layer names (the skip-connection detector's conv3_3, conv4_3, conv5_3); with them the result is
+        (conv5_3, [the post-ReLU map of every tap, in `taps` order]), the maps part of autograd's graph and all in one
+        memory format: the solver calls torch.autograd.backward(maps, d maps)."""
+        tapped = {}
         x = torch.as_tensor(blob, dtype=torch.float32, device=self.device)
         if self.cl_compute:
             x = x.contiguous(memory_format=torch.channels_last)
@@ -145,7 +149,19 @@ class VGG16Conv5(object):
             _, w, b = layer
             with torch.set_grad_enabled(bool(x.requires_grad or w.requires_grad)):
                 x = F.relu(F.conv2d(x, w, b, padding=1))
-        return x if (x.is_contiguous() or x.is_contiguous(memory_format=torch.channels_last)) else x.contiguous()
+            if layer[0] in taps:
+                tapped[layer[0]] = x
+        x = x if (x.is_contiguous() or x.is_contiguous(memory_format=torch.channels_last)) else x.contiguous()
+        if not taps:
+            return x
+        missing = [n for n in taps if n not in tapped]
+        if missing:
+            raise ValueError("forward_train: no layer named %s" % ", ".join(missing))
+        # one memory format for all (the trainer takes the maps in one): conv5_3's when every tap already has it
+        cl = all(t.is_contiguous(memory_format=torch.channels_last) for t in tapped.values()) and not \
+            all(t.is_contiguous() for t in tapped.values())
+        fmt = torch.channels_last if cl else torch.contiguous_format
+        return x, [tapped[n].contiguous(memory_format=fmt) for n in taps]
 
     @torch.no_grad()
     def normalize_output(self, blob):

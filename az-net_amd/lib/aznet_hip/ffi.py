@@ -52,6 +52,8 @@ SYMBOLS = [
     "az_det_targets", "az_det_target_stats",
     "az_det_solver_create", "az_det_solver_destroy", "az_det_solver_load", "az_det_solver_read", "az_det_solver_set_hyper",
     "az_det_solver_step", "az_det_solver_update", "az_det_solver_forward_test", "az_det_solver_fetch",
+    "az_det_solver_attach_skip", "az_det_solver_load_skip", "az_det_solver_read_skip", "az_det_solver_set_skip_hyper",
+    "az_det_solver_step_skip", "az_det_solver_forward_test_skip", "az_skip_pool_bwd_unit",
 ]
 
 
@@ -260,6 +262,14 @@ def load_library(path=None):
     L.az_det_solver_update.argtypes = [vp, cd, cd, cd, cd]
     L.az_det_solver_forward_test.argtypes = [vp, vp, ci, ci, ci, ci, fp, ci, fp, fp]
     L.az_det_solver_fetch.argtypes = [vp, ctypes.c_char_p, vp, ll, llp]
+    vpp = ctypes.POINTER(vp)
+    L.az_det_solver_attach_skip.argtypes = [vp, ci, cip, fp, cd, cd, u64]
+    L.az_det_solver_load_skip.argtypes = [vp, fp, fp]
+    L.az_det_solver_read_skip.argtypes = [vp, fp, fp]
+    L.az_det_solver_set_skip_hyper.argtypes = [vp, fp, fp]
+    L.az_det_solver_step_skip.argtypes = [vp, ci, cip, vpp, cip, cip, ci, ci, fp, ci, fp, fp, fp, u64, ll, fp, dp, vpp]
+    L.az_det_solver_forward_test_skip.argtypes = [vp, ci, cip, vpp, cip, cip, ci, ci, fp, ci, fp, fp]
+    L.az_skip_pool_bwd_unit.argtypes = [vp, ci, cip, fp, vpp, cip, cip, ci, ci, fp, ci, fp, fp, ip, vpp]
     L.az_image_blob_size.argtypes = [ci, ci, cd, cip, cip]
     L.az_image_blob_host.argtypes = [vp, u8p, ci, ci, fp, cd, fp, ci, ci]
     L.az_image_blob_dev.argtypes = [vp, u8p, ci, ci, fp, cd, vp, ci, ci]
@@ -1643,6 +1653,8 @@ class AzSolver(object):
 
 
 DET_HEAD_KEYS = ("W6", "b6", "W7", "b7", "Wc", "bc", "Wb", "bb")
+SKIP_KEYS = ("Wp", "bp")                                     # conv_pool5 of an attached skip front
+_SKIP_ROW_TENSORS = ("cat", "skip_argmax", "skip_factor", "d_y", "d_cat", "d_raw")      # rows (roi, bin)
 _DET_SOLVER_U8 = ("mask6", "mask7")
 
 
@@ -1664,8 +1676,10 @@ class AzDetSolver(object):
 
     def _shapes(self):
         d = self.dims
-        return {"W6": (d["n6"], d["K6"]), "b6": (d["n6"],), "W7": (d["n7"], d["n6"]), "b7": (d["n7"],),
-                "Wc": (d["ncls"], d["n7"]), "bc": (d["ncls"],), "Wb": (4 * d["ncls"], d["n7"]), "bb": (4 * d["ncls"],)}
+        shp = {"W6": (d["n6"], d["K6"]), "b6": (d["n6"],), "W7": (d["n7"], d["n6"]), "b7": (d["n7"],),
+               "Wc": (d["ncls"], d["n7"]), "bc": (d["ncls"],), "Wb": (4 * d["ncls"], d["n7"]), "bb": (4 * d["ncls"],)}
+        shp.update(self._skip_shapes())
+        return shp
 
     def close(self):
         if getattr(self, "h", None) and getattr(self.ctx, "h", None):
@@ -1685,7 +1699,8 @@ class AzDetSolver(object):
         self.ctx._chk(self.L.az_det_solver_load(self.h, *[_p(a, ctypes.c_float) if a is not None else None for a in arrs]))
 
     def read(self):
-        out = {k: np.empty(v, dtype=np.float32) for k, v in self._shapes().items()}
+        shp = self._shapes()
+        out = {k: np.empty(shp[k], dtype=np.float32) for k in DET_HEAD_KEYS}
         self.ctx._chk(self.L.az_det_solver_read(self.h, *[_p(out[k], ctypes.c_float) for k in DET_HEAD_KEYS]))
         return out
 
@@ -1740,16 +1755,151 @@ class AzDetSolver(object):
         self.last_rows = R
         return p, b
 
+    # ---- the skip-connection front (az_det_solver_*_skip) ----
+    def attach_skip(self, Cs, scales, gain=1000.0, eps=1e-10, seed=0, front=None):
+        """Put roi_pool3/4/5 + GRN + concat + scale + conv_pool5 in front of fc6 (az_det_solver_attach_skip); front:
+        {"Wp", "bp"} to load at once."""
+        Cs = np.ascontiguousarray(Cs, dtype=np.intc)
+        sc = _f32(scales).reshape(-1)
+        if Cs.size != sc.size:
+            raise AzError(AZ_ERR_INVALID, "attach_skip: one spatial_scale per source")
+        self.ctx._chk(self.L.az_det_solver_attach_skip(self.h, int(Cs.size), _p(Cs, ctypes.c_int), _p(sc, ctypes.c_float), float(gain),
+                                                       float(eps), int(seed) & ((1 << 64) - 1)))
+        self.skip = dict(Cs=tuple(int(c) for c in Cs), scales=tuple(float(x) for x in sc), gain=float(gain), eps=float(eps),
+                         sumC=int(Cs.sum()))
+        if front is not None:
+            self.load_skip(front)
+
+    def _skip_shapes(self):
+        sk = getattr(self, "skip", None)
+        return {} if sk is None else {"Wp": (self.dims["C"], sk["sumC"]), "bp": (self.dims["C"],)}
+
+    def load_skip(self, front):
+        shp = self._skip_shapes()
+        arrs = [_f32(front[k]).reshape(shp[k]) if k in front and k in shp else None for k in SKIP_KEYS]
+        self.ctx._chk(self.L.az_det_solver_load_skip(self.h, *[_p(a, ctypes.c_float) if a is not None else None for a in arrs]))
+
+    def read_skip(self):
+        shp = self._skip_shapes()
+        out = {k: np.empty(shp.get(k, (0,)), dtype=np.float32) for k in SKIP_KEYS}
+        self.ctx._chk(self.L.az_det_solver_read_skip(self.h, *[_p(out[k], ctypes.c_float) for k in SKIP_KEYS]))
+        return out
+
+    def set_skip_hyper(self, lr_mult=None, decay_mult=None):
+        a = None if lr_mult is None else _f32(lr_mult).reshape(2)
+        b = None if decay_mult is None else _f32(decay_mult).reshape(2)
+        f = ctypes.c_float
+        self.ctx._chk(self.L.az_det_solver_set_skip_hyper(self.h, None if a is None else _p(a, f), None if b is None else _p(b, f)))
+
+    def _maps(self, maps, dmaps=None):
+        """The argument arrays of n maps [N, C_i, H_i, W_i] (float32 CUDA tensors, all in one memory format)."""
+        import torch
+        maps = list(maps)
+        if not maps:
+            raise AzError(AZ_ERR_INVALID, "no maps")
+        n = len(maps)
+        N = int(maps[0].shape[0])
+        for m in maps:
+            if not (m.is_cuda and m.dtype == torch.float32 and m.dim() == 4 and int(m.shape[0]) == N):
+                raise AzError(AZ_ERR_INVALID, "the maps must be float32 CUDA tensors [N, C, H, W] of one batch size")
+        if all(m.is_contiguous() for m in maps):
+            cl = 0
+        elif all(m.is_contiguous(memory_format=torch.channels_last) for m in maps):
+            cl = 1
+        else:
+            raise AzError(AZ_ERR_INVALID, "the maps must all be contiguous or all channels_last")
+        Cs = np.asarray([m.shape[1] for m in maps], dtype=np.intc)
+        Hs = np.asarray([m.shape[2] for m in maps], dtype=np.intc)
+        Ws = np.asarray([m.shape[3] for m in maps], dtype=np.intc)
+        ptrs = (ctypes.c_void_p * n)(*[m.data_ptr() for m in maps])
+        dptrs = None
+        if dmaps is not None:
+            dmaps = list(dmaps)
+            if len(dmaps) != n:
+                raise AzError(AZ_ERR_INVALID, "dmaps: one entry (or None) per map")
+            for d, m in zip(dmaps, maps):
+                if d is not None:
+                    if not (d.is_cuda and d.dtype == m.dtype and d.shape == m.shape and d.stride() == m.stride()):
+                        raise AzError(AZ_ERR_INVALID, "dmaps: every buffer must have its map's device, dtype, shape and strides")
+            dptrs = (ctypes.c_void_p * n)(*[None if d is None else d.data_ptr() for d in dmaps])
+        torch.cuda.current_stream(maps[0].device).synchronize()
+        return n, Cs, ptrs, Hs, Ws, N, cl, dptrs
+
+    def step_skip(self, maps, rois, labels, bbox_targets, bbox_loss_weights, seed, iteration, dmaps=None):
+        """Forward + backward of one minibatch through the skip front and the head.  maps: CUDA tensors [N, C_i, H_i, W_i] in
+        concat order; dmaps: None, or a list with, per map, None or a tensor of the map's shape and memory format that
+        receives d loss / d map.  Returns (losses [cls, bbox] f32, sum of squares of all ten gradients)."""
+        n, Cs, ptrs, Hs, Ws, N, cl, dptrs = self._maps(maps, dmaps)
+        rois = _f32(rois).reshape(-1, 5)
+        R, nb = rois.shape[0], 4 * self.dims["ncls"]
+        lab, bt, bw = _f32(labels).reshape(R), _f32(bbox_targets).reshape(R, nb), _f32(bbox_loss_weights).reshape(R, nb)
+        losses = np.zeros(2, dtype=np.float32)
+        sq = ctypes.c_double(0.0)
+        f, ci = ctypes.c_float, ctypes.c_int
+        self.ctx._chk(self.L.az_det_solver_step_skip(self.h, n, _p(Cs, ci), ptrs, _p(Hs, ci), _p(Ws, ci), N, cl, _p(rois, f), R,
+                                                     _p(lab, f), _p(bt, f), _p(bw, f), int(seed) & ((1 << 64) - 1), int(iteration),
+                                                     _p(losses, f), ctypes.byref(sq), dptrs))
+        self.last_rows = R
+        return losses, float(sq.value)
+
+    def forward_test_skip(self, maps, rois):
+        """TEST-phase forward of the skip net: (cls_prob [R, ncls], raw bbox_pred [R, 4 ncls])."""
+        n, Cs, ptrs, Hs, Ws, N, cl, _ = self._maps(maps)
+        rois = _f32(rois).reshape(-1, 5)
+        R, K = rois.shape[0], self.dims["ncls"]
+        p, b = np.empty((R, K), np.float32), np.empty((R, 4 * K), np.float32)
+        f, ci = ctypes.c_float, ctypes.c_int
+        self.ctx._chk(self.L.az_det_solver_forward_test_skip(self.h, n, _p(Cs, ci), ptrs, _p(Hs, ci), _p(Ws, ci), N, cl,
+                                                             _p(rois, f), R, _p(p, f), _p(b, f)))
+        self.last_rows = R
+        return p, b
+
     def fetch(self, name):
         """A saved tensor of the last pass by name (az_det_solver_fetch), shaped."""
         n = ctypes.c_longlong(0)
         self.ctx._chk(self.L.az_det_solver_fetch(self.h, name.encode(), None, 0, ctypes.byref(n)))
-        dt = np.uint8 if name in _DET_SOLVER_U8 else (np.int32 if name == "argmax" else np.float32)
+        dt = np.uint8 if name in _DET_SOLVER_U8 else (np.int32 if name in ("argmax", "skip_argmax") else
+                                                      (np.float64 if name == "skip_factor" else np.float32))
         out = np.empty(n.value // np.dtype(dt).itemsize, dtype=dt)
         self.ctx._chk(self.L.az_det_solver_fetch(self.h, name.encode(), out.ctypes.data_as(ctypes.c_void_p), n.value, ctypes.byref(n)))
-        if len(name) > 2 and name[1] == "_" and name[2:] in DET_HEAD_KEYS:
+        if len(name) > 2 and name[1] == "_" and name[2:] in DET_HEAD_KEYS + SKIP_KEYS:
             return out.reshape(self._shapes()[name[2:]])
+        if name in _SKIP_ROW_TENSORS:
+            return out.reshape(self.last_rows * 49, -1) if self.last_rows else out
         return out.reshape(self.last_rows, -1) if self.last_rows else out
+
+
+def skip_pool_bwd_unit(ctx, maps, scales, rois, d_raw=None, channels_last=False, want=None):
+    """az_skip_pool_bwd_unit: roi_pool3/4/5 with arg-max on host maps [N, C_i, H_i, W_i] (NumPy, NCHW order; with
+    channels_last they are handed over -- and the gradients taken back -- in NHWC memory order) and the gather of d_raw
+    [R*49, sum C].  want: per map, whether its gradient is asked for (default: all, when d_raw is given).  Returns
+    (pooled [R*49, sum C] f32, argmax [R*49, sum C] int32, [d map_i or None])."""
+    maps = [_f32(m) for m in maps]
+    n = len(maps)
+    N = maps[0].shape[0]
+    Cs = np.asarray([m.shape[1] for m in maps], dtype=np.intc)
+    Hs = np.asarray([m.shape[2] for m in maps], dtype=np.intc)
+    Ws = np.asarray([m.shape[3] for m in maps], dtype=np.intc)
+    sc = _f32(scales).reshape(n)
+    dev = [np.ascontiguousarray(m.transpose(0, 2, 3, 1)) if channels_last else m for m in maps]
+    rois = _f32(rois).reshape(-1, 5)
+    R, sumC = rois.shape[0], int(Cs.sum())
+    pooled = np.empty((R * 49, sumC), np.float32)
+    arg = np.empty((R * 49, sumC), np.int32)
+    f, ci = ctypes.c_float, ctypes.c_int
+    ptrs = (ctypes.c_void_p * n)(*[m.ctypes.data for m in dev])
+    dr, douts, dptrs = None, [None] * n, None
+    if d_raw is not None:
+        dr = _f32(d_raw).reshape(R * 49, sumC)
+        want = [True] * n if want is None else list(want)
+        douts = [np.empty_like(m) if w else None for m, w in zip(dev, want)]
+        dptrs = (ctypes.c_void_p * n)(*[None if d is None else d.ctypes.data for d in douts])
+    ctx._chk(ctx.L.az_skip_pool_bwd_unit(ctx.h, n, _p(Cs, ci), _p(sc, f), ptrs, _p(Hs, ci), _p(Ws, ci), int(N), 1 if channels_last else 0,
+                                         _p(rois, f), R, None if dr is None else _p(dr, f), _p(pooled, f),
+                                         arg.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), dptrs))
+    if channels_last:
+        douts = [None if d is None else np.ascontiguousarray(d.transpose(0, 3, 1, 2)) for d in douts]
+    return pooled, arg, douts
 
 
 def sgd_update(ctx, w, g, hist, rate, momentum, decay, clip_scale=1.0):

@@ -17,6 +17,12 @@ DET_HEAD_LAYERS = ("fc6", "fc7", "cls_score", "bbox_pred")
 DET_DROPOUT_OF = {"fc6": 0, "fc7": 1}
 DET_FILLER_STD = {"fc6": None, "fc7": None, "cls_score": 1e-2, "bbox_pred": 1e-3}
 DET_FILLER_DEFAULT = 5e-3          # fc6 / fc7 without a pretrained model
+# the skip-connection detector (models/COCO/VGG16_skip/frcnn/{finetune,frozen}/train.prototxt): conv_pool5, a 1x1 Convolution
+# (xavier filler) behind roi_pool3/4/5 -> roi_norm3/4/5 (GRN) -> concat5 -> scale5 (Power), in front of fc6
+SKIP_HEAD_LAYERS = ("conv_pool5",) + DET_HEAD_LAYERS
+SKIP_SOURCES = ("conv3_3", "conv4_3", "conv5_3")
+SKIP_SCALES = (0.25, 0.125, 0.0625)
+SKIP_GAIN = 1000.0
 SOLVER_DEFAULTS = dict(base_lr=0.001, lr_policy="step", gamma=0.1, stepsize=120000, momentum=0.9, weight_decay=0.0005,
                        clip_gradients=-1.0, display=20, average_loss=1, snapshot_prefix="vgg16_az_net", train_net=None)
 
@@ -122,7 +128,64 @@ def read_det_train_net(path):
     return _read_net(path, DET_HEAD_LAYERS, DET_DROPOUT_OF, "detection net")
 
 
-def _read_net(path, HEAD_LAYERS, DROPOUT_OF, what):
+def _all(items, key):
+    return [v for k, v in items if k == key]
+
+
+def read_skip_train_net(path):
+    """(table, front) of the skip-connection detector's train net: read_det_train_net's table plus a `conv_pool5` row, and
+    the front's settings as the file states them: {"sources": the ROIPooling layers' map bottoms in concat order, "scales":
+    their spatial_scale, "gain": the Power layer's scale}.  Refused (ValueError): a Power layer with power != 1 or shift != 0,
+    a pooled size other than 7x7, a pooled blob without a GRN layer on it, a Concat whose bottoms are not the pooled blobs in
+    the ROIPooling layers' order."""
+    table = _read_net(path, SKIP_HEAD_LAYERS, DET_DROPOUT_OF, "skip-connection detection net", conv_heads=("conv_pool5",))
+    with open(path) as f:
+        items = parse_text(f.read())
+    layers = [v for k, v in items if k in ("layer", "layers") and isinstance(v, list)]
+    pools, normed, concat, gain = [], set(), None, 1.0
+    for L in layers:
+        name, typ = _get(L, "name"), str(_get(L, "type", ""))
+        if typ == "ROIPooling":
+            rp = _get(L, "roi_pooling_param")
+            rp = rp if isinstance(rp, list) else []
+            if int(_get(rp, "pooled_w", 0)) != 7 or int(_get(rp, "pooled_h", 0)) != 7:
+                raise ValueError("%s: %s pools to %sx%s; this backend pools 7x7" % (path, name, _get(rp, "pooled_h", 0), _get(rp, "pooled_w", 0)))
+            bottoms = _all(L, "bottom")
+            if len(bottoms) != 2 or _get(L, "top") is None:
+                raise ValueError("%s: %s needs a map and a rois bottom and a top" % (path, name))
+            pools.append((_get(L, "top"), bottoms[0], float(_get(rp, "spatial_scale", 1.0))))
+        elif typ == "GRN":
+            if _get(L, "top") != _get(L, "bottom"):
+                raise ValueError("%s: GRN layer %s is not in place" % (path, name))
+            normed.add(_get(L, "bottom"))
+        elif typ == "Concat":
+            if concat is not None:
+                raise ValueError("%s: more than one Concat layer" % path)
+            cp = _get(L, "concat_param")
+            if isinstance(cp, list) and int(_get(cp, "axis", 1)) != 1:
+                raise ValueError("%s: %s concatenates along axis %s, not the channels" % (path, name, _get(cp, "axis")))
+            concat = (_all(L, "bottom"), _get(L, "top"))
+        elif typ == "Power":
+            pp = _get(L, "power_param")
+            pp = pp if isinstance(pp, list) else []
+            if float(_get(pp, "power", 1.0)) != 1.0 or float(_get(pp, "shift", 0.0)) != 0.0:
+                raise ValueError("%s: Power layer %s with power %s, shift %s; this backend has power 1, shift 0 (a plain scale)"
+                                 % (path, name, _get(pp, "power", 1.0), _get(pp, "shift", 0.0)))
+            gain = float(_get(pp, "scale", 1.0))
+    if not pools or concat is None:
+        raise ValueError("%s: not the skip-connection detection net (no ROIPooling layers or no Concat)" % path)
+    if len(pools) > 3:
+        raise ValueError("%s: %d ROIPooling layers; this backend takes up to 3" % (path, len(pools)))
+    for top, _, _ in pools:
+        if top not in normed:
+            raise ValueError("%s: no GRN layer on the pooled blob %r" % (path, top))
+    if list(concat[0]) != [top for top, _, _ in pools]:
+        raise ValueError("%s: the Concat layer joins %s, the ROIPooling layers give %s in this order"
+                         % (path, list(concat[0]), [top for top, _, _ in pools]))
+    return table, {"sources": [b for _, b, _ in pools], "scales": [sc for _, _, sc in pools], "gain": gain}
+
+
+def _read_net(path, HEAD_LAYERS, DROPOUT_OF, what, conv_heads=()):
     with open(path) as f:
         items = parse_text(f.read())
     layers = [v for k, v in items if k in ("layer", "layers") and isinstance(v, list)]
@@ -132,7 +195,7 @@ def _read_net(path, HEAD_LAYERS, DROPOUT_OF, what):
     for L in layers:
         name, typ = _get(L, "name"), str(_get(L, "type", ""))
         if typ in ("Convolution", "InnerProduct"):
-            if name not in CONV_LAYERS + HEAD_LAYERS or (typ == "Convolution") != (name in CONV_LAYERS):
+            if name not in CONV_LAYERS + HEAD_LAYERS or (typ == "Convolution") != (name in CONV_LAYERS + tuple(conv_heads)):
                 raise ValueError("%s: learnable layer %r (%s) is not part of the %s this backend trains "
                                  "(conv1_1 .. conv5_3, %s)" % (path, name, typ, what, ", ".join(HEAD_LAYERS)))
             params = [v for k, v in L if k == "param" and isinstance(v, list)]
@@ -189,11 +252,47 @@ def det_layer_table(frozen=("conv1_1", "conv1_2", "conv2_1", "conv2_2"), dropout
     return rows
 
 
-def write_train_prototxt(path, rows, name="az_net_train"):
+def skip_layer_table(frozen=CONV_LAYERS, dropout=0.5):
+    """The skip-connection detector's learnable layers as layer_table's rows: det_layer_table's with conv_pool5 in front of
+    fc6.  The reference's frozen/ net holds all thirteen convolutions fixed (the default), its finetune/ net conv1_1 ..
+    conv2_2 only."""
+    rows = det_layer_table(frozen=frozen, dropout=dropout)
+    k = [r[0] for r in rows].index("fc6")
+    return rows[:k] + [("conv_pool5", "Convolution", 1.0, 2.0, 1.0, 0.0, None, None)] + rows[k:]
+
+
+def _skip_front_text(sources, scales, gain):
+    out, tops = [], []
+    for src, sc in zip(sources, scales):
+        tag = src[4] if src.startswith("conv") and len(src) > 4 else str(len(tops))
+        top = "roi_pool%s" % tag
+        tops.append(top)
+        out.append('layer {\n  name: "%s"\n  type: "ROIPooling"\n  bottom: "%s"\n  bottom: "rois"\n  top: "%s"\n  roi_pooling_param {\n'
+                   '    pooled_w: 7\n    pooled_h: 7\n    spatial_scale: %r\n  }\n}' % (top, src, top, float(sc)))
+        out.append('layer {\n  name: "roi_norm%s"\n  type: "GRN"\n  bottom: "%s"\n  top: "%s"\n}' % (tag, top, top))
+    out.append('layer {\n  name: "concat5"\n  type: "Concat"\n%s  top: "cat5"\n  concat_param {\n    axis: 1\n  }\n}'
+               % "".join('  bottom: "%s"\n' % t for t in tops))
+    out.append('layer {\n  name: "scale5"\n  type: "Power"\n  bottom: "cat5"\n  top: "cat5"\n  power_param {\n    power: 1\n'
+               '    scale: %r\n    shift: 0\n  }\n}' % float(gain))
+    return out
+
+
+def write_skip_train_prototxt(path, rows, name="frcnn_skip_train", sources=SKIP_SOURCES, scales=SKIP_SCALES, gain=SKIP_GAIN):
+    """write_train_prototxt for skip_layer_table's rows, with the front's layers (ROIPooling + GRN per source, Concat, Power)
+    in front of conv_pool5: a file read_skip_train_net accepts."""
+    write_train_prototxt(path, rows, name=name, before={"conv_pool5": _skip_front_text(sources, scales, gain)})
+
+
+def write_train_prototxt(path, rows, name="az_net_train", before=None):
+    """before: {layer name: [layer texts]} to put in front of that row."""
     out = ['name: "%s"' % name]
     for name, typ, lw, lb, dw, db, std, drop in rows:
+        out.extend((before or {}).get(name, []))
         out.append('layer {\n  name: "%s"\n  type: "%s"\n  param {\n    lr_mult: %g\n    decay_mult: %g\n  }\n  param {\n'
                    '    lr_mult: %g\n    decay_mult: %g\n  }' % (name, typ, lw, dw, lb, db))
+        if name == "conv_pool5":
+            out.append('  convolution_param {\n    kernel_size: 1\n    stride: 1\n    weight_filler {\n      type: "xavier"\n    }\n'
+                       '    bias_filler {\n      type: "constant"\n      value: 0\n    }\n  }')
         if std is not None:
             out.append('  inner_product_param {\n    weight_filler {\n      type: "gaussian"\n      std: %g\n    }\n'
                        '    bias_filler {\n      type: "constant"\n      value: 0\n    }\n  }' % std)

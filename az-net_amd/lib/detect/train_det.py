@@ -1,7 +1,9 @@
 """Train the detection net (reference: lib/detect/train_det.py) without Caffe: PyTorch-ROCm runs the VGG16 convolutions with
 autograd, everything from conv5_3 on -- RoIPool, fc6 / fc7 / cls_score / bbox_pred forward and backward, dropout, the softmax
 and SmoothL1 losses, the gradient norm and the SGD update -- is the HIP trainer behind az_det_solver_*
-(aznet_hip.ffi.AzDetSolver).  Shaped like detect/train_az.py, whose learning-rate and clipping rules it shares."""
+(aznet_hip.ffi.AzDetSolver).  Shaped like detect/train_az.py, whose learning-rate and clipping rules it shares.
+Under a skip configuration (cfg.SEAR.FRCNN_CONV names several maps: the rule of detect.test) the trainer carries the
+skip-connection front -- roi_pool3/4/5, GRN, concat, scale, conv_pool5 -- and autograd starts at the three tapped maps."""
 import os
 
 import numpy as np
@@ -32,11 +34,29 @@ class SolverWrapper(object):
                  dims=None, seed=None):
         self.output_dir = output_dir
         self.num_classes = int(imdb.num_classes)
+        # the configuration and the train net must name the same model (checked before any device work)
+        self.solver_param = prototxt.read_solver(solver_prototxt)
+        net_file = prototxt.resolve_train_net(solver_prototxt, self.solver_param["train_net"])
+        self.skip = None
+        if len(cfg.SEAR.FRCNN_CONV) > 1:
+            try:
+                self.net_param, self.skip = prototxt.read_skip_train_net(net_file)
+            except ValueError as e:
+                raise ValueError("cfg.SEAR.FRCNN_CONV = %s names the skip-connection detector's maps, but the train net is "
+                                 "not its net: %s" % (list(cfg.SEAR.FRCNN_CONV), e))
+            if list(self.skip["sources"]) != list(cfg.SEAR.FRCNN_CONV):
+                raise ValueError("the train net pools %s, cfg.SEAR.FRCNN_CONV names %s" % (list(self.skip["sources"]), list(cfg.SEAR.FRCNN_CONV)))
+        else:
+            try:
+                self.net_param = prototxt.read_det_train_net(net_file)
+            except ValueError as e:
+                if "conv_pool5" in str(e):
+                    raise ValueError("the train net has the skip front (conv_pool5), but cfg.SEAR.FRCNN_CONV = %s names one map: "
+                                     "use the skip configuration (voc_skip.yml): %s" % (list(cfg.SEAR.FRCNN_CONV), e))
+                raise
         print("Computing bounding-box regression targets...")
         self.bbox_means, self.bbox_stds = rdl_roidb.add_bbox_regression_targets(imdb.roidb, self.num_classes)
         print("done")
-        self.solver_param = prototxt.read_solver(solver_prototxt)
-        self.net_param = prototxt.read_det_train_net(prototxt.resolve_train_net(solver_prototxt, self.solver_param["train_net"]))
         self.seed = int(cfg.RNG_SEED if seed is None else seed)
         self.iter = 0
         self.losses = []                       # (loss_cls, loss_bbox) of every iteration
@@ -50,8 +70,10 @@ class SolverWrapper(object):
         self.trainer = trainer
         if self.trainer is None:
             self._build(layers, dims)
-        elif layers is not None:
-            self._copy_from(layers)
+        else:
+            self._attach_skip()
+            if layers is not None:
+                self._copy_from(layers)
         self._configure()
         if cfg.TRAIN.BBOX_REG and cfg.TRAIN.UN_NORMALIZE:
             # scale and shift bbox_pred into the normalised targets' units (train_det.py:46-54)
@@ -85,8 +107,20 @@ class SolverWrapper(object):
             lib_std = prototxt.DET_FILLER_STD[lname] or prototxt.DET_FILLER_DEFAULT
             if std is not None and abs(std - lib_std) > 1e-12 * std:
                 self.trainer.load({wk: rng.normal(0.0, std, shp[wk]).astype(np.float32)})
+        self._attach_skip()
         if layers:
             self._copy_from(layers)
+
+    def _attach_skip(self):
+        """The front of the train net on the trainer: scales and gain as the file states them, eps the library's."""
+        if self.skip is None or getattr(self.trainer, "skip", None) is not None:
+            return
+        conv = {layer[0]: layer[1] for layer in self.backbone.layers if layer is not None}
+        missing = [n for n in self.skip["sources"] if n not in conv]
+        if missing:
+            raise ValueError("the train net pools %s, which the backbone does not have" % ", ".join(missing))
+        self.trainer.attach_skip([int(conv[n].shape[0]) for n in self.skip["sources"]], self.skip["scales"],
+                                 gain=self.skip["gain"], eps=1e-10, seed=self.seed)
 
     def _copy_from(self, layers):
         """net.copy_from: the head layers the model has, by name (an ImageNet VGG16 brings fc6 and fc7 only)."""
@@ -100,6 +134,12 @@ class SolverWrapper(object):
             raise ValueError("pretrained model: %s of shape %s, the trainer holds %s" % (bad[0], head[bad[0]].shape, shp[bad[0]]))
         if head:
             self.trainer.load(head)
+        if self.skip is not None and "conv_pool5" in layers:          # (a model without it keeps the xavier fill)
+            from aznet_hip import caffemodel as cm
+            front = cm.skip_front_from_layers(layers, Cs=self.trainer.skip["Cs"])
+            if front["Wp"].shape != shp["Wp"]:
+                raise ValueError("pretrained model: conv_pool5 of shape %s, the trainer holds %s" % (front["Wp"].shape, shp["Wp"]))
+            self.trainer.load_skip(front)
 
     def _configure(self):
         """lr_mult / decay_mult / dropout of the prototxt -> the trainer; the trainable convolutions and their history."""
@@ -112,6 +152,8 @@ class SolverWrapper(object):
             if lname in prototxt.DET_DROPOUT_OF and n["dropout_ratio"] is not None:
                 drop[prototxt.DET_DROPOUT_OF[lname]] = n["dropout_ratio"]
         self.trainer.set_hyper([lr[k] for k in DET_HEAD_KEYS], [dc[k] for k in DET_HEAD_KEYS], drop)
+        if self.skip is not None:
+            self.trainer.set_skip_hyper(self.net_param["conv_pool5"]["lr_mult"], self.net_param["conv_pool5"]["decay_mult"])
         self.conv_train = []
         if self.backbone is not None:
             import torch
@@ -127,16 +169,31 @@ class SolverWrapper(object):
             blobs = self.layer.forward()
         import torch
         from aznet_hip import ffi
-        conv = self.backbone.forward_train(blobs["data"])
-        dmap = torch.empty_like(conv) if self.conv_train else None
-        losses, sumsq = self.trainer.step(conv.detach(), blobs["rois"], blobs["labels"], blobs["bbox_targets"],
-                                          blobs["bbox_loss_weights"], self.seed, self.iter, dmap=dmap)
+        if self.skip is not None:
+            conv, taps = self.backbone.forward_train(blobs["data"], taps=tuple(self.skip["sources"]))
+            maps = [t.detach() for t in taps]
+            # (a tap in front of the first trainable convolution takes no gradient: no buffer, no gather)
+            dmaps = [torch.empty_like(m) if t.requires_grad else None for m, t in zip(maps, taps)] if self.conv_train else None
+            if dmaps is not None and all(d is None for d in dmaps):
+                dmaps = None
+            losses, sumsq = self.trainer.step_skip(maps, blobs["rois"], blobs["labels"], blobs["bbox_targets"],
+                                                   blobs["bbox_loss_weights"], self.seed, self.iter, dmaps=dmaps)
+            self.last_maps, self.last_dmaps = maps, dmaps
+        else:
+            conv = self.backbone.forward_train(blobs["data"])
+            dmap = torch.empty_like(conv) if self.conv_train else None
+            losses, sumsq = self.trainer.step(conv.detach(), blobs["rois"], blobs["labels"], blobs["bbox_targets"],
+                                              blobs["bbox_loss_weights"], self.seed, self.iter, dmap=dmap)
         self.last_conv, self.last_blobs, self.last_head_sumsq = conv.detach(), blobs, sumsq
         if self.conv_train:
             for _, w, b, _, _, _, _ in self.conv_train:
                 w.grad = None
                 b.grad = None
-            conv.backward(dmap)
+            if self.skip is not None:
+                if dmaps is not None:
+                    torch.autograd.backward([t for t, d in zip(taps, dmaps) if d is not None], [d for d in dmaps if d is not None])
+            else:
+                conv.backward(dmap)
             sumsq += float(sum((p.grad.double() ** 2).sum() for _, w, b, _, _, _, _ in self.conv_train for p in (w, b)))
         rate = learning_rate(sp, self.iter)
         clip = clip_scale(sumsq, sp["clip_gradients"])
@@ -171,6 +228,9 @@ class SolverWrapper(object):
                     layers[layer[0]] = [layer[1].detach().contiguous().cpu().numpy(), layer[2].detach().cpu().numpy()]
         for lname, (wk, bk) in HEAD_OF.items():
             layers[lname] = [p[wk], p[bk]]
+        if self.skip is not None:
+            f = self.trainer.read_skip()
+            layers["conv_pool5"] = [f["Wp"].reshape(f["Wp"].shape[0], f["Wp"].shape[1], 1, 1), f["bp"]]
         write_caffemodel(filename, layers)
         print("Wrote snapshot to: {:s}".format(filename))
         # the trainer's own bbox_pred must be what it was (train_det.py:93-96)

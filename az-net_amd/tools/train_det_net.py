@@ -13,7 +13,11 @@ tools/train_det_net.py (same flags).  Differences forced by what exists offline:
   --def / --def_fc  accepted and ignored (the layer graphs are fixed).
   --imdb    `voc_<year>_<split>`, `synthetic_<H>x<W>_<N>` or `npy:<dir>`.
 The proposals are cached as proposals.pkl under the output directory of (imdb, AZ-net).  The snapshots
-(<snapshot_prefix>[_<infix>]_iter_<n>.caffemodel, bbox_pred un-normalised) load in tools/test_det_net.py --net."""
+(<snapshot_prefix>[_<infix>]_iter_<n>.caffemodel, bbox_pred un-normalised) load in tools/test_det_net.py --net.
+Under a skip configuration (--cfg experiments/cfgs/voc_skip.yml: SEAR.FRCNN_CONV names conv3_3, conv4_3, conv5_3) the
+skip-connection detector is trained: without --solver the written train net is the reference's frozen/ net (all
+convolutions fixed; edit its lr_mult / decay_mult and pass it through --solver to fine-tune them), the snapshots are
+vgg16_fast_rcnn_skip_iter_<n>.caffemodel with conv_pool5, and load in tools/test_det_net.py under the same --cfg."""
 import _init_paths  # noqa: F401
 import os
 import pprint
@@ -134,11 +138,22 @@ def main():
     solver = args.solver
     if solver is None:
         os.makedirs(output_dir, exist_ok=True)
-        net_file = os.path.join(output_dir, "train_det.prototxt")
-        prototxt.write_train_prototxt(net_file, prototxt.det_layer_table(), name="frcnn_train")
-        solver = os.path.join(output_dir, "solver_det.prototxt")
-        prototxt.write_solver_prototxt(solver, net_file, base_lr=args.base_lr, stepsize=60000, clip_gradients=20.0, average_loss=100,
-                                       snapshot_prefix="vgg16_frcnn")
+        if len(cfg.SEAR.FRCNN_CONV) > 1:
+            # the skip-connection detector (--cfg voc_skip.yml): the reference's frozen/ net and solver_skip values
+            if tuple(cfg.SEAR.FRCNN_CONV) != prototxt.SKIP_SOURCES:
+                raise SystemExit("cfg.SEAR.FRCNN_CONV = %s: without --solver the skip train net is written for %s"
+                                 % (list(cfg.SEAR.FRCNN_CONV), list(prototxt.SKIP_SOURCES)))
+            net_file = os.path.join(output_dir, "train_det_skip.prototxt")
+            prototxt.write_skip_train_prototxt(net_file, prototxt.skip_layer_table())
+            solver = os.path.join(output_dir, "solver_det_skip.prototxt")
+            prototxt.write_solver_prototxt(solver, net_file, base_lr=args.base_lr, gamma=0.2, stepsize=160000, clip_gradients=20.0,
+                                           average_loss=100, snapshot_prefix="vgg16_fast_rcnn_skip")
+        else:
+            net_file = os.path.join(output_dir, "train_det.prototxt")
+            prototxt.write_train_prototxt(net_file, prototxt.det_layer_table(), name="frcnn_train")
+            solver = os.path.join(output_dir, "solver_det.prototxt")
+            prototxt.write_solver_prototxt(solver, net_file, base_lr=args.base_lr, stepsize=60000, clip_gradients=20.0, average_loss=100,
+                                           snapshot_prefix="vgg16_frcnn")
     kw = {}
     if div > 1 or (args.caffemodel.startswith("synthetic") and args.pretrained_model is None):
         backbone = VGG16Conv5(device="cuda:%d" % args.gpu_id, seed=seed + 3, width_div=div)

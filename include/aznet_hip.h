@@ -770,6 +770,54 @@ int az_det_solver_forward_test(az_det_solver *s, const float *conv_dev, int N, i
  * out == NULL: only the size. */
 int az_det_solver_fetch(az_det_solver *s, const char *name, void *out, long long cap_bytes, long long *bytes_out);
 
+/* ---- training the skip-connection detector (models/COCO/VGG16_skip/frcnn/finetune/train.prototxt, frozen/train.prototxt) ---- */
+/* The trainer above with the skip front in place of roi_pool5: roi_pool3 / roi_pool4 / roi_pool5 (ROIPooling 7x7 of conv3_3,
+ * conv4_3, conv5_3, each at its own spatial_scale), roi_norm3/4/5 (GRN, as az_load_skip_front states it), concat5, scale5
+ * (Power, scale = gain) and conv_pool5 + relu_pool (1x1 Convolution sum Cs -> C with bias, xavier filler); fc6 .. loss_cls /
+ * loss_bbox behind it are az_det_solver_step's.  Same argument checks as az_load_skip_front; Cout is the trainer's C.
+ * Allocates cat, arg-max, d_cat and d_raw ([max_rois * 49][sum Cs], 4 bytes each: the backward needs them whole) and the
+ * parameters Wp [C][sum Cs] (uniform in +-sqrt(3 / sum Cs) from `seed`, drawn on the device) and bp [C] (0) with gradient
+ * and history; lr_mult / decay_mult 1 / 1 and 2 / 0.  max_rois * 49 * sum Cs must fit in 31 bits (AZ_ERR_INVALID).  One front
+ * per trainer (a second attach: AZ_ERR_STATE).  An error leaves the trainer as it was; a trainer without a front, and
+ * az_det_solver_step on one with a front, compute exactly what they did before. */
+int az_det_solver_attach_skip(az_det_solver *s, int n_src, const int *Cs, const float *spatial_scales, double gain, double eps,
+                              uint64_t seed);
+/* net.params['conv_pool5'][0 / 1].data (train_det.py:44,70-96): host Wp [C][sum Cs], bp [C]; a NULL array is skipped. */
+int az_det_solver_load_skip(az_det_solver *s, const float *Wp, const float *bp);
+int az_det_solver_read_skip(az_det_solver *s, float *Wp, float *bp);
+/* param { lr_mult decay_mult } of conv_pool5 ([2]: weight, bias); a NULL array keeps the current values. */
+int az_det_solver_set_skip_hyper(az_det_solver *s, const float *lr_mult, const float *decay_mult);
+/* net.forward() + net.backward() of one minibatch of the skip train net.  maps_dev[i]: device map [N][Cs[i]][Hs[i]][Ws[i]]
+ * (all NCHW or all channels-last); Cs must be the attached front's; rois [R][5] with the image index in column 0; the other
+ * arguments as az_det_solver_step.  dmaps_dev: NULL, or n_src device buffers of the maps' shapes and memory format that
+ * receive d loss / d map; a NULL entry gives no gradient for that source; wholly NULL: the backward stops at conv_pool5's
+ * parameters.  sumsq_out: the sum of squares of all ten gradients (the head's eight, then Wp, bp).  The backward:
+ *   d_y[(r,p)][j] = d_pool5[r][j*49+p] where pool5 > 0;  g_Wp = d_y^T cat;  g_bp = column sums;  d_cat = d_y Wp;
+ *   GRN + scale, per (row, source): d_raw[c] = f (d_cat[c] - x[c] (sum_c x[c] d_cat[c]) / (ss + eps)), f = gain / sqrt(ss + eps),
+ *     0 where ss + eps == 0;  ROIPooling backward: each d_raw to its arg-max cell (the first maximum in row-major window
+ *     order), gathered per map cell over the rois in row order and the bins in bin order.
+ * No floating-point atomics: the same step from the same state gives the same bits.  Refused before anything is enqueued: no
+ * attached front (AZ_ERR_STATE); another n_src or other channel counts, a null map, a roi naming an image >= N, a bad label
+ * (AZ_ERR_INVALID). */
+int az_det_solver_step_skip(az_det_solver *s, int n_src, const int *Cs, const void *const *maps_dev, const int *Hs, const int *Ws,
+                            int N, int channels_last, const float *rois, int R, const float *labels, const float *bbox_targets,
+                            const float *bbox_loss_weights, uint64_t seed, long long iteration, float *losses_out,
+                            double *sumsq_out, void *const *dmaps_dev);
+/* net.forward() of the skip net in the TEST phase on the trainer's current weights (az_det_solver_forward_test's twin). */
+int az_det_solver_forward_test_skip(az_det_solver *s, int n_src, const int *Cs, const void *const *maps_dev, const int *Hs,
+                                    const int *Ws, int N, int channels_last, const float *rois, int R, float *cls_prob,
+                                    float *bbox_pred);
+/* az_det_solver_update also updates Wp / bp when the last gradients came from az_det_solver_step_skip.  az_det_solver_fetch
+ * also knows, once a front is attached: cat, skip_argmax (int32), d_cat, d_raw ([R*49][sum Cs]), skip_factor (f64
+ * [R*49][n_src]), d_y ([R*49][C]), g_Wp, g_bp, h_Wp, h_bp, w_Wp, w_bp.  d_cat and d_raw exist only behind a step that was asked
+ * for a map gradient (otherwise AZ_ERR_STATE). */
+/* Unit entry (tests): roi_pool3/4/5 forward with arg-max on host maps [N][Cs[i]][Hs[i]][Ws[i]] (or channels-last) and host
+ * rois, then the ROIPooling backward gather of the host d_raw [R*49][sum Cs].  pooled_out (the raw maxima) and argmax_out are
+ * [R*49][sum Cs]; dmaps_out[i] has map i's shape; any output (and d_raw with dmaps_out) may be NULL. */
+int az_skip_pool_bwd_unit(az_ctx *ctx, int n_src, const int *Cs, const float *spatial_scales, const float *const *maps_host,
+                          const int *Hs, const int *Ws, int N, int channels_last, const float *rois, int R,
+                          const float *d_raw_host, float *pooled_out, int32_t *argmax_out, float *const *dmaps_out);
+
 /* ---- measurement ------------------------------------------------------------------ */
 /* HIP-event timing (events on the ctx stream) of the launches made by az_propose /
  * az_head_forward.  mode bits: 1 = time only the fc GEMM launches, 2 = time every launch
