@@ -199,3 +199,107 @@ def detect(orc, front, head, maps, boxes, scale, im_shape, dedup, dtype, names=N
     net = SkipOracleNet(front, head, dtype, names)
     conv = {n: m for n, m in zip(names, maps)}
     return orc.frcnn_forward({"fc": net}, im_shape, scale, boxes, head["Wc"].shape[0], conv, Cfg)
+
+
+# ---- the configurations of tests/test_skip_edges_host.py and tests/test_gpu_skip_edges.py ----------------------------------------
+# channel sets of the pool kernels' quad partition (nqb = min(256, quads left), G = 256 / nqb): one quad (G = 256), 130 (G = 1,
+# idle lanes), 256 (one full pass), 257 (a second pass of one quad), 300 (a second pass of 44: G = 5), 1024 (four passes, the
+# cap AZ_SKIP_MAX_SUMC) and three regimes side by side at non-zero offsets
+CHANNEL_SETS = ((4,), (520,), (1024,), (1028,), (1200,), (4096,), (1028, 4, 520))
+# one and two sources, scales that are no power of two on maps of odd width, maps that are not image * scale
+SOURCE_CASES = {
+    "one": dict(Cs=(20,), scales=(0.0625,), hw=((6, 8),)),
+    "two": dict(Cs=(36, 12), scales=(0.125, 0.0625), hw=((12, 16), (6, 8))),
+    "odd": dict(Cs=SMALL_CS, scales=(0.5, 0.3, 1.0 / 32.0), hw=((48, 64), (29, 39), (3, 4))),
+    "tiny": dict(Cs=SMALL_CS, scales=SCALES, hw=((5, 9), (1, 16), (1, 1))),
+}
+
+
+def geometry(Cs):
+    """(scales, map sizes) of a channel set: a single source is conv5_3's 6 x 8 map at 1/16."""
+    return ((SCALES[2],), (MAP_HW[2],)) if len(Cs) == 1 else (SCALES[:len(Cs)], MAP_HW[:len(Cs)])
+
+
+def tie_map(seed, C, h, w, N=1):
+    """[N, C, h, w] f32 of values drawn from {0, 1, 2, 3}, about half of them zeroed: every window holds ties (which fall in
+    different cell groups and, past 1024 channels, in both passes of the pool kernels), and every sum of squares is a whole
+    number."""
+    rng = np.random.Generator(np.random.PCG64(20_000 + seed))
+    return (rng.integers(0, 4, (N, C, h, w)) * (rng.random((N, C, h, w)) < 0.5)).astype(np.float32)
+
+
+def perm_map(seed, C, h, w, N=1):
+    """[N, C, h, w] f32: per image and channel a permutation of 1 .. h * w (no two cells equal)."""
+    rng = np.random.Generator(np.random.PCG64(21_000 + seed))
+    return np.stack([np.stack([rng.permutation(h * w) + 1 for _ in range(C)]) for _ in range(N)]).reshape(N, C, h, w).astype(np.float32)
+
+
+def edge_maps(kind, seed, Cs, hw, N=1):
+    """kind "relu": synth.make_feature_map per source and image (make_maps' and skip_train_ref.make_batch_maps' seeds);
+    "ties": tie_map; "perm": perm_map."""
+    from aznet_hip import synth
+    if kind == "relu":
+        return [np.concatenate([synth.make_feature_map(seed + 17 * i + 101 * n, C, h, w) for n in range(N)], axis=0)
+                for i, (C, (h, w)) in enumerate(zip(Cs, hw))]
+    f = {"ties": tie_map, "perm": perm_map}[kind]
+    return [f(seed + 17 * i, C, h, w, N) for i, (C, (h, w)) in enumerate(zip(Cs, hw))]
+
+
+def channel_rois():
+    """The hostile rois and five ordinary ones."""
+    return np.vstack([hostile_rois(), random_rois(5, seed=31)])
+
+
+def tiny_rois():
+    """Rois for maps of 5 x 9 (1/4), 1 x 16 (1/8) and 1 x 1 (1/16) cells: a roi of one cell at 1/16 at the origin has all 49
+    bins on the 1 x 1 map's only cell; strips along the 1 x 16 map; boxes over the 5 x 9 map."""
+    r = [(0.0, 0.0, 7.0, 7.0), (0.0, 0.0, 35.0, 19.0), (0.0, 0.0, 127.0, 7.0), (-20.0, -12.0, 6.0, 5.0), (4.0, 2.0, 30.0, 16.0),
+         (10.0, 0.0, 90.0, 6.0), (0.0, 0.0, 16.0, 16.0), (2.0, 1.0, 5.0, 3.0)]
+    a = np.zeros((len(r), 5), np.float32)
+    a[:, 1:] = np.asarray(r, np.float32)
+    return a
+
+
+def source_rois(name):
+    """[R, 5] rois (R of 6 to 9) of a SOURCE_CASES entry, image 0."""
+    return tiny_rois() if name == "tiny" else random_rois({"one": 6, "two": 7, "odd": 9}[name], seed=33)
+
+
+def empty_share(arg, Cs):
+    """Per source: (share of empty bins, number of non-empty bins) of an arg-max [R * 49, sum Cs]."""
+    off = np.concatenate([[0], np.cumsum(Cs)]).astype(int)
+    return [(float((arg[:, off[i]] < 0).mean()), int((arg[:, off[i]] >= 0).sum())) for i in range(len(Cs))]
+
+
+# the gather's sweep: one source of C = 4 at scale 1.0 on a 9 x 11 map; every integer range [start, start + width) per axis
+SWEEP = dict(C=4, H=9, W=11, widths=tuple(range(1, 10)) + (13, 14, 15, 20, 29), R=2048)
+
+
+def sweep_rois(x_starts=range(-3, 9), y_starts=range(-3, 7)):
+    """2048 integer rois whose x-ranges are every start with every width of SWEEP, the y-ranges likewise; roi i takes x-range
+    i mod nx and y-range (5 i + i // nx) mod ny, so every x-range and every y-range occurs.  The starts are trimmed from the
+    -3 .. W and -3 .. H of the full sweep, which leaves 62 % of the bins empty; with starts up to W - 1 and H - 1 it is
+    still 57 %, with these under half are.  The trim drops the all-empty ranges that begin past the map and also the x
+    starts 9, 10 and the y starts 7, 8, which lie on it: wider windows from start 8 or 6 still reach the last column and
+    row, clipped, but no window of one or two cells would sit there, so the last eight rois are those, added by hand."""
+    xs = [(s, s + w - 1) for s in x_starts for w in SWEEP["widths"]]
+    ys = [(s, s + w - 1) for s in y_starts for w in SWEEP["widths"]]
+    a = np.zeros((SWEEP["R"], 5), np.float32)
+    for i in range(SWEEP["R"]):
+        x, y = xs[i % len(xs)], ys[(5 * i + i // len(xs)) % len(ys)]
+        a[i, 1:] = (x[0], y[0], x[1], y[1])
+    W, H = SWEEP["W"], SWEEP["H"]
+    a[-8:, 1:] = [(W - 1, H - 1, W - 1, H - 1), (W - 2, H - 2, W - 1, H - 1), (W - 1, 0, W - 1, H - 1), (0, H - 1, W - 1, H - 1),
+                  (W - 2, 3, W - 1, 4), (3, H - 2, 4, H - 1), (W - 1, 2, W - 1, 2), (5, H - 1, 5, H - 1)]
+    return a, xs, ys
+
+
+def source_case(name):
+    """A SOURCE_CASES entry for the inference head: dict(Cs, scales, front, head, maps [1, C, H, W], rois, boxes) at Cout 12,
+    the reduced fc sizes and 21 classes; the boxes are the rois and copies of the first three (the dedup merges them)."""
+    from aznet_hip import synth
+    d = SOURCE_CASES[name]
+    rois = source_rois(name)
+    return dict(Cs=d["Cs"], scales=d["scales"], head=synth.make_det_head(seed=9, C=12, n6=260, n7=516, ncls=21),
+                front=synth.make_skip_front(seed=1, Cs=d["Cs"], Cout=12, scales=d["scales"]), maps=edge_maps("relu", 14, d["Cs"], d["hw"]),
+                rois=rois, boxes=np.vstack([rois[:, 1:], rois[:3, 1:]]).astype(np.float64))

@@ -233,3 +233,132 @@ class RefTrajectory(object):
                              R.clip_scale(r["sumsq"], self.sp["clip_gradients"]), dtype=self.dt)
         self.it += 1
         return r
+
+
+# ---- the edge steps of tests/test_skip_edges_host.py and tests/test_gpu_skip_edges.py ---------------------------------------------
+# Every entry is one step of the trainer at Cout 12, 21 classes.  Defaults: N = 1, the maps of S.MAP_HW at S.SCALES, the fc sizes
+# of SMALL, gain 1000, eps 1e-10.  rois: a name of S.source_rois, else skip_ref's random rois on the 96 x 128 image; images: the
+# image index of every roi; boxes: the rois themselves; zero: all-zero sources; shrink: the rois scaled to a smaller image.
+_SM = dict(Cs=S.SMALL_CS, scales=S.SCALES, hw=S.MAP_HW)
+STEP_CASES = {
+    "mixed": dict(Cs=(1028, 4, 520), scales=S.SCALES, hw=S.MAP_HW, N=2, R=6, n6=8, n7=8),
+    "one": dict(S.SOURCE_CASES["one"], rois="one"),
+    "two": dict(S.SOURCE_CASES["two"], rois="two"),
+    "odd": dict(S.SOURCE_CASES["odd"], rois="odd"),
+    "tiny": dict(S.SOURCE_CASES["tiny"], rois="tiny"),
+    "image_without_rois": dict(_SM, N=3, R=9, images=(0, 0, 0, 0, 2, 2, 2, 2, 2)),
+    "r1": dict(_SM, N=2, R=1, images=(1,), boxes=((20.0, 12.0, 100.0, 80.0),)),
+    "rmax": dict(_SM, N=2, R=20),
+    "shrunk": dict(_SM, hw=((12, 10), (6, 5), (3, 3)), N=2, R=3, shrink=0.3),
+    "gain0": dict(_SM, N=2, R=8, gain=0.0),
+    "gain_negative": dict(_SM, N=2, R=8, gain=-2.5),
+    "eps0_zero_source": dict(_SM, N=2, R=8, eps=0.0, zero=(1,)),
+    "gain1_eps1": dict(_SM, N=2, R=8, gain=1.0, eps=1.0),
+}
+# the seeds tried, in order, for a step none of whose float64 pre-activations (pre_pool, pre6, pre7) lies within twice the
+# forward bound of zero -- the device's ReLU gates are then float64's, exactly -- and the first that meets it, per case, as
+# tests/test_skip_edges_host.py finds it
+SEED_TRIALS = (7, 8, 9, 10, 11, 12, 13, 14)
+STEP_SEEDS = {name: 7 for name in STEP_CASES}
+
+
+def edge_step(name, seed):
+    """(head, front, maps, blobs, scales) of STEP_CASES[name]: the weights, labels, targets and random rois from `seed`, the
+    maps from the case alone."""
+    d = STEP_CASES[name]
+    Cs, N, ncls = d["Cs"], d.get("N", 1), 21
+    maps = S.edge_maps("relu", 7, Cs, d["hw"], N)
+    for i in d.get("zero", ()):
+        maps[i][:] = 0.0
+    rois = S.source_rois(d["rois"]) if "rois" in d else None
+    Rn = d["R"] if rois is None else rois.shape[0]
+    blobs = make_blobs(seed, Rn, N, ncls)
+    if rois is not None:
+        blobs["rois"] = rois
+    else:
+        blobs["rois"][:, 1:] = S.random_rois(Rn, seed=seed)[:, 1:] * np.float32(d.get("shrink", 1.0))
+    if "boxes" in d:
+        blobs["rois"][:, 1:] = np.asarray(d["boxes"], np.float32)
+    if "images" in d:
+        blobs["rois"][:, 0] = d["images"]
+    head = D.filler_head(seed, 12, d.get("n6", SMALL["n6"]), d.get("n7", SMALL["n7"]), ncls)
+    gain = d.get("gain", 1000.0)
+    front = make_front(seed + 2, Cs, 12, gain=abs(gain) if gain else 1000.0, eps=d.get("eps", 1e-10))
+    front["gain"] = float(gain)
+    return head, front, maps, blobs, tuple(d["scales"])
+
+
+def gate_margins(r64, r32):
+    """[(name, smallest |pre-activation_64|, twice the forward bound in its units)] of relu_pool, fc6 and fc7."""
+    out = []
+    for key in ("pre_pool", "pre6", "pre7"):
+        pre = np.asarray(r64[key], np.float64)
+        out.append((key, float(np.abs(pre).min()), 2.0 * bound(rel_err(r32[key], pre)) * float(np.abs(pre).max())))
+    return out
+
+
+_EDGE_REFS = {}
+
+
+def edge_reference(name, seed):
+    """The step at `seed` (dropout seed `seed`, iteration 0) in float64 with its own gates and in float32 under those gates,
+    computed once: dict(head, front, maps, blobs, scales, masks, pooled, r64, r32, margins).  Nothing in it may be changed."""
+    if (name, seed) not in _EDGE_REFS:
+        head, front, maps, blobs, scales = edge_step(name, seed)
+        pooled = pool_argmax(maps, blobs["rois"], scales)
+        masks = D.step_masks(seed, 0, blobs["rois"].shape[0], head)
+        r64 = step(head, front, maps, blobs, masks, scales=scales, pooled=pooled)
+        r32 = step(head, front, maps, blobs, masks, gates=r64["gates"], dtype=np.float32, scales=scales, pooled=pooled)
+        _EDGE_REFS[(name, seed)] = dict(head=head, front=front, maps=maps, blobs=blobs, scales=scales, masks=masks, pooled=pooled,
+                                        r64=r64, r32=r32, margins=gate_margins(r64, r32))
+    return _EDGE_REFS[(name, seed)]
+
+
+def find_seed(name):
+    """The first of SEED_TRIALS whose step keeps every pre-activation outside twice the forward bound of zero (None: none)."""
+    for seed in SEED_TRIALS:
+        if all(lo > two_fwd for _, lo, two_fwd in edge_reference(name, seed)["margins"]):
+            return seed
+    return None
+
+
+_CHANNEL_REFS = {}
+
+
+def channel_reference(Cs, kind):
+    """A CHANNEL_SETS entry on "relu" maps (eps 1e-10) or "ties" maps (eps 0; every sum of squares a whole number), N = 1, the
+    rois of S.channel_rois: dict(maps, scales, rois, front, raw, arg, f64, cat32) with f64 = front_forward in float64 and
+    cat32 its float32 `cat`.  Computed once; nothing in it may be changed."""
+    if (Cs, kind) not in _CHANNEL_REFS:
+        scales, hw = S.geometry(Cs)
+        maps, rois = S.edge_maps(kind, 11, Cs, hw), S.channel_rois()
+        front = make_front(4, Cs, 12, eps=0.0 if kind == "ties" else 1e-10)
+        raw, arg = pool_argmax(maps, rois, scales)
+        _CHANNEL_REFS[(Cs, kind)] = dict(maps=maps, scales=scales, rois=rois, front=front, raw=raw, arg=arg,
+                                         f64=front_forward(front, raw, Cs), cat32=front_forward(front, raw, Cs, np.float32)["cat"])
+    return _CHANNEL_REFS[(Cs, kind)]
+
+
+_GATHER_REFS = {}
+
+
+def gather_reference(tag):
+    """Inputs and exact answers of the gather on whole-number gradients in [-8, 8] (every sum exact in any order):
+    "sweep_ties" / "sweep_perm": S.sweep_rois on one 9 x 11 map of 4 channels at scale 1.0, tie-heavy or all-distinct;
+    "all_in_last" / "descending": the maps and rois of STEP_CASES["image_without_rois"] with every roi in image 2, or the
+    rois in descending image order.  dict(maps, scales, rois, raw, arg, d_raw, want); computed once, not to be changed."""
+    if tag not in _GATHER_REFS:
+        if tag.startswith("sweep"):
+            w = S.SWEEP
+            maps, scales = S.edge_maps(tag[6:], 5, (w["C"],), ((w["H"], w["W"]),)), (1.0,)
+            rois = S.sweep_rois()[0]
+        else:
+            _, _, maps, blobs, scales = edge_step("image_without_rois", 7)
+            rois = blobs["rois"].copy()
+            rois[:, 0] = 2 if tag == "all_in_last" else (2, 2, 2, 1, 1, 1, 0, 0, 0)
+        Cs = tuple(int(m.shape[1]) for m in maps)
+        raw, arg = pool_argmax(maps, rois, scales)
+        d_raw = np.random.Generator(np.random.PCG64(8)).integers(-8, 9, raw.shape).astype(np.float32)
+        _GATHER_REFS[tag] = dict(maps=maps, scales=scales, rois=rois, raw=raw, arg=arg, d_raw=d_raw,
+                                 want=scatter(d_raw, arg, Cs, rois, [m.shape for m in maps]))
+    return _GATHER_REFS[tag]
