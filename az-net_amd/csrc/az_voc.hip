@@ -506,3 +506,49 @@ int az_voc_eval(az_ctx *c, int n_classes, int n_images, const double *det_box, c
     HIPCHK(c, hipStreamSynchronize(s));
     return AZ_OK;
 }
+
+// rank_by_score alone on host arrays, for tests: both permutations of the D detections
+int az_rank_unit(az_ctx *c, int n_classes, int n_images, const double *score, const int32_t *det_off,
+                 uint32_t *by_seg_out, uint32_t *by_class_out)
+{
+    if (!c || n_classes < 0 || n_images < 0 || !det_off) return fail(c, AZ_ERR_INVALID, "az_rank_unit: bad arguments");
+    const long long S = (long long)n_classes * n_images;
+    if (S >= 0x7fffffffLL)
+        return fail(c, AZ_ERR_CAPACITY, "az_rank_unit: more segments than int32 offsets address");
+    if (det_off[0] != 0) return fail(c, AZ_ERR_INVALID, "az_rank_unit: offsets must start at 0");
+    for (long long s = 0; s < S; ++s)
+        if (det_off[s + 1] < det_off[s]) return fail(c, AZ_ERR_INVALID, "az_rank_unit: offsets must ascend");
+    const int D = det_off[S];
+    if (D == 0) return AZ_OK;
+    if (!score || !by_seg_out || !by_class_out) return fail(c, AZ_ERR_INVALID, "az_rank_unit: NULL array");
+    size_t hist_n = 0, sums_n = 0;
+    rank_scratch_sizes(D, &hist_n, &sums_n);
+    if (hist_n >= 0x7fffffffULL) return fail(c, AZ_ERR_CAPACITY, "az_rank_unit: too many detections");
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += align_up(bytes); return o; };
+    const size_t o_score = take((size_t)D * sizeof(double)), o_doff = take(((size_t)S + 1) * sizeof(int));
+    const size_t o_key = take((size_t)D * 8), o_seg = take((size_t)D * 4);
+    size_t o_perm[4];
+    for (auto &o : o_perm) o = take((size_t)D * 4);
+    const size_t o_hist = take(hist_n * 4), o_sums = take(sums_n * 4);
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = ev_grow(c, 8, &c->ev_voc, off)) != AZ_OK) return rc;
+    char *A = (char *)c->ev_voc;
+    hipStream_t s = c->stream;
+    auto *dscore = (double *)(A + o_score);
+    auto *doff = (int *)(A + o_doff);
+    HIPCHK(c, hipMemcpyAsync(dscore, score, (size_t)D * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(doff, det_off, ((size_t)S + 1) * sizeof(int), hipMemcpyHostToDevice, s));
+    RankScratch rs{(unsigned long long *)(A + o_key), (unsigned *)(A + o_seg),
+                   {(unsigned *)(A + o_perm[0]), (unsigned *)(A + o_perm[1]), (unsigned *)(A + o_perm[2]),
+                    (unsigned *)(A + o_perm[3])},
+                   (unsigned *)(A + o_hist), (unsigned *)(A + o_sums)};
+    const unsigned *pseg = nullptr, *pcls = nullptr;
+    rank_by_score(s, D, S, n_images, n_classes, (const double *)dscore, (const int *)doff, rs, &pseg, &pcls);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(by_seg_out, pseg, (size_t)D * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(by_class_out, pcls, (size_t)D * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    return AZ_OK;
+}

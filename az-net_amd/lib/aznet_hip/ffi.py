@@ -41,7 +41,7 @@ SYMBOLS = [
     "az_rccl_unique_id", "az_rccl_init", "az_gather_records", "az_rccl_destroy", "az_comm_stream",
     "az_bias_relu", "az_bias_relu_pool", "az_batch_launch", "az_batch_fetch", "az_batch_next_stream",
     "az_batch_stage_results_dev", "az_batch_fetch_all", "az_batch_launch_shapes", "az_abi_sizes",
-    "az_detect_batch", "az_voc_eval", "az_coco_eval", "az_diag_eval",
+    "az_detect_batch", "az_voc_eval", "az_rank_unit", "az_coco_eval", "az_diag_eval",
     "az_set_feature_pyramid_dev_nhwc", "az_roi_dedup_pyramid", "az_roi_pool_pyramid", "az_propose_pyramid",
     "az_detect_pyramid",
     "az_load_skip_front", "az_set_skip_maps_dev_nhwc", "az_detect_skip", "az_det_forward_skip", "az_skip_pool",
@@ -230,6 +230,7 @@ def load_library(path=None):
     L.az_recall_match.argtypes = [vp, ci, dp, ip, dp, ip, dp]
     L.az_voc_eval.argtypes = [vp, ci, ci, dp, dp, ip, dp, u8p, ip, cd, ci, ctypes.POINTER(ctypes.c_int8), dp, dp,
                               ctypes.POINTER(ctypes.c_int64), dp, dp]
+    L.az_rank_unit.argtypes = [vp, ci, ci, dp, ip, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
     L.az_coco_eval.argtypes = [vp, ci, ci, dp, dp, ip, dp, dp, u8p, ip, dp, dp, dp, ip, ctypes.POINTER(ctypes.c_int8)]
     tpp = ctypes.POINTER(AzTrainParams)
     L.az_diag_eval.argtypes = [vp, ci, dp, fp, ip, ip, ctypes.c_longlong, dp, ip, ctypes.c_longlong, dp, ip,
@@ -1308,6 +1309,17 @@ class AzContext(object):
                                      1 if metric_07 else 0, mp, rp, pp, _p(out["npos"], ctypes.c_int64),
                                      _p(out["ap"], ctypes.c_double), _p(out["ap_auc"], ctypes.c_double)))
         return out
+
+    def rank_unit(self, n_classes, n_images, score, det_off):
+        """az_rank_unit (tests): the evaluations' shared ranking alone -> (by_seg, by_class), uint32 [D] each."""
+        sc = _f64(score).ravel()
+        doff = np.ascontiguousarray(det_off, dtype=np.int32).ravel()
+        if doff.size != int(n_classes) * int(n_images) + 1 or sc.size != int(doff[-1]):
+            raise AzError(AZ_ERR_INVALID, "rank_unit: array sizes disagree with the offsets")
+        by_seg, by_class = np.zeros(sc.size, np.uint32), np.zeros(sc.size, np.uint32)
+        self._chk(self.L.az_rank_unit(self.h, int(n_classes), int(n_images), _p(sc, ctypes.c_double), _p(doff, ctypes.c_int32),
+                                      _p(by_seg, ctypes.c_uint32), _p(by_class, ctypes.c_uint32)))
+        return by_seg, by_class
 
     def coco_eval(self, n_classes, n_images, det_box, det_score, det_off, gt_box, gt_area, gt_crowd, gt_off,
                   want_matches=False):

@@ -486,6 +486,12 @@ int az_voc_eval(az_ctx *ctx, int n_classes, int n_images,
                 double min_overlap, int metric_07,
                 int8_t *match_out, double *rec_out, double *prec_out,
                 int64_t *npos_out, double *ap_out, double *ap_auc_out);
+/* Unit entry (tests): the ranking that az_voc_eval and az_coco_eval share, alone, on host arrays.  For the D = det_off[S]
+ * scores of n_classes x n_images class-major segments: by_seg_out [D] lists the detections segment by segment, by_class_out
+ * [D] class by class, each group by (-score, input order) with NaN last and -0 equal to +0.  Offsets are validated as
+ * az_voc_eval validates them (same codes); D = 0 returns AZ_OK and touches nothing. */
+int az_rank_unit(az_ctx *ctx, int n_classes, int n_images, const double *score, const int32_t *det_off,
+                 uint32_t *by_seg_out, uint32_t *by_class_out);
 
 /* ---- detection evaluation (imdb.evaluate_detections, lib/datasets/coco.py:_do_coco_eval) ----------- */
 /* What the reference hands to pycocotools: COCOeval's evaluate + accumulate + summarize with iouType 'bbox' (the
