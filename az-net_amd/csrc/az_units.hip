@@ -190,18 +190,19 @@ int az_decode_filter(az_ctx *c, const double *anchors, const float *deltas, cons
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     HIPCHK(c, hipMemsetAsync(c->cnt, 0, sizeof(AzCounts), s));
-    // stage: anchors -> ubox, deltas -> delta_u, scores -> Sout (scratch); inv = identity
+    // stage: anchors -> ubox, deltas -> delta_u, scores -> score_s (scratch of R * 11 floats: Sout holds max_candidates,
+    // which may be fewer); inv = identity
     std::vector<int> ident(R);
     for (int i = 0; i < R; ++i) ident[i] = i;
     if (R) {
         HIPCHK(c, hipMemcpyAsync(c->ubox, anchors, (size_t)R * 4 * sizeof(double), hipMemcpyHostToDevice, s));
         HIPCHK(c, hipMemcpyAsync(c->delta_u, deltas, (size_t)R * 4 * AZ_NSUB * 4, hipMemcpyHostToDevice, s));
-        HIPCHK(c, hipMemcpyAsync(c->Sout, scores, (size_t)R * AZ_NSUB * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(c->score_s, scores, (size_t)R * AZ_NSUB * 4, hipMemcpyHostToDevice, s));
         HIPCHK(c, hipMemcpyAsync(c->inv, ident.data(), (size_t)R * 4, hipMemcpyHostToDevice, s));
     }
     if ((rc = set_count(c, &c->cnt->P[0], R)) != AZ_OK) return rc;
     HIPCHK(c, hipMemsetAsync(c->zoom_u, 0, (size_t)(R > 0 ? R : 1) * 4, s));
-    azk_decode_unit(s, c->ubox, c->delta_u, c->Sout, R, im_h, im_w, eps, c->pred_u, c->score_u);
+    azk_decode_unit(s, c->ubox, c->delta_u, c->score_s, R, im_h, im_w, eps, c->pred_u, c->score_u);
     azk_flags_compact(s, c->cnt, 0, c->maxR, c->maxCand, c->ubox, c->inv, c->pred_u, c->score_u, c->zoom_u, 2.0,
                       min_side, 0, c->cflag, c->zflag, c->bc_c, c->bc_z, c->Yall, c->Sall, c->Z, c->zr);
     HIPCHK(c, hipMemcpyAsync(c->h_cnt, c->cnt, sizeof(AzCounts), hipMemcpyDeviceToHost, s));
@@ -211,28 +212,43 @@ int az_decode_filter(az_ctx *c, const double *anchors, const float *deltas, cons
     if (n > cap) return fail(c, AZ_ERR_CAPACITY, "az_decode_filter: output cap too small");
     if (n && boxes_out) HIPCHK(c, hipMemcpy(boxes_out, c->Yall, (size_t)n * 4 * sizeof(double), hipMemcpyDeviceToHost));
     if (n && scores_out) HIPCHK(c, hipMemcpy(scores_out, c->Sall, (size_t)n * 4, hipMemcpyDeviceToHost));
+    // more kept candidates than the context holds: k_compact clamped the count (n == max_candidates, the first n kept
+    // candidates are out) and raised the flag the search reports as AZ_ERR_CAPACITY -- so does the unit
+    if (c->h_cnt->err & 2) return fail(c, AZ_ERR_CAPACITY, "az_decode_filter: candidate capacity exceeded (raise az_set_limits)");
     return AZ_OK;
 }
 
-int az_topk(az_ctx *c, const float *scores, int n, int k, int32_t *idx_out, int *n_out)
+// az_topk and az_topk_radix: `radix` keeps the chip-wide counting kernels out (no rank scratch), so the single-workgroup
+// radix select takes every n.
+static int topk_unit(az_ctx *c, const float *scores, int n, int k, int32_t *idx_out, int *n_out, bool radix, const char *who)
 {
     int rc = check_geom(c);
     if (rc) return rc;
-    if (n < 0 || (n && !scores) || k <= 0 || !idx_out || !n_out) return fail(c, AZ_ERR_INVALID, "az_topk: bad arguments");
-    if (n > c->maxCand || k > AZ_TOPK_MAX) return fail(c, AZ_ERR_CAPACITY, "az_topk: n or k too large");
+    if (n < 0 || (n && !scores) || k <= 0 || !idx_out || !n_out) return fail(c, AZ_ERR_INVALID, std::string(who) + ": bad arguments");
+    if (n > c->maxCand || k > AZ_TOPK_MAX) return fail(c, AZ_ERR_CAPACITY, std::string(who) + ": n or k too large");
     c->cand_n = -1;                              // Sall is reused below
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     HIPCHK(c, hipMemsetAsync(c->cnt, 0, sizeof(AzCounts), s));
     if (n) HIPCHK(c, hipMemcpyAsync(c->Sall, scores, (size_t)n * 4, hipMemcpyHostToDevice, s));
     if ((rc = set_count(c, &c->cnt->scratch[0], n)) != AZ_OK) return rc;
-    azk_topk(s, c->Sall, &c->cnt->scratch[0], c->maxCand, k, c->sel_idx, &c->cnt->nsel, c->rank_part);
+    azk_topk(s, c->Sall, &c->cnt->scratch[0], c->maxCand, k, c->sel_idx, &c->cnt->nsel, radix ? nullptr : c->rank_part);
     HIPCHK(c, hipMemcpyAsync(c->h_cnt, c->cnt, sizeof(AzCounts), hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     const int m = c->h_cnt->nsel;
     *n_out = m;
     if (m) HIPCHK(c, hipMemcpy(idx_out, c->sel_idx, (size_t)m * 4, hipMemcpyDeviceToHost));
     return AZ_OK;
+}
+
+int az_topk(az_ctx *c, const float *scores, int n, int k, int32_t *idx_out, int *n_out)
+{
+    return topk_unit(c, scores, n, k, idx_out, n_out, false, "az_topk");
+}
+
+int az_topk_radix(az_ctx *c, const float *scores, int n, int k, int32_t *idx_out, int *n_out)
+{
+    return topk_unit(c, scores, n, k, idx_out, n_out, true, "az_topk_radix");
 }
 
 int az_nms(az_ctx *c, const float *dets, int n, double thresh, int64_t *keep, int *n_keep)

@@ -30,7 +30,7 @@ SYMBOLS = [
     "az_version", "az_create", "az_destroy", "az_last_error", "az_set_limits", "az_load_head",
     "az_set_feature_map_dev", "az_set_feature_map_host", "az_propose", "az_propose_launch",
     "az_propose_fetch", "az_last_candidates", "az_divide_region", "az_sift_dup", "az_roi_dedup",
-    "az_roi_pool", "az_head_forward", "az_decode_filter", "az_topk", "az_nms", "az_set_profiling",
+    "az_roi_pool", "az_head_forward", "az_decode_filter", "az_topk", "az_topk_radix", "az_nms", "az_set_profiling",
     "az_last_kernel_times", "az_stream", "az_load_det_head", "az_det_forward", "az_detect",
     "az_set_gemm_mode", "az_last_anchors", "az_tune_begin", "az_tune_end", "az_tune_kth_largest",
     "az_tune_top", "az_tune_push", "az_bbox_overlaps", "az_recall_match", "az_image_blob_size",
@@ -175,6 +175,7 @@ def load_library(path=None):
     L.az_head_forward.argtypes = [vp, fp, ci, fp, fp, fp]
     L.az_decode_filter.argtypes = [vp, dp, fp, fp, ci, ci, ci, cd, cd, dp, fp, ci, cip]
     L.az_topk.argtypes = [vp, fp, ci, ci, ip, cip]
+    L.az_topk_radix.argtypes = [vp, fp, ci, ci, ip, cip]
     L.az_nms.argtypes = [vp, fp, ci, cd, i64p, cip]
     L.az_nms_batched.argtypes = [vp, fp, ip, ci, cd, i64p, ip]
     L.az_load_det_head.argtypes = [vp, ci, ci, ci, ci] + [fp] * 8
@@ -846,13 +847,17 @@ class AzContext(object):
                                           cap, ctypes.byref(n)))
         return ob[:n.value].copy(), os_[:n.value].copy()
 
-    def topk(self, scores, k):
+    def topk(self, scores, k, radix=False):
+        """radix=True: az_topk_radix, the single-workgroup radix select at every size (same result, for tests)."""
         scores = _f32(scores).ravel()
         idx = np.empty((max(1, min(k, scores.shape[0])),), dtype=np.int32)
         n = ctypes.c_int(0)
-        self._chk(self.L.az_topk(self.h, _p(scores, ctypes.c_float), scores.shape[0], int(k),
-                                 _p(idx, ctypes.c_int32), ctypes.byref(n)))
+        fn = self.L.az_topk_radix if radix else self.L.az_topk
+        self._chk(fn(self.h, _p(scores, ctypes.c_float), scores.shape[0], int(k), _p(idx, ctypes.c_int32), ctypes.byref(n)))
         return idx[:n.value].copy()
+
+    def topk_radix(self, scores, k):
+        return self.topk(scores, k, radix=True)
 
     def nms(self, dets, thresh):
         dets = _f32(dets).reshape(-1, 5)

@@ -316,13 +316,17 @@ int az_head_forward(az_ctx *ctx, const float *rois, int R, float *zoom_prob, flo
                     float *adj_bbox);
 /* _bbox_pred + _clip_boxes + _unwrap_adj_pred (lib/detect/test.py:106-151,171-187) for R
  * regions: anchors [R,4] f64, deltas [R,44] f32, scores [R,11] f32 -> kept boxes/scores in
- * r*11+s order. */
+ * r*11+s order.  More kept candidates than the context's max_candidates: AZ_ERR_CAPACITY, with
+ * *n_out = max_candidates and the first max_candidates kept candidates written (cap permitting). */
 int az_decode_filter(az_ctx *ctx, const double *anchors, const float *deltas, const float *scores,
                      int R, int im_h, int im_w, double eps, double min_side,
                      double *boxes_out, float *scores_out, int cap, int *n_out);
 /* Final selection of lib/detect/test.py:393-401: indices of the top-k scores, descending
  * (ties: lower index first). */
 int az_topk(az_ctx *ctx, const float *scores, int n, int k, int32_t *idx_out, int *n_out);
+/* az_topk by the single-workgroup radix select at every n (az_topk hands n <= 65536 to the chip-wide counting
+ * kernels): same arguments, same result. */
+int az_topk_radix(az_ctx *ctx, const float *scores, int n, int k, int32_t *idx_out, int *n_out);
 /* utils.cython_nms.nms(dets f32[N,5], thresh) (lib/utils/nms.pyx:17-68): kept original
  * indices in descending-score order.  The reference's call site is apply_nms
  * (lib/detect/test.py:467-484); it is NOT on the proposal path. */
