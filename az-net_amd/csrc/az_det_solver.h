@@ -28,6 +28,7 @@ struct az_det_solver {
     size_t part_elems = 0;
     std::vector<void *> allocs;
     int R = 0, N = 0, H = 0, W = 0, trained = 0, has_prob = 0;
+    int prec = AZ_TRAIN_FP32;                                   // operands of every matrix product (az_det_solver_set_precision)
     // the skip front (az_det_solver_attach_skip): rows (roi, bin) x sumC channels
     struct Skip {
         bool attached = false;

@@ -337,6 +337,15 @@ int az_det_solver_step(az_det_solver *s, const float *conv_dev, int N, int H, in
     return AZ_OK;
 }
 
+int az_det_solver_set_precision(az_det_solver *s, int precision)
+{
+    if (!s) return AZ_ERR_INVALID;
+    if (precision != AZ_TRAIN_FP32 && precision != AZ_TRAIN_BF16)
+        return fail(s->c, AZ_ERR_INVALID, "az_det_solver_set_precision: AZ_TRAIN_FP32 or AZ_TRAIN_BF16");
+    s->prec = precision;
+    return AZ_OK;
+}
+
 int az_det_solver_update(az_det_solver *s, double rate, double momentum, double weight_decay, double clip_scale)
 {
     if (!s) return AZ_ERR_INVALID;

@@ -286,7 +286,7 @@ int skip_forward(az_det_solver *s, const TrainSrcs &a, const float *rois, int R,
     int S, Kc;
     pick_split(rows, Cout, k.sumC, &S, &Kc);
     const long long slab = (long long)rows * Cout;
-    { Timed t(c, "conv_pool5_fwd", 0, 1); launch_gemm(st, 0, k.cat, s->w[D_WP], s->part, slab, rows, Cout, k.sumC, S, Kc, 0); }
+    { Timed t(c, "conv_pool5_fwd", 0, 1); launch_gemm(st, 0, k.cat, s->w[D_WP], s->part, slab, rows, Cout, k.sumC, S, Kc, 0, s->prec); }
     { Timed t(c, "conv_pool5_finish", 0);
       hipLaunchKernelGGL(k_skip_finish_t, dim3(grid_for(slab)), dim3(256), 0, st, s->part, S, slab, s->w[D_BP], slab, Cout, s->pool5); }
     det_head_forward(s, R, train, seed, iter);

@@ -33,6 +33,7 @@ struct az_solver {
     std::vector<void *> allocs;
     // shape of the last step (what the debug fetch sizes its answers by)
     int R = 0, N = 0, H = 0, W = 0, trained = 0;
+    int prec = AZ_TRAIN_FP32;                                   // operands of every matrix product (az_solver_set_precision)
 };
 
 namespace {
@@ -348,9 +349,25 @@ int az_solver_fetch(az_solver *s, const char *name, void *out, long long cap_byt
     return AZ_OK;
 }
 
+int az_solver_set_precision(az_solver *s, int precision)
+{
+    if (!s) return AZ_ERR_INVALID;
+    if (precision != AZ_TRAIN_FP32 && precision != AZ_TRAIN_BF16)
+        return fail(s->c, AZ_ERR_INVALID, "az_solver_set_precision: AZ_TRAIN_FP32 or AZ_TRAIN_BF16");
+    s->prec = precision;
+    return AZ_OK;
+}
+
 int az_solver_gemm_unit(az_ctx *c, int form, const float *a, const float *b, float *d, int M, int N, int K)
 {
+    return az_solver_gemm_unit_prec(c, form, AZ_TRAIN_FP32, a, b, d, M, N, K);
+}
+
+int az_solver_gemm_unit_prec(az_ctx *c, int form, int precision, const float *a, const float *b, float *d, int M, int N, int K)
+{
     if (!c) return AZ_ERR_INVALID;
+    if (precision != AZ_TRAIN_FP32 && precision != AZ_TRAIN_BF16)
+        return fail(c, AZ_ERR_INVALID, "az_solver_gemm_unit_prec: AZ_TRAIN_FP32 or AZ_TRAIN_BF16");
     if (!a || !b || !d || form < 0 || form > 2 || M < 1 || N < 1 || K < 1 || (long long)M * N > (1LL << 28) || (long long)M * K > (1LL << 28) || (long long)N * K > (1LL << 28))
         return fail(c, AZ_ERR_INVALID, "az_solver_gemm_unit: bad form, shape or pointer");
     HIPCHK(c, hipSetDevice(c->device));
@@ -365,7 +382,7 @@ int az_solver_gemm_unit(az_ctx *c, int form, const float *a, const float *b, flo
     if (e == hipSuccess) e = hipMemcpyAsync(da, a, (size_t)M * K * 4, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(db, b, (size_t)N * K * 4, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
-        launch_gemm(c->stream, form, da, db, dp, (long long)slab, M, N, K, S, Kc, 0);
+        launch_gemm(c->stream, form, da, db, dp, (long long)slab, M, N, K, S, Kc, 0, precision);
         hipLaunchKernelGGL(k_solver_finish, dim3(grid_for((long long)slab)), dim3(256), 0, c->stream, dp, S, (long long)slab, (const float *)nullptr,
                            (long long)slab, N, 0, dd, (float *)nullptr, 0, (unsigned char *)nullptr, 0ull, 0u, 1.0f);
         e = hipMemcpyAsync(d, dd, slab * 4, hipMemcpyDeviceToHost, c->stream);

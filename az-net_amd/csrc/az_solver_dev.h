@@ -1,8 +1,8 @@
 // az_solver_dev.h -- the kernels and launch helpers that the two trainers share (az_solver.hip: AZ-net; az_det_solver.hip:
 // the detection net): the counter-based generator, RoIPool with arg-max and its gather backward, the bounds-checked fp32 MFMA
-// GEMM in its three operand orders, split-K slabs summed in slab order, bias / ReLU / dropout, column sums, SmoothL1, the
-// two-level gradient norm and the SGD update.  Everything sits in an anonymous namespace: each translation unit gets its own
-// copy.  fc_forward / gemm_any serve any trainer struct with the members c (az_ctx *), w[] and part.
+// GEMM in its three operand orders and its bf16-operand twin, split-K slabs summed in slab order, bias / ReLU / dropout,
+// column sums, SmoothL1, the two-level gradient norm and the SGD update.  Everything sits in an anonymous namespace: each translation unit gets its own
+// copy.  fc_forward / gemm_any serve any trainer struct with the members c (az_ctx *), w[], part and prec (AZ_TRAIN_*).
 #pragma once
 #include "az_ctx.h"
 
@@ -204,6 +204,128 @@ __global__ void __launch_bounds__(256) k_solver_gemm(const float *__restrict__ A
         }
 }
 
+// ---- the same GEMM with bf16 operands (AZ_TRAIN_BF16) -------------------------------------------------------------------------
+// Same arguments, forms, slabs, bounds checks and epilogue as k_solver_gemm.  The operands stay fp32 in HBM; each element is
+// rounded to bf16 (round to nearest even: v_cvt_pk_bf16_f32) on its way into LDS, and the products are summed in fp32 by
+// v_mfma_f32_32x32x16_bf16 (same C/D layout as the fp32 instruction; lane l holds A[i = l & 31][k = 8 (l >> 5) + j], j < 8).
+// LDS image: sP[i][k], k contiguous, rows of 32 k (64 B) padded to 80 B: the 16 lanes that one ds_read_b128 serves together
+// (rows {0-3, 12-15, 20-27} or {4-11, 16-19, 28-31} of one k half) then fall on 16 different 16-byte slots of the 256-byte
+// bank row (5 r mod 16 is a bijection on either set), and a fragment is one 16-byte read.  The next stage's 32 elements per
+// thread are loaded into registers before the current one is consumed.  Slabs and the stages inside them are consumed in
+// ascending k; the order of the 16 products inside one instruction is the instruction's own.
+constexpr int BLD = GK + 8;                     // row stride of the bf16 image, in elements (80 B)
+typedef __bf16 az_bf16x8 __attribute__((ext_vector_type(8)));
+
+// KC (k contiguous in memory): thread -> (row tid >> 2 [+ 64], k = 8 (tid & 3) ..+7); else (i contiguous): thread ->
+// (row tid & 127, k = 16 (tid >> 7) ..+15).  Either way a thread holds two runs of 8 consecutive k: v[0..7], v[8..15].
+template <bool KC>
+__device__ __forceinline__ void bf16_stage_load(const float *__restrict__ P, long long li, long long lk, int i0, int nI, int k0,
+                                                int kend, int tid, float (&v)[16])
+{
+    if (KC) {
+        const int kc = 8 * (tid & 3);
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int i = (tid >> 2) + 64 * q;
+            const float *p = P + (long long)(i0 + i) * li + (long long)(k0 + kc) * lk;
+            if (i0 + i < nI && k0 + kc + 8 <= kend && lk == 1 && (((unsigned long long)p) & 15ull) == 0) {
+                const float4 x = *(const float4 *)p, y = *(const float4 *)(p + 4);
+                v[8 * q + 0] = x.x; v[8 * q + 1] = x.y; v[8 * q + 2] = x.z; v[8 * q + 3] = x.w;
+                v[8 * q + 4] = y.x; v[8 * q + 5] = y.y; v[8 * q + 6] = y.z; v[8 * q + 7] = y.w;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const bool ok = (i0 + i < nI) && (k0 + kc + j < kend);
+                    v[8 * q + j] = ok ? p[(long long)j * lk] : 0.0f;
+                }
+            }
+        }
+    } else {
+        const int i = tid & 127, kb = 16 * (tid >> 7);
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const bool ok = (i0 + i < nI) && (k0 + kb + j < kend);
+            v[j] = ok ? P[(long long)(i0 + i) * li + (long long)(k0 + kb + j) * lk] : 0.0f;
+        }
+    }
+}
+
+template <bool KC>
+__device__ __forceinline__ void bf16_stage_store(const float (&v)[16], __bf16 *__restrict__ sP, int tid)
+{
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        az_bf16x8 f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) f[j] = (__bf16)v[8 * q + j];
+        const int at = KC ? ((tid >> 2) + 64 * q) * BLD + 8 * (tid & 3) : (tid & 127) * BLD + 16 * (tid >> 7) + 8 * q;
+        *(az_bf16x8 *)(sP + at) = f;
+    }
+}
+
+template <bool AK, bool BK>
+__global__ void __launch_bounds__(256) k_solver_gemm_bf16(const float *__restrict__ A, long long lai, long long lak,
+                                                          const float *__restrict__ B, long long lbj, long long lbk,
+                                                          float *__restrict__ D, long long ldd, long long slab, int M, int N,
+                                                          int K, int Kc, int accumulate)
+{
+    __shared__ __attribute__((aligned(16))) __bf16 sA[GT * BLD];
+    __shared__ __attribute__((aligned(16))) __bf16 sB[GT * BLD];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int j0 = blockIdx.x * GT, i0 = blockIdx.y * GT;
+    const int kbeg = blockIdx.z * Kc, kend = min(K, kbeg + Kc);
+    const int wi = (wave >> 1) * 64, wj = (wave & 1) * 64;
+    az_f32x16 acc[2][2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int v = 0; v < 16; ++v) acc[a][b][v] = 0.0f;
+    const int lr = lane & 31, lk = lane >> 5;
+    float va[16], vb[16];
+    if (kbeg < kend) {
+        bf16_stage_load<AK>(A, lai, lak, i0, M, kbeg, kend, tid, va);
+        bf16_stage_load<BK>(B, lbj, lbk, j0, N, kbeg, kend, tid, vb);
+    }
+    for (int k0 = kbeg; k0 < kend; k0 += GK) {
+        __syncthreads();
+        bf16_stage_store<AK>(va, sA, tid);
+        bf16_stage_store<BK>(vb, sB, tid);
+        __syncthreads();
+        if (k0 + GK < kend) {
+            bf16_stage_load<AK>(A, lai, lak, i0, M, k0 + GK, kend, tid, va);
+            bf16_stage_load<BK>(B, lbj, lbk, j0, N, k0 + GK, kend, tid, vb);
+        }
+#pragma unroll
+        for (int kk = 0; kk < GK; kk += 16) {
+            const az_bf16x8 a0 = *(const az_bf16x8 *)(sA + (wi + lr) * BLD + kk + 8 * lk);
+            const az_bf16x8 a1 = *(const az_bf16x8 *)(sA + (wi + 32 + lr) * BLD + kk + 8 * lk);
+            const az_bf16x8 b0 = *(const az_bf16x8 *)(sB + (wj + lr) * BLD + kk + 8 * lk);
+            const az_bf16x8 b1 = *(const az_bf16x8 *)(sB + (wj + 32 + lr) * BLD + kk + 8 * lk);
+            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, acc[0][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, acc[1][0], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc[1][1], 0, 0, 0);
+        }
+    }
+    float *Dz = D + (long long)blockIdx.z * slab;
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const int j = j0 + wj + 32 * b + lr;
+#pragma unroll
+            for (int v = 0; v < 16; ++v) {
+                const int i = i0 + wi + 32 * a + (v & 3) + 8 * (v >> 2) + 4 * lk;
+                if (i < M && j < N) {
+                    float *d = Dz + (long long)i * ldd + j;
+                    *d = accumulate ? *d + acc[a][b][v] : acc[a][b][v];
+                }
+            }
+        }
+}
+
 // slabs summed in slab order (+ what `out` holds when accumulate, + bias[j]); forward layers: pre-activation, ReLU, dropout
 __global__ void __launch_bounds__(256) k_solver_finish(const float *__restrict__ part, int S, long long slab, const float *__restrict__ bias,
                                                        long long MN, int N, int accumulate, float *__restrict__ out,
@@ -358,19 +480,28 @@ void pick_split(int M, int N, int K, int *S, int *Kc)
     *S = (K + kc - 1) / kc;
 }
 
-// form 0: A [M][K], B [N][K]; 1: A [M][K], B [K][N]; 2: A [K][M], B [K][N]
+// form 0: A [M][K], B [N][K]; 1: A [M][K], B [K][N]; 2: A [K][M], B [K][N]; prec: AZ_TRAIN_FP32 / AZ_TRAIN_BF16 (operands)
+template <bool AK, bool BK>
+void launch_gemm_form(hipStream_t s, int prec, dim3 grid, const float *A, long long lai, long long lak, const float *B, long long lbj,
+                      long long lbk, float *D, long long slab, int M, int N, int K, int Kc, int accumulate)
+{
+    if (prec == AZ_TRAIN_BF16)
+        hipLaunchKernelGGL((k_solver_gemm_bf16<AK, BK>), grid, dim3(256), 0, s, A, lai, lak, B, lbj, lbk, D, (long long)N, slab, M, N, K, Kc, accumulate);
+    else
+        hipLaunchKernelGGL((k_solver_gemm<AK, BK>), grid, dim3(256), 0, s, A, lai, lak, B, lbj, lbk, D, (long long)N, slab, M, N, K, Kc, accumulate);
+}
+
 void launch_gemm(hipStream_t s, int form, const float *A, const float *B, float *D, long long slab, int M, int N, int K, int S,
-                 int Kc, int accumulate)
+                 int Kc, int accumulate, int prec)
 {
     const dim3 grid((N + GT - 1) / GT, (M + GT - 1) / GT, S);
     if (form == 0)
-        hipLaunchKernelGGL((k_solver_gemm<true, true>), grid, dim3(256), 0, s, A, (long long)K, 1LL, B, (long long)K, 1LL, D, (long long)N, slab, M, N, K, Kc, accumulate);
+        launch_gemm_form<true, true>(s, prec, grid, A, (long long)K, 1LL, B, (long long)K, 1LL, D, slab, M, N, K, Kc, accumulate);
     else if (form == 1)
-        hipLaunchKernelGGL((k_solver_gemm<true, false>), grid, dim3(256), 0, s, A, (long long)K, 1LL, B, 1LL, (long long)N, D, (long long)N, slab, M, N, K, Kc, accumulate);
+        launch_gemm_form<true, false>(s, prec, grid, A, (long long)K, 1LL, B, 1LL, (long long)N, D, slab, M, N, K, Kc, accumulate);
     else
-        hipLaunchKernelGGL((k_solver_gemm<false, false>), grid, dim3(256), 0, s, A, 1LL, (long long)M, B, 1LL, (long long)N, D, (long long)N, slab, M, N, K, Kc, accumulate);
+        launch_gemm_form<false, false>(s, prec, grid, A, 1LL, (long long)M, B, 1LL, (long long)N, D, slab, M, N, K, Kc, accumulate);
 }
-
 
 // y = x W^T + b into `pre` (and, for the hidden layers, ReLU + dropout into `act`)
 template <typename Solver>
@@ -381,7 +512,7 @@ void fc_forward(Solver *s, const char *name, const float *x, int pw, int R, int 
     int S, Kc;
     pick_split(R, N, K, &S, &Kc);
     const long long slab = (long long)R * N;
-    { Timed t(c, name, 0, 1); launch_gemm(c->stream, 0, x, s->w[pw], s->part, slab, R, N, K, S, Kc, 0); }
+    { Timed t(c, name, 0, 1); launch_gemm(c->stream, 0, x, s->w[pw], s->part, slab, R, N, K, S, Kc, 0, s->prec); }
     const unsigned thr = (unsigned)((double)ratio * 16777216.0);
     Timed t(c, "fc_finish", 0);
     hipLaunchKernelGGL(k_solver_finish, dim3(grid_for(slab)), dim3(256), 0, c->stream, s->part, S, slab, s->w[pw + 1], slab, N, 0,
@@ -396,8 +527,8 @@ void gemm_any(Solver *s, const char *name, int form, const float *A, const float
     int S, Kc;
     pick_split(M, N, K, &S, &Kc);
     const long long slab = (long long)M * N;
-    if (S == 1) { Timed t(c, name, 0, 1); launch_gemm(c->stream, form, A, B, D, 0, M, N, K, 1, Kc, accumulate); return; }
-    { Timed t(c, name, 0, 1); launch_gemm(c->stream, form, A, B, s->part, slab, M, N, K, S, Kc, 0); }
+    if (S == 1) { Timed t(c, name, 0, 1); launch_gemm(c->stream, form, A, B, D, 0, M, N, K, 1, Kc, accumulate, s->prec); return; }
+    { Timed t(c, name, 0, 1); launch_gemm(c->stream, form, A, B, s->part, slab, M, N, K, S, Kc, 0, s->prec); }
     Timed t(c, "slab_sum", 0);
     hipLaunchKernelGGL(k_solver_finish, dim3(grid_for(slab)), dim3(256), 0, c->stream, s->part, S, slab, (const float *)nullptr, slab,
                        N, accumulate, D, (float *)nullptr, 0, (unsigned char *)nullptr, 0ull, 0u, 1.0f);

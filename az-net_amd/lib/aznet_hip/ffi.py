@@ -21,6 +21,7 @@ AZ_BATCH_MAX = 32          # include/aznet_hip.h
 AZ_PYRAMID_MAX = 8         # include/aznet_hip.h
 AZ_SKIP_MAX_SRC = 3        # include/aznet_hip.h
 AZ_SKIP_CHUNK = 128        # include/aznet_hip.h
+AZ_TRAIN_FP32, AZ_TRAIN_BF16 = 0, 1       # include/aznet_hip.h
 AZ_ERR_INVALID, AZ_ERR_HIP, AZ_ERR_CAPACITY, AZ_ERR_STATE, AZ_ERR_NO_DEVICE = -1, -2, -3, -4, -5
 _ERR_NAMES = {-1: "AZ_ERR_INVALID", -2: "AZ_ERR_HIP", -3: "AZ_ERR_CAPACITY", -4: "AZ_ERR_STATE",
               -5: "AZ_ERR_NO_DEVICE"}
@@ -54,6 +55,7 @@ SYMBOLS = [
     "az_det_solver_step", "az_det_solver_update", "az_det_solver_forward_test", "az_det_solver_fetch",
     "az_det_solver_attach_skip", "az_det_solver_load_skip", "az_det_solver_read_skip", "az_det_solver_set_skip_hyper",
     "az_det_solver_step_skip", "az_det_solver_forward_test_skip", "az_skip_pool_bwd_unit",
+    "az_solver_set_precision", "az_det_solver_set_precision", "az_solver_gemm_unit_prec",
 ]
 
 
@@ -253,6 +255,9 @@ def load_library(path=None):
     L.az_solver_forward_test.argtypes = [vp, vp, ci, ci, ci, ci, fp, ci, fp, fp, fp]
     L.az_solver_fetch.argtypes = [vp, ctypes.c_char_p, vp, ll, llp]
     L.az_solver_gemm_unit.argtypes = [vp, ci, fp, fp, fp, ci, ci, ci]
+    L.az_solver_gemm_unit_prec.argtypes = [vp, ci, ci, fp, fp, fp, ci, ci, ci]
+    L.az_solver_set_precision.argtypes = [vp, ci]
+    L.az_det_solver_set_precision.argtypes = [vp, ci]
     L.az_det_targets.argtypes = [vp, ci, fp, ip, fp, ip, ip, cd, cd, cd, fp, dp]
     L.az_det_target_stats.argtypes = [vp, ci, fp, ip, ci, cd, ci, dp, dp, dp]
     L.az_det_solver_create.argtypes = [vp, ci, ci, ci, ci, ci, u64, ctypes.POINTER(vp)]
@@ -1544,6 +1549,15 @@ def sgd_update_numpy(w, g, hist, rate, momentum, decay, clip_scale):
     return w - h, h
 
 
+def bf16_round(x):
+    """x (float32) with every element rounded to the nearest bfloat16, ties to even, as float32: what AZ_TRAIN_BF16 does to
+    the operands of a matrix product.  Overflow goes to inf; NaN stays NaN."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    u = x.view(np.uint32)
+    r = ((u + (np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1)))) & np.uint32(0xFFFF0000)).view(np.float32)
+    return np.where(np.isnan(x), x, r).astype(np.float32)
+
+
 class AzSolver(object):
     """The AZ-net trainer behind conv5_3 (az_solver_*): fp32 master weights, gradients and momentum history of the head in
     HBM; one `step` is forward + backward of a minibatch, `update` Caffe's SGD step."""
@@ -1604,6 +1618,10 @@ class AzSolver(object):
         b, pb = arr(decay_mult, 12)
         c, pc = arr(dropout_ratio, 3)
         self.ctx._chk(self.L.az_solver_set_hyper(self.h, pa, pb, pc))
+
+    def set_precision(self, precision):
+        """AZ_TRAIN_FP32 (0) or AZ_TRAIN_BF16 (1): the operands of every matrix product from the next step on (az_solver_set_precision)."""
+        self.ctx._chk(self.L.az_solver_set_precision(self.h, int(precision)))
 
     def _map(self, conv):
         """(pointer, N, H, W, channels_last) of a float32 CUDA tensor [N,C,H,W] in either memory format."""
@@ -1731,6 +1749,10 @@ class AzDetSolver(object):
         b, pb = arr(decay_mult, 8)
         c, pc = arr(dropout_ratio, 2)
         self.ctx._chk(self.L.az_det_solver_set_hyper(self.h, pa, pb, pc))
+
+    def set_precision(self, precision):
+        """AZ_TRAIN_FP32 (0) or AZ_TRAIN_BF16 (1): the operands of every matrix product from the next step on (az_det_solver_set_precision)."""
+        self.ctx._chk(self.L.az_det_solver_set_precision(self.h, int(precision)))
 
     _map = AzSolver._map
 
@@ -1932,8 +1954,9 @@ def sgd_update(ctx, w, g, hist, rate, momentum, decay, clip_scale=1.0):
                                  float(clip_scale)))
 
 
-def gemm_unit(ctx, form, a, b):
-    """One product of the trainer's GEMM kernel (az_solver_gemm_unit): form 0 a[M,K] b[N,K]^T, 1 a[M,K] b[K,N], 2 a[K,M]^T b[K,N]."""
+def gemm_unit(ctx, form, a, b, precision=0):
+    """One product of the trainer's GEMM kernel (az_solver_gemm_unit_prec): form 0 a[M,K] b[N,K]^T, 1 a[M,K] b[K,N],
+    2 a[K,M]^T b[K,N]; precision AZ_TRAIN_FP32 or AZ_TRAIN_BF16."""
     a, b = _f32(a), _f32(b)
     if form == 0:
         (M, K), N = a.shape, b.shape[0]
@@ -1943,7 +1966,7 @@ def gemm_unit(ctx, form, a, b):
         (K, M), N = a.shape, b.shape[1]
     d = np.empty((M, N), dtype=np.float32)
     f = ctypes.c_float
-    ctx._chk(ctx.L.az_solver_gemm_unit(ctx.h, int(form), _p(a, f), _p(b, f), _p(d, f), M, N, K))
+    ctx._chk(ctx.L.az_solver_gemm_unit_prec(ctx.h, int(form), int(precision), _p(a, f), _p(b, f), _p(d, f), M, N, K))
     return d
 
 

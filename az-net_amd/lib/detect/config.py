@@ -46,7 +46,9 @@ def _defaults():
         BBOX_THRESH=0.5, SNAPSHOT_ITERS=10000, USE_CACHE=False, SNAPSHOT_INFIX='',
         USE_PREFETCH=False, UN_NORMALIZE=False, NUM_PROPOSALS=2000, ANCHORS_PER_IMG=20,
         ADDREGIONS=[[0, 0, 1, 1], [0, 0, 0.8, 0.8], [0, 0.2, 0.8, 1], [0.2, 0, 1, 0.8],
-                    [0.2, 0.2, 1, 1]])
+                    [0.2, 0.2, 1, 1]],
+        PRECISION='fp32')    # (not in the reference) operands of the trainers' matrix products: 'fp32' or 'bf16' (rounded on
+                             # chip, summed in fp32; the master weights stay fp32)
     test = dict(         # config.py:109-133
         SCALES=(600,),       # short-side target of the single test scale
         MAX_SIZE=1000,       # long-side cap (experiments/cfgs/voc.yml:13 lowers it to 800)
@@ -86,6 +88,17 @@ def _defaults():
 
 cfg = edict(_defaults())
 __C = cfg
+
+
+TRAIN_PRECISIONS = {'fp32': 0, 'bf16': 1}        # include/aznet_hip.h: AZ_TRAIN_FP32, AZ_TRAIN_BF16
+
+
+def train_precision(name=None):
+    """The AZ_TRAIN_* value of cfg.TRAIN.PRECISION (or of `name`); anything but 'fp32' / 'bf16' is a ValueError."""
+    name = __C.TRAIN.PRECISION if name is None else name
+    if not isinstance(name, str) or name not in TRAIN_PRECISIONS:
+        raise ValueError("cfg.TRAIN.PRECISION = %r: 'fp32' or 'bf16'" % (name,))
+    return TRAIN_PRECISIONS[name]
 
 
 def get_output_dir(imdb, net):

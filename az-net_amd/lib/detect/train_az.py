@@ -103,6 +103,7 @@ class SolverWrapper(object):
     def _configure(self):
         """lr_mult / decay_mult / dropout of the prototxt -> the trainer; the trainable convolutions and their history."""
         from aznet_hip.ffi import HEAD_KEYS
+        from detect.config import train_precision
         lr, dc, drop = {}, {}, [0.0, 0.0, 0.0]
         for lname, (wk, bk) in HEAD_OF.items():
             n = self.net_param[lname]
@@ -111,6 +112,9 @@ class SolverWrapper(object):
             if lname in prototxt.DROPOUT_OF and n["dropout_ratio"] is not None:
                 drop[prototxt.DROPOUT_OF[lname]] = n["dropout_ratio"]
         self.trainer.set_hyper([lr[k] for k in HEAD_KEYS], [dc[k] for k in HEAD_KEYS], drop)
+        prec = train_precision()                 # (ValueError on anything but 'fp32' / 'bf16')
+        if prec or hasattr(self.trainer, "set_precision"):
+            self.trainer.set_precision(prec)
         self.conv_train = []
         if self.backbone is not None:
             import torch

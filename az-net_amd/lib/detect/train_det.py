@@ -144,6 +144,7 @@ class SolverWrapper(object):
     def _configure(self):
         """lr_mult / decay_mult / dropout of the prototxt -> the trainer; the trainable convolutions and their history."""
         from aznet_hip.ffi import DET_HEAD_KEYS
+        from detect.config import train_precision
         lr, dc, drop = {}, {}, [0.0, 0.0]
         for lname, (wk, bk) in HEAD_OF.items():
             n = self.net_param[lname]
@@ -152,6 +153,9 @@ class SolverWrapper(object):
             if lname in prototxt.DET_DROPOUT_OF and n["dropout_ratio"] is not None:
                 drop[prototxt.DET_DROPOUT_OF[lname]] = n["dropout_ratio"]
         self.trainer.set_hyper([lr[k] for k in DET_HEAD_KEYS], [dc[k] for k in DET_HEAD_KEYS], drop)
+        prec = train_precision()                 # (ValueError on anything but 'fp32' / 'bf16')
+        if prec or hasattr(self.trainer, "set_precision"):
+            self.trainer.set_precision(prec)
         if self.skip is not None:
             self.trainer.set_skip_hyper(self.net_param["conv_pool5"]["lr_mult"], self.net_param["conv_pool5"]["decay_mult"])
         self.conv_train = []

@@ -26,6 +26,7 @@ FLAGS = [
     ("--net", "net", "(extension) synthetic[:width_div]: seeded weights, no files", None, str),
     ("--shared", "shared", "(extension, without --solver) freeze all thirteen convolutions", None, None),
     ("--base-lr", "base_lr", "(extension, without --solver) base_lr of the written solver", 0.001, float),
+    ("--bf16", "bf16", "(extension) bf16 operands in the trainer's matrix products (cfg.TRAIN.PRECISION = 'bf16')", None, None),
 ]
 COMMON = [row for row in _cli.COMMON if row[0] in ("--gpu", "--cfg", "--exp")]
 
@@ -45,6 +46,8 @@ def main():
     else:
         np.random.seed(cfg.RNG_SEED)          # fix the random seeds (numpy and the dropout / filler generator)
     cfg.TRAIN.UN_NORMALIZE = bool(args.normalize)
+    if args.bf16:
+        cfg.TRAIN.PRECISION = 'bf16'
 
     import torch
     torch.cuda.set_device(args.gpu_id)

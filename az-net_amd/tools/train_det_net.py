@@ -37,6 +37,7 @@ FLAGS = [
     ("--def_fc", "prototxt_fc", "(ignored) prototxt defining the AZ-net's fully connected part", None, str),
     ("--net", "caffemodel", "AZ-Net model that makes the proposals (.caffemodel / .npz) or synthetic[:width_div]", None, str),
     ("--base-lr", "base_lr", "(extension, without --solver) base_lr of the written solver", 0.001, float),
+    ("--bf16", "bf16", "(extension) bf16 operands in the trainer's matrix products (cfg.TRAIN.PRECISION = 'bf16')", None, None),
 ]
 COMMON = [row for row in _cli.COMMON if row[0] in ("--gpu", "--cfg", "--exp")]
 
@@ -104,6 +105,8 @@ def main():
     else:
         np.random.seed(cfg.RNG_SEED)          # fix the random seeds (numpy and the dropout / filler generator)
     cfg.TRAIN.UN_NORMALIZE = bool(args.normalize)
+    if args.bf16:
+        cfg.TRAIN.PRECISION = 'bf16'
 
     import torch
     torch.cuda.set_device(args.gpu_id)

@@ -714,6 +714,19 @@ int az_solver_fetch(az_solver *s, const char *name, void *out, long long cap_byt
  * 1: a [M][K] b [K][N] (dx); 2: a [K][M]^T b [K][N] (dW). */
 int az_solver_gemm_unit(az_ctx *ctx, int form, const float *a, const float *b, float *d, int M, int N, int K);
 
+/* ---- training precision (not in the reference; opt-in, default AZ_TRAIN_FP32) ---------------------------------------------- */
+/* AZ_TRAIN_BF16: every matrix product of the trainer (all layers: forward, dx, dW; with a skip front attached also
+ * conv_pool5's three) rounds BOTH operands to bf16, round to nearest even, as they are staged on chip, multiplies them on
+ * the 16-bit matrix cores and sums in fp32.  Weights, activations, gradients and history stay fp32 in memory; pooling,
+ * bias / ReLU / dropout, column sums, losses, the gradient norm, GRN and the update are unchanged.  May be called between
+ * steps; the mode is read when a product is launched and nothing else is stored, so switching back leaves no trace.  Any
+ * other value: AZ_ERR_INVALID, state unchanged.  fp32 denormal operands are outside the stated behaviour. */
+#define AZ_TRAIN_FP32 0
+#define AZ_TRAIN_BF16 1
+int az_solver_set_precision(az_solver *s, int precision);
+/* az_solver_gemm_unit in the given precision. */
+int az_solver_gemm_unit_prec(az_ctx *ctx, int form, int precision, const float *a, const float *b, float *d, int M, int N, int K);
+
 /* ---- detection-net training: the box-regression targets (lib/roi_data_layer/roidb.py) ------------------------------------ */
 /* _compute_targets (roidb.py:149-207) for n_images images in ONE launch (a thread per example box, no host wait inside):
  * image i owns ex_boxes[ex_off[i]:ex_off[i+1]] (f32 [.,4] as the roidb stores them, widened to f64 as the reference's
@@ -759,6 +772,8 @@ int az_det_solver_read(az_det_solver *s, float *W6, float *b6, float *W7, float 
 /* param { lr_mult decay_mult } of the four layers ([8], parameter order) and dropout_ratio of fc6, fc7 ([2], each in [0, 1));
  * a NULL array keeps the current values. */
 int az_det_solver_set_hyper(az_det_solver *s, const float *lr_mult, const float *decay_mult, const float *dropout_ratio);
+/* AZ_TRAIN_FP32 / AZ_TRAIN_BF16, as az_solver_set_precision; covers az_det_solver_step_skip's conv_pool5 products as well. */
+int az_det_solver_set_precision(az_det_solver *s, int precision);
 /* net.forward() + net.backward() of one minibatch.  conv_dev, N, H, W, channels_last, rois [R][5], seed, iteration, sumsq_out
  * and dmap_dev as in az_solver_step (dropout layer ids: 0 = fc6, 1 = fc7); labels [R] (float, whole numbers in
  * [0, num_classes)), bbox_targets [R][4 num_classes], bbox_loss_weights [R][4 num_classes]: host arrays, the blobs of
