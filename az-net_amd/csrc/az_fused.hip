@@ -235,7 +235,7 @@ static __device__ __forceinline__ void spec_levels_body(const AzFusedArgs &a)
         // later (11 reserved slots), and its children after _sift_dup are the pre-pass's B1.
         const bool rz = (1.0 >= a.Tz);                  // zoom[0] = 1, then indZ = where(zoom >= Tz)
         P = rz ? P1spec : 0;
-        if (P > FL_R) { if (tid == 0) atomicOr(&cnt->err, 8); return; }
+        if (P > FL_R) { if (tid == 0) { atomicOr(&cnt->err, 8); cnt->scratch[5] = -1; } return; }
         if (tid == 0) {
             cnt->P[0] = 1; cnt->U[0] = 1; cnt->NC[0] = AZ_NSUB; cnt->ytot[0] = 0; cnt->PZ[0] = rz ? 1 : 0;
             cnt->CH[0] = rz ? div_nchildren(div_plan(sB[0])) : 0;
@@ -349,7 +349,7 @@ static __device__ __forceinline__ void spec_levels_body(const AzFusedArgs &a)
             }
             CH += tot;
         }
-        if (CH > FL_C || CH > a.capCh) { if (tid == 0) atomicOr(&cnt->err, 8); return; }
+        if (CH > FL_C || CH > a.capCh) { if (tid == 0) { atomicOr(&cnt->err, 8); cnt->scratch[5] = -1; } return; }
         __syncthreads();
         // (one thread per CHILD: a parent's children one after the other are ~35 dependent f64 divisions)
         for (int ci = tid; ci < CH; ci += NTL) {
@@ -364,7 +364,9 @@ static __device__ __forceinline__ void spec_levels_body(const AzFusedArgs &a)
         int Pn;
         unique_slots(skeyC, CH, sfirst, sslot, &Pn, wsum);
         TSTAMP(tsn++);
-        if (Pn > FL_R || Pn > a.capR) { if (tid == 0) atomicOr(&cnt->err, 8); return; }
+        // (scratch[5] = -1: one of levels 1-3 itself outgrew these tables -- keeping this kernel and dropping only
+        //  k_level_geom would overflow again, so the host goes to the multi-launch kernels at once)
+        if (Pn > FL_R || Pn > a.capR) { if (tid == 0) { atomicOr(&cnt->err, 8); cnt->scratch[5] = -1; } return; }
         for (int i = tid; i < CH; i += NTL)
             if (sfirst[i]) {
                 const int slot = sslot[i];

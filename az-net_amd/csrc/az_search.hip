@@ -577,11 +577,15 @@ int fetch_entry(az_ctx *c, size_t idx, double *boxes_out, float *scores_out, int
     if ((h.err & 8) && !(q.p.reserved & 2)) {
         // a fused level outgrew its LDS tables: rerun with the multi-launch kernels and remember
         // the image shape so that later calls skip the fused attempt -- first only for the levels after the
-        // speculative ones (az_level.hip), then, if levels 1-3 themselves overflow, for everything
+        // speculative ones (az_level.hip: also level 3 past batch_size at the hand-over); for everything when levels 1-3
+        // themselves outgrew k_spec_levels (it says so in scratch[5]: ONE rerun, not one per kernel given up)
         const bool lv_was_on = !(q.p.reserved & 16) &&
                                !(q.p.im_h == c->nofuse_lv_h && q.p.im_w == c->nofuse_lv_w);
         az_params p2 = q.p;
-        const int ovf = h.scratch[5] - 1;          // the level whose fused geometry kernel overflowed (-1: an earlier stage)
+        // scratch[5]: l + 1 from k_level_geom at level l; 0 from the hand-over of k_spec_levels (level 3 past batch_size);
+        // -1 from k_spec_levels when one of levels 1-3 outgrew its own tables (only the multi-launch form fits then)
+        const int ovf = h.scratch[5] - 1;          // the level whose k_level_geom overflowed (< 0: none did)
+        const bool spec_ovf = h.scratch[5] < 0;
         bool limited = false;
         if (lv_was_on && ovf > 3) {
             // a level behind the first fused one: the levels before it keep their fused kernels
@@ -596,7 +600,7 @@ int fetch_entry(az_ctx *c, size_t idx, double *boxes_out, float *scores_out, int
             }
         }
         if (limited) { }
-        else if (lv_was_on) { c->nofuse_lv_h = q.p.im_h; c->nofuse_lv_w = q.p.im_w; p2.reserved |= 16; }
+        else if (lv_was_on && !spec_ovf) { c->nofuse_lv_h = q.p.im_h; c->nofuse_lv_w = q.p.im_w; p2.reserved |= 16; }
         else { c->nofuse_h = q.p.im_h; c->nofuse_w = q.p.im_w; p2.reserved |= 2; }
         return rerun(p2);
     }
