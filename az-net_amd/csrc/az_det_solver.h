@@ -1,7 +1,7 @@
 // az_det_solver.h -- the detection trainer's state, shared by az_det_solver.hip (the head behind pool5) and
 // az_skip_train.hip (the skip-connection front in TRAIN phase, which produces pool5 in place of roi_pool5).
 #pragma once
-#include "az_solver_dev.h"
+#include "az_trainer.h"
 
 // parameter order of the ABI: W6 b6 W7 b7 Wc bc Wb bb (fc6, fc7, cls_score, bbox_pred); behind them, once a skip front is
 // attached, conv_pool5's Wp bp
@@ -9,26 +9,16 @@ enum { D_W6, D_B6, D_W7, D_B7, D_WC, D_BC, D_WB, D_BB, DNPARAM, D_WP = DNPARAM, 
 static const char *const DPNAME[DNALL] = {"W6", "b6", "W7", "b7", "Wc", "bc", "Wb", "bb", "Wp", "bp"};
 static const float DET_FILLER_STD[4] = {5e-3f, 5e-3f, 1e-2f, 1e-3f};      // fc6 fc7 (without a pretrained model) cls_score bbox_pred
 
-struct az_det_solver {
-    az_ctx *c = nullptr;
-    int C = 0, n6 = 0, n7 = 0, ncls = 0, K6 = 0, maxR = 0;
-    size_t pn[DNALL] = {0};
-    float *w[DNALL] = {nullptr}, *g[DNALL] = {nullptr}, *h[DNALL] = {nullptr};
-    float lr_mult[DNALL], decay_mult[DNALL];
+struct az_det_solver : az_trainer {
+    int n6 = 0, n7 = 0, ncls = 0;
     float drop[2] = {0.5f, 0.5f};
     // one step's activations and gradients (rows: maxR)
-    float *rois = nullptr, *labels = nullptr, *tgt = nullptr, *wgt = nullptr;
-    int *geo = nullptr, *argmax = nullptr;
-    float *pool5 = nullptr, *pre6 = nullptr, *a6 = nullptr, *pre7 = nullptr, *a7 = nullptr;
+    float *labels = nullptr, *tgt = nullptr, *wgt = nullptr;
+    float *pre6 = nullptr, *a6 = nullptr, *pre7 = nullptr, *a7 = nullptr;
     unsigned char *m6 = nullptr, *m7 = nullptr;
     float *s_cls = nullptr, *prob = nullptr, *s_bb = nullptr;                  // raw cls_score, cls_prob, bbox_pred
-    float *d_cls = nullptr, *d_bb = nullptr, *d7 = nullptr, *d6 = nullptr, *dpool = nullptr;
-    float *part = nullptr, *loss = nullptr;
-    double *sq_part = nullptr, *sq = nullptr;
-    size_t part_elems = 0;
-    std::vector<void *> allocs;
-    int R = 0, N = 0, H = 0, W = 0, trained = 0, has_prob = 0;
-    int prec = AZ_TRAIN_FP32;                                   // operands of every matrix product (az_det_solver_set_precision)
+    float *d_cls = nullptr, *d_bb = nullptr, *d7 = nullptr, *d6 = nullptr;
+    int has_prob = 0;
     // the skip front (az_det_solver_attach_skip): rows (roi, bin) x sumC channels
     struct Skip {
         bool attached = false;
@@ -37,7 +27,7 @@ struct az_det_solver {
         double gain = 0.0, eps = 0.0;
         int *geo = nullptr, *arg = nullptr;                     // geo [n][maxR][8]; arg-max [rows][sumC]
         float *cat = nullptr, *d_y = nullptr, *d_cat = nullptr, *d_raw = nullptr;
-        double *fac = nullptr, *sq_part = nullptr;              // f = gain / sqrt(ss + eps) [rows][n]; DNALL x SQ_BLOCKS partials
+        double *fac = nullptr;                                  // f = gain / sqrt(ss + eps) [rows][n]
         int rows = 0, trained = 0, has_dcat = 0;                // of the last skip pass (has_dcat: it computed d_cat / d_raw)
     } sk;
 };
@@ -51,6 +41,6 @@ void det_head_backward(az_det_solver *s, int R, bool want_dpool);
 int det_stage_targets(az_det_solver *s, int R, const float *labels, const float *bbox_targets, const float *bbox_loss_weights,
                       long long iteration, const std::string &who);
 void det_softmax_test(az_det_solver *s, int R);
-int det_check_rois(az_det_solver *s, int N, const float *rois, int R, const std::string &who);
 // ---- az_skip_train.hip ----------------------------------------------------------------------------------------------------------
-bool skip_train_fetch(az_det_solver *s, const std::string &name, const void **src, size_t *bytes, bool *is_param);
+// the front's saved tensors by name (cat, skip_argmax, skip_factor, d_y, d_cat, d_raw)
+bool skip_train_fetch(az_det_solver *s, const std::string &name, const void **src, size_t *bytes);

@@ -1,9 +1,9 @@
 // az_det_solver.hip -- detection-net (Fast R-CNN) TRAINING from conv5_3 on (models/*/VGG16/frcnn/train.prototxt): RoIPool with
 // arg-max -> fc6 -> fc7 -> {cls_score, bbox_pred}, SoftmaxWithLoss and SmoothL1Loss, the backward pass, the gradient norm and
-// Caffe's momentum-SGD update.  The kernels are the AZ-net trainer's (az_solver_dev.h) in this graph's order; the one new
-// kernel is the softmax loss.  fp32 master weights in Caffe layout ([out][in], roi_pool5 flattened c*49 + p).
+// Caffe's momentum-SGD update.  The parameter store and the kernels are the trainer core's (az_trainer.h) in this graph's order;
+// the one kernel of its own is the softmax loss.  fp32 master weights in Caffe layout ([out][in], roi_pool5 flattened c*49 + p).
 //
-// Every reduction has a fixed order (no floating-point atomics): see az_solver.hip; the softmax sums a row lane-strided and
+// Every reduction has a fixed order (no floating-point atomics): see az_trainer.hip; the softmax sums a row lane-strided and
 // then over a fixed butterfly, the row losses in row order per wave and then over the LDS tree.  The same step from the same
 // state gives the same bits.
 #include "az_det_solver.h"
@@ -72,41 +72,6 @@ __global__ void __launch_bounds__(256) k_solver_softmax_loss(const float *__rest
 
 }  // namespace
 
-namespace {
-
-template <typename T>
-int dsalloc(az_det_solver *s, T **p, size_t n)
-{
-    void *q = nullptr;
-    if (hipMalloc(&q, n * sizeof(T) + 256) != hipSuccess) return fail(s->c, AZ_ERR_HIP, "az_det_solver: hipMalloc(" + std::to_string(n * sizeof(T)) + " B) failed");
-    s->allocs.push_back(q);
-    *p = (T *)q;
-    return AZ_OK;
-}
-
-int det_check_args(az_det_solver *s, const float *conv, int N, int H, int W, const float *rois, int R, const std::string &who)
-{
-    if (!s) return AZ_ERR_INVALID;
-    if (!conv || !rois) return fail(s->c, AZ_ERR_INVALID, who + ": null conv5_3 or rois");
-    if (N < 1 || H < 1 || W < 1 || (long long)H * W > 0x3fffffff) return fail(s->c, AZ_ERR_INVALID, who + ": bad map shape");
-    return det_check_rois(s, N, rois, R, who);
-}
-
-}  // namespace
-
-int det_check_rois(az_det_solver *s, int N, const float *rois, int R, const std::string &who)
-{
-    if (R < 1 || R > s->maxR) return fail(s->c, AZ_ERR_INVALID, who + ": R must be in [1, max_rois = " + std::to_string(s->maxR) + "]");
-    for (int r = 0; r < R; ++r) {
-        const float *roi = rois + 5 * (size_t)r;
-        if (!(roi[0] >= 0.0f && roi[0] < (float)N) || roi[0] != std::floor(roi[0]))
-            return fail(s->c, AZ_ERR_INVALID, who + ": roi " + std::to_string(r) + " names image " + std::to_string(roi[0]) + " of " + std::to_string(N));
-        for (int q = 1; q < 5; ++q)
-            if (!std::isfinite(roi[q]) || std::fabs(roi[q]) > 1e8f) return fail(s->c, AZ_ERR_INVALID, who + ": roi coordinate not finite");
-    }
-    return AZ_OK;
-}
-
 // fc6 -> fc7 -> {cls_score, bbox_pred}; train: dropout on fc6 / fc7 with the step's masks (layer ids 0 / 1)
 void det_head_forward(az_det_solver *s, int R, bool train, unsigned long long seed, unsigned long long iter)
 {
@@ -144,29 +109,21 @@ void det_head_backward(az_det_solver *s, int R, bool want_dpool)
     const int nc = s->ncls, nb = 4 * s->ncls, n6 = s->n6, n7 = s->n7, K6 = s->K6;
     { Timed t(c, "losses", 0);
       hipLaunchKernelGGL(k_solver_softmax_loss, dim3(1), dim3(256), 0, st, s->s_cls, s->labels, R, nc, s->prob, s->d_cls, s->loss + 0);
-      hipLaunchKernelGGL(k_solver_smooth_l1, dim3(1), dim3(256), 0, st, s->s_bb, s->tgt, s->wgt, R * nb, R, s->d_bb, s->loss + 1); }
+      tr_smooth_l1(s, s->s_bb, s->tgt, s->wgt, R * nb, R, s->d_bb, s->loss + 1); }
     s->has_prob = 1;
-    auto colsum = [&](const float *dy, int Nc, float *db) {
-        hipLaunchKernelGGL(k_solver_colsum, dim3((Nc + 255) / 256), dim3(256), 0, st, dy, R, Nc, db);
-    };
-    auto act_bwd = [&](float *d, const float *pre, const unsigned char *mask, float ratio, int Nc) {
-        Timed t(c, "act_bwd", 0);
-        hipLaunchKernelGGL(k_solver_act_bwd, dim3(grid_for((long long)R * Nc)), dim3(256), 0, st, d, pre, ratio > 0.f ? mask : nullptr,
-                           1.0f / (1.0f - ratio), (long long)R * Nc);
-    };
     // the two output layers: dW = dy^T x, db, and their two dx, which add into d7
     gemm_any(s, "cls_score_dw", 2, s->d_cls, s->a7, s->g[D_WC], nc, n7, R, 0);
     gemm_any(s, "bbox_pred_dw", 2, s->d_bb, s->a7, s->g[D_WB], nb, n7, R, 0);
-    { Timed t(c, "bias_grads", 0); colsum(s->d_cls, nc, s->g[D_BC]); colsum(s->d_bb, nb, s->g[D_BB]); }
+    { Timed t(c, "bias_grads", 0); tr_colsum(s, s->d_cls, R, nc, s->g[D_BC]); tr_colsum(s, s->d_bb, R, nb, s->g[D_BB]); }
     gemm_any(s, "cls_score_dx", 1, s->d_cls, s->w[D_WC], s->d7, R, n7, nc, 0);
     gemm_any(s, "bbox_pred_dx", 1, s->d_bb, s->w[D_WB], s->d7, R, n7, nb, 1);
-    act_bwd(s->d7, s->pre7, s->m7, s->drop[1], n7);
+    tr_act_bwd(s, s->d7, s->pre7, s->m7, s->drop[1], R, n7);
     gemm_any(s, "fc7_dw", 2, s->d7, s->a6, s->g[D_W7], n7, n6, R, 0);
-    { Timed t(c, "bias_grads", 0); colsum(s->d7, n7, s->g[D_B7]); }
+    { Timed t(c, "bias_grads", 0); tr_colsum(s, s->d7, R, n7, s->g[D_B7]); }
     gemm_any(s, "fc7_dx", 1, s->d7, s->w[D_W7], s->d6, R, n6, n7, 0);
-    act_bwd(s->d6, s->pre6, s->m6, s->drop[0], n6);
+    tr_act_bwd(s, s->d6, s->pre6, s->m6, s->drop[0], R, n6);
     gemm_any(s, "fc6_dw", 2, s->d6, s->pool5, s->g[D_W6], n6, K6, R, 0);
-    { Timed t(c, "bias_grads", 0); colsum(s->d6, n6, s->g[D_B6]); }
+    { Timed t(c, "bias_grads", 0); tr_colsum(s, s->d6, R, n6, s->g[D_B6]); }
     if (want_dpool) gemm_any(s, "fc6_dx", 1, s->d6, s->w[D_W6], s->dpool, R, K6, n6, 0);
 }
 
@@ -177,26 +134,6 @@ void det_softmax_test(az_det_solver *s, int R)
                        (float *)nullptr, (float *)nullptr);
     s->has_prob = 1;
 }
-
-namespace {
-
-// RoIPool -> the head
-int det_forward(az_det_solver *s, const float *conv, int N, int H, int W, int cl, const float *rois, int R, bool train,
-                unsigned long long seed, unsigned long long iter)
-{
-    az_ctx *c = s->c;
-    HIPCHK(c, hipMemcpyAsync(s->rois, rois, (size_t)R * 5 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    const MapView m{N, s->C, H, W, cl ? 1 : 0};
-    { Timed t(c, "roi_pool_argmax", 0);
-      hipLaunchKernelGGL(k_solver_roi_geo, dim3((R + 255) / 256), dim3(256), 0, c->stream, s->rois, R, c->spatial_scale, s->geo);
-      hipLaunchKernelGGL(k_solver_roi_pool, dim3(grid_for((long long)R * s->K6, 16384)), dim3(256), 0, c->stream, conv, m, s->geo, R,
-                         s->pool5, s->argmax); }
-    det_head_forward(s, R, train, seed, iter);
-    s->R = R; s->N = N; s->H = H; s->W = W;
-    return AZ_OK;
-}
-
-}  // namespace
 
 void az_det_solver_free_all(az_ctx *c)
 {
@@ -214,165 +151,86 @@ int az_det_solver_create(az_ctx *c, int C, int n6, int n7, int num_classes, int 
         return fail(c, AZ_ERR_INVALID, "az_det_solver_create: C, n6, n7 must be positive multiples of 4, 2 <= num_classes <= 256, 1 <= max_rois <= 4096");
     HIPCHK(c, hipSetDevice(c->device));
     az_det_solver *s = new az_det_solver();
-    s->c = c; s->C = C; s->n6 = n6; s->n7 = n7; s->ncls = num_classes; s->K6 = C * 49; s->maxR = max_rois;
-    const size_t K6 = (size_t)s->K6, nc = (size_t)num_classes, nb = 4 * nc;
-    const size_t pn[DNPARAM] = {n6 * K6, (size_t)n6, (size_t)n7 * n6, (size_t)n7, nc * n7, nc, nb * n7, nb};
-    int rc = AZ_OK;
-    for (int p = 0; p < DNPARAM && rc == AZ_OK; ++p) {
-        s->pn[p] = pn[p];
-        s->lr_mult[p] = (p & 1) ? 2.0f : 1.0f;
-        s->decay_mult[p] = (p & 1) ? 0.0f : 1.0f;
-        if ((rc = dsalloc(s, &s->w[p], pn[p])) == AZ_OK && (rc = dsalloc(s, &s->g[p], pn[p])) == AZ_OK) rc = dsalloc(s, &s->h[p], pn[p]);
-    }
-    const size_t R = (size_t)max_rois;
+    s->n6 = n6; s->n7 = n7; s->ncls = num_classes; s->np = DNPARAM;
+    const size_t K6 = (size_t)C * 49, R = (size_t)max_rois, nc = (size_t)num_classes, nb = 4 * nc;
     // the slabs of a split-K product hold at most 256 tiles of 128 x 128 (pick_split); an unsplit forward layer R x its width
-    // (az_det_solver_attach_skip relies on this 4M-float floor for the front's split products)
+    // (az_det_solver_attach_skip relies on the 4M-float floor for the front's split products)
     size_t nmax = (size_t)(n6 > n7 ? n6 : n7); nmax = nmax > nb ? nmax : nb; nmax = nmax > K6 ? nmax : K6;
-    s->part_elems = R * nmax > (size_t)4 << 20 ? R * nmax : (size_t)4 << 20;
-#define SA(p, n) if (rc == AZ_OK) rc = dsalloc(s, &s->p, (n))
-    SA(rois, R * 5); SA(labels, R); SA(tgt, R * nb); SA(wgt, R * nb); SA(geo, R * 8);
-    SA(argmax, R * K6); SA(pool5, R * K6); SA(dpool, R * K6);
+    int rc = tr_init(s, c, "az_det_solver", DPNAME, C, max_rois, nmax);
+    const size_t pn[DNPARAM] = {n6 * K6, (size_t)n6, (size_t)n7 * n6, (size_t)n7, nc * n7, nc, nb * n7, nb};
+    if (rc == AZ_OK) rc = tr_alloc_params(s, 0, DNPARAM, pn);
+#define SA(p, n) if (rc == AZ_OK) rc = tr_alloc(s, &s->p, (n))
+    SA(labels, R); SA(tgt, R * nb); SA(wgt, R * nb);
     SA(pre6, R * n6); SA(a6, R * n6); SA(d6, R * n6); SA(m6, R * n6);
     SA(pre7, R * n7); SA(a7, R * n7); SA(d7, R * n7); SA(m7, R * n7);
     SA(s_cls, R * nc); SA(prob, R * nc); SA(d_cls, R * nc); SA(s_bb, R * nb); SA(d_bb, R * nb);
-    SA(part, s->part_elems); SA(loss, 4); SA(sq_part, (size_t)DNPARAM * SQ_BLOCKS); SA(sq, 2);
 #undef SA
-    if (rc != AZ_OK) { for (void *q : s->allocs) hipFree(q); delete s; return rc; }
-    for (int p = 0; p < DNPARAM; ++p) {
-        hipMemsetAsync(s->h[p], 0, pn[p] * sizeof(float), c->stream);
-        hipMemsetAsync(s->g[p], 0, pn[p] * sizeof(float), c->stream);
-        if (p & 1) hipMemsetAsync(s->w[p], 0, pn[p] * sizeof(float), c->stream);
-        else hipLaunchKernelGGL(k_solver_fill_gauss, dim3(grid_for((long long)pn[p], 8192)), dim3(256), 0, c->stream, s->w[p], (long long)pn[p],
-                                DET_FILLER_STD[p / 2], az_layer_key(seed, 0, 16 + p));
-    }
-    if (hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess) {
-        for (void *q : s->allocs) hipFree(q);
-        delete s;
-        return fail(c, AZ_ERR_HIP, "az_det_solver_create: initialising the parameters failed");
-    }
+    if (rc == AZ_OK && tr_fill_params(s, 0, DNPARAM, DET_FILLER_STD, seed) != AZ_OK)
+        rc = fail(c, AZ_ERR_HIP, "az_det_solver_create: initialising the parameters failed");
+    if (rc != AZ_OK) { tr_release(s, 0); delete s; return rc; }
     c->det_solvers.push_back(s);
     *out = s;
     return AZ_OK;
 }
 
-int az_det_solver_destroy(az_det_solver *s)
-{
-    if (!s) return AZ_ERR_INVALID;
-    az_ctx *c = s->c;
-    hipSetDevice(c->device);
-    hipStreamSynchronize(c->stream);
-    for (void *q : s->allocs) hipFree(q);
-    for (size_t i = 0; i < c->det_solvers.size(); ++i) if (c->det_solvers[i] == s) { c->det_solvers.erase(c->det_solvers.begin() + i); break; }
-    delete s;
-    return AZ_OK;
-}
+int az_det_solver_destroy(az_det_solver *s) { return s ? tr_destroy(s, s->c->det_solvers) : AZ_ERR_INVALID; }
 
 int az_det_solver_load(az_det_solver *s, const float *W6, const float *b6, const float *W7, const float *b7, const float *Wc,
                        const float *bc, const float *Wb, const float *bb)
 {
     if (!s) return AZ_ERR_INVALID;
-    az_ctx *c = s->c;
     const float *src[DNPARAM] = {W6, b6, W7, b7, Wc, bc, Wb, bb};
-    HIPCHK(c, hipSetDevice(c->device));
-    for (int p = 0; p < DNPARAM; ++p)       // a null array keeps what the trainer holds
-        if (src[p]) HIPCHK(c, hipMemcpyAsync(s->w[p], src[p], s->pn[p] * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return AZ_OK;
+    return tr_load(s, 0, DNPARAM, src);
 }
 
 int az_det_solver_read(az_det_solver *s, float *W6, float *b6, float *W7, float *b7, float *Wc, float *bc, float *Wb, float *bb)
 {
     if (!s) return AZ_ERR_INVALID;
-    az_ctx *c = s->c;
     float *dst[DNPARAM] = {W6, b6, W7, b7, Wc, bc, Wb, bb};
-    HIPCHK(c, hipSetDevice(c->device));
-    for (int p = 0; p < DNPARAM; ++p)
-        if (dst[p]) HIPCHK(c, hipMemcpyAsync(dst[p], s->w[p], s->pn[p] * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return AZ_OK;
+    return tr_read(s, 0, DNPARAM, dst);
 }
 
 int az_det_solver_set_hyper(az_det_solver *s, const float *lr_mult, const float *decay_mult, const float *dropout_ratio)
 {
     if (!s) return AZ_ERR_INVALID;
-    if (dropout_ratio) for (int i = 0; i < 2; ++i) if (!(dropout_ratio[i] >= 0.0f && dropout_ratio[i] < 1.0f)) return fail(s->c, AZ_ERR_INVALID, "az_det_solver_set_hyper: dropout ratio outside [0, 1)");
-    if (lr_mult) for (int p = 0; p < DNPARAM; ++p) if (!(lr_mult[p] >= 0.0f)) return fail(s->c, AZ_ERR_INVALID, "az_det_solver_set_hyper: negative lr_mult");
-    if (decay_mult) for (int p = 0; p < DNPARAM; ++p) if (!(decay_mult[p] >= 0.0f)) return fail(s->c, AZ_ERR_INVALID, "az_det_solver_set_hyper: negative decay_mult");
-    if (lr_mult) for (int p = 0; p < DNPARAM; ++p) s->lr_mult[p] = lr_mult[p];
-    if (decay_mult) for (int p = 0; p < DNPARAM; ++p) s->decay_mult[p] = decay_mult[p];
-    if (dropout_ratio) for (int i = 0; i < 2; ++i) s->drop[i] = dropout_ratio[i];
-    return AZ_OK;
+    return tr_set_hyper(s, DNPARAM, lr_mult, decay_mult, dropout_ratio, s->drop, 2);
 }
 
 int az_det_solver_step(az_det_solver *s, const float *conv_dev, int N, int H, int W, int channels_last, const float *rois, int R,
                        const float *labels, const float *bbox_targets, const float *bbox_loss_weights, uint64_t seed,
                        long long iteration, float *losses_out, double *sumsq_out, float *dmap_dev)
 {
-    int rc = det_check_args(s, conv_dev, N, H, W, rois, R, "az_det_solver_step");
+    int rc = tr_check_step(s, conv_dev, N, H, W, rois, R, "az_det_solver_step");
     if (rc != AZ_OK) return rc;
-    az_ctx *c = s->c;
     if ((rc = det_stage_targets(s, R, labels, bbox_targets, bbox_loss_weights, iteration, "az_det_solver_step")) != AZ_OK) return rc;
-    hipStream_t st = c->stream;
-    if ((rc = det_forward(s, conv_dev, N, H, W, channels_last, rois, R, true, seed, (unsigned long long)iteration)) != AZ_OK) return rc;
+    if ((rc = tr_roi_pool_forward(s, conv_dev, N, H, W, channels_last, rois, R)) != AZ_OK) return rc;
+    det_head_forward(s, R, true, seed, (unsigned long long)iteration);
     det_head_backward(s, R, dmap_dev != nullptr);
     s->sk.trained = 0;
-    if (dmap_dev) {
-        const MapView m{N, s->C, H, W, channels_last ? 1 : 0};
-        Timed t(c, "roi_pool_bwd", 0);
-        hipLaunchKernelGGL(k_solver_roi_pool_bwd, dim3(grid_for((long long)N * s->C * H * W, 1 << 30)), dim3(256), 0, st, s->dpool,
-                           s->argmax, s->geo, R, m, dmap_dev);
-    }
-    { Timed t(c, "grad_sumsq", 0);
-      for (int p = 0; p < DNPARAM; ++p)
-          hipLaunchKernelGGL(k_solver_sumsq, dim3(SQ_BLOCKS), dim3(256), 0, st, s->g[p], (long long)s->pn[p], s->sq_part + (size_t)p * SQ_BLOCKS);
-      hipLaunchKernelGGL(k_solver_sumsq_final, dim3(1), dim3(256), 0, st, s->sq_part, DNPARAM * SQ_BLOCKS, s->sq); }
-    float hl[2]; double hs = 0.0;
-    HIPCHK(c, hipMemcpyAsync(hl, s->loss, sizeof(hl), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(&hs, s->sq, sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    HIPCHK(c, hipGetLastError());
+    if (dmap_dev) tr_roi_pool_backward(s, N, H, W, channels_last, dmap_dev);
+    if ((rc = tr_grad_norm(s, DNPARAM, 2, losses_out, sumsq_out)) != AZ_OK) return rc;
     s->trained = dmap_dev ? 2 : 1;
-    if (losses_out) { losses_out[0] = hl[0]; losses_out[1] = hl[1]; }
-    if (sumsq_out) *sumsq_out = hs;
     return AZ_OK;
 }
 
-int az_det_solver_set_precision(az_det_solver *s, int precision)
-{
-    if (!s) return AZ_ERR_INVALID;
-    if (precision != AZ_TRAIN_FP32 && precision != AZ_TRAIN_BF16)
-        return fail(s->c, AZ_ERR_INVALID, "az_det_solver_set_precision: AZ_TRAIN_FP32 or AZ_TRAIN_BF16");
-    s->prec = precision;
-    return AZ_OK;
-}
+int az_det_solver_set_precision(az_det_solver *s, int precision) { return tr_set_precision(s, precision); }
 
 int az_det_solver_update(az_det_solver *s, double rate, double momentum, double weight_decay, double clip_scale)
 {
     if (!s) return AZ_ERR_INVALID;
-    az_ctx *c = s->c;
-    if (!(rate >= 0.0) || !(momentum >= 0.0) || !(weight_decay >= 0.0) || !(clip_scale > 0.0) || !std::isfinite(rate + momentum + weight_decay + clip_scale))
-        return fail(c, AZ_ERR_INVALID, "az_det_solver_update: rate, momentum, weight_decay >= 0 and clip_scale > 0, all finite");
-    if (!s->trained) return fail(c, AZ_ERR_STATE, "az_det_solver_update: no az_det_solver_step has produced gradients");
-    HIPCHK(c, hipSetDevice(c->device));
-    { Timed t(c, "sgd_update", 0);
-      for (int p = 0; p < (s->sk.trained ? DNALL : DNPARAM); ++p)       // conv_pool5 too, behind a skip step
-          hipLaunchKernelGGL(k_solver_sgd, dim3(grid_for((long long)s->pn[p], 16384)), dim3(256), 0, c->stream, s->w[p], s->g[p], s->h[p],
-                             (long long)s->pn[p], (float)(rate * (double)s->lr_mult[p]), (float)momentum,
-                             (float)(weight_decay * (double)s->decay_mult[p]), (float)clip_scale); }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipGetLastError());
-    return AZ_OK;
+    return tr_update(s, s->sk.trained ? DNALL : DNPARAM, rate, momentum, weight_decay, clip_scale);       // conv_pool5 too, behind a skip step
 }
 
 int az_det_solver_forward_test(az_det_solver *s, const float *conv_dev, int N, int H, int W, int channels_last, const float *rois,
                                int R, float *cls_prob, float *bbox_pred)
 {
-    int rc = det_check_args(s, conv_dev, N, H, W, rois, R, "az_det_solver_forward_test");
+    int rc = tr_check_step(s, conv_dev, N, H, W, rois, R, "az_det_solver_forward_test");
     if (rc != AZ_OK) return rc;
     az_ctx *c = s->c;
     HIPCHK(c, hipSetDevice(c->device));
     if (!(c->profiling & 4)) clear_events(c);
-    if ((rc = det_forward(s, conv_dev, N, H, W, channels_last, rois, R, false, 0, 0)) != AZ_OK) return rc;
+    if ((rc = tr_roi_pool_forward(s, conv_dev, N, H, W, channels_last, rois, R)) != AZ_OK) return rc;
+    det_head_forward(s, R, false, 0, 0);
     s->trained = 0; s->sk.trained = 0;
     det_softmax_test(s, R);
     if (cls_prob) HIPCHK(c, hipMemcpyAsync(cls_prob, s->prob, (size_t)R * s->ncls * sizeof(float), hipMemcpyDeviceToHost, c->stream));
@@ -385,7 +243,6 @@ int az_det_solver_forward_test(az_det_solver *s, const float *conv_dev, int N, i
 int az_det_solver_fetch(az_det_solver *s, const char *name, void *out, long long cap_bytes, long long *bytes_out)
 {
     if (!s || !name || !bytes_out) return AZ_ERR_INVALID;
-    az_ctx *c = s->c;
     const std::string nm(name);
     const size_t R = (size_t)s->R, nc = (size_t)s->ncls;
     const void *src = nullptr;
@@ -398,22 +255,11 @@ int az_det_solver_fetch(az_det_solver *s, const char *name, void *out, long long
         {"cls_score", s->s_cls, R * nc * 4}, {"cls_prob", s->prob, R * nc * 4}, {"bbox_pred", s->s_bb, R * nc * 16},
         {"d_cls_score", s->d_cls, R * nc * 4}, {"d_bbox_pred", s->d_bb, R * nc * 16},
     };
-    bool is_param = false;
     for (const Ent &e : tab) if (nm == e.n) { src = e.p; bytes = e.b; }
-    if (!src && skip_train_fetch(s, nm, &src, &bytes, &is_param)) {}
-    else if (!src && nm.size() > 2 && nm[1] == '_' && (nm[0] == 'g' || nm[0] == 'h' || nm[0] == 'w'))
-        for (int p = 0; p < DNPARAM; ++p)
-            if (nm.substr(2) == DPNAME[p]) { src = nm[0] == 'g' ? s->g[p] : (nm[0] == 'h' ? s->h[p] : s->w[p]); bytes = s->pn[p] * 4; is_param = true; }
-    if (!src) return fail(c, AZ_ERR_INVALID, "az_det_solver_fetch: no saved tensor named '" + nm + "'");
-    if ((nm == "d_cat" || nm == "d_raw") && !s->sk.has_dcat)
-        return fail(c, AZ_ERR_STATE, "az_det_solver_fetch: the last skip pass asked for no map gradient, so it computed no '" + nm + "'");
-    if (!is_param && s->R == 0) return fail(c, AZ_ERR_STATE, "az_det_solver_fetch: no forward pass has run");
-    *bytes_out = (long long)bytes;
-    if (!out) return AZ_OK;
-    if (cap_bytes < (long long)bytes) return fail(c, AZ_ERR_CAPACITY, "az_det_solver_fetch: '" + nm + "' needs " + std::to_string(bytes) + " bytes");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost));
-    return AZ_OK;
+    if (!src) skip_train_fetch(s, nm, &src, &bytes);
+    if ((nm == "d_cat" || nm == "d_raw") && src && !s->sk.has_dcat)
+        return fail(s->c, AZ_ERR_STATE, "az_det_solver_fetch: the last skip pass asked for no map gradient, so it computed no '" + nm + "'");
+    return tr_fetch(s, nm, src, bytes, out, cap_bytes, bytes_out);
 }
 
 }  // extern "C"

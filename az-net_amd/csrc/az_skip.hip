@@ -7,7 +7,7 @@
 //   k_skip_pool_norm  one workgroup per (roi, bin, source): window maximum per channel, sum of squares, scaled store into
 //                     the row-major `cat` [rows][sumC]
 //   k_skip_conv       pool5[rows][Cout] = relu(cat . Wp^T + bp) on the fp32 matrix cores: the trainer's 128 x 128 tile
-//                     (k_solver_gemm form 0, az_solver_dev.h) with the row count read from the device, the whole K in one
+//                     (k_solver_gemm form 0, az_trainer.hip; gemm_stage, az_solver_dev.h) with the row count read from the device, the whole K in one
 //                     pass and the bias / ReLU epilogue
 // `cat` holds AZ_SKIP_CHUNK rois (49 x sumC x 4 B each: 251 KB at the VGG16 sizes); both kernels run once per chunk over
 // the host-known bound on the row count, and rows past the device-side count leave at once.

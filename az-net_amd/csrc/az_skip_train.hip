@@ -235,8 +235,7 @@ int check_maps(az_ctx *c, const std::string &who, int n_src, const int *Cs, cons
 
 void launch_geo(hipStream_t st, const float *rois_dev, int R, int n, const float *scales, int *geo)
 {
-    for (int i = 0; i < n; ++i)
-        hipLaunchKernelGGL(k_solver_roi_geo, dim3((R + 255) / 256), dim3(256), 0, st, rois_dev, R, scales[i], geo + (size_t)i * R * 8);
+    for (int i = 0; i < n; ++i) tr_roi_geo(st, rois_dev, R, scales[i], geo + (size_t)i * R * 8);
 }
 
 void launch_gather(az_ctx *c, hipStream_t st, const TrainSrcs &a, int i, const float *draw, const int *arg, const int *geo, int R, float *dmap)
@@ -269,7 +268,7 @@ int skip_step_check(az_det_solver *s, const std::string &who, int n_src, const i
     int rc = check_maps(c, who, n_src, Cs, maps, Hs, Ws, N);
     if (rc != AZ_OK) return rc;
     if (!rois) return fail(c, AZ_ERR_INVALID, who + ": null rois");
-    return det_check_rois(s, N, rois, R, who);
+    return tr_check_rois(s, N, rois, R, who);
 }
 
 // roi_pool* .. relu_pool into s->pool5, then the head
@@ -297,7 +296,7 @@ int skip_forward(az_det_solver *s, const TrainSrcs &a, const float *rois, int R,
 
 }  // namespace
 
-bool skip_train_fetch(az_det_solver *s, const std::string &nm, const void **src, size_t *bytes, bool *is_param)
+bool skip_train_fetch(az_det_solver *s, const std::string &nm, const void **src, size_t *bytes)
 {
     const az_det_solver::Skip &k = s->sk;
     if (!k.attached) return false;
@@ -305,13 +304,7 @@ bool skip_train_fetch(az_det_solver *s, const std::string &nm, const void **src,
     struct Ent { const char *n; const void *p; size_t b; };
     const Ent tab[] = {{"cat", k.cat, big}, {"skip_argmax", k.arg, big}, {"skip_factor", k.fac, rows * k.n * 8},
                        {"d_y", k.d_y, rows * s->C * 4}, {"d_cat", k.d_cat, big}, {"d_raw", k.d_raw, big}};
-    for (const Ent &e : tab) if (nm == e.n) { *src = e.p; *bytes = e.b; *is_param = false; return true; }
-    if (nm.size() == 4 && nm[1] == '_' && (nm[0] == 'g' || nm[0] == 'h' || nm[0] == 'w'))
-        for (int p = D_WP; p < DNALL; ++p)
-            if (nm.substr(2) == DPNAME[p]) {
-                *src = nm[0] == 'g' ? s->g[p] : (nm[0] == 'h' ? s->h[p] : s->w[p]); *bytes = s->pn[p] * 4; *is_param = true;
-                return true;
-            }
+    for (const Ent &e : tab) if (nm == e.n) { *src = e.p; *bytes = e.b; return true; }
     return false;
 }
 
@@ -334,49 +327,34 @@ int az_det_solver_attach_skip(az_det_solver *s, int n_src, const int *Cs, const 
     // the slabs: a split product never asks for more than az_det_solver_create's floor of 4M floats (pick_split: at most 256
     // tiles of 128 x 128 over all slabs; az_det_solver.hip, part_elems), an unsplit forward for rows x Cout
     const size_t part_need = (size_t)rows * Cout;
-    // (everything new first: an error leaves the trainer as it was)
-    std::vector<void *> fresh;
-    auto grab = [&](size_t bytes) -> void * {
-        void *q = nullptr;
-        if (rc != AZ_OK) return nullptr;
-        if (hipMalloc(&q, bytes + 256) != hipSuccess) { (void)hipGetLastError(); rc = AZ_ERR_HIP; return nullptr; }
-        fresh.push_back(q);
-        return q;
-    };
-    float *w2[2], *g2[2], *h2[2];
+    // (everything new is allocated behind `mark` and kept aside: an error releases it and leaves the trainer as it was)
+    const size_t mark = s->allocs.size();
     const size_t pn2[2] = {wn, Cout};
-    for (int p = 0; p < 2; ++p) { w2[p] = (float *)grab(pn2[p] * 4); g2[p] = (float *)grab(pn2[p] * 4); h2[p] = (float *)grab(pn2[p] * 4); }
-    int *geo = (int *)grab((size_t)n_src * s->maxR * 8 * 4), *arg = (int *)grab(big * 4);
-    float *cat = (float *)grab(big * 4), *d_y = (float *)grab((size_t)rows * Cout * 4), *d_cat = (float *)grab(big * 4), *d_raw = (float *)grab(big * 4);
-    double *fac = (double *)grab((size_t)rows * n_src * 8), *sqp = (double *)grab((size_t)DNALL * SQ_BLOCKS * 8);
-    float *part = part_need > s->part_elems ? (float *)grab(part_need * 4) : nullptr;
+    az_det_solver::Skip k;
+    float *part = nullptr;
+    rc = tr_alloc_params(s, D_WP, DNALL, pn2);
+#define SA(p, n) if (rc == AZ_OK) rc = tr_alloc(s, &k.p, (n))
+    SA(geo, (size_t)n_src * s->maxR * 8); SA(arg, big); SA(cat, big); SA(d_y, (size_t)rows * Cout); SA(d_cat, big); SA(d_raw, big);
+    SA(fac, (size_t)rows * n_src);
+#undef SA
+    if (rc == AZ_OK && part_need > s->part_elems) rc = tr_alloc(s, &part, part_need);
     if (rc == AZ_OK) {
-        for (int p = 0; p < 2; ++p) {
-            hipMemsetAsync(g2[p], 0, pn2[p] * 4, c->stream);
-            hipMemsetAsync(h2[p], 0, pn2[p] * 4, c->stream);
-        }
-        hipMemsetAsync(w2[1], 0, Cout * 4, c->stream);
-        hipLaunchKernelGGL(k_solver_fill_uniform, dim3(grid_for((long long)wn, 8192)), dim3(256), 0, c->stream, w2[0], (long long)wn,
+        hipLaunchKernelGGL(k_solver_fill_uniform, dim3(grid_for((long long)wn, 8192)), dim3(256), 0, c->stream, s->w[D_WP], (long long)wn,
                            sqrtf(3.0f / (float)sumC), az_layer_key(seed, 0, 16 + D_WP));
-        if (hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess) rc = AZ_ERR_HIP;
+        rc = tr_fill_params(s, D_WP, DNALL, nullptr, seed);
     }
     if (rc != AZ_OK) {
-        for (void *q : fresh) hipFree(q);
+        (void)hipGetLastError();
+        tr_release(s, mark);
         return fail(c, AZ_ERR_HIP, "az_det_solver_attach_skip: device memory or fill");
     }
-    for (void *q : fresh) s->allocs.push_back(q);
     if (part) { s->part = part; s->part_elems = part_need; }         // (the smaller slab buffer stays in allocs until destroy)
-    for (int p = 0; p < 2; ++p) {
-        s->pn[D_WP + p] = pn2[p]; s->w[D_WP + p] = w2[p]; s->g[D_WP + p] = g2[p]; s->h[D_WP + p] = h2[p];
-        s->lr_mult[D_WP + p] = p ? 2.0f : 1.0f; s->decay_mult[D_WP + p] = p ? 0.0f : 1.0f;
-    }
-    az_det_solver::Skip &k = s->sk;
+    s->np = DNALL;
     k.n = n_src; k.sumC = (int)sumC; k.gain = gain; k.eps = eps;
     int off = 0;
     for (int i = 0; i < n_src; ++i) { k.C[i] = Cs[i]; k.off[i] = off; k.scale[i] = spatial_scales[i]; off += Cs[i]; }
-    k.geo = geo; k.arg = arg; k.cat = cat; k.d_y = d_y; k.d_cat = d_cat; k.d_raw = d_raw; k.fac = fac; k.sq_part = sqp;
-    k.rows = 0; k.trained = 0; k.has_dcat = 0;
     k.attached = true;
+    s->sk = k;
     return AZ_OK;
 }
 
@@ -385,11 +363,8 @@ int az_det_solver_load_skip(az_det_solver *s, const float *Wp, const float *bp)
     if (!s) return AZ_ERR_INVALID;
     az_ctx *c = s->c;
     if (!s->sk.attached) return fail(c, AZ_ERR_STATE, "az_det_solver_load_skip: no skip front attached");
-    HIPCHK(c, hipSetDevice(c->device));
-    if (Wp) HIPCHK(c, hipMemcpyAsync(s->w[D_WP], Wp, s->pn[D_WP] * 4, hipMemcpyHostToDevice, c->stream));
-    if (bp) HIPCHK(c, hipMemcpyAsync(s->w[D_BP], bp, s->pn[D_BP] * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return AZ_OK;
+    const float *src[2] = {Wp, bp};
+    return tr_load(s, D_WP, DNALL, src);
 }
 
 int az_det_solver_read_skip(az_det_solver *s, float *Wp, float *bp)
@@ -397,11 +372,8 @@ int az_det_solver_read_skip(az_det_solver *s, float *Wp, float *bp)
     if (!s) return AZ_ERR_INVALID;
     az_ctx *c = s->c;
     if (!s->sk.attached) return fail(c, AZ_ERR_STATE, "az_det_solver_read_skip: no skip front attached");
-    HIPCHK(c, hipSetDevice(c->device));
-    if (Wp) HIPCHK(c, hipMemcpyAsync(Wp, s->w[D_WP], s->pn[D_WP] * 4, hipMemcpyDeviceToHost, c->stream));
-    if (bp) HIPCHK(c, hipMemcpyAsync(bp, s->w[D_BP], s->pn[D_BP] * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return AZ_OK;
+    float *dst[2] = {Wp, bp};
+    return tr_read(s, D_WP, DNALL, dst);
 }
 
 int az_det_solver_set_skip_hyper(az_det_solver *s, const float *lr_mult, const float *decay_mult)
@@ -438,8 +410,7 @@ int az_det_solver_step_skip(az_det_solver *s, int n_src, const int *Cs, const vo
       hipLaunchKernelGGL(k_skip_dy, dim3(grid_for((long long)rows * Cout)), dim3(256), 0, st, s->dpool, s->pool5, (long long)rows * Cout,
                          Cout, k.d_y); }
     gemm_any(s, "conv_pool5_dw", 2, k.d_y, k.cat, s->g[D_WP], Cout, k.sumC, rows, 0);
-    { Timed t(c, "bias_grads", 0);
-      hipLaunchKernelGGL(k_solver_colsum, dim3((Cout + 255) / 256), dim3(256), 0, st, k.d_y, rows, Cout, s->g[D_BP]); }
+    { Timed t(c, "bias_grads", 0); tr_colsum(s, k.d_y, rows, Cout, s->g[D_BP]); }
     bool any = false;
     if (dmaps_dev) for (int i = 0; i < k.n; ++i) any = any || dmaps_dev[i];
     if (any) {
@@ -451,19 +422,9 @@ int az_det_solver_step_skip(az_det_solver *s, int n_src, const int *Cs, const vo
             if (dmaps_dev[i]) launch_gather(c, st, a, i, k.d_raw, k.arg, k.geo, R, (float *)dmaps_dev[i]);
         k.has_dcat = 1;
     }
-    { Timed t(c, "grad_sumsq", 0);
-      for (int p = 0; p < DNALL; ++p)
-          hipLaunchKernelGGL(k_solver_sumsq, dim3(SQ_BLOCKS), dim3(256), 0, st, s->g[p], (long long)s->pn[p], k.sq_part + (size_t)p * SQ_BLOCKS);
-      hipLaunchKernelGGL(k_solver_sumsq_final, dim3(1), dim3(256), 0, st, k.sq_part, DNALL * SQ_BLOCKS, s->sq); }
-    float hl[2]; double hs = 0.0;
-    HIPCHK(c, hipMemcpyAsync(hl, s->loss, sizeof(hl), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(&hs, s->sq, sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    HIPCHK(c, hipGetLastError());
+    if ((rc = tr_grad_norm(s, DNALL, 2, losses_out, sumsq_out)) != AZ_OK) return rc;
     s->trained = any ? 2 : 1;
     k.trained = 1;
-    if (losses_out) { losses_out[0] = hl[0]; losses_out[1] = hl[1]; }
-    if (sumsq_out) *sumsq_out = hs;
     return AZ_OK;
 }
 

@@ -1516,7 +1516,6 @@ _default_ctx = None
 
 
 HEAD_KEYS = ("W6", "b6", "W71", "b71", "W72", "b72", "Was", "bas", "Wab", "bab", "Wz", "bz")
-_SOLVER_U8 = ("mask6", "mask71", "mask72")
 
 
 def dropout_mask(seed, iteration, layer, n, ratio=0.5):
@@ -1558,31 +1557,32 @@ def bf16_round(x):
     return np.where(np.isnan(x), x, r).astype(np.float32)
 
 
-class AzSolver(object):
-    """The AZ-net trainer behind conv5_3 (az_solver_*): fp32 master weights, gradients and momentum history of the head in
-    HBM; one `step` is forward + backward of a minibatch, `update` Caffe's SGD step."""
+class _Trainer(object):
+    """What the two trainers behind conv5_3 share: the handle, the parameters and hyper-parameters, the map / roi arguments
+    of a pass, `update` and the debug `fetch`.  A subclass names its C prefix, its parameters in the ABI's order, how many
+    dropout ratios it has and which saved tensors are not float32, sets `dims` and calls `_create`."""
+    _C = None               # "az_solver" / "az_det_solver"
+    KEYS = ()
+    _NDROP = 0
+    _U8, _I32, _F64 = (), ("argmax",), ()
+    _ROWS49 = ()            # saved tensors whose rows are (roi, bin)
 
-    def __init__(self, ctx, C, n6, n71, n72, max_rois=256, seed=0, head=None):
+    def _fn(self, name):
+        return getattr(self.L, self._C + "_" + name)
+
+    def _create(self, ctx, sizes, max_rois, seed, head):
         self.ctx, self.L = ctx, ctx.L
         h = ctypes.c_void_p()
-        ctx._chk(self.L.az_solver_create(ctx.h, int(C), int(n6), int(n71), int(n72), int(max_rois), int(seed) & ((1 << 64) - 1),
-                                         ctypes.byref(h)))
+        ctx._chk(self._fn("create")(ctx.h, *([int(x) for x in sizes] + [int(max_rois), int(seed) & ((1 << 64) - 1), ctypes.byref(h)])))
         self.h = h
-        self.dims = dict(C=int(C), n6=int(n6), n71=int(n71), n72=int(n72), K6=int(C) * 49)
         self.max_rois = int(max_rois)
         self.last_rows = 0
         if head is not None:
             self.load(head)
 
-    def _shapes(self):
-        d = self.dims
-        return {"W6": (d["n6"], d["K6"]), "b6": (d["n6"],), "W71": (d["n71"], d["n6"]), "b71": (d["n71"],),
-                "W72": (d["n72"], d["n6"]), "b72": (d["n72"],), "Was": (11, d["n71"]), "bas": (11,),
-                "Wab": (44, d["n71"]), "bab": (44,), "Wz": (1, d["n72"]), "bz": (1,)}
-
     def close(self):
         if getattr(self, "h", None) and getattr(self.ctx, "h", None):
-            self.L.az_solver_destroy(self.h)
+            self._fn("destroy")(self.h)
         self.h = None
 
     def __del__(self):
@@ -1592,36 +1592,25 @@ class AzSolver(object):
             pass
 
     def load(self, head):
-        """head: {name: Caffe-layout array} for any subset of HEAD_KEYS."""
+        """head: {name: Caffe-layout array} for any subset of KEYS."""
         shp = self._shapes()
-        arrs = []
-        for k in HEAD_KEYS:
-            if k in head:
-                a = _f32(head[k]).reshape(shp[k])
-                arrs.append(a)
-            else:
-                arrs.append(None)
-        self.ctx._chk(self.L.az_solver_load(self.h, *[_p(a, ctypes.c_float) if a is not None else None for a in arrs]))
+        arrs = [_f32(head[k]).reshape(shp[k]) if k in head else None for k in self.KEYS]
+        self.ctx._chk(self._fn("load")(self.h, *[_p(a, ctypes.c_float) if a is not None else None for a in arrs]))
 
     def read(self):
-        out = {k: np.empty(v, dtype=np.float32) for k, v in self._shapes().items()}
-        self.ctx._chk(self.L.az_solver_read(self.h, *[_p(out[k], ctypes.c_float) for k in HEAD_KEYS]))
+        shp = self._shapes()
+        out = {k: np.empty(shp[k], dtype=np.float32) for k in self.KEYS}
+        self.ctx._chk(self._fn("read")(self.h, *[_p(out[k], ctypes.c_float) for k in self.KEYS]))
         return out
 
     def set_hyper(self, lr_mult=None, decay_mult=None, dropout_ratio=None):
-        def arr(v, n):
-            if v is None:
-                return None, None
-            a = _f32(v).reshape(n)
-            return a, _p(a, ctypes.c_float)
-        a, pa = arr(lr_mult, 12)
-        b, pb = arr(decay_mult, 12)
-        c, pc = arr(dropout_ratio, 3)
-        self.ctx._chk(self.L.az_solver_set_hyper(self.h, pa, pb, pc))
+        arrs = [None if v is None else _f32(v).reshape(n)
+                for v, n in ((lr_mult, len(self.KEYS)), (decay_mult, len(self.KEYS)), (dropout_ratio, self._NDROP))]
+        self.ctx._chk(self._fn("set_hyper")(self.h, *[None if a is None else _p(a, ctypes.c_float) for a in arrs]))
 
     def set_precision(self, precision):
-        """AZ_TRAIN_FP32 (0) or AZ_TRAIN_BF16 (1): the operands of every matrix product from the next step on (az_solver_set_precision)."""
-        self.ctx._chk(self.L.az_solver_set_precision(self.h, int(precision)))
+        """AZ_TRAIN_FP32 (0) or AZ_TRAIN_BF16 (1): the operands of every matrix product from the next step on (*_set_precision)."""
+        self.ctx._chk(self._fn("set_precision")(self.h, int(precision)))
 
     def _map(self, conv):
         """(pointer, N, H, W, channels_last) of a float32 CUDA tensor [N,C,H,W] in either memory format."""
@@ -1636,78 +1625,100 @@ class AzSolver(object):
             raise AzError(AZ_ERR_INVALID, "conv5_3 must be contiguous or channels_last")
         return ctypes.c_void_p(conv.data_ptr()), N, H, W, cl
 
-    def step(self, conv, rois, adj_labels, adj_targets, adj_loss_weights, zoom_labels, seed, iteration, dmap=None):
-        """Forward + backward of one minibatch.  conv: CUDA tensor [N,C,H,W]; dmap: None or a CUDA tensor of conv's shape and
-        memory format that receives d loss / d conv5_3.  Returns (losses [zoom, adj, bbox] f32, sum of squares of the head's
-        gradients)."""
+    def _pass_args(self, conv, rois, dmap=None):
+        """The leading arguments of *_step / *_forward_test (map, rois [R,5], R), the rois array that backs them, and the
+        pointer of dmap (None, or a CUDA tensor of conv's shape and memory format); waits for conv's stream."""
         import torch
         ptr, N, H, W, cl = self._map(conv)
         rois = _f32(rois).reshape(-1, 5)
-        R = rois.shape[0]
-        al, at, aw = _f32(adj_labels).reshape(R, 11), _f32(adj_targets).reshape(R, 44), _f32(adj_loss_weights).reshape(R, 44)
-        zl = _f32(zoom_labels).reshape(R)
         dptr = None
         if dmap is not None:
             assert dmap.is_cuda and dmap.dtype == conv.dtype and dmap.shape == conv.shape and dmap.stride() == conv.stride()
             dptr = ctypes.c_void_p(dmap.data_ptr())
         torch.cuda.current_stream(conv.device).synchronize()
-        losses = np.zeros(3, dtype=np.float32)
+        return (ptr, N, H, W, cl, _p(rois, ctypes.c_float), rois.shape[0]), rois, dptr
+
+    def _step(self, fn, lead, targets, seed, iteration, nloss, dptr):
+        """fn(handle, lead ..., targets ..., seed, iteration, losses, sumsq, dptr): (losses f32 [nloss], sum of squares)."""
+        losses = np.zeros(nloss, dtype=np.float32)
         sq = ctypes.c_double(0.0)
         f = ctypes.c_float
-        self.ctx._chk(self.L.az_solver_step(self.h, ptr, N, H, W, cl, _p(rois, f), R, _p(al, f), _p(at, f), _p(aw, f), _p(zl, f),
-                                            int(seed) & ((1 << 64) - 1), int(iteration), _p(losses, f), ctypes.byref(sq), dptr))
-        self.last_rows = R
+        self.ctx._chk(fn(self.h, *(list(lead) + [_p(t, f) for t in targets] +
+                                   [int(seed) & ((1 << 64) - 1), int(iteration), _p(losses, f), ctypes.byref(sq), dptr])))
+        self.last_rows = lead[-1]
         return losses, float(sq.value)
 
+    def _forward(self, fn, lead, outs):
+        """fn(handle, lead ..., outs ...): the filled float32 arrays `outs`."""
+        self.ctx._chk(fn(self.h, *(list(lead) + [_p(o, ctypes.c_float) for o in outs])))
+        self.last_rows = lead[-1]
+        return outs
+
     def update(self, rate, momentum, weight_decay, clip_scale=1.0):
-        self.ctx._chk(self.L.az_solver_update(self.h, float(rate), float(momentum), float(weight_decay), float(clip_scale)))
+        self.ctx._chk(self._fn("update")(self.h, float(rate), float(momentum), float(weight_decay), float(clip_scale)))
+
+    def fetch(self, name):
+        """A saved tensor of the last pass by name (*_fetch), shaped."""
+        fn = self._fn("fetch")
+        n = ctypes.c_longlong(0)
+        self.ctx._chk(fn(self.h, name.encode(), None, 0, ctypes.byref(n)))
+        dt = (np.uint8 if name in self._U8 else np.int32 if name in self._I32 else np.float64 if name in self._F64 else np.float32)
+        out = np.empty(n.value // np.dtype(dt).itemsize, dtype=dt)
+        self.ctx._chk(fn(self.h, name.encode(), out.ctypes.data_as(ctypes.c_void_p), n.value, ctypes.byref(n)))
+        shp = self._shapes()
+        if len(name) > 2 and name[1] == "_" and name[2:] in shp:
+            return out.reshape(shp[name[2:]])
+        rows = self.last_rows * (49 if name in self._ROWS49 else 1)
+        return out.reshape(rows, -1) if rows else out
+
+
+class AzSolver(_Trainer):
+    """The AZ-net trainer behind conv5_3 (az_solver_*): fp32 master weights, gradients and momentum history of the head in
+    HBM; one `step` is forward + backward of a minibatch, `update` Caffe's SGD step."""
+    _C, KEYS, _NDROP, _U8 = "az_solver", HEAD_KEYS, 3, ("mask6", "mask71", "mask72")
+
+    def __init__(self, ctx, C, n6, n71, n72, max_rois=256, seed=0, head=None):
+        self.dims = dict(C=int(C), n6=int(n6), n71=int(n71), n72=int(n72), K6=int(C) * 49)
+        self._create(ctx, (C, n6, n71, n72), max_rois, seed, head)
+
+    def _shapes(self):
+        d = self.dims
+        return {"W6": (d["n6"], d["K6"]), "b6": (d["n6"],), "W71": (d["n71"], d["n6"]), "b71": (d["n71"],),
+                "W72": (d["n72"], d["n6"]), "b72": (d["n72"],), "Was": (11, d["n71"]), "bas": (11,),
+                "Wab": (44, d["n71"]), "bab": (44,), "Wz": (1, d["n72"]), "bz": (1,)}
+
+    def step(self, conv, rois, adj_labels, adj_targets, adj_loss_weights, zoom_labels, seed, iteration, dmap=None):
+        """Forward + backward of one minibatch.  conv: CUDA tensor [N,C,H,W]; dmap: None or a CUDA tensor of conv's shape and
+        memory format that receives d loss / d conv5_3.  Returns (losses [zoom, adj, bbox] f32, sum of squares of the head's
+        gradients)."""
+        lead, _rois, dptr = self._pass_args(conv, rois, dmap)
+        R = lead[-1]
+        targets = (_f32(adj_labels).reshape(R, 11), _f32(adj_targets).reshape(R, 44), _f32(adj_loss_weights).reshape(R, 44),
+                   _f32(zoom_labels).reshape(R))
+        return self._step(self.L.az_solver_step, lead, targets, seed, iteration, 3, dptr)
 
     def forward_test(self, conv, rois):
         """TEST-phase forward (dropout off): raw (zoom_score [R], adj_score [R,11], adj_bbox [R,44])."""
-        import torch
-        ptr, N, H, W, cl = self._map(conv)
-        rois = _f32(rois).reshape(-1, 5)
-        R = rois.shape[0]
-        z, a, b = np.empty(R, np.float32), np.empty((R, 11), np.float32), np.empty((R, 44), np.float32)
-        torch.cuda.current_stream(conv.device).synchronize()
-        f = ctypes.c_float
-        self.ctx._chk(self.L.az_solver_forward_test(self.h, ptr, N, H, W, cl, _p(rois, f), R, _p(z, f), _p(a, f), _p(b, f)))
-        self.last_rows = R
-        return z, a, b
-
-    def fetch(self, name):
-        """A saved tensor of the last pass by name (az_solver_fetch), shaped."""
-        n = ctypes.c_longlong(0)
-        self.ctx._chk(self.L.az_solver_fetch(self.h, name.encode(), None, 0, ctypes.byref(n)))
-        dt = np.uint8 if name in _SOLVER_U8 else (np.int32 if name == "argmax" else np.float32)
-        out = np.empty(n.value // np.dtype(dt).itemsize, dtype=dt)
-        self.ctx._chk(self.L.az_solver_fetch(self.h, name.encode(), out.ctypes.data_as(ctypes.c_void_p), n.value, ctypes.byref(n)))
-        if len(name) > 2 and name[1] == "_" and name[2:] in HEAD_KEYS:
-            return out.reshape(self._shapes()[name[2:]])
-        return out.reshape(self.last_rows, -1) if self.last_rows else out
+        lead, _rois, _ = self._pass_args(conv, rois)
+        R = lead[-1]
+        return self._forward(self.L.az_solver_forward_test, lead,
+                             (np.empty(R, np.float32), np.empty((R, 11), np.float32), np.empty((R, 44), np.float32)))
 
 
 DET_HEAD_KEYS = ("W6", "b6", "W7", "b7", "Wc", "bc", "Wb", "bb")
 SKIP_KEYS = ("Wp", "bp")                                     # conv_pool5 of an attached skip front
-_SKIP_ROW_TENSORS = ("cat", "skip_argmax", "skip_factor", "d_y", "d_cat", "d_raw")      # rows (roi, bin)
-_DET_SOLVER_U8 = ("mask6", "mask7")
 
 
-class AzDetSolver(object):
+class AzDetSolver(_Trainer):
     """The detection-net trainer behind conv5_3 (az_det_solver_*): fc6 -> fc7 -> {cls_score, bbox_pred} with fp32 master
     weights, gradients and momentum history in HBM; `step` is forward + backward of a minibatch, `update` Caffe's SGD step."""
+    _C, KEYS, _NDROP, _U8 = "az_det_solver", DET_HEAD_KEYS, 2, ("mask6", "mask7")
+    _I32, _F64 = ("argmax", "skip_argmax"), ("skip_factor",)
+    _ROWS49 = ("cat", "skip_argmax", "skip_factor", "d_y", "d_cat", "d_raw")
 
     def __init__(self, ctx, C, n6, n7, num_classes, max_rois=256, seed=0, head=None):
-        self.ctx, self.L = ctx, ctx.L
-        h = ctypes.c_void_p()
-        ctx._chk(self.L.az_det_solver_create(ctx.h, int(C), int(n6), int(n7), int(num_classes), int(max_rois),
-                                             int(seed) & ((1 << 64) - 1), ctypes.byref(h)))
-        self.h = h
         self.dims = dict(C=int(C), n6=int(n6), n7=int(n7), ncls=int(num_classes), K6=int(C) * 49)
-        self.max_rois = int(max_rois)
-        self.last_rows = 0
-        if head is not None:
-            self.load(head)
+        self._create(ctx, (C, n6, n7, num_classes), max_rois, seed, head)
 
     def _shapes(self):
         d = self.dims
@@ -1716,83 +1727,26 @@ class AzDetSolver(object):
         shp.update(self._skip_shapes())
         return shp
 
-    def close(self):
-        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
-            self.L.az_det_solver_destroy(self.h)
-        self.h = None
+    def _targets(self, R, labels, bbox_targets, bbox_loss_weights):
+        nb = 4 * self.dims["ncls"]
+        return _f32(labels).reshape(R), _f32(bbox_targets).reshape(R, nb), _f32(bbox_loss_weights).reshape(R, nb)
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def load(self, head):
-        """head: {name: Caffe-layout array} for any subset of DET_HEAD_KEYS."""
-        shp = self._shapes()
-        arrs = [_f32(head[k]).reshape(shp[k]) if k in head else None for k in DET_HEAD_KEYS]
-        self.ctx._chk(self.L.az_det_solver_load(self.h, *[_p(a, ctypes.c_float) if a is not None else None for a in arrs]))
-
-    def read(self):
-        shp = self._shapes()
-        out = {k: np.empty(shp[k], dtype=np.float32) for k in DET_HEAD_KEYS}
-        self.ctx._chk(self.L.az_det_solver_read(self.h, *[_p(out[k], ctypes.c_float) for k in DET_HEAD_KEYS]))
-        return out
-
-    def set_hyper(self, lr_mult=None, decay_mult=None, dropout_ratio=None):
-        def arr(v, n):
-            if v is None:
-                return None, None
-            a = _f32(v).reshape(n)
-            return a, _p(a, ctypes.c_float)
-        a, pa = arr(lr_mult, 8)
-        b, pb = arr(decay_mult, 8)
-        c, pc = arr(dropout_ratio, 2)
-        self.ctx._chk(self.L.az_det_solver_set_hyper(self.h, pa, pb, pc))
-
-    def set_precision(self, precision):
-        """AZ_TRAIN_FP32 (0) or AZ_TRAIN_BF16 (1): the operands of every matrix product from the next step on (az_det_solver_set_precision)."""
-        self.ctx._chk(self.L.az_det_solver_set_precision(self.h, int(precision)))
-
-    _map = AzSolver._map
+    def _outs(self, R):
+        K = self.dims["ncls"]
+        return np.empty((R, K), np.float32), np.empty((R, 4 * K), np.float32)
 
     def step(self, conv, rois, labels, bbox_targets, bbox_loss_weights, seed, iteration, dmap=None):
         """Forward + backward of one minibatch.  conv: CUDA tensor [N,C,H,W]; dmap: None or a CUDA tensor of conv's shape and
         memory format that receives d loss / d conv5_3.  Returns (losses [cls, bbox] f32, sum of squares of the head's
         gradients)."""
-        import torch
-        ptr, N, H, W, cl = self._map(conv)
-        rois = _f32(rois).reshape(-1, 5)
-        R, nb = rois.shape[0], 4 * self.dims["ncls"]
-        lab, bt, bw = _f32(labels).reshape(R), _f32(bbox_targets).reshape(R, nb), _f32(bbox_loss_weights).reshape(R, nb)
-        dptr = None
-        if dmap is not None:
-            assert dmap.is_cuda and dmap.dtype == conv.dtype and dmap.shape == conv.shape and dmap.stride() == conv.stride()
-            dptr = ctypes.c_void_p(dmap.data_ptr())
-        torch.cuda.current_stream(conv.device).synchronize()
-        losses = np.zeros(2, dtype=np.float32)
-        sq = ctypes.c_double(0.0)
-        f = ctypes.c_float
-        self.ctx._chk(self.L.az_det_solver_step(self.h, ptr, N, H, W, cl, _p(rois, f), R, _p(lab, f), _p(bt, f), _p(bw, f),
-                                                int(seed) & ((1 << 64) - 1), int(iteration), _p(losses, f), ctypes.byref(sq), dptr))
-        self.last_rows = R
-        return losses, float(sq.value)
-
-    def update(self, rate, momentum, weight_decay, clip_scale=1.0):
-        self.ctx._chk(self.L.az_det_solver_update(self.h, float(rate), float(momentum), float(weight_decay), float(clip_scale)))
+        lead, _rois, dptr = self._pass_args(conv, rois, dmap)
+        targets = self._targets(lead[-1], labels, bbox_targets, bbox_loss_weights)
+        return self._step(self.L.az_det_solver_step, lead, targets, seed, iteration, 2, dptr)
 
     def forward_test(self, conv, rois):
         """TEST-phase forward (dropout off): (cls_prob [R, ncls], raw bbox_pred [R, 4 ncls])."""
-        import torch
-        ptr, N, H, W, cl = self._map(conv)
-        rois = _f32(rois).reshape(-1, 5)
-        R, K = rois.shape[0], self.dims["ncls"]
-        p, b = np.empty((R, K), np.float32), np.empty((R, 4 * K), np.float32)
-        torch.cuda.current_stream(conv.device).synchronize()
-        f = ctypes.c_float
-        self.ctx._chk(self.L.az_det_solver_forward_test(self.h, ptr, N, H, W, cl, _p(rois, f), R, _p(p, f), _p(b, f)))
-        self.last_rows = R
-        return p, b
+        lead, _rois, _ = self._pass_args(conv, rois)
+        return self._forward(self.L.az_det_solver_forward_test, lead, self._outs(lead[-1]))
 
     # ---- the skip-connection front (az_det_solver_*_skip) ----
     def attach_skip(self, Cs, scales, gain=1000.0, eps=1e-10, seed=0, front=None):
@@ -1864,48 +1818,25 @@ class AzDetSolver(object):
         torch.cuda.current_stream(maps[0].device).synchronize()
         return n, Cs, ptrs, Hs, Ws, N, cl, dptrs
 
+    def _skip_args(self, maps, rois, dmaps=None):
+        """The leading arguments of *_step_skip / *_forward_test_skip, the arrays that back them, and dmaps' pointers."""
+        n, Cs, ptrs, Hs, Ws, N, cl, dptrs = self._maps(maps, dmaps)
+        rois = _f32(rois).reshape(-1, 5)
+        f, ci = ctypes.c_float, ctypes.c_int
+        return (n, _p(Cs, ci), ptrs, _p(Hs, ci), _p(Ws, ci), N, cl, _p(rois, f), rois.shape[0]), (Cs, Hs, Ws, rois), dptrs
+
     def step_skip(self, maps, rois, labels, bbox_targets, bbox_loss_weights, seed, iteration, dmaps=None):
         """Forward + backward of one minibatch through the skip front and the head.  maps: CUDA tensors [N, C_i, H_i, W_i] in
         concat order; dmaps: None, or a list with, per map, None or a tensor of the map's shape and memory format that
         receives d loss / d map.  Returns (losses [cls, bbox] f32, sum of squares of all ten gradients)."""
-        n, Cs, ptrs, Hs, Ws, N, cl, dptrs = self._maps(maps, dmaps)
-        rois = _f32(rois).reshape(-1, 5)
-        R, nb = rois.shape[0], 4 * self.dims["ncls"]
-        lab, bt, bw = _f32(labels).reshape(R), _f32(bbox_targets).reshape(R, nb), _f32(bbox_loss_weights).reshape(R, nb)
-        losses = np.zeros(2, dtype=np.float32)
-        sq = ctypes.c_double(0.0)
-        f, ci = ctypes.c_float, ctypes.c_int
-        self.ctx._chk(self.L.az_det_solver_step_skip(self.h, n, _p(Cs, ci), ptrs, _p(Hs, ci), _p(Ws, ci), N, cl, _p(rois, f), R,
-                                                     _p(lab, f), _p(bt, f), _p(bw, f), int(seed) & ((1 << 64) - 1), int(iteration),
-                                                     _p(losses, f), ctypes.byref(sq), dptrs))
-        self.last_rows = R
-        return losses, float(sq.value)
+        lead, _keep, dptrs = self._skip_args(maps, rois, dmaps)
+        targets = self._targets(lead[-1], labels, bbox_targets, bbox_loss_weights)
+        return self._step(self.L.az_det_solver_step_skip, lead, targets, seed, iteration, 2, dptrs)
 
     def forward_test_skip(self, maps, rois):
         """TEST-phase forward of the skip net: (cls_prob [R, ncls], raw bbox_pred [R, 4 ncls])."""
-        n, Cs, ptrs, Hs, Ws, N, cl, _ = self._maps(maps)
-        rois = _f32(rois).reshape(-1, 5)
-        R, K = rois.shape[0], self.dims["ncls"]
-        p, b = np.empty((R, K), np.float32), np.empty((R, 4 * K), np.float32)
-        f, ci = ctypes.c_float, ctypes.c_int
-        self.ctx._chk(self.L.az_det_solver_forward_test_skip(self.h, n, _p(Cs, ci), ptrs, _p(Hs, ci), _p(Ws, ci), N, cl,
-                                                             _p(rois, f), R, _p(p, f), _p(b, f)))
-        self.last_rows = R
-        return p, b
-
-    def fetch(self, name):
-        """A saved tensor of the last pass by name (az_det_solver_fetch), shaped."""
-        n = ctypes.c_longlong(0)
-        self.ctx._chk(self.L.az_det_solver_fetch(self.h, name.encode(), None, 0, ctypes.byref(n)))
-        dt = np.uint8 if name in _DET_SOLVER_U8 else (np.int32 if name in ("argmax", "skip_argmax") else
-                                                      (np.float64 if name == "skip_factor" else np.float32))
-        out = np.empty(n.value // np.dtype(dt).itemsize, dtype=dt)
-        self.ctx._chk(self.L.az_det_solver_fetch(self.h, name.encode(), out.ctypes.data_as(ctypes.c_void_p), n.value, ctypes.byref(n)))
-        if len(name) > 2 and name[1] == "_" and name[2:] in DET_HEAD_KEYS + SKIP_KEYS:
-            return out.reshape(self._shapes()[name[2:]])
-        if name in _SKIP_ROW_TENSORS:
-            return out.reshape(self.last_rows * 49, -1) if self.last_rows else out
-        return out.reshape(self.last_rows, -1) if self.last_rows else out
+        lead, _keep, _ = self._skip_args(maps, rois)
+        return self._forward(self.L.az_det_solver_forward_test_skip, lead, self._outs(lead[-1]))
 
 
 def skip_pool_bwd_unit(ctx, maps, scales, rois, d_raw=None, channels_last=False, want=None):
