@@ -9,6 +9,9 @@ BLOB_NAMES = ("data", "rois", "adj_labels", "adj_targets", "adj_loss_weights", "
 
 
 class AZDataLayer(object):
+    """The shuffling layer, written once: roi_data_layer.layer.RoIDataLayer is this class with its own get_minibatch."""
+    get_minibatch = staticmethod(get_minibatch)
+
     def __init__(self, num_classes=None, ctx=None):
         self._num_classes = int(num_classes if num_classes is not None else cfg.SEAR.NUM_SUBREG)
         self._ctx = ctx
@@ -32,5 +35,5 @@ class AZDataLayer(object):
 
     def forward(self):
         db_inds = self._get_next_minibatch_inds()
-        blobs = get_minibatch([self._roidb[i] for i in db_inds], self._num_classes, self._ctx)
+        blobs = self.get_minibatch([self._roidb[i] for i in db_inds], self._num_classes, self._ctx)
         return {k: np.asarray(v).astype(np.float32, copy=False) for k, v in blobs.items()}

@@ -229,27 +229,25 @@ def resolve_train_net(solver_path, train_net):
 
 
 # ---- writers ------------------------------------------------------------------------------------------------------------
-def layer_table(frozen=("conv1_1", "conv1_2", "conv2_1", "conv2_2"), dropout=0.5):
-    """The AZ-net's learnable layers as rows (name, type, lr_mult w, lr_mult b, decay_mult w, decay_mult b, std, dropout):
-    train.prototxt freezes conv1_1 .. conv2_2, the shared variant all thirteen convolutions."""
+def _layer_rows(heads, filler_std, dropout_of, frozen, dropout):
     rows = []
     for n in CONV_LAYERS:
         f = n in frozen
         rows.append((n, "Convolution", 0.0 if f else 1.0, 0.0 if f else 2.0, 0.0 if f else 1.0, 0.0, None, None))
-    for n in HEAD_LAYERS:
-        rows.append((n, "InnerProduct", 1.0, 2.0, 1.0, 0.0, FILLER_STD[n], dropout if n in DROPOUT_OF else None))
+    for n in heads:
+        rows.append((n, "InnerProduct", 1.0, 2.0, 1.0, 0.0, filler_std[n], dropout if n in dropout_of else None))
     return rows
+
+
+def layer_table(frozen=("conv1_1", "conv1_2", "conv2_1", "conv2_2"), dropout=0.5):
+    """The AZ-net's learnable layers as rows (name, type, lr_mult w, lr_mult b, decay_mult w, decay_mult b, std, dropout):
+    train.prototxt freezes conv1_1 .. conv2_2, the shared variant all thirteen convolutions."""
+    return _layer_rows(HEAD_LAYERS, FILLER_STD, DROPOUT_OF, frozen, dropout)
 
 
 def det_layer_table(frozen=("conv1_1", "conv1_2", "conv2_1", "conv2_2"), dropout=0.5):
     """The detection net's learnable layers as layer_table's rows: frcnn/train.prototxt freezes conv1_1 .. conv2_2."""
-    rows = []
-    for n in CONV_LAYERS:
-        f = n in frozen
-        rows.append((n, "Convolution", 0.0 if f else 1.0, 0.0 if f else 2.0, 0.0 if f else 1.0, 0.0, None, None))
-    for n in DET_HEAD_LAYERS:
-        rows.append((n, "InnerProduct", 1.0, 2.0, 1.0, 0.0, DET_FILLER_STD[n], dropout if n in DET_DROPOUT_OF else None))
-    return rows
+    return _layer_rows(DET_HEAD_LAYERS, DET_FILLER_STD, DET_DROPOUT_OF, frozen, dropout)
 
 
 def skip_layer_table(frozen=CONV_LAYERS, dropout=0.5):

@@ -20,6 +20,19 @@ THRESH = [
     ("--thresh", "thresh_file", "file that stores the zoom threshold (pickle)", None, str),
     ("--tz", "tz", "zoom threshold given directly (instead of --thresh)", None, float),
 ]
+# tools/train_az_net.py and tools/train_det_net.py: the reference's flags of both, and (behind each tool's own) the extensions of both
+TRAIN = [
+    ("--solver", "solver", "solver prototxt", None, str),
+    ("--iters", "max_iters", "number of iterations to train", 40000, int),
+    ("--weights", "pretrained_model", "initialize with pretrained model weights", None, str),
+    ("--imdb", "imdb_name", "dataset to train on", "voc_2007_trainval", str),
+    ("--rand", "randomize", "randomize (do not use a fixed seed)", None, None),
+    ("--norm", "normalize", "to un-normalize (use when pre-trained model is normalized)", None, None),
+]
+TRAIN_EXT = [
+    ("--base-lr", "base_lr", "(extension, without --solver) base_lr of the written solver", 0.001, float),
+    ("--bf16", "bf16", "(extension) bf16 operands in the trainer's matrix products (cfg.TRAIN.PRECISION = 'bf16')", None, None),
+]
 
 
 def build_parser(description, tables):
@@ -72,6 +85,30 @@ def setup_cfg(args, mode):
     print("Using config:")
     pprint.pprint(cfg)
     return cfg
+
+
+def train_seed(args):
+    """What both training tools do behind setup_cfg(args, "Train"): the seed of the dropout / filler generator -- a fresh one
+    under --rand, else cfg.RNG_SEED, which then seeds numpy as well -- and cfg.TRAIN.UN_NORMALIZE from --norm."""
+    import numpy as np
+    from detect.config import cfg
+    seed = cfg.RNG_SEED
+    if args.randomize:
+        seed = int.from_bytes(os.urandom(4), "little")
+    else:
+        np.random.seed(cfg.RNG_SEED)          # fix the random seeds (numpy and the dropout / filler generator)
+    cfg.TRAIN.UN_NORMALIZE = bool(args.normalize)
+    return seed
+
+
+def reduced_net(device, seed, div, full_dims, keys):
+    """(backbone, dims) of a --net synthetic[:width_div] run: a seeded VGG16Conv5 1 / div as wide, its output normalised on
+    an image of ones, and the head's sizes `keys` of `full_dims` divided alike (at least 4)."""
+    import numpy as np
+    from aznet_hip.backbone import VGG16Conv5
+    backbone = VGG16Conv5(device="cuda:%d" % device, seed=seed, width_div=div)
+    backbone.normalize_output(np.ones((1, 3, 600, 1000), dtype=np.float32))
+    return backbone, {k: max(4, full_dims[k] // div) for k in keys}
 
 
 def ranks():

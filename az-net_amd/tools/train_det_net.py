@@ -20,25 +20,16 @@ convolutions fixed; edit its lr_mult / decay_mult and pass it through --solver t
 vgg16_fast_rcnn_skip_iter_<n>.caffemodel with conv_pool5, and load in tools/test_det_net.py under the same --cfg."""
 import _init_paths  # noqa: F401
 import os
-import pprint
 
 import numpy as np
 
 import _cli
 
-FLAGS = [
-    ("--solver", "solver", "solver prototxt", None, str),
-    ("--iters", "max_iters", "number of iterations to train", 40000, int),
-    ("--weights", "pretrained_model", "initialize with pretrained model weights", None, str),
-    ("--imdb", "imdb_name", "dataset to train on", "voc_2007_trainval", str),
-    ("--rand", "randomize", "randomize (do not use a fixed seed)", None, None),
-    ("--norm", "normalize", "to un-normalize (use when pre-trained model is normalized)", None, None),
+FLAGS = _cli.TRAIN + [
     ("--def", "prototxt", "(ignored) prototxt defining the AZ-net", None, str),
     ("--def_fc", "prototxt_fc", "(ignored) prototxt defining the AZ-net's fully connected part", None, str),
     ("--net", "caffemodel", "AZ-Net model that makes the proposals (.caffemodel / .npz) or synthetic[:width_div]", None, str),
-    ("--base-lr", "base_lr", "(extension, without --solver) base_lr of the written solver", 0.001, float),
-    ("--bf16", "bf16", "(extension) bf16 operands in the trainer's matrix products (cfg.TRAIN.PRECISION = 'bf16')", None, None),
-]
+] + _cli.TRAIN_EXT
 COMMON = [row for row in _cli.COMMON if row[0] in ("--gpu", "--cfg", "--exp")]
 
 
@@ -48,11 +39,8 @@ def synthetic_az_net(device, seed, div):
     at every scale -- boxes of all sizes, some on the objects -- where a head of large random weights throws every box to
     the image border."""
     from aznet_hip import ffi, synth
-    from aznet_hip.backbone import VGG16Conv5
     from aznet_hip.net import HipAZNet
-    backbone = VGG16Conv5(device="cuda:%d" % device, seed=seed + 1, width_div=div)
-    backbone.normalize_output(np.zeros((1, 3, 600, 1000), dtype=np.float32) + 1.0)
-    dims = {k: max(4, v // div) for k, v in synth.FULL_DIMS.items() if k != "C"}
+    backbone, dims = _cli.reduced_net(device, seed + 1, div, synth.FULL_DIMS, ("n6", "n71", "n72"))
     ctx = ffi.AzContext(device)
     sol = ffi.AzSolver(ctx, backbone.out_channels, dims["n6"], dims["n71"], dims["n72"], max_rois=8, seed=seed)
     head = sol.read()
@@ -92,28 +80,17 @@ def write_synthetic_proposals(net, imdb, seed, copies=6, amount=0.1):
 
 def main():
     args = _cli.parse("Train a detection network", [COMMON, FLAGS])
-    from detect.config import cfg, cfg_from_file, cfg_set_mode, cfg_set_path, get_output_dir
-    if args.cfg_file is not None:
-        cfg_from_file(args.cfg_file)
-    cfg_set_path(args.exp_dir)
-    cfg_set_mode("Train")
-    print("Using config:")
-    pprint.pprint(cfg)
-    seed = cfg.RNG_SEED
-    if args.randomize:
-        seed = int.from_bytes(os.urandom(4), "little")
-    else:
-        np.random.seed(cfg.RNG_SEED)          # fix the random seeds (numpy and the dropout / filler generator)
-    cfg.TRAIN.UN_NORMALIZE = bool(args.normalize)
+    cfg = _cli.setup_cfg(args, "Train")
+    seed = _cli.train_seed(args)
     if args.bf16:
         cfg.TRAIN.PRECISION = 'bf16'
 
     import torch
     torch.cuda.set_device(args.gpu_id)
     from aznet_hip import ffi, synth
-    from aznet_hip.backbone import VGG16Conv5
     from datasets.factory import get_imdb
     from detect import prototxt
+    from detect.config import get_output_dir
     from detect.train_det import get_training_roidb, train_net
 
     # the AZ-net that makes the proposals (its own context, closed before the trainer's is made)
@@ -159,9 +136,8 @@ def main():
                                            snapshot_prefix="vgg16_frcnn")
     kw = {}
     if div > 1 or (args.caffemodel.startswith("synthetic") and args.pretrained_model is None):
-        backbone = VGG16Conv5(device="cuda:%d" % args.gpu_id, seed=seed + 3, width_div=div)
-        backbone.normalize_output(np.ones((1, 3, 600, 1000), dtype=np.float32))
-        kw = dict(backbone=backbone, dims={k: max(4, v // div) for k, v in synth.FULL_DET_DIMS.items() if k in ("n6", "n7")})
+        backbone, dims = _cli.reduced_net(args.gpu_id, seed + 3, div, synth.FULL_DET_DIMS, ("n6", "n7"))
+        kw = dict(backbone=backbone, dims=dims)
     train_net(solver, imdb, output_dir, pretrained_model=args.pretrained_model, max_iters=args.max_iters, ctx=ctx,
               seed=seed, **kw)
 
