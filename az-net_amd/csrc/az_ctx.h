@@ -815,6 +815,10 @@ void az_det_solver_free_all(az_ctx *c);
 // ---- az_skip.hip --------------------------------------------------------------------------------------------------------
 // what every skip entry refuses before it enqueues anything (`who`: the entry's name); need_maps: the maps must be set
 int skip_check(az_ctx *c, const char *who, bool need_maps);
+// what a front's description must satisfy (sources, channel counts, scales, gain, eps), for the inference front, the trainer's
+// and the unit entry alike; *sumC_out: the channels in all
+int skip_front_check(az_ctx *c, const std::string &who, int n_src, const int *Cs, const float *scales, double gain, double eps,
+                     long long *sumC_out);
 // the front on the rois in c->urois (row count *Uptr, at most rows_bound): pool5 [U][49][Cout] as the head's fc6 reads it
 void skip_front_launch(az_ctx *c, const int *Uptr, int rows_bound);
 void skip_free(az_ctx *c);                // az_destroy

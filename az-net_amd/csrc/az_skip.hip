@@ -5,97 +5,47 @@
 // W6's columns are permuted to match), so the convolution is ONE plain GEMM whose rows are (roi, bin): its result, bias and
 // ReLU applied as it is stored, IS the pool5 the unchanged fc6 ... cls_prob / bbox_pred chain reads.
 //   k_skip_pool_norm  one workgroup per (roi, bin, source): window maximum per channel, sum of squares, scaled store into
-//                     the row-major `cat` [rows][sumC]
+//                     the row-major `cat` [rows][sumC].  The entry works out the bin's window (roi_window, bin_range:
+//                     az_solver_dev.h); the body is skip_pool_grn<false> (az_skip_dev.h), which the training front's
+//                     k_skip_train_pool (az_skip_train.hip) instantiates with the arg-max
 //   k_skip_conv       pool5[rows][Cout] = relu(cat . Wp^T + bp) on the fp32 matrix cores: the trainer's 128 x 128 tile
-//                     (k_solver_gemm form 0, az_trainer.hip; gemm_stage, az_solver_dev.h) with the row count read from the device, the whole K in one
-//                     pass and the bias / ReLU epilogue
+//                     (tile_fp32 / tile_store, az_solver_dev.h: k_solver_gemm form 0's own code) with the row count read from
+//                     the device, the whole K in one pass and the bias / ReLU store
 // `cat` holds AZ_SKIP_CHUNK rois (49 x sumC x 4 B each: 251 KB at the VGG16 sizes); both kernels run once per chunk over
 // the host-known bound on the row count, and rows past the device-side count leave at once.
-#include "az_solver_dev.h"
+// skip_front_check, what az_load_skip_front, az_det_solver_attach_skip and az_skip_pool_bwd_unit refuse in a front's
+// description, is defined here.
+#include "az_skip_dev.h"
 
 namespace {
 
-struct SkipSrcs {
-    const float *map[AZ_SKIP_MAX_SRC];
-    int C[AZ_SKIP_MAX_SRC], H[AZ_SKIP_MAX_SRC], W[AZ_SKIP_MAX_SRC], off[AZ_SKIP_MAX_SRC];
-    float scale[AZ_SKIP_MAX_SRC];
-    int sumC;
-};
-
-// Row `blockIdx.x` of the chunk = bin p of roi roi0 + blockIdx.x / 49; source src0 + blockIdx.y.  The window is
-// k_roi_pool's (az_head.hip): the same roundf / floorf / ceilf expressions (bin_range, az_solver_dev.h) with this source's
-// scale and map size; max() is exact, so how the cells are dealt to the threads does not show in a bit.  A lane holds
-// four consecutive channels (the maps are channel-last); with fewer than 256 channel quads the workgroup splits the
-// window's cells over 256 / quads groups and the partial maxima meet in LDS.
+// Row `blockIdx.x` of the chunk = bin p of roi roi0 + blockIdx.x / 49; source src0 + blockIdx.y, at its own scale and map size.
 __global__ void __launch_bounds__(256) k_skip_pool_norm(SkipSrcs a, int src0, const float *__restrict__ urois, const int *Uptr,
                                                         int roi0, int normalise, double gain, double eps,
                                                         float *__restrict__ cat)
 {
-    __shared__ float4 smax[256];
-    __shared__ double sred[4];
     const int row = blockIdx.x, u = roi0 + row / 49, p = row % 49;
     if (u >= *Uptr) return;
-    const int s = src0 + blockIdx.y, tid = threadIdx.x;
-    const int C = a.C[s], fH = a.H[s], fW = a.W[s], nq = C >> 2;
-    const float ss_ = a.scale[s];
-    const float *roi = urois + 5 * (size_t)u;
-    const int rsw = (int)roundf(roi[1] * ss_), rsh = (int)roundf(roi[2] * ss_);
-    const int rew = (int)roundf(roi[3] * ss_), reh = (int)roundf(roi[4] * ss_);
-    int rh = reh - rsh + 1; rh = rh < 1 ? 1 : rh;
-    int rw = rew - rsw + 1; rw = rw < 1 ? 1 : rw;
+    const int s = src0 + blockIdx.y;
+    const RoiWindow w = roi_window(urois + 5 * (size_t)u, a.scale[s]);
     const int ph = p / 7, pw = p - ph * 7;
     int hs, he, ws, we;
-    bin_range(ph, (float)rh / 7.0f, rsh, fH, &hs, &he);
-    bin_range(pw, (float)rw / 7.0f, rsw, fW, &ws, &we);
-    const bool empty = (he <= hs) || (we <= ws);
-    const int nw = we - ws, ncell = empty ? 0 : (he - hs) * nw;
-    const float *fm = a.map[s];
-    float *out = cat + (size_t)row * a.sumC + a.off[s];
-    double ssq = 0.0;
-    for (int q0 = 0; q0 < nq; q0 += 256) {
-        const int nqb = min(256, nq - q0), G = 256 / nqb;
-        const int g = tid / nqb, q = tid - g * nqb;
-        float4 m = make_float4(-FLT_MAX, -FLT_MAX, -FLT_MAX, -FLT_MAX);
-        if (g < G)
-            for (int i = g; i < ncell; i += G) {
-                const int hh = hs + i / nw, ww = ws + i % nw;
-                const float4 v = *reinterpret_cast<const float4 *>(fm + ((size_t)hh * fW + ww) * C + 4 * (q0 + q));
-                m.x = v.x > m.x ? v.x : m.x; m.y = v.y > m.y ? v.y : m.y;
-                m.z = v.z > m.z ? v.z : m.z; m.w = v.w > m.w ? v.w : m.w;
-            }
-        smax[tid] = m;
-        __syncthreads();
-        if (tid < nqb) {
-            float4 r = smax[tid];
-            for (int g2 = 1; g2 < G; ++g2) {
-                const float4 v = smax[g2 * nqb + tid];
-                r.x = v.x > r.x ? v.x : r.x; r.y = v.y > r.y ? v.y : r.y;
-                r.z = v.z > r.z ? v.z : r.z; r.w = v.w > r.w ? v.w : r.w;
-            }
-            if (empty) r = make_float4(0.f, 0.f, 0.f, 0.f);            // an empty bin pools to 0 (Caffe)
-            *reinterpret_cast<float4 *>(out + 4 * (q0 + tid)) = r;
-            ssq += (double)r.x * r.x;
-            ssq += (double)r.y * r.y;
-            ssq += (double)r.z * r.z;
-            ssq += (double)r.w * r.w;
-        }
-        __syncthreads();
-    }
-    if (!normalise) return;
-    // sum of squares over the source's channels: a fixed tree (lanes, then waves in order), so a row's bits do not depend
-    // on where it runs; in f64, as is the factor -- the stored value is gain * x / sqrt(ss + eps) rounded once
-    for (int o = 32; o > 0; o >>= 1) ssq += __shfl_down(ssq, o, 64);
-    if ((tid & 63) == 0) sred[tid >> 6] = ssq;
-    __syncthreads();
-    const double tot = ((sred[0] + sred[1]) + sred[2]) + sred[3] + eps;
-    const double f = tot > 0.0 ? gain / sqrt(tot) : 0.0;               // (all-zero vector, eps 0: zeros, never NaN)
-    for (int q = tid; q < nq; q += 256) {                              // (the quads this thread stored itself)
-        float4 r = *reinterpret_cast<float4 *>(out + 4 * q);
-        r.x = (float)((double)r.x * f); r.y = (float)((double)r.y * f);
-        r.z = (float)((double)r.z * f); r.w = (float)((double)r.w * f);
-        *reinterpret_cast<float4 *>(out + 4 * q) = r;
-    }
+    bin_range(ph, w.bh, w.rsh, a.H[s], &hs, &he);
+    bin_range(pw, w.bw, w.rsw, a.W[s], &ws, &we);
+    skip_pool_grn<false>(a.map[s], a.C[s], a.H[s], a.W[s], 1, hs, he, ws, we, cat + (size_t)row * a.sumC + a.off[s], nullptr, nullptr,
+                         gain, eps, normalise);
 }
+
+// what k_skip_conv does with an output (tile_store's functor): the column's bias, read once per column, and the ReLU
+struct BiasRelu {
+    const float *bias; float *D; int N;
+    __device__ __forceinline__ float column(int j) const { return bias[j]; }
+    __device__ __forceinline__ void operator()(int i, int j, float v, float bj) const
+    {
+        const float y = v + bj;
+        D[(long long)i * N + j] = y > 0.0f ? y : 0.0f;
+    }
+};
 
 // D[i][j] = relu(sum_k A[i][k] * B[j][k] + bias[j]), i < M, j < N: k_solver_gemm<true, true>'s tile and k order (ascending:
 // bitwise an fmaf chain per output, whatever the tile) with M = the rows of this chunk that exist on the device --
@@ -104,66 +54,14 @@ __global__ void __launch_bounds__(256) k_skip_conv(const float *__restrict__ A, 
                                                    const float *__restrict__ bias, float *__restrict__ D, const int *Uptr,
                                                    int row0, int cap, int N, int K)
 {
-    __shared__ float sA[GK * GLD];
-    __shared__ float sB[GK * GLD];
     int M = cap;
     if (Uptr) { const long long left = (long long)*Uptr * 49 - row0; M = left < cap ? (int)(left < 0 ? 0 : left) : cap; }
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int j0 = blockIdx.x * GT, i0 = blockIdx.y * GT;
     if (i0 >= M) return;
-    const int wi = (wave >> 1) * 64, wj = (wave & 1) * 64;
     az_f32x16 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int v = 0; v < 16; ++v) acc[a][b][v] = 0.0f;
-    const int lr = lane & 31, lk = lane >> 5;
-    for (int k0 = 0; k0 < K; k0 += GK) {
-        __syncthreads();
-        gemm_stage<true>(A, (long long)K, 1LL, i0, M, k0, K, sA, tid);
-        gemm_stage<true>(B, (long long)K, 1LL, j0, N, k0, K, sB, tid);
-        __syncthreads();
-#pragma unroll
-        for (int kk = 0; kk < GK; kk += 2) {
-            const float a0 = sA[(kk + lk) * GLD + wi + lr], a1 = sA[(kk + lk) * GLD + wi + 32 + lr];
-            const float b0 = sB[(kk + lk) * GLD + wj + lr], b1 = sB[(kk + lk) * GLD + wj + 32 + lr];
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-        }
-    }
-    // C/D layout of the 32x32 MFMA: col = lane & 31, row = (v & 3) + 8 * (v >> 2) + 4 * (lane >> 5)
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const int j = j0 + wj + 32 * b + lr;
-            const float bj = j < N ? bias[j] : 0.0f;
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const int i = i0 + wi + 32 * a + (v & 3) + 8 * (v >> 2) + 4 * lk;
-                if (i < M && j < N) {
-                    const float y = acc[a][b][v] + bj;
-                    D[(long long)i * N + j] = y > 0.0f ? y : 0.0f;
-                }
-            }
-        }
-}
-
-SkipSrcs skip_srcs(const az_ctx *c)
-{
-    const az_ctx::SkipFront &k = c->skip;
-    SkipSrcs a{};
-    int off = 0;
-    for (int i = 0; i < k.n; ++i) {
-        a.map[i] = k.maps[i]; a.C[i] = k.C[i]; a.H[i] = k.H[i]; a.W[i] = k.W[i]; a.off[i] = off; a.scale[i] = k.scale[i];
-        off += k.C[i];
-    }
-    a.sumC = k.sumC;
-    return a;
+    tile_fp32<true, true>(A, (long long)K, 1LL, B, (long long)K, 1LL, i0, M, j0, N, 0, K, tid, acc);
+    tile_store(acc, tid, i0, M, j0, N, BiasRelu{bias, D, N});
 }
 
 // rois per pass of the front: what `cat` holds (a context limited to fewer regions never needs more)
@@ -173,7 +71,8 @@ int skip_chunk(const az_ctx *c) { return c->maxR < AZ_SKIP_CHUNK ? c->maxR : AZ_
 void launch_pool_norm(az_ctx *c, const int *Uptr, int roi0, int n, int normalise)
 {
     const az_ctx::SkipFront &k = c->skip;
-    const SkipSrcs a = skip_srcs(c);
+    // (one image, channel-last; the builder takes the trainer ABI's untyped map pointers)
+    const SkipSrcs a = skip_srcs(k.n, k.C, k.H, k.W, (const void *const *)k.maps, /* N */ 1, /* cl */ 1, k.scale);
     if (c->profiling & 2) {
         static const char *names[AZ_SKIP_MAX_SRC] = {"skip_pool_norm_0", "skip_pool_norm_1", "skip_pool_norm_2"};
         for (int s = 0; s < k.n; ++s) {
@@ -207,6 +106,22 @@ int skip_check(az_ctx *c, const char *who, bool need_maps)
     if (c->pyr_S) return fail(c, AZ_ERR_STATE, w + ": the skip front does not read a pyramid set");
     if (need_maps && !c->skip.maps_set) return fail(c, AZ_ERR_STATE, w + ": no maps set (az_set_skip_maps_dev_nhwc)");
     join_s2(c);
+    return AZ_OK;
+}
+
+int skip_front_check(az_ctx *c, const std::string &who, int n_src, const int *Cs, const float *scales, double gain, double eps,
+                     long long *sumC_out)
+{
+    if (n_src < 1 || n_src > AZ_SKIP_MAX_SRC || !Cs || !scales) return fail(c, AZ_ERR_INVALID, who + ": 1 to 3 sources; no null pointer");
+    long long sumC = 0;
+    for (int i = 0; i < n_src; ++i) {
+        if (Cs[i] <= 0 || (Cs[i] & 3)) return fail(c, AZ_ERR_INVALID, who + ": channel counts are positive multiples of 4");
+        if (!(scales[i] > 0.0f) || !std::isfinite(scales[i])) return fail(c, AZ_ERR_INVALID, who + ": every spatial_scale must be positive and finite");
+        sumC += Cs[i];
+    }
+    if (sumC > AZ_SKIP_MAX_SUMC) return fail(c, AZ_ERR_INVALID, who + ": more than AZ_SKIP_MAX_SUMC channels in all");
+    if (!std::isfinite(gain) || !(eps >= 0.0) || !std::isfinite(eps)) return fail(c, AZ_ERR_INVALID, who + ": gain finite, eps >= 0");
+    *sumC_out = sumC;
     return AZ_OK;
 }
 
@@ -247,18 +162,10 @@ int az_load_skip_front(az_ctx *c, int n_src, const int *Cs, const float *spatial
                        const float *Wp, const float *bp)
 {
     if (!c) return AZ_ERR_INVALID;
-    if (n_src < 1 || n_src > AZ_SKIP_MAX_SRC || !Cs || !spatial_scales || !Wp || !bp)
-        return fail(c, AZ_ERR_INVALID, "az_load_skip_front: 1 to 3 sources; no null pointer");
+    if (!Wp || !bp) return fail(c, AZ_ERR_INVALID, "az_load_skip_front: 1 to 3 sources; no null pointer");
     long long sumC = 0;
-    for (int i = 0; i < n_src; ++i) {
-        if (Cs[i] <= 0 || (Cs[i] & 3)) return fail(c, AZ_ERR_INVALID, "az_load_skip_front: channel counts are positive multiples of 4");
-        if (!(spatial_scales[i] > 0.0f) || !std::isfinite(spatial_scales[i]))
-            return fail(c, AZ_ERR_INVALID, "az_load_skip_front: every spatial_scale must be positive and finite");
-        sumC += Cs[i];
-    }
-    if (sumC > AZ_SKIP_MAX_SUMC) return fail(c, AZ_ERR_INVALID, "az_load_skip_front: more than AZ_SKIP_MAX_SUMC channels in all");
-    if (!std::isfinite(gain) || !(eps >= 0.0) || !std::isfinite(eps))
-        return fail(c, AZ_ERR_INVALID, "az_load_skip_front: gain finite, eps >= 0");
+    int rc = skip_front_check(c, "az_load_skip_front", n_src, Cs, spatial_scales, gain, eps, &sumC);
+    if (rc != AZ_OK) return rc;
     if (!c->det_loaded) return fail(c, AZ_ERR_STATE, "az_load_skip_front: az_load_det_head has not been called");
     if (c->gemm_parts) return fail(c, AZ_ERR_STATE, "az_load_skip_front: fp32 only (the 16-bit-term GEMM modes are not supported)");
     if (Cout != c->d.C) return fail(c, AZ_ERR_INVALID, "az_load_skip_front: Cout differs from the detection head's C");

@@ -1,9 +1,10 @@
 // az_skip_train.hip -- the skip-connection front of the detection net in TRAIN phase (models/COCO/VGG16_skip/frcnn/finetune
 // and frozen train nets): roi_pool3/4/5 with arg-max, roi_norm3/4/5 (GRN), concat5, scale5, conv_pool5 + relu_pool in front
 // of the detection trainer's fc6 .. losses (az_det_solver.hip), and their backward down to the three maps.
-//   k_skip_train_pool    one workgroup per (roi, bin, source): k_skip_pool_norm's arithmetic (az_skip.hip) on a batch of N
-//                        maps in either memory format; it also stores the arg-max cell of every channel (the first
-//                        maximum in row-major window order) and the row's factor f = gain / sqrt(ss + eps)
+//   k_skip_train_pool    one workgroup per (roi, bin, source): k_skip_pool_norm's body (skip_pool_grn, az_skip_dev.h: one
+//                        function, instantiated with the arg-max here) on a batch of N maps in either memory format; it
+//                        also stores the arg-max cell of every channel (the first maximum in row-major window order) and
+//                        the row's factor f = gain / sqrt(ss + eps).  The entry takes its window from geo
 //   conv_pool5 forward   cat . Wp^T: k_solver_gemm form 0, rows (roi, bin); k_skip_finish_t sums the slabs in slab order, adds
 //                        the bias, applies the ReLU and stores Caffe-flattened: pool5[r][j * 49 + p]
 //   k_skip_dy            d_y[(r, p)][j] = d_pool5[r][j * 49 + p] * (pool5 > 0): gate and transpose in one pass
@@ -11,113 +12,34 @@
 //   k_skip_grn_bwd       per (row, source): d_raw[c] = f * (d_cat[c] - y[c] * (sum_c y[c] d_cat[c]) / gain^2), the sum in f64
 //                        over a fixed tree.  (y = f x, so x * (sum_c x dy) / (ss + eps) == y * (sum_c y dy) / gain^2: `cat`
 //                        and f are enough, the raw maxima are not kept.)
-//   k_skip_pool_bwd      one thread per map cell GATHERS: the rois of its image in row order, the candidate bins in bin
-//                        order, decided by the stored arg-max.  No floating-point atomics anywhere: the same step from the
-//                        same state gives the same bits.
+//   pool backward        the trainers' gather (k_solver_roi_pool_bwd through tr_pool_gather, az_trainer.hip) with this
+//                        layout's strides, one launch per map: one thread per map cell GATHERS the rois of its image in row
+//                        order, the candidate bins in bin order, decided by the stored arg-max.  No floating-point atomics
+//                        anywhere: the same step from the same state gives the same bits.
 // cat, arg-max, d_cat and d_raw are [rows][sumC], the arg-max beside the value it belongs to: a channel-last map's
 // neighbouring threads (channels) read neighbouring words of it in the gather.
 #include "az_det_solver.h"
+#include "az_skip_dev.h"
 
 namespace {
 
-struct TrainSrcs {
-    const float *map[AZ_SKIP_MAX_SRC];
-    int C[AZ_SKIP_MAX_SRC], H[AZ_SKIP_MAX_SRC], W[AZ_SKIP_MAX_SRC], off[AZ_SKIP_MAX_SRC];
-    int sumC, n, N, cl;
-};
-
-__device__ __forceinline__ void take(float v, int cell, float &m, int &at)
-{
-    if (v > m) { m = v; at = cell; }
-}
-// the partial result of a later cell group meets an earlier one's: the larger value, among equal ones the lower cell
-__device__ __forceinline__ void meet(float v, int cell, float &m, int &at)
-{
-    if (v > m || (v == m && cell >= 0 && (at < 0 || cell < at))) { m = v; at = cell; }
-}
-
 // Row blockIdx.x = bin p of roi r = blockIdx.x / 49; source src0 + blockIdx.y.  geo [n][R][8] is k_solver_roi_geo's record at
-// the source's scale.  The window's cells are dealt to 256 / quads thread groups as k_skip_pool_norm deals them; a group
-// scans its cells in ascending order with a strict >, and the groups' results meet lowest cell first, so the arg-max is
-// the first maximum of the row-major scan, as k_solver_roi_pool picks it.  The sum of squares takes k_skip_pool_norm's
-// tree: the stored values have its bits.
-__global__ void __launch_bounds__(256) k_skip_train_pool(TrainSrcs a, int src0, const int *__restrict__ geo, int R, int normalise,
+// the source's scale: the roi's image and its window.
+__global__ void __launch_bounds__(256) k_skip_train_pool(SkipSrcs a, int src0, const int *__restrict__ geo, int R, int normalise,
                                                          double gain, double eps, float *__restrict__ cat,
                                                          int *__restrict__ arg, double *__restrict__ fac)
 {
-    __shared__ float4 smax[256];
-    __shared__ int4 sarg[256];
-    __shared__ double sred[4];
     const int row = blockIdx.x, r = row / 49, p = row % 49;
-    const int s = src0 + blockIdx.y, tid = threadIdx.x;
-    const int C = a.C[s], fH = a.H[s], fW = a.W[s], nq = C >> 2;
+    const int s = src0 + blockIdx.y;
+    const int C = a.C[s], fH = a.H[s], fW = a.W[s];
     const int *g = geo + ((size_t)s * R + r) * 8;
-    const int n = g[0];
     const int ph = p / 7, pw = p - ph * 7;
     int hs, he, ws, we;
     bin_range(ph, __int_as_float(g[5]), g[2], fH, &hs, &he);
     bin_range(pw, __int_as_float(g[6]), g[1], fW, &ws, &we);
-    const bool empty = (he <= hs) || (we <= ws);
-    const int nw = we - ws, ncell = empty ? 0 : (he - hs) * nw;
-    const float *fm = a.map[s] + (size_t)n * C * fH * fW;
     const size_t o0 = (size_t)row * a.sumC + a.off[s];
-    float *out = cat + o0;
-    int *aout = arg + o0;
-    double ssq = 0.0;
-    for (int q0 = 0; q0 < nq; q0 += 256) {
-        const int nqb = min(256, nq - q0), G = 256 / nqb;
-        const int gi = tid / nqb, q = tid - gi * nqb;
-        float4 m = make_float4(-FLT_MAX, -FLT_MAX, -FLT_MAX, -FLT_MAX);
-        int4 at = make_int4(-1, -1, -1, -1);
-        if (gi < G)
-            for (int i = gi; i < ncell; i += G) {
-                const int hh = hs + i / nw, ww = ws + i % nw, cell = hh * fW + ww;
-                const int c0 = 4 * (q0 + q);
-                float4 v;
-                if (a.cl) v = *reinterpret_cast<const float4 *>(fm + (size_t)cell * C + c0);
-                else {
-                    const size_t hw = (size_t)fH * fW;
-                    v.x = fm[(size_t)c0 * hw + cell]; v.y = fm[(size_t)(c0 + 1) * hw + cell];
-                    v.z = fm[(size_t)(c0 + 2) * hw + cell]; v.w = fm[(size_t)(c0 + 3) * hw + cell];
-                }
-                take(v.x, cell, m.x, at.x); take(v.y, cell, m.y, at.y);
-                take(v.z, cell, m.z, at.z); take(v.w, cell, m.w, at.w);
-            }
-        smax[tid] = m;
-        sarg[tid] = at;
-        __syncthreads();
-        if (tid < nqb) {
-            float4 rr = smax[tid];
-            int4 ra = sarg[tid];
-            for (int g2 = 1; g2 < G; ++g2) {
-                const float4 v = smax[g2 * nqb + tid];
-                const int4 va = sarg[g2 * nqb + tid];
-                meet(v.x, va.x, rr.x, ra.x); meet(v.y, va.y, rr.y, ra.y);
-                meet(v.z, va.z, rr.z, ra.z); meet(v.w, va.w, rr.w, ra.w);
-            }
-            if (empty) { rr = make_float4(0.f, 0.f, 0.f, 0.f); ra = make_int4(-1, -1, -1, -1); }   // an empty bin pools to 0 (Caffe)
-            *reinterpret_cast<float4 *>(out + 4 * (q0 + tid)) = rr;
-            *reinterpret_cast<int4 *>(aout + 4 * (q0 + tid)) = ra;
-            ssq += (double)rr.x * rr.x;
-            ssq += (double)rr.y * rr.y;
-            ssq += (double)rr.z * rr.z;
-            ssq += (double)rr.w * rr.w;
-        }
-        __syncthreads();
-    }
-    if (!normalise) return;
-    for (int o = 32; o > 0; o >>= 1) ssq += __shfl_down(ssq, o, 64);
-    if ((tid & 63) == 0) sred[tid >> 6] = ssq;
-    __syncthreads();
-    const double tot = ((sred[0] + sred[1]) + sred[2]) + sred[3] + eps;
-    const double f = tot > 0.0 ? gain / sqrt(tot) : 0.0;               // (all-zero vector, eps 0: zeros, never NaN)
-    if (tid == 0) fac[(size_t)row * a.n + s] = f;
-    for (int q = tid; q < nq; q += 256) {                              // (the quads this thread stored itself)
-        float4 v = *reinterpret_cast<float4 *>(out + 4 * q);
-        v.x = (float)((double)v.x * f); v.y = (float)((double)v.y * f);
-        v.z = (float)((double)v.z * f); v.w = (float)((double)v.w * f);
-        *reinterpret_cast<float4 *>(out + 4 * q) = v;
-    }
+    skip_pool_grn<true>(a.map[s] + (size_t)g[0] * C * fH * fW, C, fH, fW, a.cl, hs, he, ws, we, cat + o0, arg + o0,
+                        fac + (size_t)row * a.n + s, gain, eps, normalise);
 }
 
 // pool5[r][j * 49 + p] = relu(sum over the slabs in slab order of part[(r, p)][j] + bias[j])
@@ -148,7 +70,7 @@ __global__ void __launch_bounds__(256) k_skip_dy(const float *__restrict__ dpool
 
 // GRN + scale backward of row blockIdx.x, source blockIdx.y
 __global__ void __launch_bounds__(256) k_skip_grn_bwd(const float *__restrict__ cat, const float *__restrict__ dcat,
-                                                      const double *__restrict__ fac, TrainSrcs a, double inv_gain2,
+                                                      const double *__restrict__ fac, SkipSrcs a, double inv_gain2,
                                                       float *__restrict__ draw)
 {
     __shared__ double sred[4];
@@ -165,36 +87,6 @@ __global__ void __launch_bounds__(256) k_skip_grn_bwd(const float *__restrict__ 
     for (int c = tid; c < C; c += 256) draw[o0 + c] = (float)(f * ((double)dy[c] - (double)y[c] * k));
 }
 
-// d map of one source: k_solver_roi_pool_bwd's gather on the [rows][sumC] layout (geo: this source's records)
-__global__ void __launch_bounds__(256) k_skip_pool_bwd(const float *__restrict__ draw, const int *__restrict__ arg,
-                                                       const int *__restrict__ geo, int R, MapView m, int sumC, int off,
-                                                       float *__restrict__ dmap)
-{
-    const long long total = (long long)m.N * m.C * m.H * m.W;
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= total) return;
-    int n, c, h, w;
-    if (m.cl) { c = (int)(idx % m.C); w = (int)((idx / m.C) % m.W); h = (int)((idx / ((long long)m.C * m.W)) % m.H); n = (int)(idx / ((long long)m.C * m.W * m.H)); }
-    else { w = (int)(idx % m.W); h = (int)((idx / m.W) % m.H); c = (int)((idx / ((long long)m.W * m.H)) % m.C); n = (int)(idx / ((long long)m.W * m.H * m.C)); }
-    const int cell = h * m.W + w;
-    float sum = 0.0f;
-    for (int r = 0; r < R; ++r) {
-        const int *g = geo + 8 * (size_t)r;
-        if (g[0] != n) continue;
-        const float bh = __int_as_float(g[5]), bw = __int_as_float(g[6]);
-        int p0 = (int)floorf((float)(h - g[2]) / bh) - 1, p1 = (int)ceilf((float)(h - g[2] + 1) / bh) + 1;
-        int q0 = (int)floorf((float)(w - g[1]) / bw) - 1, q1 = (int)ceilf((float)(w - g[1] + 1) / bw) + 1;
-        p0 = min(max(p0, 0), 7); p1 = min(max(p1, 0), 7); q0 = min(max(q0, 0), 7); q1 = min(max(q1, 0), 7);
-        const size_t base = (size_t)r * 49 * sumC + off + c;
-        for (int ph = p0; ph < p1; ++ph)
-            for (int pw = q0; pw < q1; ++pw) {
-                const size_t o = base + (size_t)(ph * 7 + pw) * sumC;
-                if (arg[o] == cell) sum += draw[o];
-            }
-    }
-    dmap[idx] = sum;
-}
-
 // Caffe's xavier filler (fan_in): uniform in +-a from the 24 high bits of the element's word
 __global__ void __launch_bounds__(256) k_solver_fill_uniform(float *__restrict__ w, long long n, float a, unsigned long long key)
 {
@@ -203,22 +95,6 @@ __global__ void __launch_bounds__(256) k_solver_fill_uniform(float *__restrict__
         const float u = ((float)(unsigned)(b >> 40) + 0.5f) * (1.0f / 16777216.0f);
         w[e] = a * (2.0f * u - 1.0f);
     }
-}
-
-int check_front_args(az_ctx *c, const std::string &who, int n_src, const int *Cs, const float *scales, double gain, double eps,
-                     long long *sumC_out)
-{
-    if (n_src < 1 || n_src > AZ_SKIP_MAX_SRC || !Cs || !scales) return fail(c, AZ_ERR_INVALID, who + ": 1 to 3 sources; no null pointer");
-    long long sumC = 0;
-    for (int i = 0; i < n_src; ++i) {
-        if (Cs[i] <= 0 || (Cs[i] & 3)) return fail(c, AZ_ERR_INVALID, who + ": channel counts are positive multiples of 4");
-        if (!(scales[i] > 0.0f) || !std::isfinite(scales[i])) return fail(c, AZ_ERR_INVALID, who + ": every spatial_scale must be positive and finite");
-        sumC += Cs[i];
-    }
-    if (sumC > AZ_SKIP_MAX_SUMC) return fail(c, AZ_ERR_INVALID, who + ": more than AZ_SKIP_MAX_SUMC channels in all");
-    if (!std::isfinite(gain) || !(eps >= 0.0) || !std::isfinite(eps)) return fail(c, AZ_ERR_INVALID, who + ": gain finite, eps >= 0");
-    *sumC_out = sumC;
-    return AZ_OK;
 }
 
 int check_maps(az_ctx *c, const std::string &who, int n_src, const int *Cs, const void *const *maps, const int *Hs, const int *Ws, int N)
@@ -238,22 +114,12 @@ void launch_geo(hipStream_t st, const float *rois_dev, int R, int n, const float
     for (int i = 0; i < n; ++i) tr_roi_geo(st, rois_dev, R, scales[i], geo + (size_t)i * R * 8);
 }
 
-void launch_gather(az_ctx *c, hipStream_t st, const TrainSrcs &a, int i, const float *draw, const int *arg, const int *geo, int R, float *dmap)
+// d map of source i: the trainers' gather on the [rows][sumC] layout (geo: this source's records)
+void launch_gather(az_ctx *c, const SkipSrcs &a, int i, const float *draw, const int *arg, const int *geo, int R, float *dmap)
 {
     static const char *names[AZ_SKIP_MAX_SRC] = {"skip_pool_bwd_0", "skip_pool_bwd_1", "skip_pool_bwd_2"};
     const MapView m{a.N, a.C[i], a.H[i], a.W[i], a.cl};
-    Timed t(c, names[i], 0);
-    hipLaunchKernelGGL(k_skip_pool_bwd, dim3(grid_for((long long)a.N * a.C[i] * a.H[i] * a.W[i], 1 << 30)), dim3(256), 0, st, draw, arg,
-                       geo + (size_t)i * R * 8, R, m, a.sumC, a.off[i], dmap);
-}
-
-TrainSrcs train_srcs(const az_det_solver *s, const void *const *maps, const int *Hs, const int *Ws, int N, int cl)
-{
-    TrainSrcs a{};
-    const az_det_solver::Skip &k = s->sk;
-    for (int i = 0; i < k.n; ++i) { a.map[i] = (const float *)maps[i]; a.C[i] = k.C[i]; a.H[i] = Hs[i]; a.W[i] = Ws[i]; a.off[i] = k.off[i]; }
-    a.sumC = k.sumC; a.n = k.n; a.N = N; a.cl = cl ? 1 : 0;
-    return a;
+    tr_pool_gather(c, names[i], draw, arg, geo + (size_t)i * R * 8, R, m, PoolStrides{49 * a.sumC, 1, a.sumC, a.off[i]}, dmap);
 }
 
 int skip_step_check(az_det_solver *s, const std::string &who, int n_src, const int *Cs, const void *const *maps, const int *Hs,
@@ -272,7 +138,7 @@ int skip_step_check(az_det_solver *s, const std::string &who, int n_src, const i
 }
 
 // roi_pool* .. relu_pool into s->pool5, then the head
-int skip_forward(az_det_solver *s, const TrainSrcs &a, const float *rois, int R, bool train, unsigned long long seed, unsigned long long iter)
+int skip_forward(az_det_solver *s, const SkipSrcs &a, const float *rois, int R, bool train, unsigned long long seed, unsigned long long iter)
 {
     az_ctx *c = s->c;
     az_det_solver::Skip &k = s->sk;
@@ -316,7 +182,7 @@ int az_det_solver_attach_skip(az_det_solver *s, int n_src, const int *Cs, const 
     if (!s) return AZ_ERR_INVALID;
     az_ctx *c = s->c;
     long long sumC = 0;
-    int rc = check_front_args(c, "az_det_solver_attach_skip", n_src, Cs, spatial_scales, gain, eps, &sumC);
+    int rc = skip_front_check(c, "az_det_solver_attach_skip", n_src, Cs, spatial_scales, gain, eps, &sumC);
     if (rc != AZ_OK) return rc;
     if (s->sk.attached) return fail(c, AZ_ERR_STATE, "az_det_solver_attach_skip: a front is attached already");
     const long long rows = (long long)s->maxR * 49;
@@ -402,7 +268,7 @@ int az_det_solver_step_skip(az_det_solver *s, int n_src, const int *Cs, const vo
     az_det_solver::Skip &k = s->sk;
     if ((rc = det_stage_targets(s, R, labels, bbox_targets, bbox_loss_weights, iteration, "az_det_solver_step_skip")) != AZ_OK) return rc;
     hipStream_t st = c->stream;
-    const TrainSrcs a = train_srcs(s, maps_dev, Hs, Ws, N, channels_last);
+    const SkipSrcs a = skip_srcs(s->sk.n, s->sk.C, Hs, Ws, maps_dev, N, channels_last);
     if ((rc = skip_forward(s, a, rois, R, true, seed, (unsigned long long)iteration)) != AZ_OK) return rc;
     det_head_backward(s, R, true);
     const int rows = R * 49, Cout = s->C;
@@ -419,7 +285,7 @@ int az_det_solver_step_skip(az_det_solver *s, int n_src, const int *Cs, const vo
           hipLaunchKernelGGL(k_skip_grn_bwd, dim3(rows, k.n), dim3(256), 0, st, k.cat, k.d_cat, k.fac, a,
                              k.gain != 0.0 ? 1.0 / (k.gain * k.gain) : 0.0, k.d_raw); }
         for (int i = 0; i < k.n; ++i)
-            if (dmaps_dev[i]) launch_gather(c, st, a, i, k.d_raw, k.arg, k.geo, R, (float *)dmaps_dev[i]);
+            if (dmaps_dev[i]) launch_gather(c, a, i, k.d_raw, k.arg, k.geo, R, (float *)dmaps_dev[i]);
         k.has_dcat = 1;
     }
     if ((rc = tr_grad_norm(s, DNALL, 2, losses_out, sumsq_out)) != AZ_OK) return rc;
@@ -437,7 +303,7 @@ int az_det_solver_forward_test_skip(az_det_solver *s, int n_src, const int *Cs, 
     az_ctx *c = s->c;
     HIPCHK(c, hipSetDevice(c->device));
     if (!(c->profiling & 4)) clear_events(c);
-    const TrainSrcs a = train_srcs(s, maps_dev, Hs, Ws, N, channels_last);
+    const SkipSrcs a = skip_srcs(s->sk.n, s->sk.C, Hs, Ws, maps_dev, N, channels_last);
     if ((rc = skip_forward(s, a, rois, R, false, 0, 0)) != AZ_OK) return rc;
     s->trained = 0; s->sk.trained = 0;
     det_softmax_test(s, R);
@@ -455,7 +321,7 @@ int az_skip_pool_bwd_unit(az_ctx *c, int n_src, const int *Cs, const float *spat
     if (!c) return AZ_ERR_INVALID;
     const std::string who = "az_skip_pool_bwd_unit";
     long long sumC = 0;
-    int rc = check_front_args(c, who, n_src, Cs, spatial_scales, 1.0, 0.0, &sumC);
+    int rc = skip_front_check(c, who, n_src, Cs, spatial_scales, 1.0, 0.0, &sumC);
     if (rc != AZ_OK) return rc;
     if ((rc = check_maps(c, who, n_src, Cs, (const void *const *)maps_host, Hs, Ws, N)) != AZ_OK) return rc;
     if (!rois || R < 1 || R > 4096 || (long long)R * 49 * sumC > 0x7fffffffLL) return fail(c, AZ_ERR_INVALID, who + ": 1 <= R <= 4096, R * 49 * sumC in 31 bits");
@@ -478,28 +344,26 @@ int az_skip_pool_bwd_unit(az_ctx *c, int n_src, const int *Cs, const float *spat
         return q;
     };
     auto release = [&]() { for (void *q : tmp) hipFree(q); };
-    TrainSrcs a{};
+    void *dmaps[AZ_SKIP_MAX_SRC] = {nullptr, nullptr, nullptr};
     float *dm[AZ_SKIP_MAX_SRC] = {nullptr, nullptr, nullptr};
     size_t msz[AZ_SKIP_MAX_SRC] = {0, 0, 0};
-    int off = 0;
     for (int i = 0; i < n_src; ++i) {
         msz[i] = (size_t)N * Cs[i] * Hs[i] * Ws[i] * 4;
-        a.map[i] = (const float *)grab(msz[i]); dm[i] = (float *)grab(msz[i]);
-        a.C[i] = Cs[i]; a.H[i] = Hs[i]; a.W[i] = Ws[i]; a.off[i] = off; off += Cs[i];
+        dmaps[i] = grab(msz[i]); dm[i] = (float *)grab(msz[i]);
     }
-    a.sumC = (int)sumC; a.n = n_src; a.N = N; a.cl = channels_last ? 1 : 0;
+    const SkipSrcs a = skip_srcs(n_src, Cs, Hs, Ws, dmaps, N, channels_last);
     float *drois = (float *)grab((size_t)R * 5 * 4), *cat = (float *)grab(big * 4), *draw = (float *)grab(big * 4);
     int *geo = (int *)grab((size_t)n_src * R * 8 * 4), *arg = (int *)grab(big * 4);
     double *fac = (double *)grab((size_t)R * 49 * n_src * 8);
     if (!ok) { release(); return fail(c, AZ_ERR_HIP, who + ": device memory"); }
 #define UCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { release(); return fail(c, AZ_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); } } while (0)
-    for (int i = 0; i < n_src; ++i) UCHK(hipMemcpyAsync((void *)a.map[i], maps_host[i], msz[i], hipMemcpyHostToDevice, st));
+    for (int i = 0; i < n_src; ++i) UCHK(hipMemcpyAsync(dmaps[i], maps_host[i], msz[i], hipMemcpyHostToDevice, st));
     UCHK(hipMemcpyAsync(drois, rois, (size_t)R * 5 * 4, hipMemcpyHostToDevice, st));
     if (d_raw_host) UCHK(hipMemcpyAsync(draw, d_raw_host, big * 4, hipMemcpyHostToDevice, st));
     launch_geo(st, drois, R, n_src, spatial_scales, geo);
     hipLaunchKernelGGL(k_skip_train_pool, dim3(R * 49, n_src), dim3(256), 0, st, a, 0, geo, R, 0, 1.0, 0.0, cat, arg, fac);
     if (d_raw_host && dmaps_out)
-        for (int i = 0; i < n_src; ++i) if (dmaps_out[i]) launch_gather(c, st, a, i, draw, arg, geo, R, dm[i]);
+        for (int i = 0; i < n_src; ++i) if (dmaps_out[i]) launch_gather(c, a, i, draw, arg, geo, R, dm[i]);
     UCHK(hipStreamSynchronize(st));
     UCHK(hipGetLastError());
     if (pooled_out) UCHK(hipMemcpy(pooled_out, cat, big * 4, hipMemcpyDeviceToHost));

@@ -69,6 +69,9 @@ void tr_roi_geo(hipStream_t st, const float *rois_dev, int R, float scale, int *
 // rois to the device, RoIPool 7x7 with arg-max into pool5 / argmax; notes the step's shape
 int tr_roi_pool_forward(az_trainer *t, const float *conv, int N, int H, int W, int cl, const float *rois, int R);
 void tr_roi_pool_backward(az_trainer *t, int N, int H, int W, int cl, float *dmap);       // dpool -> d conv5_3 by arg-max
+// the gather behind it, for any layout of the pooled gradient (PoolStrides, az_solver_dev.h), timed as `name`
+void tr_pool_gather(az_ctx *c, const char *name, const float *dpool, const int *argmax, const int *geo, int R, const MapView &m,
+                    const PoolStrides &st, float *dmap);
 // y = x W^T + b into `pre` (and, for the hidden layers, ReLU + dropout into `act`); pw: the layer's W (its b follows)
 void fc_forward(az_trainer *t, const char *name, const float *x, int pw, int R, int N, int K, float *pre, float *act,
                 unsigned char *mask, unsigned long long key, float ratio);

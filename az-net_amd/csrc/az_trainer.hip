@@ -1,6 +1,7 @@
 // az_trainer.hip -- the core of the two trainers (az_trainer.h): every kernel they share, defined once, and the host functions
-// on az_trainer.  The kernels: RoIPool with arg-max and its gather backward, the bounds-checked fp32 MFMA GEMM in its three
-// operand orders and its bf16-operand twin, split-K slabs summed in slab order, bias / ReLU / dropout, column sums, the sigmoid
+// on az_trainer.  The kernels: RoIPool with arg-max and its gather backward (the skip front's gathers are launches of the same
+// kernel with other strides), the bounds-checked fp32 MFMA GEMM in its three operand orders and its bf16-operand twin (the tile
+// they and k_skip_conv share is az_solver_dev.h's: tile_fp32, tile_store), split-K slabs summed in slab order, bias / ReLU / dropout, column sums, the sigmoid
 // and SmoothL1 losses, the two-level gradient norm, the SGD update and the gaussian filler.
 //
 // Every reduction has a fixed order (no floating-point atomics): split-K slabs are summed in slab order, column sums walk
@@ -17,13 +18,10 @@ __global__ void __launch_bounds__(256) k_solver_roi_geo(const float *__restrict_
     const int r = blockIdx.x * 256 + threadIdx.x;
     if (r >= R) return;
     const float *roi = rois + 5 * (size_t)r;
-    const int rsw = (int)roundf(roi[1] * ss), rsh = (int)roundf(roi[2] * ss);
-    const int rew = (int)roundf(roi[3] * ss), reh = (int)roundf(roi[4] * ss);
-    int rh = reh - rsh + 1; rh = rh < 1 ? 1 : rh;
-    int rw = rew - rsw + 1; rw = rw < 1 ? 1 : rw;
+    const RoiWindow w = roi_window(roi, ss);
     int *g = geo + 8 * (size_t)r;
-    g[0] = (int)roi[0]; g[1] = rsw; g[2] = rsh; g[3] = rew; g[4] = reh;
-    g[5] = __float_as_int((float)rh / 7.0f); g[6] = __float_as_int((float)rw / 7.0f); g[7] = 0;
+    g[0] = (int)roi[0]; g[1] = w.rsw; g[2] = w.rsh; g[3] = w.rew; g[4] = w.reh;
+    g[5] = __float_as_int(w.bh); g[6] = __float_as_int(w.bw); g[7] = 0;
 }
 
 __global__ void __launch_bounds__(256) k_solver_roi_pool(const float *__restrict__ feat, MapView m, const int *__restrict__ geo,
@@ -53,11 +51,12 @@ __global__ void __launch_bounds__(256) k_solver_roi_pool(const float *__restrict
     }
 }
 
-// d conv5_3: each pooled gradient goes to its arg-max cell.  One thread per cell GATHERS over the rois of its image in row
+// d map: each pooled gradient goes to its arg-max cell.  One thread per cell GATHERS over the rois of its image in row
 // order and over the bins whose window can hold the cell (the float bin range widened by one on both sides, then decided by
-// the stored arg-max: exactly the adjoint of the forward).
+// the stored arg-max: exactly the adjoint of the forward).  Channel c's bin p of roi r is word r * sr + off + c * sc + p * sp
+// of dpool / argmax: the trainers' pool5 [r][c * 49 + p], or one source's columns of the skip front's [(r, p)][sumC].
 __global__ void __launch_bounds__(256) k_solver_roi_pool_bwd(const float *__restrict__ dpool, const int *__restrict__ argmax,
-                                                             const int *__restrict__ geo, int R, MapView m,
+                                                             const int *__restrict__ geo, int R, MapView m, PoolStrides st,
                                                              float *__restrict__ dmap)
 {
     const long long total = (long long)m.N * m.C * m.H * m.W;
@@ -75,20 +74,33 @@ __global__ void __launch_bounds__(256) k_solver_roi_pool_bwd(const float *__rest
         int p0 = (int)floorf((float)(h - g[2]) / bh) - 1, p1 = (int)ceilf((float)(h - g[2] + 1) / bh) + 1;
         int q0 = (int)floorf((float)(w - g[1]) / bw) - 1, q1 = (int)ceilf((float)(w - g[1] + 1) / bw) + 1;
         p0 = min(max(p0, 0), 7); p1 = min(max(p1, 0), 7); q0 = min(max(q0, 0), 7); q1 = min(max(q1, 0), 7);
-        const size_t base = (size_t)r * 49 * m.C + (size_t)c * 49;
+        const size_t base = (size_t)r * st.sr + st.off + (size_t)c * st.sc;
         for (int ph = p0; ph < p1; ++ph)
-            for (int pw = q0; pw < q1; ++pw)
-                if (argmax[base + ph * 7 + pw] == cell) sum += dpool[base + ph * 7 + pw];
+            for (int pw = q0; pw < q1; ++pw) {
+                const size_t o = base + (size_t)(ph * 7 + pw) * st.sp;
+                if (argmax[o] == cell) sum += dpool[o];
+            }
     }
     dmap[idx] = sum;
 }
 
 // ---- fp32 GEMM on the matrix cores ------------------------------------------------------------------------------------------
+// what both GEMM kernels do with an output: into the slab, or added to what it holds
+struct SlabStore {
+    float *__restrict__ Dz; long long ldd; int accumulate;
+    __device__ __forceinline__ int column(int) const { return 0; }     // (nothing per column)
+    __device__ __forceinline__ void operator()(int i, int j, float v, int) const
+    {
+        float *d = Dz + (long long)i * ldd + j;
+        *d = accumulate ? *d + v : v;
+    }
+};
+
 // D[i][j] = sum_{k in slab} A(i, k) * B(j, k), i < M, j < N; A(i, k) = A[i * lai + k * lak], B(j, k) = B[j * lbj + k * lbk].
 // A 256-thread workgroup owns a 128 x 128 tile of D, each of its four waves 64 x 64 of it as 2 x 2 v_mfma_f32_32x32x2_f32
-// accumulators; K goes through LDS 32 at a time as sA[k][i] / sB[k][j] (an operand fragment is one conflict-free 4-byte read:
-// lane l holds A[i = l & 31][k = l >> 5]).  blockIdx.z is the split-K slab: its result goes to D + z * slab.  The three
-// products of a layer differ only in which index is contiguous in memory (AK / BK: along k):
+// accumulators; K goes through LDS 32 at a time as sA[k][i] / sB[k][j] (tile_fp32, az_solver_dev.h).  blockIdx.z is the
+// split-K slab: its result goes to D + z * slab.  The three products of a layer differ only in which index is contiguous in
+// memory (AK / BK: along k):
 //   forward  y  = x W^T     A = x  [M][K]  (AK)   B = W  [N][K]  (BK)
 //   dx          = dy W      A = dy [M][K]  (AK)   B = W  [K][N]
 //   dW          = dy^T x    A = dy [K][M]         B = x  [K][N]
@@ -100,51 +112,12 @@ __global__ void __launch_bounds__(256) k_solver_gemm(const float *__restrict__ A
                                                      float *__restrict__ D, long long ldd, long long slab, int M, int N, int K,
                                                      int Kc, int accumulate)
 {
-    __shared__ float sA[GK * GLD];
-    __shared__ float sB[GK * GLD];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int j0 = blockIdx.x * GT, i0 = blockIdx.y * GT;
     const int kbeg = blockIdx.z * Kc, kend = min(K, kbeg + Kc);
-    const int wi = (wave >> 1) * 64, wj = (wave & 1) * 64;
     az_f32x16 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int v = 0; v < 16; ++v) acc[a][b][v] = 0.0f;
-    const int lr = lane & 31, lk = lane >> 5;
-    for (int k0 = kbeg; k0 < kend; k0 += GK) {
-        __syncthreads();
-        gemm_stage<AK>(A, lai, lak, i0, M, k0, kend, sA, tid);
-        gemm_stage<BK>(B, lbj, lbk, j0, N, k0, kend, sB, tid);
-        __syncthreads();
-#pragma unroll
-        for (int kk = 0; kk < GK; kk += 2) {
-            const float a0 = sA[(kk + lk) * GLD + wi + lr], a1 = sA[(kk + lk) * GLD + wi + 32 + lr];
-            const float b0 = sB[(kk + lk) * GLD + wj + lr], b1 = sB[(kk + lk) * GLD + wj + 32 + lr];
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-        }
-    }
-    // C/D layout of the 32x32 MFMA: col = lane & 31, row = (v & 3) + 8 * (v >> 2) + 4 * (lane >> 5)
-    float *Dz = D + (long long)blockIdx.z * slab;
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const int j = j0 + wj + 32 * b + lr;
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const int i = i0 + wi + 32 * a + (v & 3) + 8 * (v >> 2) + 4 * lk;
-                if (i < M && j < N) {
-                    float *d = Dz + (long long)i * ldd + j;
-                    *d = accumulate ? *d + acc[a][b][v] : acc[a][b][v];
-                }
-            }
-        }
+    tile_fp32<AK, BK>(A, lai, lak, B, lbj, lbk, i0, M, j0, N, kbeg, kend, tid, acc);
+    tile_store(acc, tid, i0, M, j0, N, SlabStore{D + (long long)blockIdx.z * slab, ldd, accumulate});
 }
 
 // ---- the same GEMM with bf16 operands (AZ_TRAIN_BF16) -------------------------------------------------------------------------
@@ -213,18 +186,13 @@ __global__ void __launch_bounds__(256) k_solver_gemm_bf16(const float *__restric
 {
     __shared__ __attribute__((aligned(16))) __bf16 sA[GT * BLD];
     __shared__ __attribute__((aligned(16))) __bf16 sB[GT * BLD];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
+    const TileLane t(tid);
     const int j0 = blockIdx.x * GT, i0 = blockIdx.y * GT;
     const int kbeg = blockIdx.z * Kc, kend = min(K, kbeg + Kc);
-    const int wi = (wave >> 1) * 64, wj = (wave & 1) * 64;
+    const int wi = t.wi, wj = t.wj, lr = t.lr, lk = t.lk;
     az_f32x16 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int v = 0; v < 16; ++v) acc[a][b][v] = 0.0f;
-    const int lr = lane & 31, lk = lane >> 5;
+    tile_zero(acc);
     float va[16], vb[16];
     if (kbeg < kend) {
         bf16_stage_load<AK>(A, lai, lak, i0, M, kbeg, kend, tid, va);
@@ -251,21 +219,7 @@ __global__ void __launch_bounds__(256) k_solver_gemm_bf16(const float *__restric
             acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc[1][1], 0, 0, 0);
         }
     }
-    float *Dz = D + (long long)blockIdx.z * slab;
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const int j = j0 + wj + 32 * b + lr;
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const int i = i0 + wi + 32 * a + (v & 3) + 8 * (v >> 2) + 4 * lk;
-                if (i < M && j < N) {
-                    float *d = Dz + (long long)i * ldd + j;
-                    *d = accumulate ? *d + acc[a][b][v] : acc[a][b][v];
-                }
-            }
-        }
+    tile_store(acc, tid, i0, M, j0, N, SlabStore{D + (long long)blockIdx.z * slab, ldd, accumulate});
 }
 
 // slabs summed in slab order (+ what `out` holds when accumulate, + bias[j]); forward layers: pre-activation, ReLU, dropout
@@ -571,13 +525,18 @@ int tr_roi_pool_forward(az_trainer *t, const float *conv, int N, int H, int W, i
     return AZ_OK;
 }
 
+void tr_pool_gather(az_ctx *c, const char *name, const float *dpool, const int *argmax, const int *geo, int R, const MapView &m,
+                    const PoolStrides &st, float *dmap)
+{
+    Timed tm(c, name, 0);
+    hipLaunchKernelGGL(k_solver_roi_pool_bwd, dim3(grid_for((long long)m.N * m.C * m.H * m.W, 1 << 30)), dim3(256), 0, c->stream, dpool,
+                       argmax, geo, R, m, st, dmap);
+}
+
 void tr_roi_pool_backward(az_trainer *t, int N, int H, int W, int cl, float *dmap)
 {
-    az_ctx *c = t->c;
     const MapView m{N, t->C, H, W, cl ? 1 : 0};
-    Timed tm(c, "roi_pool_bwd", 0);
-    hipLaunchKernelGGL(k_solver_roi_pool_bwd, dim3(grid_for((long long)N * t->C * H * W, 1 << 30)), dim3(256), 0, c->stream, t->dpool,
-                       t->argmax, t->geo, t->R, m, dmap);
+    tr_pool_gather(t->c, "roi_pool_bwd", t->dpool, t->argmax, t->geo, t->R, m, PoolStrides{49 * t->C, 49, 1, 0}, dmap);
 }
 
 void fc_forward(az_trainer *t, const char *name, const float *x, int pw, int R, int N, int K, float *pre, float *act,

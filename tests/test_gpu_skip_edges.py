@@ -11,6 +11,7 @@ references alone.
   5. the profiled launch form (one launch per source) of both fronts: the bits of the unprofiled calls, the launch names
   6. a device row count far below the host bound: a trailing chunk without rows
   7. the gather over a sweep of window sizes, bit for bit
+  8. conv_pool5's GEMM (k_skip_conv) against the trainer's form-0 GEMM (k_solver_gemm), whose tile it shares: bit for bit
 References: train_step_ref.roi_pool, skip_train_ref.pool_argmax / scatter / front_forward / step, skip_ref.det_forward.
 Tolerance: train_step_ref.bound (8 x the float32 restatement's error against float64, floor 1e-6); what is exact is compared
 bit for bit.  The steps' seeds (skip_train_ref.STEP_SEEDS) keep every float64 pre-activation outside twice the forward bound
@@ -508,3 +509,31 @@ def test_gather_over_a_sweep_of_window_sizes(ctx, kind):
             np.abs(g["want"][0]).max()))
         assert same_bits(pooled, g["raw"]) and same_bits(uarg, g["arg"])
         assert same_bits(dm[0], g["want"][0])
+
+
+# ---- 8. conv_pool5 is the trainer's form-0 tile ----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("Cout", [12, 132])
+@pytest.mark.parametrize("sumC", [36, 64])
+@pytest.mark.parametrize("rows", [1, 129])
+def test_conv_pool5_has_the_trainer_gemms_bits(ctx, rows, sumC, Cout):
+    """skip_conv(cat) with bp = 0 == max(gemm_unit form 0 (cat, Wp), 0), bit for bit: one tile (az_solver_dev.h) behind both
+    kernels.  129 rows need a second, one-row tile in M, 132 outputs a partial tile in N, sumC = 36 a partial K stage past 32.
+    The unit entry splits K (pick_split: two slabs of 32 at these shapes) and adds the slabs in a second kernel, conv_pool5 runs
+    K in one pass; so the operands are multiples of 1/8 in [-2, 2]: every product is a multiple of 1/64, every partial sum
+    of at most 64 of them is below 2^8 and so a multiple of 2^-6 below 2^14 -- exact in float32 in any order.  What is compared
+    is then the staging, the bounds, the MFMA operand order and the C/D walk, not a summation order."""
+    from aznet_hip import ffi, synth
+    rng = np.random.Generator(np.random.PCG64(1000 * rows + 10 * sumC + Cout))
+    cat = (rng.integers(-16, 17, (rows, sumC)) / 8.0).astype(np.float32)
+    Wp = (rng.integers(-16, 17, (Cout, sumC)) / 8.0).astype(np.float32)
+    front = dict(Cs=(sumC,), scales=S.SCALES[-1:], Wp=Wp, bp=np.zeros(Cout, np.float32), gain=1000.0, eps=1e-10)
+    prod = ffi.gemm_unit(ctx, 0, cat, Wp)
+    want = np.where(prod > 0, prod, np.float32(0))                   # (the kernel's own ReLU: y > 0 ? y : +0)
+    with inference_context(synth.make_det_head(seed=9, C=Cout, n6=4, n7=4, ncls=2), front) as ictx:
+        got = ictx.skip_conv(cat)
+    exact = np.maximum(cat.astype(np.float64) @ Wp.astype(np.float64).T, 0.0)
+    print("  rows %d sumC %d Cout %d: %d of %d outputs differ from the trainer's GEMM, %d from float64; %d positive" % (
+        rows, sumC, Cout, int((got != want).sum()), got.size, int((got != exact).sum()), int((got > 0).sum())))
+    assert (got > 0).any() and (got == 0).any()
+    assert same_bits(got, want)
+    assert np.array_equal(got.astype(np.float64), exact)
