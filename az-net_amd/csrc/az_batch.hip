@@ -193,15 +193,14 @@ int batch_launch_impl(az_ctx *L, az_ctx::Batch &B, int n_all, az_ctx **slots_all
     // (before anything can decide that the images are searched one by one: those searches use the slices, too)
     const size_t res_slot = RES_HDR + (size_t)AZ_TOPK_MAX * 36;
     if (!B.res_dev) {
-        HIPCHK(L, hipMalloc((void **)&B.res_dev, res_slot * AZ_BATCH_MAX));
-        HIPCHK(L, hipHostMalloc((void **)&B.res_host, res_slot * AZ_BATCH_MAX));
+        HIPCHK(L, reserve_group({{&B.res_own[0], res_slot * AZ_BATCH_MAX}, {&B.res_own[1], res_slot * AZ_BATCH_MAX}}));
+        B.res_dev = B.res_own[0].as<unsigned char>(); B.res_host = B.res_own[1].as<unsigned char>();
         HIPCHK(L, hipMemsetAsync(B.res_dev, 0, res_slot * AZ_BATCH_MAX, s));
     }
     // this batch's blocks: k proposals each, side by side
     const size_t res_stride = (RES_HDR + (size_t)k * 36 + 255) & ~(size_t)255;
     for (int b = 0; b < n_all; ++b) {
         az_ctx *t = slots_all[b];
-        if (!t->h_res_own0) t->h_res_own0 = t->h_res[0];
         t->cnt = reinterpret_cast<AzCounts *>(B.res_dev + (size_t)b * res_stride);
         t->h_res[0] = B.res_host + (size_t)b * res_stride;
     }
@@ -237,20 +236,20 @@ int batch_launch_impl(az_ctx *L, az_ctx::Batch &B, int n_all, az_ctx **slots_all
     }
     if ((size_t)rows0_all > (size_t)L->maxR) return skip();
     if (!B.off) {
-        HIPCHK(L, hipMalloc((void **)&B.off, (AZ_BATCH_MAX + 2) * sizeof(int)));
-        HIPCHK(L, hipMalloc((void **)&B.rois_cat, (size_t)L->maxR * 5 * sizeof(float)));
-        HIPCHK(L, hipMalloc((void **)&B.ubox_cat, (size_t)L->maxR * 4 * sizeof(double)));
-        HIPCHK(L, hipMalloc((void **)&B.feats, AZ_BATCH_MAX * sizeof(float *)));
-        HIPCHK(L, hipMalloc((void **)&B.feat_hw, AZ_BATCH_MAX * 2 * sizeof(int)));
-        HIPCHK(L, hipMalloc((void **)&B.row_hw, (size_t)L->maxR * 2 * sizeof(int)));
+        Buf *o = B.own;
+        HIPCHK(L, reserve_group({{&o[0], (AZ_BATCH_MAX + 2) * sizeof(int)}, {&o[1], (size_t)L->maxR * 5 * sizeof(float)},
+                                 {&o[2], (size_t)L->maxR * 4 * sizeof(double)}, {&o[3], AZ_BATCH_MAX * sizeof(float *)},
+                                 {&o[4], AZ_BATCH_MAX * 2 * sizeof(int)}, {&o[5], (size_t)L->maxR * 2 * sizeof(int)}}));
+        B.off = o[0].as<int>(); B.rois_cat = o[1].as<float>(); B.ubox_cat = o[2].as<double>(); B.feats = o[3].as<const float *>();
+        B.feat_hw = o[4].as<int>(); B.row_hw = o[5].as<int>();
         HIPCHK(L, hipMemsetAsync(B.ubox_cat, 0, (size_t)L->maxR * 4 * sizeof(double), s));
     }
     const size_t need = 64 + ((sizeof(AzFusedArgs) + 16) + (sizeof(AzLevelArgs) + sizeof(AzFinalArgs) + 32) * (size_t)nlev) * AZ_BATCH_MAX;
     if (B.args_cap < need) {
-        if (B.args_dev) { HIPCHK(L, hipStreamSynchronize(s)); hipFree(B.args_dev); hipHostFree(B.args_host); B.args_dev = nullptr; B.args_host = nullptr; B.args_cap = 0; }
-        HIPCHK(L, hipMalloc((void **)&B.args_dev, need));
-        HIPCHK(L, hipHostMalloc((void **)&B.args_host, need));
-        B.args_cap = need;
+        if (B.args_dev) HIPCHK(L, hipStreamSynchronize(s));
+        B.args_dev = nullptr; B.args_host = nullptr; B.args_cap = 0;
+        HIPCHK(L, reserve_group({{&B.args_own[0], need}, {&B.args_own[1], need}}));
+        B.args_dev = B.args_own[0].as<unsigned char>(); B.args_host = B.args_own[1].as<unsigned char>(); B.args_cap = need;
     }
     // A batch whose levels would not fit the head's buffers (max_regions rows per pass) -- going by the rows per image of the
     // last batch fetched on this lane -- is enqueued as several lockstep programs, one after the other, of as many images each

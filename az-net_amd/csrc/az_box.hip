@@ -4,6 +4,7 @@
 // probe's operands are pseudo-random floats, rotated every instruction: a zero-filled loop clocks ~19 % higher than one on
 // real data (DVFS, /opt/skills/guides/MI355X_MICROARCH.md) and would overstate what a GEMM can be held to.
 #include "az_dev.h"
+#include "az_res.h"
 
 #include <algorithm>
 #include <vector>
@@ -77,12 +78,10 @@ double median_ms(std::vector<float> &v)
 // copy_tbps: (bytes read + bytes written) / time of a float4 copy of copy_bytes (best median of three launch shapes).  Returns 0 or a hipError_t.
 int azk_measure_box(hipStream_t s, double *mfma_tflops, double *copy_tbps, size_t copy_bytes)
 {
-    hipEvent_t ea = nullptr, eb = nullptr;
+    Event ea, eb;
     hipError_t e;
-    if ((e = hipEventCreate(&ea)) != hipSuccess) return (int)e;
-    if ((e = hipEventCreate(&eb)) != hipSuccess) { hipEventDestroy(ea); return (int)e; }
-    struct Guard { hipEvent_t a, b; void *p0 = nullptr, *p1 = nullptr, *p2 = nullptr;
-                   ~Guard() { hipEventDestroy(a); hipEventDestroy(b); if (p0) hipFree(p0); if (p1) hipFree(p1); if (p2) hipFree(p2); } } g{ea, eb};
+    if ((e = ea.create(hipEventDefault)) != hipSuccess || (e = eb.create(hipEventDefault)) != hipSuccess) return (int)e;
+    Buf b0, b1, b2;
     int rc = 0;
     auto timed = [&](auto &&launch, std::vector<float> &ms, int warm, int n) {
         for (int i = 0; i < warm + n && !rc; ++i) {
@@ -96,13 +95,13 @@ int azk_measure_box(hipStream_t s, double *mfma_tflops, double *copy_tbps, size_
     };
     if (mfma_tflops) {
         *mfma_tflops = 0.0;
-        if ((e = hipMalloc(&g.p0, 4096)) != hipSuccess) return (int)e;
+        if ((e = b0.reserve(4096)) != hipSuccess) return (int)e;
         int ncu = 256;
         { int dev = 0; hipDeviceProp_t prop; if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ncu = prop.multiProcessorCount; }
         // 8 MFMAs of 64 cycles per iteration and wave: 14 000 iterations ~ 3 ms at 2.4 GHz
         const int iters = 14000, grid = ncu;
         std::vector<float> ms;
-        timed([&]() { hipLaunchKernelGGL(k_mfma_probe, dim3(grid), dim3(256), 0, s, (float *)g.p0, iters, 12345u); }, ms, 4, 7);
+        timed([&]() { hipLaunchKernelGGL(k_mfma_probe, dim3(grid), dim3(256), 0, s, b0.as<float>(), iters, 12345u); }, ms, 4, 7);
         if (rc) return (int)hipErrorUnknown;
         const double flop = (double)grid * 4.0 * iters * 8.0 * (32.0 * 32.0 * 2.0 * 2.0);
         *mfma_tflops = flop / (median_ms(ms) * 1e-3) / 1e12;
@@ -111,18 +110,17 @@ int azk_measure_box(hipStream_t s, double *mfma_tflops, double *copy_tbps, size_
         *copy_tbps = 0.0;
         const size_t n4 = copy_bytes / 16;
         if (n4 == 0) return 0;
-        if ((e = hipMalloc(&g.p1, n4 * 16)) != hipSuccess) return (int)e;
-        if ((e = hipMalloc(&g.p2, n4 * 16)) != hipSuccess) return (int)e;
-        if ((e = hipMemsetAsync(g.p1, 0x3b, n4 * 16, s)) != hipSuccess) return (int)e;
+        if ((e = reserve_group({{&b1, n4 * 16}, {&b2, n4 * 16}})) != hipSuccess) return (int)e;
+        if ((e = hipMemsetAsync(b1.p, 0x3b, n4 * 16, s)) != hipSuccess) return (int)e;
         // (which launch shape streams best differs a little from box to box -- measured 4.5-5.7 TB/s among these on one
         //  box --: the best median of three forms is the box's figure)
         double best = 1e30;
         for (int form = 0; form < 3 && !rc; ++form) {
             std::vector<float> ms;
             timed([&]() {
-                if (form == 0) hipLaunchKernelGGL((k_copy_probe<1>), dim3(1024), dim3(256), 0, s, (const f4 *)g.p1, (f4 *)g.p2, n4);
-                else if (form == 1) hipLaunchKernelGGL((k_copy_probe<1>), dim3(65536), dim3(256), 0, s, (const f4 *)g.p1, (f4 *)g.p2, n4);
-                else hipLaunchKernelGGL((k_copy_probe<4>), dim3(8192), dim3(256), 0, s, (const f4 *)g.p1, (f4 *)g.p2, n4);
+                if (form == 0) hipLaunchKernelGGL((k_copy_probe<1>), dim3(1024), dim3(256), 0, s, b1.as<const f4>(), b2.as<f4>(), n4);
+                else if (form == 1) hipLaunchKernelGGL((k_copy_probe<1>), dim3(65536), dim3(256), 0, s, b1.as<const f4>(), b2.as<f4>(), n4);
+                else hipLaunchKernelGGL((k_copy_probe<4>), dim3(8192), dim3(256), 0, s, b1.as<const f4>(), b2.as<f4>(), n4);
             }, ms, 2, 5);
             const double m = median_ms(ms);
             if (m > 0 && m < best) best = m;

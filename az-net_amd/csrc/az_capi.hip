@@ -23,17 +23,49 @@ int az_create(int device, az_ctx **out)
     c->device = device;
     c->env = az_read_env();
     c->use_graphs = c->env.graph ? 1 : 0; c->plan_cache_max = c->env.plan_cache; c->gemm12_min_rows = c->env.gemm12_min;
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return AZ_ERR_HIP; }
-    if (hipHostMalloc((void **)&c->h_cnt, RES_HDR + (size_t)AZ_TOPK_MAX * 36) != hipSuccess) { delete c; return AZ_ERR_HIP; }
-    for (int i = 0; i < 3; ++i)
-        if (hipHostMalloc((void **)&c->h_res[i], RES_HDR + (size_t)AZ_TOPK_MAX * 36) != hipSuccess ||
-            hipEventCreateWithFlags(&c->ev_res[i], hipEventDisableTiming) != hipSuccess) { az_destroy(c); return AZ_ERR_HIP; }
+    bool ok = c->stream.create(hipStreamNonBlocking) == hipSuccess && c->h_cnt_own.reserve(RES_HDR + (size_t)AZ_TOPK_MAX * 36) == hipSuccess;
+    for (int i = 0; i < 3 && ok; ++i) {
+        ok = c->h_res_own[i].reserve(RES_HDR + (size_t)AZ_TOPK_MAX * 36) == hipSuccess && c->ev_res[i].create(hipEventDisableTiming) == hipSuccess;
+        c->h_res[i] = c->h_res_own[i].as<unsigned char>();
+    }
+    if (!ok) { delete c; return AZ_ERR_HIP; }
+    c->h_cnt = c->h_cnt_own.as<AzCounts>();
     *out = c;
     return AZ_OK;
 }
 
 static void destroy_twin(az_ctx *c);
 static void destroy_batch(az_ctx *c);
+
+// One head buffer set for the dims / limits / GEMM mode of `t`, allocated in o->allocs (o's error is set on failure):
+// pool5, the split-K slabs (`part`: both layers' slabs, at least part_min elements), h6, h7, int7's slabs and, in the
+// 16-bit-term modes, the operand planes and the scale block, cleared on stream s and waited for.
+static int alloc_head_set(az_ctx *o, const az_ctx *t, size_t part_min, hipStream_t s, const char *clear_msg, az_ctx::HeadSet *h)
+{
+    const size_t R = (size_t)t->maxR;
+    const AzHeadDims &d = t->d;
+    const size_t p6 = (size_t)t->S6 * R * d.n6, p7 = (size_t)t->S7 * R * d.n7, planes = (size_t)t->gemm_parts * azk_act_plane_elems((int)R, d.K6);
+    auto A = [&](auto **p, size_t n) { return dalloc(o, o->allocs, p, n); };
+    int rc = A(&h->pool5, R * d.K6);
+    if (!rc) rc = A(&h->part, std::max(std::max(p6, p7), part_min));
+    if (!rc) rc = A(&h->h6, R * d.n6);
+    if (!rc) rc = A(&h->h7, R * d.n7);
+    if (!rc) rc = A(&h->part7, p7);
+    if (!rc && t->gemm_parts) rc = A(&h->pool5p, planes);
+    if (!rc && t->gemm_parts) rc = A(&h->gscale, 4);
+    if (rc) return rc;
+    if (t->gemm_parts) {
+        if (hipMemsetAsync(h->pool5p, 0, planes * 2, s) != hipSuccess || hipMemsetAsync(h->gscale, 0, 4 * sizeof(float), s) != hipSuccess ||
+            hipStreamSynchronize(s) != hipSuccess)
+            return fail(o, AZ_ERR_HIP, clear_msg);
+    }
+    return AZ_OK;
+}
+
+static void use_head_set(az_ctx *t, const az_ctx::HeadSet &h)
+{
+    t->pool5 = h.pool5; t->part = h.part; t->h6 = h.h6; t->h7 = h.h7; t->part7 = h.part7; t->pool5p = h.pool5p; t->gscale = h.gscale;
+}
 
 int az_destroy(az_ctx *c)
 {
@@ -43,58 +75,12 @@ int az_destroy(az_ctx *c)
     destroy_twin(c);
     destroy_batch(c);
     if (c->comm) { if (c->comm_stream) hipStreamSynchronize(c->comm_stream); azk_rccl_destroy(c->comm); c->comm = nullptr; }
-    if (c->comm_stream) { hipStreamDestroy(c->comm_stream); c->comm_stream = nullptr; }
-    for (auto &e : c->comm_ev) if (e) { hipEventDestroy(e); e = nullptr; }
     hipSetDevice(c->device);
-    if (c->stream) hipStreamSynchronize(c->stream);
-    if (c->stream2) { hipStreamSynchronize(c->stream2); hipStreamDestroy(c->stream2); c->stream2 = nullptr; }
-    if (c->stream3) { hipStreamSynchronize(c->stream3); hipStreamDestroy(c->stream3); c->stream3 = nullptr; }
-    for (hipEvent_t *e : {&c->ev_h6, &c->ev_i7, &c->ev_s2, &c->ev_tail, &c->ev_s3, &c->ev_geo[0], &c->ev_geo[1]})
-        if (*e) { hipEventDestroy(*e); *e = nullptr; }
+    for (hipStream_t s : {(hipStream_t)c->stream, (hipStream_t)c->stream2, (hipStream_t)c->stream3}) if (s) hipStreamSynchronize(s);
     clear_events(c);
-    for (hipEvent_t ev : c->event_pool) hipEventDestroy(ev);
-    c->event_pool.clear();
     for (auto &g : c->graphs) hipGraphExecDestroy(g.second.exec);
-    c->graphs.clear();
-    free_all(c);
-    for (void *p : c->allocs_geom) hipFree(p);
-    c->allocs_geom.clear();
-    for (void *p : c->allocs_det) hipFree(p);
-    c->allocs_det.clear();
-    skip_free(c);
-    for (auto *q : c->plans) { free_plan(q); delete q; }
-    for (auto &e : c->spec_store) for (void *q2 : {(void *)e.urois, (void *)e.B1, (void *)e.choff, (void *)e.Udev}) if (q2) hipFree(q2);
-    c->spec_store.clear();
-    c->plans.clear();
-    if (c->feat_owned[0]) { for (float *f : c->feat_owned) hipFree(f); hipFree(c->feat_stage); }
-    for (void *p : {c->ev_a, c->ev_b, c->ev_c, c->ev_d, c->ev_e, c->ev_f, c->ev_g, c->ev_h, c->ev_voc, c->ev_coco, c->ev_diag,
-                    (void *)c->pyr_feats, (void *)c->pyr_hw, (void *)c->hisB,
-                    (void *)c->hisZ, (void *)c->pool, (void *)c->pool_tmp, (void *)c->pool_n, (void *)c->pool_hist})
-        if (p) hipFree(p);
-    if (c->nms_dets) { hipFree(c->nms_dets); hipFree(c->nms_sdets); hipFree(c->nms_order); hipFree(c->nms_mask); hipFree(c->nms_keep); hipFree(c->nms_rank); }
-    if (c->h_cnt) hipHostFree(c->h_cnt);
-    for (int i = 0; i < 3; ++i) {
-        if (c->h_res[i]) hipHostFree(c->h_res[i]);
-        if (c->ev_res[i]) hipEventDestroy(c->ev_res[i]);
-    }
-    for (auto &q : c->io) {
-        if (q.host) hipHostFree(q.host);
-        if (q.dev) hipFree(q.dev);
-        if (q.ev) hipEventDestroy(q.ev);
-    }
-    c->io.clear();
-    if (c->spare.ev) { hipEventDestroy(c->spare.ev); c->spare.ev = nullptr; }
-    if (c->ev_hand) hipEventDestroy(c->ev_hand);
-    if (c->ev_copy) hipEventDestroy(c->ev_copy);
-    if (c->span_ring) hipFree(c->span_ring);
-    if (c->h_nms) hipHostFree(c->h_nms);
-    if (c->h_nmsb) hipHostFree(c->h_nmsb);
-    if (c->h_nmsg) hipHostFree(c->h_nmsg);
-    if (c->nms_done) hipFree(c->nms_done);
-    if (c->h_Y) { hipHostFree(c->h_Y); hipHostFree(c->h_S); }
-    if (c->dseg_host) hipHostFree(c->dseg_host);
-    if (c->stream) hipStreamDestroy(c->stream);
-    delete c;
+    for (auto *q : c->plans) delete q;
+    delete c;                                 // (the members' destructors release everything else: az_res.h)
     return AZ_OK;
 }
 
@@ -141,8 +127,8 @@ int az_load_head(az_ctx *c, int C, int n6, int n71, int n72, const float *W6, co
     c->s3_live = false; c->g_live[0] = c->g_live[1] = false;
     destroy_twin(c);                          // (the second lane reads this head's buffers: rebuilt at the next launch)
     destroy_batch(c);
-    free_all(c);
-    c->spare.ready = false; c->spare.ev_live = false;      // (its buffers were in the list free_all walked; the slots are gone)
+    c->allocs.release();
+    c->spare.ready = false; c->spare.ev_live = false;      // (its buffers were in `allocs`, released above; the slots are gone)
     c->head_loaded = false;
     {
         int rg = ensure_geom(c);
@@ -153,37 +139,24 @@ int az_load_head(az_ctx *c, int C, int n6, int n71, int n72, const float *W6, co
     d.H = d.W = 0;
     c->S6 = azk_fc_split(d.K6);
     c->S7 = azk_fc_split(d.n6);
-    const size_t R = (size_t)c->maxR;
     int rc;
-#define A(p, n) if ((rc = dalloc(c, &c->p, (n))) != AZ_OK) return rc
-    A(W6, azk_tiled_elems(n6, d.K6)); A(b6, n6); A(W7, azk_tiled_elems(d.n7, n6)); A(b7, d.n7);
-    A(Wt, 64 * azk_tail_weight_rows(d.n7)); A(bt, 64);
-    A(pool5, R * d.K6);
-    {
-        const size_t p6 = (size_t)c->S6 * R * n6, p7 = (size_t)c->S7 * R * d.n7;
-        size_t pm = p6 > p7 ? p6 : p7;
-        const size_t pw = (size_t)n6 * d.K6;          // also stages W6 for the column permutation
-        const size_t pr = R * d.K6;                   // ... and az_roi_pool's rows in Caffe's order (more than the slabs when S6 n6 < K6)
-        pm = pm > pw ? pm : pw;
-        A(part, pm > pr ? pm : pr);
+    DevList &list = c->allocs;
+    AZ_A(W6, azk_tiled_elems(n6, d.K6)); AZ_A(b6, n6); AZ_A(W7, azk_tiled_elems(d.n7, n6)); AZ_A(b7, d.n7);
+    AZ_A(Wt, 64 * azk_tail_weight_rows(d.n7)); AZ_A(bt, 64);
+    if (c->gemm_parts) AZ_A(W6p, (size_t)c->gemm_parts * azk_weight_plane_elems(n6, d.K6));
+    {   // (`part` also stages W6 for the column permutation, and az_roi_pool's rows in Caffe's order: more than the slabs when S6 n6 < K6)
+        az_ctx::HeadSet hs;
+        if ((rc = alloc_head_set(c, c, std::max((size_t)n6 * d.K6, (size_t)c->maxR * d.K6), c->stream, "az_load_head: clearing the operand planes", &hs)) != AZ_OK) return rc;
+        use_head_set(c, hs);
     }
-    A(h6, R * n6); A(h7, R * d.n7);
-    A(part7, (size_t)c->S7 * R * d.n7);
-    if (c->gemm_parts) { A(W6p, (size_t)c->gemm_parts * azk_weight_plane_elems(n6, d.K6)); A(pool5p, (size_t)c->gemm_parts * azk_act_plane_elems((int)R, d.K6)); A(gscale, 4);
-        HIPCHK(c, hipMemsetAsync(c->pool5p, 0, (size_t)c->gemm_parts * azk_act_plane_elems((int)R, d.K6) * 2, c->stream)); }
-#undef A
     // Weights: Caffe [out, in] row-major is already the K-contiguous "B^T" layout the GEMM reads.
     // int6 reads pool5, which this library keeps bin-major ([p][c], see az_head.hip): permute
     // W6's columns to match (c*49 + p  ->  p*C + c).  `part` is big enough to stage it.
     // The GEMM streams weights tile-major (azk_tile_weights): permute / stack in a row-major temporary, then tile.
     // (`tmp` serves both layers: the larger of the two row-major blocks)
-    struct TmpGuard { float *p = nullptr; ~TmpGuard() { if (p) hipFree(p); } } tg;
-    {
-        size_t te = (size_t)n6 * d.K6;
-        if ((size_t)d.n7 * n6 > te) te = (size_t)d.n7 * n6;
-        HIPCHK(c, hipMalloc((void **)&tg.p, te * 4));
-    }
-    float *tmp = tg.p;
+    Buf tg;
+    HIPCHK(c, tg.reserve(std::max((size_t)n6 * d.K6, (size_t)d.n7 * n6) * 4));
+    float *tmp = tg.as<float>();
     HIPCHK(c, hipMemcpy(c->part, W6, (size_t)n6 * d.K6 * 4, hipMemcpyHostToDevice));
     azk_permute_k(c->stream, c->part, tmp, n6, C, 1);
     if (c->gemm_parts) {          // 16-bit terms of the (permuted, row-major) int6 weights
@@ -194,7 +167,6 @@ int az_load_head(az_ctx *c, int C, int n6, int n71, int n72, const float *W6, co
             for (size_t i = 0, n = (size_t)n6 * d.K6; i < n; ++i) { const float a = fabsf(W6[i]); if (a > mx) mx = a; }
             c->w6_scale = 1.f;
             if (mx > 0.f && mx < INFINITY) { int e; (void)frexpf(mx, &e); c->w6_scale = ldexpf(1.f, 15 - e); }
-            HIPCHK(c, hipMemsetAsync(c->gscale, 0, 4 * sizeof(float), c->stream));
         }
         azk_split_weight_planes(c->stream, tmp, c->W6p, n6, d.K6, c->gemm_parts, c->w6_scale);
     }
@@ -242,13 +214,13 @@ static int ensure_feat_copies(az_ctx *c, size_t n)
     if (n <= c->feat_owned_elems) return AZ_OK;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->twin) HIPCHK(c, hipStreamSynchronize(c->twin->stream));      // (a lane may be copying out of the old buffers)
-    if (c->feat_owned[0]) { for (float *f : c->feat_owned) hipFree(f); hipFree(c->feat_stage); }
     for (float *&f : c->feat_owned) f = nullptr;
     c->feat_stage = nullptr; c->feat_owned_elems = 0;
     ++c->feat_gen;
-    for (float *&f : c->feat_owned) HIPCHK(c, hipMalloc((void **)&f, n * 4));
-    HIPCHK(c, hipMalloc((void **)&c->feat_stage, n * 4));
-    c->feat_owned_elems = n;
+    Buf *b = c->feat_own;
+    HIPCHK(c, reserve_group({{&b[0], n * 4}, {&b[1], n * 4}, {&b[2], n * 4}, {&b[3], n * 4}}));
+    for (int i = 0; i < az_ctx::NFEAT; ++i) c->feat_owned[i] = b[i].as<float>();
+    c->feat_stage = b[az_ctx::NFEAT].as<float>(); c->feat_owned_elems = n;
     return AZ_OK;
 }
 
@@ -285,54 +257,23 @@ int ensure_lane_head(az_ctx *t)
     if (!t || t->head_bufs) return AZ_OK;
     int rc;
     HIPCHK(t, hipSetDevice(t->device));
-    const size_t R = (size_t)t->maxR;
-    const AzHeadDims &d = t->d;
     if (t->batch_set && t->owner) {
         // a batch slot: the owner's spare set (az_ctx.h: SpareHead), created at its first use
         az_ctx *o = t->owner;
         auto &sp = o->spare;
         if (!sp.ready) {
-            auto bad = [&](int code) { t->err = o->err; return code; };
-#define A(p, n) if ((rc = dalloc(o, &sp.p, (n))) != AZ_OK) return bad(rc)
-            A(pool5, R * d.K6);
-            {
-                const size_t p6 = (size_t)t->S6 * R * d.n6, p7 = (size_t)t->S7 * R * d.n7;
-                A(part, p6 > p7 ? p6 : p7);
-            }
-            A(h6, R * d.n6); A(h7, R * d.n7);
-            A(part7, (size_t)t->S7 * R * d.n7);
-            if (t->gemm_parts) {
-                A(pool5p, (size_t)t->gemm_parts * azk_act_plane_elems((int)R, d.K6)); A(gscale, 4);
-                if (hipMemsetAsync(sp.pool5p, 0, (size_t)t->gemm_parts * azk_act_plane_elems((int)R, d.K6) * 2, o->stream) != hipSuccess ||
-                    hipMemsetAsync(sp.gscale, 0, 4 * sizeof(float), o->stream) != hipSuccess || hipStreamSynchronize(o->stream) != hipSuccess)
-                    return fail(t, AZ_ERR_HIP, "batch slot: clearing the spare operand planes");
-            }
-#undef A
-            if (!sp.ev && hipEventCreateWithFlags(&sp.ev, hipEventDisableTiming) != hipSuccess)
-                return fail(t, AZ_ERR_HIP, "batch slot: the spare head set's event");
+            if ((rc = alloc_head_set(o, t, 0, o->stream, "batch slot: clearing the spare operand planes", &sp)) != AZ_OK) { t->err = o->err; return rc; }
+            if (sp.ev.create(hipEventDisableTiming) != hipSuccess) return fail(t, AZ_ERR_HIP, "batch slot: the spare head set's event");
             sp.ready = true; sp.ev_live = false;
         }
-        t->pool5 = sp.pool5; t->part = sp.part; t->h6 = sp.h6; t->h7 = sp.h7; t->part7 = sp.part7;
-        t->pool5p = sp.pool5p; t->gscale = sp.gscale;
+        use_head_set(t, sp);
         t->head_shared = true;
         t->head_bufs = true;
         return AZ_OK;
     }
-#define A(p, n) if ((rc = dalloc(t, &t->p, (n))) != AZ_OK) return rc
-    A(pool5, R * d.K6);
-    {
-        const size_t p6 = (size_t)t->S6 * R * d.n6, p7 = (size_t)t->S7 * R * d.n7;
-        A(part, p6 > p7 ? p6 : p7);
-    }
-    A(h6, R * d.n6); A(h7, R * d.n7);
-    A(part7, (size_t)t->S7 * R * d.n7);
-    if (t->gemm_parts) {
-        A(pool5p, (size_t)t->gemm_parts * azk_act_plane_elems((int)R, d.K6)); A(gscale, 4);
-        if (hipMemsetAsync(t->pool5p, 0, (size_t)t->gemm_parts * azk_act_plane_elems((int)R, d.K6) * 2, t->stream) != hipSuccess ||
-            hipMemsetAsync(t->gscale, 0, 4 * sizeof(float), t->stream) != hipSuccess || hipStreamSynchronize(t->stream) != hipSuccess)
-            return fail(t, AZ_ERR_HIP, "lane: clearing the operand planes");
-    }
-#undef A
+    az_ctx::HeadSet hs;
+    if ((rc = alloc_head_set(t, t, 0, t->stream, "lane: clearing the operand planes", &hs)) != AZ_OK) return rc;
+    use_head_set(t, hs);
     t->head_bufs = true;
     return AZ_OK;
 }
@@ -385,14 +326,10 @@ static void destroy_batch(az_ctx *c)
     for (auto &B : c->bsets) {
         for (az_ctx *t : B.slots) {
             if (t->stream) hipStreamSynchronize(t->stream);
-            if (t->h_res_own0) { t->h_res[0] = t->h_res_own0; t->h_res_own0 = nullptr; }     // (its own block again: az_destroy frees that)
             az_destroy(t);
         }
         B.slots.clear();
-        for (void *q : {(void *)B.off, (void *)B.rois_cat, (void *)B.ubox_cat, (void *)B.feats, (void *)B.feat_hw, (void *)B.row_hw, (void *)B.args_dev, (void *)B.res_dev}) if (q) hipFree(q);
-        if (B.args_host) hipHostFree(B.args_host);
-        if (B.res_host) hipHostFree(B.res_host);
-        B = az_ctx::Batch();
+        B = az_ctx::Batch();                  // (its owners release the pass buffers and the arenas)
     }
     c->bset_turn = 0;
     c->batch_order.clear();
@@ -490,7 +427,7 @@ static int launch_routed(az_ctx *c, const az_params *p, const float *dev_map, in
         // after the context has been handed the map after next.
         if (!c->feat) return fail(c, AZ_ERR_STATE, "no feature map set");
         t->d.H = c->d.H; t->d.W = c->d.W;
-        if (!t->ev_hand) HIPCHK(c, hipEventCreateWithFlags(&t->ev_hand, hipEventDisableTiming));
+        HIPCHK(c, t->ev_hand.create(hipEventDisableTiming));
         HIPCHK(c, hipEventRecord(t->ev_hand, c->stream));
         HIPCHK(c, hipStreamWaitEvent(t->stream, t->ev_hand, 0));
         if (c->feat == c->feat_owned[0] || c->feat == c->feat_owned[1] || c->feat == c->feat_owned[2]) {
@@ -498,7 +435,7 @@ static int launch_routed(az_ctx *c, const az_params *p, const float *dev_map, in
             if ((rc = ensure_feat_copies(t, n)) != AZ_OK) { c->err = t->err; return rc; }
             t->feat_turn = (t->feat_turn + 1) % az_ctx::NFEAT;
             HIPCHK(c, hipMemcpyAsync(t->feat_owned[t->feat_turn], c->feat, n * 4, hipMemcpyDeviceToDevice, t->stream));
-            if (!t->ev_copy) HIPCHK(c, hipEventCreateWithFlags(&t->ev_copy, hipEventDisableTiming));
+            HIPCHK(c, t->ev_copy.create(hipEventDisableTiming));
             HIPCHK(c, hipEventRecord(t->ev_copy, t->stream));
             t->ev_copy_live = true;
             t->feat = t->feat_owned[t->feat_turn];
@@ -617,7 +554,7 @@ int az_batch_launch_shapes(az_ctx *c, int n, const az_params *pa, const float *c
     if (not_taken) {
         // this shape / these settings: one search per image, each on its slot's own stream, behind whatever the caller made
         // the batch's stream wait for
-        if (!L->ev_hand) HIPCHK(c, hipEventCreateWithFlags(&L->ev_hand, hipEventDisableTiming));
+        HIPCHK(c, L->ev_hand.create(hipEventDisableTiming));
         HIPCHK(c, hipEventRecord(L->ev_hand, L->stream));
         for (int b = 0; b < n; ++b) {
             az_ctx *t = B.slots[b];
@@ -751,8 +688,8 @@ int az_rccl_init(az_ctx *c, const void *id, size_t id_bytes, int nranks, int ran
     if (!c || c->owner || !id || id_bytes < 128 || nranks < 1 || rank < 0 || rank >= nranks)
         return fail(c, AZ_ERR_INVALID, "az_rccl_init: bad arguments");
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->comm_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->comm_stream, hipStreamNonBlocking));
-    for (auto &e : c->comm_ev) if (!e) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    HIPCHK(c, c->comm_stream.create(hipStreamNonBlocking));
+    for (auto &e : c->comm_ev) HIPCHK(c, e.create(hipEventDisableTiming));
     if (c->comm) { HIPCHK(c, hipStreamSynchronize(c->comm_stream)); azk_rccl_destroy(c->comm); c->comm = nullptr; }
     std::string why;
     if (azk_rccl_init(id, nranks, rank, &c->comm, &why)) return fail(c, AZ_ERR_HIP, "az_rccl_init: " + why);
@@ -904,7 +841,8 @@ int az_set_profiling(az_ctx *c, int on)
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (c->stream2) HIPCHK(c, hipStreamSynchronize(c->stream2));
         if (c->stream3) HIPCHK(c, hipStreamSynchronize(c->stream3));
-        if (!c->span_ring) HIPCHK(c, hipMalloc((void **)&c->span_ring, (size_t)az_ctx::SPAN_SLOTS * 16));
+        HIPCHK(c, c->span_own.reserve((size_t)az_ctx::SPAN_SLOTS * 16));
+        c->span_ring = c->span_own.as<unsigned long long>();
         std::vector<unsigned long long> init((size_t)az_ctx::SPAN_SLOTS * 2);
         for (size_t i = 0; i < init.size(); i += 2) { init[i] = ~0ull; init[i + 1] = 0ull; }
         HIPCHK(c, hipMemcpy(c->span_ring, init.data(), init.size() * 8, hipMemcpyHostToDevice));
@@ -995,8 +933,8 @@ int az_zoom_labels(az_ctx *c, const double *rois, int R, const double *gt, int N
     TrainArena ar;
     const size_t o_r = ar.add((size_t)R * 32), o_g = ar.add((size_t)N * 32 + 32), o_l = ar.add((size_t)R);
     int rc;
-    if ((rc = ev_grow(c, 0, &c->ev_a, ar.total)) != AZ_OK) return rc;
-    char *base = (char *)c->ev_a;
+    if ((rc = scratch_grow(c, 0, ar.total)) != AZ_OK) return rc;
+    char *base = (char *)c->scratch[0].p;
     hipStream_t s = c->stream;
     HIPCHK(c, hipMemcpyAsync(base + o_r, rois, (size_t)R * 32, hipMemcpyHostToDevice, s));
     if (N) HIPCHK(c, hipMemcpyAsync(base + o_g, gt, (size_t)N * 32, hipMemcpyHostToDevice, s));
@@ -1036,8 +974,8 @@ int az_train_ex_rois(az_ctx *c, const az_train_params *p, int n_images, const in
                  o_eo = ar.add(((size_t)n_images + 1) * 4), o_us = ar.add((size_t)n_images * 8),
                  o_B = ar.add((size_t)azk_train_level_cap() * 8 * 8), o_st = ar.add(16);
     int rc;
-    if ((rc = ev_grow(c, 0, &c->ev_a, ar.total)) != AZ_OK) return rc;
-    char *base = (char *)c->ev_a;
+    if ((rc = scratch_grow(c, 0, ar.total)) != AZ_OK) return rc;
+    char *base = (char *)c->scratch[0].p;
     hipStream_t s = c->stream;
     HIPCHK(c, hipMemcpyAsync(base + o_sz, sizes3.data(), sizes3.size() * 4, hipMemcpyHostToDevice, s));
     if (NG) HIPCHK(c, hipMemcpyAsync(base + o_gt, gt, (size_t)NG * 32, hipMemcpyHostToDevice, s));
@@ -1101,9 +1039,9 @@ int az_train_adj_targets(az_ctx *c, const az_train_params *p, int n_images, cons
     const size_t o_ex = ar.add((size_t)E * 16 + 16), o_eo = ar.add(((size_t)n_images + 1) * 4), o_gt = ar.add((size_t)NG * 16 + 16),
                  o_go = ar.add(((size_t)n_images + 1) * 4), o_cn = ar.add(((size_t)E + 1) * 4), o_to = ar.add(((size_t)n_images + 1) * 4);
     int rc;
-    if ((rc = ev_grow(c, 0, &c->ev_a, ar.total)) != AZ_OK) return rc;
-    if ((rc = ev_grow(c, 1, &c->ev_b, (size_t)cap * 56 + 56)) != AZ_OK) return rc;
-    char *base = (char *)c->ev_a;
+    if ((rc = scratch_grow(c, 0, ar.total)) != AZ_OK) return rc;
+    if ((rc = scratch_grow(c, 1, (size_t)cap * 56 + 56)) != AZ_OK) return rc;
+    char *base = (char *)c->scratch[0].p;
     hipStream_t s = c->stream;
     if (E) HIPCHK(c, hipMemcpyAsync(base + o_ex, ex_boxes, (size_t)E * 16, hipMemcpyHostToDevice, s));
     if (NG) HIPCHK(c, hipMemcpyAsync(base + o_gt, gt, (size_t)NG * 16, hipMemcpyHostToDevice, s));
@@ -1115,13 +1053,13 @@ int az_train_adj_targets(az_ctx *c, const az_train_params *p, int n_images, cons
     // (the rows are written behind the counts without a host wait; a `cap` that turns out too small makes the kernel
     //  write nothing for the rows past it, and the call fails below)
     if (azk_train_adj_write(s, p, n_images, E, max_gt, (const float *)(base + o_ex), (const int *)(base + o_eo),
-                            (const float *)(base + o_gt), (const int *)(base + o_go), (int *)(base + o_cn), (double *)c->ev_b, cap))
+                            (const float *)(base + o_gt), (const int *)(base + o_go), (int *)(base + o_cn), (double *)c->scratch[1].p, cap))
         return fail(c, AZ_ERR_HIP, "az_train_adj_targets: launch failed");
     HIPCHK(c, hipMemcpyAsync(tgt_off_out, base + o_to, ((size_t)n_images + 1) * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     const int T = tgt_off_out[n_images];
     if (T > cap) return fail(c, AZ_ERR_CAPACITY, "az_train_adj_targets: cap too small; " + std::to_string(T) + " targets");
-    if (T) HIPCHK(c, hipMemcpy(targets_out, c->ev_b, (size_t)T * 56, hipMemcpyDeviceToHost));
+    if (T) HIPCHK(c, hipMemcpy(targets_out, c->scratch[1].p, (size_t)T * 56, hipMemcpyDeviceToHost));
     return AZ_OK;
 }
 
@@ -1134,17 +1072,17 @@ int az_train_target_stats(az_ctx *c, int n_sub, double eps, double *targets, lon
     TrainArena ar;
     const size_t o_pt = ar.add(azk_stats_part_doubles(T, n_sub) * 8), o_m = ar.add((size_t)n_sub * 32), o_s = ar.add((size_t)n_sub * 32);
     int rc;
-    if ((rc = ev_grow(c, 0, &c->ev_a, ar.total)) != AZ_OK) return rc;
-    if ((rc = ev_grow(c, 1, &c->ev_b, (size_t)T * 56 + 56)) != AZ_OK) return rc;
-    char *base = (char *)c->ev_a;
+    if ((rc = scratch_grow(c, 0, ar.total)) != AZ_OK) return rc;
+    if ((rc = scratch_grow(c, 1, (size_t)T * 56 + 56)) != AZ_OK) return rc;
+    char *base = (char *)c->scratch[0].p;
     hipStream_t s = c->stream;
-    if (T) HIPCHK(c, hipMemcpyAsync(c->ev_b, targets, (size_t)T * 56, hipMemcpyHostToDevice, s));
-    if (azk_train_target_stats(s, n_sub, eps, (double *)c->ev_b, T, (double *)(base + o_pt), (double *)(base + o_m),
+    if (T) HIPCHK(c, hipMemcpyAsync(c->scratch[1].p, targets, (size_t)T * 56, hipMemcpyHostToDevice, s));
+    if (azk_train_target_stats(s, n_sub, eps, (double *)c->scratch[1].p, T, (double *)(base + o_pt), (double *)(base + o_m),
                                (double *)(base + o_s), normalise_in_place))
         return fail(c, AZ_ERR_HIP, "az_train_target_stats: launch failed");
     HIPCHK(c, hipMemcpyAsync(means_out, base + o_m, (size_t)n_sub * 32, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipMemcpyAsync(stds_out, base + o_s, (size_t)n_sub * 32, hipMemcpyDeviceToHost, s));
-    if (T && normalise_in_place) HIPCHK(c, hipMemcpyAsync(targets, c->ev_b, (size_t)T * 56, hipMemcpyDeviceToHost, s));
+    if (T && normalise_in_place) HIPCHK(c, hipMemcpyAsync(targets, c->scratch[1].p, (size_t)T * 56, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     return AZ_OK;
 }

@@ -304,8 +304,8 @@ int az_coco_eval(az_ctx *c, int n_classes, int n_images, const double *det_box, 
         const size_t o_prec = take(nprec * 8), o_rec = take(nrec * 8);
         HIPCHK(c, hipSetDevice(c->device));
         int rc;
-        if ((rc = ev_grow(c, 9, &c->ev_coco, off)) != AZ_OK) return rc;
-        char *A = (char *)c->ev_coco;
+        if ((rc = scratch_grow(c, 9, off)) != AZ_OK) return rc;
+        char *A = (char *)c->scratch[9].p;
         hipStream_t s = c->stream;
         auto *dbox = (double *)(A + o_box), *dscore = (double *)(A + o_score), *gbox = (double *)(A + o_gbox);
         auto *garea = (double *)(A + o_garea);

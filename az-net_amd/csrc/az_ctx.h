@@ -3,9 +3,13 @@
 // az_search.hip / az_batch.hip (the forms of a search: cost model and planner, per-shape caches, launch sequence and collecting
 // a result, lockstep batches; az_search.h), az_units.hip (unit entry points, detection head,
 // NMS, tuner, recall, front-end).  Helpers are internal (anonymous namespace: one copy per translation unit).
+// Who owns what: az_res.h.  Every allocation, pinned block, event and stream below is held by an owner (DevList, Buf, Event,
+// Stream, EventPool) that releases it when the context is deleted; the raw pointers beside them are views.
 #pragma once
 #include "az_dev.h"
+#include "az_res.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstddef>
 #include <cstdio>
@@ -53,7 +57,8 @@ inline AzEnv az_read_env()
 struct az_ctx {
     int device = 0;
     AzEnv env;
-    hipStream_t stream = nullptr;
+    // (declared first, so destroyed last: the streams outlive every event and buffer used on them)
+    Stream stream, stream2, stream3, comm_stream;
     std::string err;
     int maxR = 16384, maxCand = 16384 * AZ_NSUB, maxCh = 65536;
     bool head_loaded = false;
@@ -78,12 +83,14 @@ struct az_ctx {
     int feat_turn = 0;
     unsigned feat_gen = 0;              // bumped when the copies are reallocated
     float *feat_stage = nullptr;        // NCHW staging for host uploads
+    Buf feat_own[NFEAT + 1];            // (owners of feat_owned[] and feat_stage)
     size_t feat_owned_elems = 0;
     // image pyramid (az_pyramid.hip): S borrowed channel-last maps of one padded size and the device table RoIPool reads
     // them through (roi column 0 = level); pyr_now: a pyramid search / detection is being enqueued
     int pyr_S = 0, pyr_now = 0;
     const float **pyr_feats = nullptr;  // [AZ_PYRAMID_MAX] (device)
     int *pyr_hw = nullptr;              // [AZ_PYRAMID_MAX][2] (device)
+    Buf pyr_own[2];
     AzPyrScales pyr_sc{};               // the scales of the pyramid search being enqueued
     // level-loop buffers (HBM)
     AzCounts *cnt = nullptr;
@@ -116,7 +123,7 @@ struct az_ctx {
     double *spec_scr_B1[2] = {nullptr, nullptr};
     int *spec_scr_choff[2] = {nullptr, nullptr};
     struct SpecEntry { int h = -1, w = -1, defer = 0; double scale = 0, min_side = 0; int P1 = 0, CH = 0, U = 0;
-                       float *urois = nullptr; double *B1 = nullptr; int *choff = nullptr, *Udev = nullptr;
+                       float *urois = nullptr; double *B1 = nullptr; int *choff = nullptr, *Udev = nullptr; Buf own[4];
                        unsigned long long use = 0; };
     std::vector<SpecEntry> spec_store;
     unsigned long long spec_clock = 0;
@@ -130,6 +137,7 @@ struct az_ctx {
         float *urois = nullptr;
         double *ubox = nullptr;
         int *reg_u = nullptr, *cand_src = nullptr, *meta = nullptr;
+        DevList own;                          // (what the five views above point into)
         unsigned long long last_use = 0;
         // whole-tree speculation (SearchPlan::full): window table over the pass's rows, the speculative rows' map, the
         // pass's rois.  Two row sets per shape:
@@ -143,6 +151,7 @@ struct az_ctx {
             unsigned long long *htab = nullptr; unsigned hT = 0;
             int *spec_map = nullptr, *full_meta = nullptr;
             float *full_urois = nullptr; double *full_ubox = nullptr;
+            DevList own;
             int Ufull = 0, full_state = 0;    // 0: not built, 1: ready, -1: cannot be used for this shape
         } fs[2];
     };
@@ -196,15 +205,14 @@ struct az_ctx {
     //   run on a THIRD stream behind the heads (ev_tail).  They are single-workgroup kernels that get a CU only between two
     //   int6 launches; on the second stream they held the NEXT search's int7 back for ~70 us.  The head outputs they read
     //   (zoom_s / score_s / delta_s) exist twice, used in turn (out_par); ev_geo[p] = the geometry that read set p is done.
-    hipStream_t stream2 = nullptr, stream3 = nullptr;
-    hipEvent_t ev_tail = nullptr, ev_s3 = nullptr, ev_geo[2] = {nullptr, nullptr};
+    Event ev_tail, ev_s3, ev_geo[2];
     bool s3_live = false, g_live[2] = {false, false};
     int out_par = 0, three_now = 0;
     float *zoom_s2 = nullptr, *score_s2 = nullptr, *delta_s2 = nullptr;
     hipStream_t gs = nullptr;                 // while a search is being enqueued: where the kernels behind its head pass go (nullptr: `stream`)
     hipStream_t ts = nullptr;                 // ... and where profiling events are recorded (nullptr: `stream`)
     hipStream_t last_s = nullptr;             // the stream the search launched last ends on
-    hipEvent_t ev_h6 = nullptr, ev_i7 = nullptr, ev_s2 = nullptr;
+    Event ev_h6, ev_i7, ev_s2;
     bool i7_live = false, s2_live = false;
     int split_now = 0, async_err = 0;
     bool no_stage_streams = false;            // this device / runtime did not give the extra streams: every search in one stage
@@ -231,6 +239,8 @@ struct az_ctx {
         int *feat_hw = nullptr, *row_hw = nullptr;   // every image's map size [AZ_BATCH_MAX][2]; every row's image size [maxR][2]
         unsigned char *args_dev = nullptr, *args_host = nullptr;   // the geometry kernels' arguments, one block per image and launch
         size_t args_cap = 0;
+        // (owners: off .. row_hw, the args pair, the result pair)
+        Buf own[6], args_own[2] = {Buf::DEVICE, Buf::PINNED}, res_own[2] = {Buf::DEVICE, Buf::PINNED};
         // the images' result blocks (counters + selected boxes and scores) lie side by side, on the device and in pinned host
         // memory: ONE device-to-host copy per batch (eight copies of 12 KB cost 75 us of stream time, one of 95 KB ~10)
         unsigned char *res_dev = nullptr, *res_host = nullptr;
@@ -249,31 +259,31 @@ struct az_ctx {
     // head set of its own -- at max_regions 16384 and the VGG16 dims that is ~8.5 GB, times 32 slots, times two sets per
     // lane -- but takes the OWNER's one spare set in turn: `ev` (recorded behind each such search) orders the next user's
     // stream behind the previous one.  The searches were chip-wide one after the other anyway.
-    struct SpareHead {
+    struct HeadSet {                          // (views; alloc_head_set, az_capi.hip)
         float *pool5 = nullptr, *part = nullptr, *h6 = nullptr, *h7 = nullptr, *part7 = nullptr, *gscale = nullptr;
         unsigned short *pool5p = nullptr;
-        bool ready = false, ev_live = false;
-        hipEvent_t ev = nullptr;
+    };
+    struct SpareHead : HeadSet {
+        bool ready = false, ev_live = false;     // (the buffers are in the owner's `allocs`)
+        Event ev;
     } spare;                                  // (owner)
     bool head_shared = false;                 // (a batch slot) pool5 / part / h6 / h7 / part7 are the owner's spare set
     Batch *batch_set = nullptr;               // (a batch slot) the batch set it belongs to
-    // (a batch slot) its counters / result block and its first host result slot are slices of the lane's arenas
-    // (Batch::res_dev / res_host); the slot's own allocations stay in its lists and are freed with it
-    unsigned char *h_res_own0 = nullptr;
+    // (a batch slot) its counters / result block and its first host result slot are views into the lane's arenas
+    // (Batch::res_dev / res_host); the slot's own blocks stay with their owners and are freed with it
     int lanes = 1, lane_next = 0, last_fetch_lane = 0;
     std::deque<int> lane_order;               // lanes of the searches launched through the public entry points, oldest first
-    hipEvent_t ev_hand = nullptr;             // (in a twin) orders the lane behind the owner's stream when it reads the owner's map
+    Event ev_hand;                            // (in a twin) orders the lane behind the owner's stream when it reads the owner's map
     // (in a twin) recorded behind the lane's private copy of an owner-held map: the owner's stream waits for it before it
     // writes its channel-last copies again (the lane may still be busy with an earlier search when the owner is handed
     // the map after next)
-    hipEvent_t ev_copy = nullptr;
+    Event ev_copy;
     bool ev_copy_live = false;
     void *comm = nullptr;                     // ncclComm_t of az_rccl_init
     int comm_ranks = 0, comm_rank = 0;
     // the collective runs on a stream of its own, behind events of the lanes: in a lane's stream it would hold that lane's
     // next search back until the collective's kernel finds free CUs, i.e. until the OTHER lane's GEMM is done
-    hipStream_t comm_stream = nullptr;
-    hipEvent_t comm_ev[2] = {nullptr, nullptr};
+    Event comm_ev[2];
     // cost of one head pass (RoIPool + int6 + reduce + int7 + heads) at a few row counts, measured on THIS device with HIP
     // events the first time a search is launched (calibrate_passes): what the choice between the search forms goes by
     struct PassCal { int state = 0; int n = 0; int rows[6] = {0}; double us[6] = {0}; } cal;   // state 0: not yet, 1: measured, -1: off
@@ -291,7 +301,7 @@ struct az_ctx {
     // Fast R-CNN head on the shared map (az_load_det_head)
     bool det_loaded = false;
     int det_n6 = 0, det_n7 = 0, det_ncls = 0, det_S6 = 1, det_S7 = 1;
-    std::vector<void *> allocs_det;
+    DevList allocs_det;
     float *dW6 = nullptr, *db6 = nullptr, *dW7 = nullptr, *db7 = nullptr, *dWt = nullptr, *dbt = nullptr;
     // 16-bit-term modes: the detection head's fc6 on the same kernel as int6 (its own weight planes, weight scale and
     // -- two fp16 terms -- its own {pool5 scale, 1 / (sx * sw)} pair)
@@ -307,11 +317,13 @@ struct az_ctx {
         float scale[AZ_SKIP_MAX_SRC] = {0.f, 0.f, 0.f};
         double gain = 1000.0, eps = 1e-10;       // scale5 (test_fc.prototxt of the skip model); the GRN layers' eps
         float *Wp = nullptr, *bp = nullptr, *cat = nullptr;
+        DevList own;
         const float *maps[AZ_SKIP_MAX_SRC] = {nullptr, nullptr, nullptr};
         int H[AZ_SKIP_MAX_SRC] = {0, 0, 0}, W[AZ_SKIP_MAX_SRC] = {0, 0, 0};
     } skip;
     // az_detect_batch: one pass's AzDetSeg + boxes (pinned staging and its device copy), per-row image sizes
     unsigned char *dseg_host = nullptr, *dseg_dev = nullptr;
+    Buf dseg_own{Buf::PINNED};
     int *drow_hw = nullptr;
     // nms scratch (grown on demand)
     int nms_cap = 0;
@@ -320,9 +332,11 @@ struct az_ctx {
     unsigned long long *nms_mask = nullptr;
     int *nms_rank = nullptr;            // [nms_cap] rank scratch of k_nms_rank_count: zero between calls
     long long *nms_keep = nullptr;
+    Buf nms_own[6];                     // (dets, sdets, order, mask, rank, keep: grown together, nms_cap boxes)
     unsigned char *h_nms = nullptr;     // host-mapped block of az_nms's small case
     unsigned char *h_nmsg = nullptr; size_t h_nmsg_cap = 0;     // ... of az_nms's general case (keep list + count)
     unsigned char *h_nmsb = nullptr; size_t h_nmsb_cap = 0; int *nms_done = nullptr; int nms_seq = 0;   // ... of az_nms_batched's
+    Buf h_nms_own{Buf::MAPPED}, h_nmsg_own{Buf::MAPPED}, h_nmsb_own{Buf::MAPPED}, nms_done_own;
     unsigned nms_tag = 0;               // sequence number carried by every word an NMS kernel writes to host-mapped memory
     // tuner (az_eval.hip): anchor history of the last search, score pool over an image set
     double *hisB = nullptr;
@@ -331,20 +345,17 @@ struct az_ctx {
     float *pool = nullptr, *pool_tmp = nullptr;
     unsigned long long *pool_n = nullptr, *pool_hist = nullptr;      // [2], [256]
     long long pool_cap = 0;
+    Buf his_own[2], pool_own[4];        // (hisB, hisZ; pool, pool_tmp, pool_n, pool_hist)
     // grow-on-demand scratch of the evaluation / front-end entry points
-    void *ev_a = nullptr, *ev_b = nullptr, *ev_c = nullptr, *ev_d = nullptr, *ev_e = nullptr, *ev_f = nullptr,
-         *ev_g = nullptr, *ev_h = nullptr;
-    void *ev_voc = nullptr;             // slot 8: the arena of az_voc_eval
-    void *ev_coco = nullptr;            // slot 9: the arena of az_coco_eval
-    void *ev_diag = nullptr;            // slot 10: the arena of az_diag_eval
-    size_t ev_sz[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    // (slots 0-7: whatever the entry point wants; 8, 9, 10: the arenas of az_voc_eval, az_coco_eval, az_diag_eval)
+    Buf scratch[11];
     // front-end on a caller's stream (az_image_blob_dev_on): two pinned host slots and two device slots for the uint8 image,
     // used in turn; a slot's event says its last upload + kernel are done
     // upload slots of az_image_blob_dev_on (pinned host + device staging + "slot free" event).  Two to start with; a slot
     // whose previous upload is still queued on the GPU (a lockstep batch's uploads wait behind the previous batch's search)
     // makes the ring GROW, up to IO_SLOTS_MAX, instead of making the host wait.
     static constexpr int IO_SLOTS_MAX = 40;
-    struct IoSlot { unsigned char *host = nullptr, *dev = nullptr; hipEvent_t ev = nullptr; };
+    struct IoSlot { Buf host{Buf::PINNED}, dev; Event ev; };
     std::vector<IoSlot> io;
     size_t io_cap = 0;
     int io_turn = 0;
@@ -353,6 +364,7 @@ struct az_ctx {
     double *h_Y = nullptr;
     float *h_S = nullptr;
     int h_cap = 0;
+    Buf h_cnt_own{Buf::PINNED}, h_own[2] = {Buf::PINNED, Buf::PINNED};      // (h_cnt; h_Y, h_S: grown together, h_cap rows)
     // Searches launched and not yet fetched, oldest first (at most two: the host may enqueue the next image's launch
     // sequence while the GPU still works on the current one -- same stream, so the searches never overlap on the GPU).
     // With a fixed proposal count the result block's device-to-host copy is enqueued right behind the search's kernels,
@@ -377,7 +389,8 @@ struct az_ctx {
     };
     std::deque<PendingSearch> pend;
     unsigned char *h_res[3] = {nullptr, nullptr, nullptr};
-    hipEvent_t ev_res[3] = {nullptr, nullptr, nullptr};
+    Buf h_res_own[3] = {Buf::PINNED, Buf::PINNED, Buf::PINNED};
+    Event ev_res[3];
     bool slot_busy[3] = {false, false, false};
     // parameters of the last FETCHED search
     az_params last{};
@@ -415,11 +428,12 @@ struct az_ctx {
     // clock) into slots of this ring -- exact also when another lane's kernels delay the launch, and free of the ~7 us of
     // stream time an event pair costs
     unsigned long long *span_ring = nullptr;
+    Buf span_own;
     int span_next = 0;
     static constexpr int SPAN_SLOTS = 32768;
-    std::vector<hipEvent_t> event_pool;   // recycled events
-    std::vector<void *> allocs;        // head-sized buffers (az_load_head)
-    std::vector<void *> allocs_geom;   // geometry buffers (first use)
+    EventPool event_pool;              // recycled events
+    DevList allocs;                    // head-sized buffers (az_load_head)
+    DevList allocs_geom;               // geometry buffers (first use)
     std::vector<az_solver *> solvers;  // trainers created on this context (az_solver.hip), freed with it
     std::vector<az_det_solver *> det_solvers;  // the detection net's trainers (az_det_solver.hip), freed with it
     bool geom_ready = false;
@@ -440,36 +454,17 @@ int fail(az_ctx *c, int code, const std::string &msg)
             return fail((c), AZ_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
+// One allocation of n elements (+ the list's slack) into `list`, a view of it in *p; the context's error set on failure.
 template <typename T>
-int dalloc(az_ctx *c, T **p, size_t n, bool geom = false)
+int dalloc(az_ctx *c, DevList &list, T **p, size_t n)
 {
-    void *q = nullptr;
-    hipError_t e = hipMalloc(&q, n * sizeof(T) + 256);
-    if (e != hipSuccess)
-        return fail(c, AZ_ERR_HIP, std::string("hipMalloc(") + std::to_string(n * sizeof(T)) + " B): " +
-                                       hipGetErrorString(e));
-    (geom ? c->allocs_geom : c->allocs).push_back(q);
-    *p = (T *)q;
-    return AZ_OK;
+    const hipError_t e = list.alloc(p, n);
+    if (e == hipSuccess) return AZ_OK;
+    return fail(c, AZ_ERR_HIP, (&list == &c->allocs_det ? "hipMalloc: " : alloc_what(n * sizeof(T)) + ": ") +
+                                   hipGetErrorString(e));
 }
-
-template <typename T>
-int dalloc_det(az_ctx *c, T **p, size_t n)
-{
-    void *q = nullptr;
-    hipError_t e = hipMalloc(&q, n * sizeof(T) + 256);
-    if (e != hipSuccess) return fail(c, AZ_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
-    c->allocs_det.push_back(q);
-    *p = (T *)q;
-    return AZ_OK;
-}
-
-void free_all(az_ctx *c)
-{
-    for (void *p : c->allocs) hipFree(p);
-    c->allocs.clear();
-}
-
+// ... member `p` of the context `c`, from inside a function that has `rc` and names the list it fills `list`
+#define AZ_A(p, n) if ((rc = dalloc(c, list, &c->p, (n))) != AZ_OK) return rc
 
 // Buffers that depend only on the ctx limits (region / candidate capacity).
 int ensure_geom(az_ctx *c)
@@ -479,29 +474,28 @@ int ensure_geom(az_ctx *c)
     if (e0 != hipSuccess) return fail(c, AZ_ERR_HIP, "hipSetDevice failed");
     const size_t R = (size_t)c->maxR, CAND = (size_t)c->maxCand, CH = (size_t)c->maxCh;
     int rc;
-#define A(p, n) if ((rc = dalloc(c, &c->p, (n), true)) != AZ_OK) return rc
+    DevList &list = c->allocs_geom;
     {   // result block: the counters, then (fixed proposal count) the selected boxes and scores, so that
         // az_propose_fetch is ONE device-to-host copy
         unsigned char *blk = nullptr;
-        if ((rc = dalloc(c, &blk, RES_HDR + (size_t)AZ_TOPK_MAX * 36, true)) != AZ_OK) return rc;
+        if ((rc = dalloc(c, list, &blk, RES_HDR + (size_t)AZ_TOPK_MAX * 36)) != AZ_OK) return rc;
         c->cnt = (AzCounts *)blk;
     }
-    A(B[0], R * 4); A(B[1], R * 4); A(rois, R * 5); A(urois, R * 5); A(key, R); A(ckey, CH);
-    A(grp, R); A(index, R); A(inv, R); A(inv_odd, R); A(choff, R); A(bc_c, (R * AZ_NSUB + 255) / 256 + 1);
-    A(bc_z, (R * AZ_NSUB + 255) / 256 + 1);
-    A(first, CH > R ? CH : R); A(cflag, R * AZ_NSUB); A(zflag, R); A(keep_u, R * AZ_NSUB);
-    A(ubox, R * 4); A(pred_u, R * AZ_NSUB * 4); A(Yall, CAND * 4); A(Z, R * 4); A(child, CH * 4);
-    A(Yout, CAND * 4); A(Sout, CAND); A(sel_idx, CAND); A(rank_part, (size_t)azk_topk_scratch_ints((int)CAND));
-    A(zoom_u, R); A(score_u, R * AZ_NSUB); A(delta_u, R * 4 * AZ_NSUB); A(Sall, CAND);
-    A(zr, R); A(csrc, CH); A(choff_all, R); A(srcB[0], R); A(srcB[1], R);
-    A(zoom_s, R); A(score_s, R * AZ_NSUB); A(delta_s, R * 4 * AZ_NSUB);
-    A(zoom_s2, R); A(score_s2, R * AZ_NSUB); A(delta_s2, R * 4 * AZ_NSUB);
-    for (int i = 0; i < 2; ++i) { A(spec_scr_urois[i], R * 5); A(spec_scr_B1[i], R * 4); A(spec_scr_choff[i], R); }
-    A(key_u, R * AZ_NSUB);
-    A(choff_pair, R); A(crow, CH > 8192 ? CH : 8192);
-    A(pred_v, R * AZ_NSUB * 4); A(score_v, R * AZ_NSUB); A(zoom_v, R); A(keep_v, R * AZ_NSUB); A(key_v, R * AZ_NSUB);
-    A(pred_w, R * AZ_NSUB * 4); A(score_w, R * AZ_NSUB); A(zoom_w, R); A(keep_w, R * AZ_NSUB); A(key_w, R * AZ_NSUB);
-#undef A
+    AZ_A(B[0], R * 4); AZ_A(B[1], R * 4); AZ_A(rois, R * 5); AZ_A(urois, R * 5); AZ_A(key, R); AZ_A(ckey, CH);
+    AZ_A(grp, R); AZ_A(index, R); AZ_A(inv, R); AZ_A(inv_odd, R); AZ_A(choff, R); AZ_A(bc_c, (R * AZ_NSUB + 255) / 256 + 1);
+    AZ_A(bc_z, (R * AZ_NSUB + 255) / 256 + 1);
+    AZ_A(first, CH > R ? CH : R); AZ_A(cflag, R * AZ_NSUB); AZ_A(zflag, R); AZ_A(keep_u, R * AZ_NSUB);
+    AZ_A(ubox, R * 4); AZ_A(pred_u, R * AZ_NSUB * 4); AZ_A(Yall, CAND * 4); AZ_A(Z, R * 4); AZ_A(child, CH * 4);
+    AZ_A(Yout, CAND * 4); AZ_A(Sout, CAND); AZ_A(sel_idx, CAND); AZ_A(rank_part, (size_t)azk_topk_scratch_ints((int)CAND));
+    AZ_A(zoom_u, R); AZ_A(score_u, R * AZ_NSUB); AZ_A(delta_u, R * 4 * AZ_NSUB); AZ_A(Sall, CAND);
+    AZ_A(zr, R); AZ_A(csrc, CH); AZ_A(choff_all, R); AZ_A(srcB[0], R); AZ_A(srcB[1], R);
+    AZ_A(zoom_s, R); AZ_A(score_s, R * AZ_NSUB); AZ_A(delta_s, R * 4 * AZ_NSUB);
+    AZ_A(zoom_s2, R); AZ_A(score_s2, R * AZ_NSUB); AZ_A(delta_s2, R * 4 * AZ_NSUB);
+    for (int i = 0; i < 2; ++i) { AZ_A(spec_scr_urois[i], R * 5); AZ_A(spec_scr_B1[i], R * 4); AZ_A(spec_scr_choff[i], R); }
+    AZ_A(key_u, R * AZ_NSUB);
+    AZ_A(choff_pair, R); AZ_A(crow, CH > 8192 ? CH : 8192);
+    AZ_A(pred_v, R * AZ_NSUB * 4); AZ_A(score_v, R * AZ_NSUB); AZ_A(zoom_v, R); AZ_A(keep_v, R * AZ_NSUB); AZ_A(key_v, R * AZ_NSUB);
+    AZ_A(pred_w, R * AZ_NSUB * 4); AZ_A(score_w, R * AZ_NSUB); AZ_A(zoom_w, R); AZ_A(keep_w, R * AZ_NSUB); AZ_A(key_w, R * AZ_NSUB);
     if (hipMemset(c->ubox, 0, R * 4 * sizeof(double)) != hipSuccess) return fail(c, AZ_ERR_HIP, "hipMemset failed");
     // (a search whose fused level kernel overflows is rerun by the host, but the kernels already enqueued behind it still
     //  run, on whatever the level's inv_index buffer holds: it must always hold valid rows)
@@ -517,11 +511,6 @@ int ensure_geom(az_ctx *c)
 struct Timed {
     az_ctx *c; bool on; hipEvent_t a{}, b{}; const char *name; int level;
     // (events are recycled through c->event_pool: creating one costs about as much as recording it)
-    static bool grab(az_ctx *c, hipEvent_t *e)
-    {
-        if (!c->event_pool.empty()) { *e = c->event_pool.back(); c->event_pool.pop_back(); return true; }
-        return hipEventCreate(e) == hipSuccess;
-    }
     // AZ_TRACE=1 (debugging): every launch group is announced on stderr and waited for, so a faulting kernel is the one
     // named last
     static bool trace() { static const bool t = az_read_env().trace; return t; }
@@ -531,15 +520,15 @@ struct Timed {
         on = (c_->profiling & 2) || ((c_->profiling & 1) && cls == 1);
         if (!on) return;
         // a failed event call drops this measurement (and is reported by az_last_kernel_times), never the search
-        if (!grab(c, &a)) { on = false; ++c->event_errors; return; }
-        if (!grab(c, &b)) { hipEventDestroy(a); on = false; ++c->event_errors; return; }
-        if (hipEventRecord(a, c->ts ? c->ts : c->stream) != hipSuccess) { hipEventDestroy(a); hipEventDestroy(b); on = false; ++c->event_errors; }
+        if (!c->event_pool.grab(&a)) { on = false; ++c->event_errors; return; }
+        if (!c->event_pool.grab(&b)) { c->event_pool.put(a); on = false; ++c->event_errors; return; }
+        if (hipEventRecord(a, c->ts ? c->ts : c->stream) != hipSuccess) { c->event_pool.put(a); c->event_pool.put(b); on = false; ++c->event_errors; }
     }
     ~Timed()
     {
         if (trace()) { const hipError_t e = hipStreamSynchronize(c->ts ? c->ts : c->stream); fprintf(stderr, " %s\n", e == hipSuccess ? "ok" : hipGetErrorString(e)); }
         if (!on) return;
-        if (hipEventRecord(b, c->ts ? c->ts : c->stream) != hipSuccess) { hipEventDestroy(a); hipEventDestroy(b); ++c->event_errors; return; }
+        if (hipEventRecord(b, c->ts ? c->ts : c->stream) != hipSuccess) { c->event_pool.put(a); c->event_pool.put(b); ++c->event_errors; return; }
         c->events.push_back({name, level, a, b, -1});
     }
 };
@@ -548,9 +537,7 @@ void clear_events(az_ctx *c)
 {
     for (auto &e : c->events) {
         if (e.slot >= 0) continue;
-        for (hipEvent_t ev : {e.a, e.b}) {
-            if (c->event_pool.size() < 4096) c->event_pool.push_back(ev); else hipEventDestroy(ev);
-        }
+        for (hipEvent_t ev : {e.a, e.b}) c->event_pool.put(ev);
     }
     c->events.clear();
 }
@@ -569,9 +556,9 @@ int num_levels(int h, int w, double min_side)
 int ensure_host(az_ctx *c, int cap)
 {
     if (cap <= c->h_cap) return AZ_OK;
-    if (c->h_Y) { hipHostFree(c->h_Y); hipHostFree(c->h_S); }
-    HIPCHK(c, hipHostMalloc((void **)&c->h_Y, (size_t)cap * 4 * sizeof(double)));
-    HIPCHK(c, hipHostMalloc((void **)&c->h_S, (size_t)cap * sizeof(float)));
+    c->h_cap = 0; c->h_Y = nullptr; c->h_S = nullptr;
+    HIPCHK(c, reserve_group({{&c->h_own[0], (size_t)cap * 4 * sizeof(double)}, {&c->h_own[1], (size_t)cap * sizeof(float)}}));
+    c->h_Y = c->h_own[0].as<double>(); c->h_S = c->h_own[1].as<float>();
     c->h_cap = cap;
     return AZ_OK;
 }
@@ -669,7 +656,7 @@ void launch_head(az_ctx *c, const int *Uptr, int level, int im_h, int im_w, doub
         if (!c->part7_no_room && !c->part7_ring[1]) {
             c->part7_ring[0] = c->part7;
             for (int q = 1; q < 3 && !c->part7_no_room; ++q)
-                if (dalloc(c, &c->part7_ring[q], (size_t)c->S7 * c->maxR * d.n7) != AZ_OK) { c->err.clear(); (void)hipGetLastError(); c->part7_no_room = true; }
+                if (c->allocs.alloc(&c->part7_ring[q], (size_t)c->S7 * c->maxR * d.n7) != hipSuccess) { c->err.clear(); (void)hipGetLastError(); c->part7_no_room = true; }
             if (c->part7_no_room) c->part7_ring[1] = c->part7_ring[2] = nullptr;     // (no room: one buffer + the wait)
         }
         if (!c->part7_no_room && c->part7_ring[2] && c->part7_ring[0] == c->part7) {
@@ -708,30 +695,12 @@ void launch_head(az_ctx *c, const int *Uptr, int level, int im_h, int im_w, doub
     }
 }
 
-// Scratch slot `i` of the evaluation entry points, grown to at least `bytes`.
-int ev_grow(az_ctx *c, int i, void **slot, size_t bytes)
+// Scratch slot `i` of the evaluation entry points, grown to at least `bytes` (half as much again + 256 when it grows).
+int scratch_grow(az_ctx *c, int i, size_t bytes)
 {
-    if (bytes <= c->ev_sz[i] && *slot) return AZ_OK;
-    if (*slot) hipFree(*slot);
-    *slot = nullptr;
-    c->ev_sz[i] = 0;
-    const size_t want = bytes + bytes / 2 + 256;
-    hipError_t e = hipMalloc(slot, want);
+    const hipError_t e = c->scratch[i].reserve(bytes, bytes + bytes / 2 + 256);
     if (e != hipSuccess) return fail(c, AZ_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
-    c->ev_sz[i] = want;
     return AZ_OK;
-}
-
-void free_plan(az_ctx::StaticPlan *q)
-{
-    for (void *p : {(void *)q->urois, (void *)q->ubox, (void *)q->reg_u, (void *)q->cand_src, (void *)q->meta})
-        if (p) hipFree(p);
-    q->urois = nullptr; q->ubox = nullptr; q->reg_u = nullptr; q->cand_src = nullptr; q->meta = nullptr;
-    for (auto &f : q->fs) {
-        for (void *p : {(void *)f.htab, (void *)f.spec_map, (void *)f.full_meta, (void *)f.full_urois, (void *)f.full_ubox})
-            if (p) hipFree(p);
-        f = az_ctx::StaticPlan::FullSet();
-    }
 }
 
 // `stream` waits for everything the context has enqueued on its second stream (stage 2 of two-stage searches): called by
@@ -821,7 +790,6 @@ int skip_front_check(az_ctx *c, const std::string &who, int n_src, const int *Cs
                      long long *sumC_out);
 // the front on the rois in c->urois (row count *Uptr, at most rows_bound): pool5 [U][49][Cout] as the head's fc6 reads it
 void skip_front_launch(az_ctx *c, const int *Uptr, int rows_bound);
-void skip_free(az_ctx *c);                // az_destroy
 int skip_pool_unit(az_ctx *c, int R, int normalise, float *out);      // az_skip_pool past its checks, the rois staged
 // ---- az_capi.hip --------------------------------------------------------------------------------------------------------
 int set_feature_map_common(az_ctx *c, const float *src, bool src_is_host, int C, int H, int W, bool wait = true);

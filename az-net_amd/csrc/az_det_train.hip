@@ -158,8 +158,8 @@ int az_det_targets(az_ctx *c, int n_images, const float *ex_boxes, const int32_t
     const size_t o_ex = ar.add((size_t)E * 16), o_eo = ar.add(no), o_gt = ar.add((size_t)NG * 16 + 16), o_gl = ar.add((size_t)NG * 4 + 16),
                  o_go = ar.add(no), o_t = ar.add((size_t)E * 20), o_m = ar.add((size_t)E * 8);
     int rc;
-    if ((rc = ev_grow(c, 0, &c->ev_a, ar.total)) != AZ_OK) return rc;
-    char *base = (char *)c->ev_a;
+    if ((rc = scratch_grow(c, 0, ar.total)) != AZ_OK) return rc;
+    char *base = (char *)c->scratch[0].p;
     hipStream_t s = c->stream;
     HIPCHK(c, hipMemcpyAsync(base + o_ex, ex_boxes, (size_t)E * 16, hipMemcpyHostToDevice, s));
     HIPCHK(c, hipMemcpyAsync(base + o_eo, ex_off, no, hipMemcpyHostToDevice, s));
@@ -193,8 +193,8 @@ int az_det_target_stats(az_ctx *c, int n_images, float *targets, const int32_t *
     const size_t o_t = ar.add((size_t)E * 20 + 16), o_eo = ar.add(no), o_p = ar.add(cells * 36), o_c = ar.add((size_t)num_classes * 8),
                  o_m = ar.add((size_t)num_classes * 32), o_s = ar.add((size_t)num_classes * 32);
     int rc;
-    if ((rc = ev_grow(c, 0, &c->ev_a, ar.total)) != AZ_OK) return rc;
-    char *base = (char *)c->ev_a;
+    if ((rc = scratch_grow(c, 0, ar.total)) != AZ_OK) return rc;
+    char *base = (char *)c->scratch[0].p;
     hipStream_t s = c->stream;
     if (E) HIPCHK(c, hipMemcpyAsync(base + o_t, targets, (size_t)E * 20, hipMemcpyHostToDevice, s));
     HIPCHK(c, hipMemcpyAsync(base + o_eo, ex_off, no, hipMemcpyHostToDevice, s));

@@ -177,8 +177,8 @@ int az_diag_eval(az_ctx *c, int n_images, const double *anchors, const float *zo
     const size_t o_tab = take((n_lt + n_rt) * 8);
     HIPCHK(c, hipSetDevice(c->device));
     int rc;
-    if ((rc = ev_grow(c, 10, &c->ev_diag, off)) != AZ_OK) return rc;
-    char *B = (char *)c->ev_diag;
+    if ((rc = scratch_grow(c, 10, off)) != AZ_OK) return rc;
+    char *B = (char *)c->scratch[10].p;
     hipStream_t s = c->stream;
     auto *d_anc = (double *)(B + o_anc), *d_gt = (double *)(B + o_gt), *d_prop = (double *)(B + o_prop);
     auto *d_zoom = (float *)(B + o_zoom);
@@ -198,10 +198,10 @@ int az_diag_eval(az_ctx *c, int n_images, const double *anchors, const float *zo
     HIPCHK(c, hipMemcpyAsync(d_goff, gt_off, ((size_t)n_images + 1) * 4, hipMemcpyHostToDevice, s));
     HIPCHK(c, hipMemcpyAsync(d_poff, prop_off, ((size_t)n_images + 1) * 4, hipMemcpyHostToDevice, s));
     HIPCHK(c, hipMemsetAsync(d_lt, 0, (n_lt + n_rt) * 8, s));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    Event e0, e1;
     if (kernel_ms_out) {
-        HIPCHK(c, hipEventCreate(&e0));
-        if (hipEventCreate(&e1) != hipSuccess) { hipEventDestroy(e0); return fail(c, AZ_ERR_HIP, "az_diag_eval: hipEventCreate"); }
+        HIPCHK(c, e0.create(hipEventDefault));
+        if (e1.create(hipEventDefault) != hipSuccess) return fail(c, AZ_ERR_HIP, "az_diag_eval: hipEventCreate");
         hipEventRecord(e0, s);
     }
     if (A)
@@ -232,8 +232,6 @@ int az_diag_eval(az_ctx *c, int n_images, const double *anchors, const float *zo
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     float ms = 0.f;
     if (e == hipSuccess && kernel_ms_out) e = hipEventElapsedTime(&ms, e0, e1);
-    if (e0) hipEventDestroy(e0);
-    if (e1) hipEventDestroy(e1);
     if (e != hipSuccess) return fail(c, AZ_ERR_HIP, std::string("az_diag_eval: ") + hipGetErrorString(e));
     // the tables reach the caller only once the whole call has succeeded
     if (level_table_out) memcpy(level_table_out, lt, sizeof(int64_t) * n_lt);

@@ -55,9 +55,8 @@ int calibrate_passes(az_ctx *c)
         HIPCHK(c, hipMemcpyAsync(c->urois, r.data(), r.size() * sizeof(float), hipMemcpyHostToDevice, s));
         HIPCHK(c, hipStreamSynchronize(s));
     }
-    hipEvent_t ea = nullptr, eb = nullptr;
-    if (hipEventCreate(&ea) != hipSuccess || hipEventCreate(&eb) != hipSuccess) {
-        if (ea) hipEventDestroy(ea);
+    Event ea, eb;
+    if (ea.create(hipEventDefault) != hipSuccess || eb.create(hipEventDefault) != hipSuccess) {
         (void)hipGetLastError();
         return AZ_OK;
     }
@@ -80,7 +79,6 @@ int calibrate_passes(az_ctx *c)
         }
         k.rows[i] = sizes[i]; k.us[i] = best;
     }
-    hipEventDestroy(ea); hipEventDestroy(eb);
     c->profiling = prof;
     c->npass = 0;
     (void)hipGetLastError();

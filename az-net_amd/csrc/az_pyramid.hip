@@ -37,8 +37,8 @@ int az_set_feature_pyramid_dev_nhwc(az_ctx *c, const float *const *maps, int S, 
         return fail(c, AZ_ERR_INVALID, "az_set_feature_pyramid_dev_nhwc: channel count must match the loaded head");
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->pyr_feats) {
-        HIPCHK(c, hipMalloc((void **)&c->pyr_feats, AZ_PYRAMID_MAX * sizeof(const float *)));
-        HIPCHK(c, hipMalloc((void **)&c->pyr_hw, AZ_PYRAMID_MAX * 2 * sizeof(int)));
+        HIPCHK(c, reserve_group({{&c->pyr_own[0], AZ_PYRAMID_MAX * sizeof(const float *)}, {&c->pyr_own[1], AZ_PYRAMID_MAX * 2 * sizeof(int)}}));
+        c->pyr_feats = c->pyr_own[0].as<const float *>(); c->pyr_hw = c->pyr_own[1].as<int>();
     }
     const float *tab[AZ_PYRAMID_MAX] = {};
     int hw[2 * AZ_PYRAMID_MAX] = {};

@@ -61,8 +61,8 @@ static int enqueue_search(az_ctx *c, const az_params *p, int K, int nlev, int k,
     const bool fused = plan.fused, fused_lv = plan.fused_lv, defer_root = plan.defer_root;
     if (tune && !c->hisB) {
         c->capHis = 2 * c->maxR;
-        HIPCHK(c, hipMalloc((void **)&c->hisB, (size_t)c->capHis * 4 * sizeof(double)));
-        HIPCHK(c, hipMalloc((void **)&c->hisZ, (size_t)c->capHis * sizeof(float)));
+        HIPCHK(c, reserve_group({{&c->his_own[0], (size_t)c->capHis * 4 * sizeof(double)}, {&c->his_own[1], (size_t)c->capHis * sizeof(float)}}));
+        c->hisB = c->his_own[0].as<double>(); c->hisZ = c->his_own[1].as<float>();
     }
     if (!fused) azk_init_root(s, c->cnt, c->B[0], p->im_h, p->im_w);       // also zeroes the counters
     if (fused) {
@@ -324,15 +324,11 @@ static int launch_impl_body(az_ctx *c, const az_params *p)
     if (c->split_now && !c->stream2) {
         int lo = 0, hi = 0;
         (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-        if (hipStreamCreateWithPriority(&c->stream2, hipStreamNonBlocking, lo) != hipSuccess ||
-            hipEventCreateWithFlags(&c->ev_h6, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&c->ev_i7, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&c->ev_s2, hipEventDisableTiming) != hipSuccess ||
-            hipStreamCreateWithPriority(&c->stream3, hipStreamNonBlocking, lo) != hipSuccess ||
-            hipEventCreateWithFlags(&c->ev_tail, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&c->ev_s3, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&c->ev_geo[0], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&c->ev_geo[1], hipEventDisableTiming) != hipSuccess) {
+        bool ok = c->stream2.create(hipStreamNonBlocking, lo) == hipSuccess;
+        for (Event *e : {&c->ev_h6, &c->ev_i7, &c->ev_s2}) ok = ok && e->create(hipEventDisableTiming) == hipSuccess;
+        ok = ok && c->stream3.create(hipStreamNonBlocking, lo) == hipSuccess;
+        for (Event *e : {&c->ev_tail, &c->ev_s3, &c->ev_geo[0], &c->ev_geo[1]}) ok = ok && e->create(hipEventDisableTiming) == hipSuccess;
+        if (!ok) {
             (void)hipGetLastError();
             c->split_now = 0; c->no_stage_streams = true;          // (this device / runtime does not give the extra streams: one stage)
         }

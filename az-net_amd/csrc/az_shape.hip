@@ -38,13 +38,10 @@ int ensure_spec_cache(az_ctx *c, const az_params *p, const SearchPlan &q)
     az_ctx::SpecEntry e;
     e.h = p->im_h; e.w = p->im_w; e.defer = defer; e.scale = p->scale; e.min_side = p->min_side;
     e.P1 = c->h_cnt->specP1; e.CH = c->h_cnt->specCH; e.U = c->h_cnt->specU;
-    if (hipMalloc((void **)&e.urois, (size_t)(e.U + 1) * 5 * sizeof(float)) != hipSuccess ||
-        hipMalloc((void **)&e.B1, (size_t)(e.P1 + 1) * 4 * sizeof(double)) != hipSuccess ||
-        hipMalloc((void **)&e.choff, (size_t)(e.P1 + 1) * sizeof(int)) != hipSuccess ||
-        hipMalloc((void **)&e.Udev, 16) != hipSuccess) {
-        for (void *q2 : {(void *)e.urois, (void *)e.B1, (void *)e.choff, (void *)e.Udev}) if (q2) hipFree(q2);
+    if (reserve_group({{&e.own[0], (size_t)(e.U + 1) * 5 * sizeof(float)}, {&e.own[1], (size_t)(e.P1 + 1) * 4 * sizeof(double)},
+                       {&e.own[2], (size_t)(e.P1 + 1) * sizeof(int)}, {&e.own[3], 16}}) != hipSuccess)
         return fail(c, AZ_ERR_HIP, "hipMalloc failed for a speculative pre-pass entry");
-    }
+    e.urois = e.own[0].as<float>(); e.B1 = e.own[1].as<double>(); e.choff = e.own[2].as<int>(); e.Udev = e.own[3].as<int>();
     HIPCHK(c, hipMemcpyAsync(e.urois, c->spec_scr_urois[defer], (size_t)e.U * 5 * sizeof(float), hipMemcpyDeviceToDevice, s));
     HIPCHK(c, hipMemcpyAsync(e.B1, c->spec_scr_B1[defer], (size_t)e.P1 * 4 * sizeof(double), hipMemcpyDeviceToDevice, s));
     HIPCHK(c, hipMemcpyAsync(e.choff, c->spec_scr_choff[defer], (size_t)e.P1 * sizeof(int), hipMemcpyDeviceToDevice, s));
@@ -60,10 +57,9 @@ int ensure_spec_cache(az_ctx *c, const az_params *p, const SearchPlan &q)
         c->graphs.clear();
         auto &d = c->spec_store[lru];
         for (int i = 0; i < 2; ++i) if (c->spec_urois[i] == d.urois) { c->spc[i].h = -1; }
-        for (void *q2 : {(void *)d.urois, (void *)d.B1, (void *)d.choff, (void *)d.Udev}) hipFree(q2);
         c->spec_store.erase(c->spec_store.begin() + (long)lru);
     }
-    c->spec_store.push_back(e);
+    c->spec_store.push_back(std::move(e));
     use(c->spec_store.back());
     return AZ_OK;
 }
@@ -93,9 +89,7 @@ int ensure_static_plan(az_ctx *c, const az_params *p, int nlev)
         c->nostatic.emplace_back(p->im_h, p->im_w);
         return (int)AZ_OK;
     };
-    // (the plan under construction owns five device buffers until it is handed to the cache: freed on every other exit)
-    struct PlanGuard { az_ctx::StaticPlan k; bool keep = false; ~PlanGuard() { if (!keep) free_plan(&k); } } pg;
-    az_ctx::StaticPlan &k = pg.k;
+    az_ctx::StaticPlan k;      // (owns its five device buffers: freed on every exit but the one that moves it into the cache)
     // Two passes over the tree: sizes first, then placement.  Rows of the one head pass: levels 2, 3, ... in order, the
     // root last (RoIPool treats that one whole-image roi cooperatively: a workgroup per bin instead of a wave.
     // Deepest level first with levels 1-3 cooperative was measured too: 26.2 us against 24.5).
@@ -141,11 +135,9 @@ int ensure_static_plan(az_ctx *c, const az_params *p, int nlev)
             if (k.Utot > c->maxR || roff > c->maxR) return give_up();
             k.coop = 1;
             // exact-size buffers of this shape's plan
-            auto grab = [&](void **q, size_t bytes) { return hipMalloc(q, bytes + 256) == hipSuccess; };
-            if (!grab((void **)&k.urois, (size_t)k.Utot * 5 * sizeof(float)) ||
-                !grab((void **)&k.ubox, (size_t)k.Utot * 4 * sizeof(double)) ||
-                !grab((void **)&k.reg_u, (size_t)roff * sizeof(int)) ||
-                !grab((void **)&k.cand_src, (size_t)roff * AZ_NSUB * sizeof(int)) || !grab((void **)&k.meta, 16))
+            if (k.own.alloc(&k.urois, (size_t)k.Utot * 5) != hipSuccess || k.own.alloc(&k.ubox, (size_t)k.Utot * 4) != hipSuccess ||
+                k.own.alloc(&k.reg_u, (size_t)roff) != hipSuccess || k.own.alloc(&k.cand_src, (size_t)roff * AZ_NSUB) != hipSuccess ||
+                k.own.alloc(&k.meta, 4) != hipSuccess)
                 return fail(c, AZ_ERR_HIP, "hipMalloc failed for a static plan");
         }
     }
@@ -162,12 +154,10 @@ int ensure_static_plan(az_ctx *c, const az_params *p, int nlev)
         for (size_t i = 1; i < c->plans.size(); ++i) if (c->plans[i]->last_use < c->plans[lru]->last_use) lru = i;
         for (auto &g : c->graphs) hipGraphExecDestroy(g.second.exec);
         c->graphs.clear();
-        free_plan(c->plans[lru]);
         delete c->plans[lru];
         c->plans.erase(c->plans.begin() + (long)lru);
     }
-    c->plans.push_back(new az_ctx::StaticPlan(k));
-    pg.keep = true;
+    c->plans.push_back(new az_ctx::StaticPlan(std::move(k)));
     c->plan = c->plans.back();
     return AZ_OK;
 }
@@ -191,10 +181,9 @@ static int build_full_set(az_ctx *c, const az_params *p, int nlev, int variant)
     const auto &sp = c->spc[0];
     join_s2(c);
     hipStream_t s = c->stream;
-    auto grab = [&](void **q, size_t bytes) { return hipMalloc(q, bytes + 256) == hipSuccess; };
+    f.own.release();                               // (what an earlier attempt that ended in an error left behind)
     auto give_up = [&]() {
         (void)hipGetLastError();
-        for (void *q : {(void *)f.htab, (void *)f.spec_map, (void *)f.full_meta, (void *)f.full_urois, (void *)f.full_ubox}) if (q) hipFree(q);
         f = az_ctx::StaticPlan::FullSet();
         f.full_state = -1;
         return (int)AZ_OK;
@@ -202,12 +191,12 @@ static int build_full_set(az_ctx *c, const az_params *p, int nlev, int variant)
     if (sp.U > 64) return give_up();
     const int root = k.Utot - 1;                   // the plan's last row
     int base_rows = 0;                             // rows of the pass before the extra rows
-    struct Tmp { float *all = nullptr; int *newrow = nullptr; ~Tmp() { if (all) hipFree(all); if (newrow) hipFree(newrow); } } tmp;
+    struct Tmp { float *all = nullptr; int *newrow = nullptr; DevList own; } tmp;
     int N = 0;
     if (variant == 1) {
         // every region any pruning can produce, level by level (no _sift_dup: whichever duplicate survives is among them)
         const int capAll = (int)AZ_TAB_ROOT_HOST - 2;
-        if (!grab((void **)&tmp.all, (size_t)capAll * 5 * sizeof(float)) || !grab((void **)&tmp.newrow, (size_t)capAll * sizeof(int)))
+        if (tmp.own.alloc(&tmp.all, (size_t)capAll * 5) != hipSuccess || tmp.own.alloc(&tmp.newrow, (size_t)capAll) != hipSuccess)
             return give_up();
         const double rootb[4] = {0.0, 0.0, p->im_w - 1.0, p->im_h - 1.0};           // test.py:355
         HIPCHK(c, hipMemsetAsync(c->cnt, 0, sizeof(AzCounts), s));
@@ -238,9 +227,9 @@ static int build_full_set(az_ctx *c, const az_params *p, int nlev, int variant)
     const int cap = (variant == 1 ? N : k.Utot) + sp.U + 1;
     unsigned T = 64; while (T < 2u * (unsigned)cap) T <<= 1;
     if (cap > c->maxR || cap >= (int)AZ_TAB_ROOT_HOST ||
-        !grab((void **)&f.htab, (size_t)T * 8) || !grab((void **)&f.spec_map, (size_t)sp.U * sizeof(int)) ||
-        !grab((void **)&f.full_meta, 16) || !grab((void **)&f.full_urois, (size_t)cap * 5 * sizeof(float)) ||
-        !grab((void **)&f.full_ubox, (size_t)cap * 4 * sizeof(double)))
+        f.own.alloc(&f.htab, (size_t)T) != hipSuccess || f.own.alloc(&f.spec_map, (size_t)sp.U) != hipSuccess ||
+        f.own.alloc(&f.full_meta, 4) != hipSuccess || f.own.alloc(&f.full_urois, (size_t)cap * 5) != hipSuccess ||
+        f.own.alloc(&f.full_ubox, (size_t)cap * 4) != hipSuccess)
         return give_up();
     f.hT = T;
     HIPCHK(c, hipMemsetAsync(f.full_meta, 0, 16, s));

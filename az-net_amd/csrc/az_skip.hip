@@ -135,12 +135,6 @@ void skip_front_launch(az_ctx *c, const int *Uptr, int rows_bound)
     }
 }
 
-void skip_free(az_ctx *c)
-{
-    for (void *p : {(void *)c->skip.Wp, (void *)c->skip.bp, (void *)c->skip.cat}) if (p) hipFree(p);
-    c->skip = az_ctx::SkipFront();
-}
-
 // az_skip_pool past its argument checks (the rois staged in c->urois, their count in cnt->U[0])
 int skip_pool_unit(az_ctx *c, int R, int normalise, float *out)
 {
@@ -173,21 +167,18 @@ int az_load_skip_front(az_ctx *c, int n_src, const int *Cs, const float *spatial
     join_s2(c);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     // (the new front's buffers first: an error leaves the front loaded before in place)
-    float *nW = nullptr, *nb = nullptr, *ncat = nullptr;
+    az_ctx::SkipFront nk;
+    float *&nW = nk.Wp, *&nb = nk.bp;
     const size_t wn = (size_t)Cout * sumC, catn = (size_t)skip_chunk(c) * 49 * sumC;
-    if (hipMalloc((void **)&nW, wn * 4 + 256) != hipSuccess || hipMalloc((void **)&nb, (size_t)Cout * 4 + 256) != hipSuccess ||
-        hipMalloc((void **)&ncat, catn * 4 + 256) != hipSuccess ||
+    if (nk.own.alloc(&nW, wn) != hipSuccess || nk.own.alloc(&nb, (size_t)Cout) != hipSuccess || nk.own.alloc(&nk.cat, catn) != hipSuccess ||
         hipMemcpy(nW, Wp, wn * 4, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(nb, bp, (size_t)Cout * 4, hipMemcpyHostToDevice) != hipSuccess) {
         (void)hipGetLastError();
-        for (void *p : {(void *)nW, (void *)nb, (void *)ncat}) if (p) hipFree(p);
         return fail(c, AZ_ERR_HIP, "az_load_skip_front: device memory");
     }
-    skip_free(c);
-    az_ctx::SkipFront &k = c->skip;
+    az_ctx::SkipFront &k = c->skip = std::move(nk);
     k.n = n_src; k.sumC = (int)sumC; k.Cout = Cout; k.gain = gain; k.eps = eps;
     for (int i = 0; i < n_src; ++i) { k.C[i] = Cs[i]; k.scale[i] = spatial_scales[i]; }
-    k.Wp = nW; k.bp = nb; k.cat = ncat;
     k.loaded = true;
     return AZ_OK;
 }

@@ -194,7 +194,7 @@ int az_det_solver_attach_skip(az_det_solver *s, int n_src, const int *Cs, const 
     // tiles of 128 x 128 over all slabs; az_det_solver.hip, part_elems), an unsplit forward for rows x Cout
     const size_t part_need = (size_t)rows * Cout;
     // (everything new is allocated behind `mark` and kept aside: an error releases it and leaves the trainer as it was)
-    const size_t mark = s->allocs.size();
+    const size_t mark = s->allocs.mark();
     const size_t pn2[2] = {wn, Cout};
     az_det_solver::Skip k;
     float *part = nullptr;
@@ -334,16 +334,13 @@ int az_skip_pool_bwd_unit(az_ctx *c, int n_src, const int *Cs, const float *spat
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
     const size_t big = (size_t)R * 49 * sumC;
-    std::vector<void *> tmp;
+    DevList tmp;                // (released on every exit)
     bool ok = true;
     auto grab = [&](size_t bytes) -> void * {
-        void *q = nullptr;
-        if (!ok) return nullptr;
-        if (hipMalloc(&q, bytes + 256) != hipSuccess) { (void)hipGetLastError(); ok = false; return nullptr; }
-        tmp.push_back(q);
+        char *q = nullptr;
+        if (ok && tmp.alloc(&q, bytes) != hipSuccess) { (void)hipGetLastError(); ok = false; }
         return q;
     };
-    auto release = [&]() { for (void *q : tmp) hipFree(q); };
     void *dmaps[AZ_SKIP_MAX_SRC] = {nullptr, nullptr, nullptr};
     float *dm[AZ_SKIP_MAX_SRC] = {nullptr, nullptr, nullptr};
     size_t msz[AZ_SKIP_MAX_SRC] = {0, 0, 0};
@@ -355,23 +352,20 @@ int az_skip_pool_bwd_unit(az_ctx *c, int n_src, const int *Cs, const float *spat
     float *drois = (float *)grab((size_t)R * 5 * 4), *cat = (float *)grab(big * 4), *draw = (float *)grab(big * 4);
     int *geo = (int *)grab((size_t)n_src * R * 8 * 4), *arg = (int *)grab(big * 4);
     double *fac = (double *)grab((size_t)R * 49 * n_src * 8);
-    if (!ok) { release(); return fail(c, AZ_ERR_HIP, who + ": device memory"); }
-#define UCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { release(); return fail(c, AZ_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); } } while (0)
-    for (int i = 0; i < n_src; ++i) UCHK(hipMemcpyAsync(dmaps[i], maps_host[i], msz[i], hipMemcpyHostToDevice, st));
-    UCHK(hipMemcpyAsync(drois, rois, (size_t)R * 5 * 4, hipMemcpyHostToDevice, st));
-    if (d_raw_host) UCHK(hipMemcpyAsync(draw, d_raw_host, big * 4, hipMemcpyHostToDevice, st));
+    if (!ok) return fail(c, AZ_ERR_HIP, who + ": device memory");
+    for (int i = 0; i < n_src; ++i) HIPCHK(c, hipMemcpyAsync(dmaps[i], maps_host[i], msz[i], hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(drois, rois, (size_t)R * 5 * 4, hipMemcpyHostToDevice, st));
+    if (d_raw_host) HIPCHK(c, hipMemcpyAsync(draw, d_raw_host, big * 4, hipMemcpyHostToDevice, st));
     launch_geo(st, drois, R, n_src, spatial_scales, geo);
     hipLaunchKernelGGL(k_skip_train_pool, dim3(R * 49, n_src), dim3(256), 0, st, a, 0, geo, R, 0, 1.0, 0.0, cat, arg, fac);
     if (d_raw_host && dmaps_out)
         for (int i = 0; i < n_src; ++i) if (dmaps_out[i]) launch_gather(c, a, i, draw, arg, geo, R, dm[i]);
-    UCHK(hipStreamSynchronize(st));
-    UCHK(hipGetLastError());
-    if (pooled_out) UCHK(hipMemcpy(pooled_out, cat, big * 4, hipMemcpyDeviceToHost));
-    if (argmax_out) UCHK(hipMemcpy(argmax_out, arg, big * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipStreamSynchronize(st));
+    HIPCHK(c, hipGetLastError());
+    if (pooled_out) HIPCHK(c, hipMemcpy(pooled_out, cat, big * 4, hipMemcpyDeviceToHost));
+    if (argmax_out) HIPCHK(c, hipMemcpy(argmax_out, arg, big * 4, hipMemcpyDeviceToHost));
     if (d_raw_host && dmaps_out)
-        for (int i = 0; i < n_src; ++i) if (dmaps_out[i]) UCHK(hipMemcpy(dmaps_out[i], dm[i], msz[i], hipMemcpyDeviceToHost));
-#undef UCHK
-    release();
+        for (int i = 0; i < n_src; ++i) if (dmaps_out[i]) HIPCHK(c, hipMemcpy(dmaps_out[i], dm[i], msz[i], hipMemcpyDeviceToHost));
     return AZ_OK;
 }
 

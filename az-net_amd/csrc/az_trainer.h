@@ -23,16 +23,19 @@ struct az_trainer {
     float *part = nullptr, *loss = nullptr;
     double *sq_part = nullptr, *sq = nullptr;
     size_t part_elems = 0;
-    std::vector<void *> allocs;
+    DevList allocs;
     // shape of the last step (what the debug fetch sizes its answers by)
     int R = 0, N = 0, H = 0, W = 0, trained = 0;
     int prec = AZ_TRAIN_FP32;             // operands of every matrix product (*_set_precision)
 };
 
 // ---- memory ------------------------------------------------------------------------------------------------------------------
-int tr_alloc_bytes(az_trainer *t, void **p, size_t bytes);                   // hipMalloc, remembered in t->allocs
 template <typename T>
-int tr_alloc(az_trainer *t, T **p, size_t n) { return tr_alloc_bytes(t, (void **)p, n * sizeof(T)); }
+int tr_alloc(az_trainer *t, T **p, size_t n)                                  // n elements in t->allocs, a view of them in *p
+{
+    if (t->allocs.alloc(p, n) == hipSuccess) return AZ_OK;
+    return fail(t->c, AZ_ERR_HIP, std::string(t->tag) + ": " + alloc_what(n * sizeof(T)) + " failed");
+}
 // frees what was allocated from allocs[mark] on (0: everything) and forgets the parameters from t->np on
 void tr_release(az_trainer *t, size_t mark);
 // *_destroy: waits for the stream, frees the trainer's memory, takes it off its context's list and deletes it

@@ -388,19 +388,9 @@ void launch_gemm(hipStream_t s, int form, const float *A, const float *B, float 
 }
 
 // ---- memory ------------------------------------------------------------------------------------------------------------------
-int tr_alloc_bytes(az_trainer *t, void **p, size_t bytes)
-{
-    void *q = nullptr;
-    if (hipMalloc(&q, bytes + 256) != hipSuccess) return fail(t->c, AZ_ERR_HIP, std::string(t->tag) + ": hipMalloc(" + std::to_string(bytes) + " B) failed");
-    t->allocs.push_back(q);
-    *p = q;
-    return AZ_OK;
-}
-
 void tr_release(az_trainer *t, size_t mark)
 {
-    for (size_t i = mark; i < t->allocs.size(); ++i) hipFree(t->allocs[i]);
-    t->allocs.resize(mark);
+    t->allocs.release(mark);
     for (int p = t->np; p < TR_MAXP; ++p) { t->pn[p] = 0; t->w[p] = t->g[p] = t->h[p] = nullptr; }
 }
 
@@ -675,12 +665,10 @@ int az_solver_gemm_unit_prec(az_ctx *c, int form, int precision, const float *a,
     HIPCHK(c, hipSetDevice(c->device));
     int S, Kc;
     pick_split(M, N, K, &S, &Kc);
-    float *da = nullptr, *db = nullptr, *dp = nullptr, *dd = nullptr;
     const size_t slab = (size_t)M * N;
-    hipError_t e = hipMalloc((void **)&da, (size_t)M * K * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&db, (size_t)N * K * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&dp, slab * S * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&dd, slab * 4);
+    Buf buf[4];
+    hipError_t e = reserve_group({{&buf[0], (size_t)M * K * 4}, {&buf[1], (size_t)N * K * 4}, {&buf[2], slab * S * 4}, {&buf[3], slab * 4}});
+    float *da = buf[0].as<float>(), *db = buf[1].as<float>(), *dp = buf[2].as<float>(), *dd = buf[3].as<float>();
     if (e == hipSuccess) e = hipMemcpyAsync(da, a, (size_t)M * K * 4, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(db, b, (size_t)N * K * 4, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
@@ -691,7 +679,6 @@ int az_solver_gemm_unit_prec(az_ctx *c, int form, int precision, const float *a,
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = hipGetLastError();
-    for (float *q : {da, db, dp, dd}) if (q) hipFree(q);
     if (e != hipSuccess) return fail(c, AZ_ERR_HIP, std::string("az_solver_gemm_unit: ") + hipGetErrorString(e));
     return AZ_OK;
 }

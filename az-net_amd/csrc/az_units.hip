@@ -262,7 +262,8 @@ int az_nms(az_ctx *c, const float *dets, int n, double thresh, int64_t *keep, in
     if (n <= azk_nms_small_max()) {
         // the reference's own call-site size (apply_nms, test.py:467-484: <= 100 boxes per class): ONE launch, no copy
         // commands -- the workgroup reads the boxes from and writes the keep list to host-mapped memory
-        if (!c->h_nms) HIPCHK(c, hipHostMalloc((void **)&c->h_nms, 8192, hipHostMallocMapped));
+        HIPCHK(c, c->h_nms_own.reserve(8192));
+        c->h_nms = c->h_nms_own.as<unsigned char>();
         float *hd = (float *)c->h_nms;                                  // [256][5] f32 = 5120 B
         long long *hk = (long long *)(c->h_nms + 5120);                 // [256] i64 = 2048 B, then the count
         int *hn = (int *)(c->h_nms + 5120 + 2048);
@@ -295,19 +296,19 @@ int az_nms(az_ctx *c, const float *dets, int n, double thresh, int64_t *keep, in
     }
     if (n > c->nms_cap) {
         HIPCHK(c, hipStreamSynchronize(s));
-        if (c->nms_dets) { hipFree(c->nms_dets); hipFree(c->nms_sdets); hipFree(c->nms_order); hipFree(c->nms_mask); hipFree(c->nms_keep); hipFree(c->nms_rank); }
-        c->nms_dets = nullptr; c->nms_cap = 0;
+        Buf *b = c->nms_own;
+        for (int i = 0; i < 6; ++i) b[i].reset();
+        c->nms_cap = 0;
         int cap = 1024;
         while (cap < n) cap *= 2;
         const size_t W = (size_t)(cap + 63) / 64;
         if (azk_nms_scan_lds_bytes(cap) > 150000) return fail(c, AZ_ERR_CAPACITY, "az_nms: n too large");
-        HIPCHK(c, hipMalloc((void **)&c->nms_dets, (size_t)cap * 5 * 4));
-        HIPCHK(c, hipMalloc((void **)&c->nms_sdets, (size_t)cap * 5 * 4));
-        HIPCHK(c, hipMalloc((void **)&c->nms_order, (size_t)cap * 4 + 16));
-        HIPCHK(c, hipMalloc((void **)&c->nms_mask, ((size_t)cap * W + azk_nms_band_words(cap)) * 8));      // mask, then band
-        HIPCHK(c, hipMalloc((void **)&c->nms_rank, (size_t)cap * 4));
+        HIPCHK(c, reserve_group({{&b[0], (size_t)cap * 5 * 4}, {&b[1], (size_t)cap * 5 * 4}, {&b[2], (size_t)cap * 4 + 16},
+                                 {&b[3], ((size_t)cap * W + azk_nms_band_words(cap)) * 8},      // mask, then band
+                                 {&b[4], (size_t)cap * 4}, {&b[5], (size_t)cap * 8 + 16}}));
+        c->nms_dets = b[0].as<float>(); c->nms_sdets = b[1].as<float>(); c->nms_order = b[2].as<int>();
+        c->nms_mask = b[3].as<unsigned long long>(); c->nms_rank = b[4].as<int>(); c->nms_keep = b[5].as<long long>();
         HIPCHK(c, hipMemset(c->nms_rank, 0, (size_t)cap * 4));
-        HIPCHK(c, hipMalloc((void **)&c->nms_keep, (size_t)cap * 8 + 16));
         c->nms_cap = cap;
     }
     int *nk = c->nms_order + c->nms_cap;      // spare int after the order array
@@ -319,10 +320,9 @@ int az_nms(az_ctx *c, const float *dets, int n, double thresh, int64_t *keep, in
         const size_t need = (size_t)n * 8 + 64;
         if (need > c->h_nmsg_cap) {
             HIPCHK(c, hipStreamSynchronize(s));
-            if (c->h_nmsg) hipHostFree(c->h_nmsg);
             c->h_nmsg = nullptr; c->h_nmsg_cap = 0;
-            HIPCHK(c, hipHostMalloc((void **)&c->h_nmsg, need * 2, hipHostMallocMapped));
-            c->h_nmsg_cap = need * 2;
+            HIPCHK(c, c->h_nmsg_own.reserve(need, need * 2));
+            c->h_nmsg = c->h_nmsg_own.as<unsigned char>(); c->h_nmsg_cap = need * 2;
         }
         volatile long long *hn = (volatile long long *)c->h_nmsg;      // (tag << 32) | count
         long long *hk = (long long *)(c->h_nmsg + 64);                 // (tag << 32) | index
@@ -372,41 +372,38 @@ int az_load_det_head(az_ctx *c, int C, int n6, int n7, int ncls, const float *W6
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (void *p : c->allocs_det) hipFree(p);
-    c->allocs_det.clear();
+    c->allocs_det.release();
+    if (!c->head_loaded) c->pool5 = nullptr;     // (without an AZ head pool5 was the detection head's own: gone with the list)
     c->det_loaded = false;
     const size_t R = (size_t)c->maxR, K6 = (size_t)C * 49, NO = (size_t)5 * ncls;
     c->det_n6 = n6; c->det_n7 = n7; c->det_ncls = ncls;
     c->det_S6 = azk_fc_split((int)K6); c->det_S7 = azk_fc_split(n6);
-#define A(p, n) if ((rc = dalloc_det(c, &c->p, (n))) != AZ_OK) return rc
-    A(dW6, azk_tiled_elems(n6, (int)K6)); A(db6, n6); A(dW7, azk_tiled_elems(n7, n6)); A(db7, n7);
-    A(dWt, azk_tiled_elems((int)NO, n7)); A(dbt, NO);
-    A(dh6, R * n6); A(dh7, R * n7);
+    DevList &list = c->allocs_det;
+    AZ_A(dW6, azk_tiled_elems(n6, (int)K6)); AZ_A(db6, n6); AZ_A(dW7, azk_tiled_elems(n7, n6)); AZ_A(db7, n7);
+    AZ_A(dWt, azk_tiled_elems((int)NO, n7)); AZ_A(dbt, NO);
+    AZ_A(dh6, R * n6); AZ_A(dh7, R * n7);
     {
         size_t pm = (size_t)c->det_S6 * R * n6;
         const size_t p7 = (size_t)c->det_S7 * R * n7, pt = (size_t)AZK_TAIL_SPLIT * R * NO, pw = (size_t)n6 * K6;
         pm = pm > p7 ? pm : p7; pm = pm > pt ? pm : pt; pm = pm > pw ? pm : pw;
-        A(dpart, pm);
+        AZ_A(dpart, pm);
     }
-    A(dprob_u, R * ncls); A(ddelta_u, R * 4 * ncls); A(dpred_u, R * ncls * 4); A(dprob, R * ncls); A(dpred, R * ncls * 4);
-    A(dseg_dev, det_seg_bytes(c)); A(drow_hw, R * 2);
-    if (c->dseg_host) { hipHostFree(c->dseg_host); c->dseg_host = nullptr; }
-    HIPCHK(c, hipHostMalloc((void **)&c->dseg_host, det_seg_bytes(c)));
-    if (!c->pool5) { A(pool5, R * K6); }     // normally the AZ head's buffer is shared
+    AZ_A(dprob_u, R * ncls); AZ_A(ddelta_u, R * 4 * ncls); AZ_A(dpred_u, R * ncls * 4); AZ_A(dprob, R * ncls); AZ_A(dpred, R * ncls * 4);
+    AZ_A(dseg_dev, det_seg_bytes(c)); AZ_A(drow_hw, R * 2);
+    c->dseg_own.reset(); c->dseg_host = nullptr;
+    HIPCHK(c, c->dseg_own.reserve(det_seg_bytes(c)));
+    c->dseg_host = c->dseg_own.as<unsigned char>();
+    if (!c->pool5) { AZ_A(pool5, R * K6); }     // normally the AZ head's buffer is shared
     c->dW6p = nullptr; c->dgscale = nullptr;
     if (c->gemm_parts && c->pool5p && azk_fc_terms_prepare(c->gemm_parts) == 0) {
-        A(dW6p, (size_t)c->gemm_parts * azk_weight_plane_elems(n6, (int)K6)); A(dgscale, 4);
+        AZ_A(dW6p, (size_t)c->gemm_parts * azk_weight_plane_elems(n6, (int)K6)); AZ_A(dgscale, 4);
         HIPCHK(c, hipMemsetAsync(c->dgscale, 0, 4 * sizeof(float), c->stream));
     }
-#undef A
     if (!c->head_loaded) { c->d.C = C; c->d.pooled = 7; c->d.K6 = (int)K6; }
     {
-        struct TmpGuard { float *p = nullptr; ~TmpGuard() { if (p) hipFree(p); } } tg;
-        size_t te = (size_t)n6 * K6;
-        if ((size_t)n7 * n6 > te) te = (size_t)n7 * n6;
-        if (NO * n7 > te) te = NO * n7;
-        HIPCHK(c, hipMalloc((void **)&tg.p, te * 4));
-        float *tmp = tg.p;
+        Buf tg;
+        HIPCHK(c, tg.reserve(std::max(std::max((size_t)n6 * K6, (size_t)n7 * n6), NO * n7) * 4));
+        float *tmp = tg.as<float>();
         HIPCHK(c, hipMemcpy(c->dpart, W6, (size_t)n6 * K6 * 4, hipMemcpyHostToDevice));
         azk_permute_k(c->stream, c->dpart, tmp, n6, C, 1);          // bin-major columns, like the AZ head
         azk_tile_weights(c->stream, tmp, c->dW6, n6, (int)K6);
@@ -436,7 +433,7 @@ int az_load_det_head(az_ctx *c, int C, int n6, int n7, int ncls, const float *W6
     HIPCHK(c, hipMemcpy(c->dbt + ncls, bb, (size_t)4 * ncls * 4, hipMemcpyHostToDevice));
     HIPCHK(c, hipDeviceSynchronize());
     c->det_loaded = true;
-    if (c->skip.loaded && c->skip.Cout != C) skip_free(c);     // (a skip front folds to the head's C)
+    if (c->skip.loaded && c->skip.Cout != C) c->skip = az_ctx::SkipFront();     // (a skip front folds to the head's C)
     return AZ_OK;
 }
 
@@ -711,13 +708,13 @@ int az_nms_batched(az_ctx *c, const float *dets, const int32_t *offsets, int n_g
         const size_t need = o_flag + 64;
         if (need > c->h_nmsb_cap) {
             HIPCHK(c, hipStreamSynchronize(s));
-            if (c->h_nmsb) hipHostFree(c->h_nmsb);
             c->h_nmsb = nullptr; c->h_nmsb_cap = 0;
-            HIPCHK(c, hipHostMalloc((void **)&c->h_nmsb, need + need / 2, hipHostMallocMapped));
-            c->h_nmsb_cap = need + need / 2;
+            HIPCHK(c, c->h_nmsb_own.reserve(need, need + need / 2));
+            c->h_nmsb = c->h_nmsb_own.as<unsigned char>(); c->h_nmsb_cap = need + need / 2;
         }
         if (!c->nms_done) {
-            HIPCHK(c, hipMalloc((void **)&c->nms_done, 16));
+            HIPCHK(c, c->nms_done_own.reserve(16));
+            c->nms_done = c->nms_done_own.as<int>();
             HIPCHK(c, hipMemsetAsync(c->nms_done, 0, 16, s));
         }
         unsigned char *b = c->h_nmsb;
@@ -757,22 +754,22 @@ int az_nms_batched(az_ctx *c, const float *dets, const int32_t *offsets, int n_g
     } else
     if (!small.empty()) {
         int rc;
-        if ((rc = ev_grow(c, 0, &c->ev_a, (size_t)total * 5 * sizeof(float))) != AZ_OK) return rc;
-        if ((rc = ev_grow(c, 1, &c->ev_b, ((size_t)n_groups + 1) * sizeof(int))) != AZ_OK) return rc;
-        if ((rc = ev_grow(c, 2, &c->ev_c, small.size() * sizeof(int))) != AZ_OK) return rc;
-        if ((rc = ev_grow(c, 3, &c->ev_d, (size_t)total * sizeof(long long))) != AZ_OK) return rc;
-        if ((rc = ev_grow(c, 4, &c->ev_e, (size_t)n_groups * sizeof(int))) != AZ_OK) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->ev_a, dets, (size_t)total * 5 * sizeof(float), hipMemcpyHostToDevice, s));
-        HIPCHK(c, hipMemcpyAsync(c->ev_b, offsets, ((size_t)n_groups + 1) * sizeof(int), hipMemcpyHostToDevice, s));
-        HIPCHK(c, hipMemcpyAsync(c->ev_c, small.data(), small.size() * sizeof(int), hipMemcpyHostToDevice, s));
-        HIPCHK(c, hipMemsetAsync(c->ev_e, 0, (size_t)n_groups * sizeof(int), s));
+        if ((rc = scratch_grow(c, 0, (size_t)total * 5 * sizeof(float))) != AZ_OK) return rc;
+        if ((rc = scratch_grow(c, 1, ((size_t)n_groups + 1) * sizeof(int))) != AZ_OK) return rc;
+        if ((rc = scratch_grow(c, 2, small.size() * sizeof(int))) != AZ_OK) return rc;
+        if ((rc = scratch_grow(c, 3, (size_t)total * sizeof(long long))) != AZ_OK) return rc;
+        if ((rc = scratch_grow(c, 4, (size_t)n_groups * sizeof(int))) != AZ_OK) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->scratch[0].p, dets, (size_t)total * 5 * sizeof(float), hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(c->scratch[1].p, offsets, ((size_t)n_groups + 1) * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(c->scratch[2].p, small.data(), small.size() * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemsetAsync(c->scratch[4].p, 0, (size_t)n_groups * sizeof(int), s));
         if (!(c->profiling & 4)) clear_events(c);
         { Timed t(c, "nms_batched", (int)small.size());
-          azk_nms_small(s, (const float *)c->ev_a, (const int *)c->ev_b, (const int *)c->ev_c, (int)small.size(), thresh,
-                        (long long *)c->ev_d, (int *)c->ev_e); }
+          azk_nms_small(s, (const float *)c->scratch[0].p, (const int *)c->scratch[1].p, (const int *)c->scratch[2].p, (int)small.size(), thresh,
+                        (long long *)c->scratch[3].p, (int *)c->scratch[4].p); }
         std::vector<long long> hk((size_t)total);
-        HIPCHK(c, hipMemcpyAsync(hk.data(), c->ev_d, (size_t)total * sizeof(long long), hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipMemcpyAsync(n_keep, c->ev_e, (size_t)n_groups * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(hk.data(), c->scratch[3].p, (size_t)total * sizeof(long long), hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(n_keep, c->scratch[4].p, (size_t)n_groups * sizeof(int), hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipStreamSynchronize(s));           // `small`, `hk` live on this frame
         HIPCHK(c, hipGetLastError());
         for (int g : small)
@@ -812,14 +809,13 @@ int az_tune_begin(az_ctx *c, long long capacity)
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (capacity > c->pool_cap) {
-        if (c->pool) { hipFree(c->pool); hipFree(c->pool_tmp); c->pool = c->pool_tmp = nullptr; c->pool_cap = 0; }
-        HIPCHK(c, hipMalloc((void **)&c->pool, (size_t)capacity * sizeof(float)));
-        HIPCHK(c, hipMalloc((void **)&c->pool_tmp, (size_t)capacity * sizeof(float)));
-        c->pool_cap = capacity;
+        c->pool = c->pool_tmp = nullptr; c->pool_cap = 0;
+        HIPCHK(c, reserve_group({{&c->pool_own[0], (size_t)capacity * sizeof(float)}, {&c->pool_own[1], (size_t)capacity * sizeof(float)}}));
+        c->pool = c->pool_own[0].as<float>(); c->pool_tmp = c->pool_own[1].as<float>(); c->pool_cap = capacity;
     }
     if (!c->pool_n) {
-        HIPCHK(c, hipMalloc((void **)&c->pool_n, 4 * sizeof(unsigned long long)));
-        HIPCHK(c, hipMalloc((void **)&c->pool_hist, 256 * sizeof(unsigned long long)));
+        HIPCHK(c, reserve_group({{&c->pool_own[2], 4 * sizeof(unsigned long long)}, {&c->pool_own[3], 256 * sizeof(unsigned long long)}}));
+        c->pool_n = c->pool_own[2].as<unsigned long long>(); c->pool_hist = c->pool_own[3].as<unsigned long long>();
     }
     HIPCHK(c, hipMemsetAsync(c->pool_n, 0, 4 * sizeof(unsigned long long), c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -831,7 +827,7 @@ int az_tune_end(az_ctx *c)
     if (!c) return AZ_ERR_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->pool) { hipFree(c->pool); hipFree(c->pool_tmp); }
+    c->pool_own[0].reset(); c->pool_own[1].reset();
     c->pool = c->pool_tmp = nullptr;
     c->pool_cap = 0;
     return AZ_OK;
@@ -939,14 +935,14 @@ int az_bbox_overlaps(az_ctx *c, const double *boxes, int N, const double *query,
     if (N == 0 || K == 0) return AZ_OK;
     HIPCHK(c, hipSetDevice(c->device));
     int rc;
-    if ((rc = ev_grow(c, 0, &c->ev_a, (size_t)N * 4 * sizeof(double))) != AZ_OK) return rc;
-    if ((rc = ev_grow(c, 1, &c->ev_b, (size_t)K * 4 * sizeof(double))) != AZ_OK) return rc;
-    if ((rc = ev_grow(c, 2, &c->ev_c, (size_t)N * K * sizeof(double))) != AZ_OK) return rc;
+    if ((rc = scratch_grow(c, 0, (size_t)N * 4 * sizeof(double))) != AZ_OK) return rc;
+    if ((rc = scratch_grow(c, 1, (size_t)K * 4 * sizeof(double))) != AZ_OK) return rc;
+    if ((rc = scratch_grow(c, 2, (size_t)N * K * sizeof(double))) != AZ_OK) return rc;
     hipStream_t s = c->stream;
-    HIPCHK(c, hipMemcpyAsync(c->ev_a, boxes, (size_t)N * 4 * sizeof(double), hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(c->ev_b, query, (size_t)K * 4 * sizeof(double), hipMemcpyHostToDevice, s));
-    azk_bbox_overlaps(s, (const double *)c->ev_a, N, (const double *)c->ev_b, K, (double *)c->ev_c);
-    HIPCHK(c, hipMemcpyAsync(overlaps_out, c->ev_c, (size_t)N * K * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(c->scratch[0].p, boxes, (size_t)N * 4 * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(c->scratch[1].p, query, (size_t)K * 4 * sizeof(double), hipMemcpyHostToDevice, s));
+    azk_bbox_overlaps(s, (const double *)c->scratch[0].p, N, (const double *)c->scratch[1].p, K, (double *)c->scratch[2].p);
+    HIPCHK(c, hipMemcpyAsync(overlaps_out, c->scratch[2].p, (size_t)N * K * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     return AZ_OK;
 }
@@ -971,27 +967,27 @@ int az_recall_match(az_ctx *c, int n_images, const double *boxes, const int32_t 
     HIPCHK(c, hipSetDevice(c->device));
     int rc;
     const size_t offb = ((size_t)n_images + 1) * sizeof(int32_t);
-    if ((rc = ev_grow(c, 0, &c->ev_a, (size_t)NB * 4 * sizeof(double))) != AZ_OK) return rc;
-    if ((rc = ev_grow(c, 1, &c->ev_b, (size_t)NG * 4 * sizeof(double))) != AZ_OK) return rc;
-    if ((rc = ev_grow(c, 2, &c->ev_c, (size_t)ov_off[n_images] * sizeof(double) + 8)) != AZ_OK) return rc;
-    if ((rc = ev_grow(c, 3, &c->ev_d, offb)) != AZ_OK) return rc;
-    if ((rc = ev_grow(c, 4, &c->ev_e, offb)) != AZ_OK) return rc;
-    if ((rc = ev_grow(c, 5, &c->ev_f, ((size_t)n_images + 1) * sizeof(long long))) != AZ_OK) return rc;
-    if ((rc = ev_grow(c, 6, &c->ev_g, (size_t)NG * sizeof(double))) != AZ_OK) return rc;
-    if ((rc = ev_grow(c, 7, &c->ev_h, (size_t)n_images * sizeof(int))) != AZ_OK) return rc;
+    if ((rc = scratch_grow(c, 0, (size_t)NB * 4 * sizeof(double))) != AZ_OK) return rc;
+    if ((rc = scratch_grow(c, 1, (size_t)NG * 4 * sizeof(double))) != AZ_OK) return rc;
+    if ((rc = scratch_grow(c, 2, (size_t)ov_off[n_images] * sizeof(double) + 8)) != AZ_OK) return rc;
+    if ((rc = scratch_grow(c, 3, offb)) != AZ_OK) return rc;
+    if ((rc = scratch_grow(c, 4, offb)) != AZ_OK) return rc;
+    if ((rc = scratch_grow(c, 5, ((size_t)n_images + 1) * sizeof(long long))) != AZ_OK) return rc;
+    if ((rc = scratch_grow(c, 6, (size_t)NG * sizeof(double))) != AZ_OK) return rc;
+    if ((rc = scratch_grow(c, 7, (size_t)n_images * sizeof(int))) != AZ_OK) return rc;
     hipStream_t s = c->stream;
-    HIPCHK(c, hipMemcpyAsync(c->ev_a, boxes, (size_t)NB * 4 * sizeof(double), hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(c->ev_b, gt, (size_t)NG * 4 * sizeof(double), hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(c->ev_d, box_off, offb, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(c->ev_e, gt_off, offb, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(c->ev_f, ov_off.data(), ((size_t)n_images + 1) * sizeof(long long), hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemsetAsync(c->ev_h, 0, (size_t)n_images * sizeof(int), s));
-    azk_recall_match(s, n_images, (const double *)c->ev_a, (const int *)c->ev_d, (const double *)c->ev_b,
-                     (const int *)c->ev_e, (const long long *)c->ev_f, (double *)c->ev_c, (double *)c->ev_g,
-                     (int *)c->ev_h);
+    HIPCHK(c, hipMemcpyAsync(c->scratch[0].p, boxes, (size_t)NB * 4 * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(c->scratch[1].p, gt, (size_t)NG * 4 * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(c->scratch[3].p, box_off, offb, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(c->scratch[4].p, gt_off, offb, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(c->scratch[5].p, ov_off.data(), ((size_t)n_images + 1) * sizeof(long long), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemsetAsync(c->scratch[7].p, 0, (size_t)n_images * sizeof(int), s));
+    azk_recall_match(s, n_images, (const double *)c->scratch[0].p, (const int *)c->scratch[3].p, (const double *)c->scratch[1].p,
+                     (const int *)c->scratch[4].p, (const long long *)c->scratch[5].p, (double *)c->scratch[2].p, (double *)c->scratch[6].p,
+                     (int *)c->scratch[7].p);
     std::vector<int> bad((size_t)n_images);
-    HIPCHK(c, hipMemcpyAsync(gt_overlaps_out, c->ev_g, (size_t)NG * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipMemcpyAsync(bad.data(), c->ev_h, (size_t)n_images * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(gt_overlaps_out, c->scratch[6].p, (size_t)NG * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(bad.data(), c->scratch[7].p, (size_t)n_images * sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));     // ov_off / bad live on this frame
     for (int i = 0; i < n_images; ++i)
         if (bad[i])
@@ -1020,15 +1016,15 @@ static int image_blob_common(az_ctx *c, const uint8_t *im, int h, int w, const f
     HIPCHK(c, hipSetDevice(c->device));
     int rc;
     const size_t nin = (size_t)h * w * 3, nout = (size_t)oh * ow * 3;
-    if ((rc = ev_grow(c, 0, &c->ev_a, nin)) != AZ_OK) return rc;
+    if ((rc = scratch_grow(c, 0, nin)) != AZ_OK) return rc;
     hipStream_t s = c->stream;
-    HIPCHK(c, hipMemcpyAsync(c->ev_a, im, nin, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(c->scratch[0].p, im, nin, hipMemcpyHostToDevice, s));
     float *dst = out;
     if (!out_is_dev) {
-        if ((rc = ev_grow(c, 1, &c->ev_b, nout * sizeof(float))) != AZ_OK) return rc;
-        dst = (float *)c->ev_b;
+        if ((rc = scratch_grow(c, 1, nout * sizeof(float))) != AZ_OK) return rc;
+        dst = (float *)c->scratch[1].p;
     }
-    azk_image_blob(s, (const unsigned char *)c->ev_a, h, w, means, 1.0 / scale, 1.0 / scale, oh, ow, dst);
+    azk_image_blob(s, (const unsigned char *)c->scratch[0].p, h, w, means, 1.0 / scale, 1.0 / scale, oh, ow, dst);
     if (!out_is_dev) HIPCHK(c, hipMemcpyAsync(out, dst, nout * sizeof(float), hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     return AZ_OK;
@@ -1058,27 +1054,18 @@ int az_image_blob_dev_on(az_ctx *c, const uint8_t *im, int h, int w, const float
     const size_t nin = (size_t)h * w * 3;
     if (nin > c->io_cap) {
         // (larger images: nothing may still be reading the old slots)
-        for (auto &q : c->io) {
-            if (q.ev) HIPCHK(c, hipEventSynchronize(q.ev));
-            if (q.host) hipHostFree(q.host);
-            if (q.dev) hipFree(q.dev);
-            if (q.ev) hipEventDestroy(q.ev);
-        }
+        for (auto &q : c->io) HIPCHK(c, hipEventSynchronize(q.ev));
         c->io.clear();
         c->io_cap = nin + nin / 4 + 256;
         c->io_turn = 0;
     }
     auto add_slot = [&](size_t at) {
         az_ctx::IoSlot q;
-        if (hipHostMalloc((void **)&q.host, c->io_cap) != hipSuccess || hipMalloc((void **)&q.dev, c->io_cap) != hipSuccess ||
-            hipEventCreateWithFlags(&q.ev, hipEventDisableTiming) != hipSuccess) {
+        if (q.host.reserve(c->io_cap) != hipSuccess || q.dev.reserve(c->io_cap) != hipSuccess || q.ev.create(hipEventDisableTiming) != hipSuccess) {
             (void)hipGetLastError();
-            if (q.host) hipHostFree(q.host);
-            if (q.dev) hipFree(q.dev);
-            if (q.ev) hipEventDestroy(q.ev);
-            return false;
+            return false;                      // (q's owners release whatever it got)
         }
-        c->io.insert(c->io.begin() + (long)at, q);
+        c->io.insert(c->io.begin() + (long)at, std::move(q));
         return true;
     };
     while (c->io.size() < 2)
@@ -1093,9 +1080,9 @@ int az_image_blob_dev_on(az_ctx *c, const uint8_t *im, int h, int w, const float
     az_ctx::IoSlot &q = c->io[c->io_turn];
     c->io_turn = (c->io_turn + 1) % (int)c->io.size();
     HIPCHK(c, hipEventSynchronize(q.ev));                   // (a fresh slot's event was never recorded: returns at once)
-    std::memcpy(q.host, im, nin);                           // the caller's array may go away as soon as this returns
-    HIPCHK(c, hipMemcpyAsync(q.dev, q.host, nin, hipMemcpyHostToDevice, s));
-    azk_image_blob(s, q.dev, h, w, means, 1.0 / scale, 1.0 / scale, oh, ow, blob_dev);
+    std::memcpy(q.host.p, im, nin);                         // the caller's array may go away as soon as this returns
+    HIPCHK(c, hipMemcpyAsync(q.dev.p, q.host.p, nin, hipMemcpyHostToDevice, s));
+    azk_image_blob(s, q.dev.as<unsigned char>(), h, w, means, 1.0 / scale, 1.0 / scale, oh, ow, blob_dev);
     HIPCHK(c, hipEventRecord(q.ev, s));
     HIPCHK(c, hipGetLastError());
     return AZ_OK;

@@ -458,8 +458,8 @@ int az_voc_eval(az_ctx *c, int n_classes, int n_images, const double *det_box, c
     const size_t o_np = take((size_t)n_classes * 8), o_ap = take((size_t)n_classes * 8), o_auc = take((size_t)n_classes * 8);
     HIPCHK(c, hipSetDevice(c->device));
     int rc;
-    if ((rc = ev_grow(c, 8, &c->ev_voc, off)) != AZ_OK) return rc;
-    char *A = (char *)c->ev_voc;
+    if ((rc = scratch_grow(c, 8, off)) != AZ_OK) return rc;
+    char *A = (char *)c->scratch[8].p;
     hipStream_t s = c->stream;
     auto *dbox = (double *)(A + o_box), *dconf = (double *)(A + o_conf), *gbox = (double *)(A + o_gbox);
     auto *doff = (int *)(A + o_doff), *goff = (int *)(A + o_goff);
@@ -533,8 +533,8 @@ int az_rank_unit(az_ctx *c, int n_classes, int n_images, const double *score, co
     const size_t o_hist = take(hist_n * 4), o_sums = take(sums_n * 4);
     HIPCHK(c, hipSetDevice(c->device));
     int rc;
-    if ((rc = ev_grow(c, 8, &c->ev_voc, off)) != AZ_OK) return rc;
-    char *A = (char *)c->ev_voc;
+    if ((rc = scratch_grow(c, 8, off)) != AZ_OK) return rc;
+    char *A = (char *)c->scratch[8].p;
     hipStream_t s = c->stream;
     auto *dscore = (double *)(A + o_score);
     auto *doff = (int *)(A + o_doff);
