@@ -329,7 +329,8 @@ int az_topk(az_ctx *ctx, const float *scores, int n, int k, int32_t *idx_out, in
 int az_topk_radix(az_ctx *ctx, const float *scores, int n, int k, int32_t *idx_out, int *n_out);
 /* utils.cython_nms.nms(dets f32[N,5], thresh) (lib/utils/nms.pyx:17-68): kept original
  * indices in descending-score order.  The reference's call site is apply_nms
- * (lib/detect/test.py:467-484); it is NOT on the proposal path. */
+ * (lib/detect/test.py:467-484); it is NOT on the proposal path.  Equal scores: the higher original index first.  NaN
+ * scores are outside the stated behaviour (unspecified order; here and in az_nms_batched). */
 int az_nms(az_ctx *ctx, const float *dets, int n, double thresh, int64_t *keep, int *n_keep);
 /* The call site itself, apply_nms (lib/detect/test.py:467-484): one nms per class per image, i.e.
  * many small independent problems.  Group g owns dets[offsets[g] .. offsets[g+1]) (rows of 5 f32);
@@ -377,7 +378,9 @@ int az_detect_batch(az_ctx *ctx, int n, const float *const *maps_nhwc_dev, int C
  * S conv5_3 maps of one padded size; _project_im_rois (:73-97) sends each roi to the level whose scaled area is closest
  * to 224 x 224, and roi column 0 holds that level.  Every entry below refuses a bad argument before any device work:
  * S outside [1, AZ_PYRAMID_MAX], a scale that is not positive and finite, a pyramid of another S than the one set, the
- * 16-bit-term GEMM modes (AZ_ERR_STATE).  S == 1 gives the bits of the single-scale entries. */
+ * 16-bit-term GEMM modes (AZ_ERR_STATE).  S == 1 gives the bits of the single-scale entries.  The level is the FIRST
+ * minimum (equal scales: the first of them); a box whose area is infinite or NaN takes level 0, as np.argmin does on
+ * distances that are all inf / all NaN (its roi is then not finite: use dedup <= 0 with such boxes). */
 #define AZ_PYRAMID_MAX 8
 /* S channel-last maps [H][W][C] (device memory, all of one size: the padded blob's conv5_3), borrowed as
  * az_set_feature_map_dev_nhwc borrows one; level 0 also becomes the context's single map. */
