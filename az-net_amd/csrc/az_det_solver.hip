@@ -112,18 +112,18 @@ void det_head_backward(az_det_solver *s, int R, bool want_dpool)
       tr_smooth_l1(s, s->s_bb, s->tgt, s->wgt, R * nb, R, s->d_bb, s->loss + 1); }
     s->has_prob = 1;
     // the two output layers: dW = dy^T x, db, and their two dx, which add into d7
-    gemm_any(s, "cls_score_dw", 2, s->d_cls, s->a7, s->g[D_WC], nc, n7, R, 0);
-    gemm_any(s, "bbox_pred_dw", 2, s->d_bb, s->a7, s->g[D_WB], nb, n7, R, 0);
-    { Timed t(c, "bias_grads", 0); tr_colsum(s, s->d_cls, R, nc, s->g[D_BC]); tr_colsum(s, s->d_bb, R, nb, s->g[D_BB]); }
+    gemm_any(s, "cls_score_dw", 2, s->d_cls, s->a7, s->g[D_WC], nc, n7, R, s->acc);
+    gemm_any(s, "bbox_pred_dw", 2, s->d_bb, s->a7, s->g[D_WB], nb, n7, R, s->acc);
+    { Timed t(c, "bias_grads", 0); tr_colsum(s, s->d_cls, R, nc, s->g[D_BC], s->acc); tr_colsum(s, s->d_bb, R, nb, s->g[D_BB], s->acc); }
     gemm_any(s, "cls_score_dx", 1, s->d_cls, s->w[D_WC], s->d7, R, n7, nc, 0);
     gemm_any(s, "bbox_pred_dx", 1, s->d_bb, s->w[D_WB], s->d7, R, n7, nb, 1);
     tr_act_bwd(s, s->d7, s->pre7, s->m7, s->drop[1], R, n7);
-    gemm_any(s, "fc7_dw", 2, s->d7, s->a6, s->g[D_W7], n7, n6, R, 0);
-    { Timed t(c, "bias_grads", 0); tr_colsum(s, s->d7, R, n7, s->g[D_B7]); }
+    gemm_any(s, "fc7_dw", 2, s->d7, s->a6, s->g[D_W7], n7, n6, R, s->acc);
+    { Timed t(c, "bias_grads", 0); tr_colsum(s, s->d7, R, n7, s->g[D_B7], s->acc); }
     gemm_any(s, "fc7_dx", 1, s->d7, s->w[D_W7], s->d6, R, n6, n7, 0);
     tr_act_bwd(s, s->d6, s->pre6, s->m6, s->drop[0], R, n6);
-    gemm_any(s, "fc6_dw", 2, s->d6, s->pool5, s->g[D_W6], n6, K6, R, 0);
-    { Timed t(c, "bias_grads", 0); tr_colsum(s, s->d6, R, n6, s->g[D_B6]); }
+    gemm_any(s, "fc6_dw", 2, s->d6, s->pool5, s->g[D_W6], n6, K6, R, s->acc);
+    { Timed t(c, "bias_grads", 0); tr_colsum(s, s->d6, R, n6, s->g[D_B6], s->acc); }
     if (want_dpool) gemm_any(s, "fc6_dx", 1, s->d6, s->w[D_W6], s->dpool, R, K6, n6, 0);
 }
 
@@ -214,6 +214,16 @@ int az_det_solver_step(az_det_solver *s, const float *conv_dev, int N, int H, in
 }
 
 int az_det_solver_set_precision(az_det_solver *s, int precision) { return tr_set_precision(s, precision); }
+
+int az_det_solver_set_accumulate(az_det_solver *s, int on) { return tr_set_accumulate(s, on); }
+
+int az_det_solver_load_history(az_det_solver *s, const float *W6, const float *b6, const float *W7, const float *b7,
+                               const float *Wc, const float *bc, const float *Wb, const float *bb)
+{
+    if (!s) return AZ_ERR_INVALID;
+    const float *src[DNPARAM] = {W6, b6, W7, b7, Wc, bc, Wb, bb};
+    return tr_load_history(s, 0, DNPARAM, src);
+}
 
 int az_det_solver_update(az_det_solver *s, double rate, double momentum, double weight_decay, double clip_scale)
 {

@@ -233,6 +233,15 @@ int az_det_solver_load_skip(az_det_solver *s, const float *Wp, const float *bp)
     return tr_load(s, D_WP, DNALL, src);
 }
 
+int az_det_solver_load_skip_history(az_det_solver *s, const float *Wp, const float *bp)
+{
+    if (!s) return AZ_ERR_INVALID;
+    az_ctx *c = s->c;
+    if (!s->sk.attached) return fail(c, AZ_ERR_STATE, "az_det_solver_load_skip_history: no skip front attached");
+    const float *src[2] = {Wp, bp};
+    return tr_load_history(s, D_WP, DNALL, src);
+}
+
 int az_det_solver_read_skip(az_det_solver *s, float *Wp, float *bp)
 {
     if (!s) return AZ_ERR_INVALID;
@@ -275,8 +284,8 @@ int az_det_solver_step_skip(az_det_solver *s, int n_src, const int *Cs, const vo
     { Timed t(c, "relu_pool_bwd", 0);
       hipLaunchKernelGGL(k_skip_dy, dim3(grid_for((long long)rows * Cout)), dim3(256), 0, st, s->dpool, s->pool5, (long long)rows * Cout,
                          Cout, k.d_y); }
-    gemm_any(s, "conv_pool5_dw", 2, k.d_y, k.cat, s->g[D_WP], Cout, k.sumC, rows, 0);
-    { Timed t(c, "bias_grads", 0); tr_colsum(s, k.d_y, rows, Cout, s->g[D_BP]); }
+    gemm_any(s, "conv_pool5_dw", 2, k.d_y, k.cat, s->g[D_WP], Cout, k.sumC, rows, s->acc);
+    { Timed t(c, "bias_grads", 0); tr_colsum(s, k.d_y, rows, Cout, s->g[D_BP], s->acc); }
     bool any = false;
     if (dmaps_dev) for (int i = 0; i < k.n; ++i) any = any || dmaps_dev[i];
     if (any) {

@@ -127,25 +127,25 @@ int az_solver_step(az_solver *s, const float *conv_dev, int N, int H, int W, int
       tr_sigmoid_ce(s, s->s_as, s->lab_as, R * 11, R, s->d_as, s->loss + 1);
       tr_smooth_l1(s, s->s_ab, s->tgt_ab, s->wgt_ab, R * 44, R, s->d_ab, s->loss + 2); }
     // the three output layers: dW = dy^T x, db, and the gradients of int7_1 / int7_2's outputs (two dx add into d71)
-    gemm_any(s, "adj_score_dw", 2, s->d_as, s->a71, s->g[P_WAS], 11, n71, R, 0);
-    gemm_any(s, "adj_bbox_dw", 2, s->d_ab, s->a71, s->g[P_WAB], 44, n71, R, 0);
-    gemm_any(s, "zoom_score_dw", 2, s->d_z, s->a72, s->g[P_WZ], 1, n72, R, 0);
+    gemm_any(s, "adj_score_dw", 2, s->d_as, s->a71, s->g[P_WAS], 11, n71, R, s->acc);
+    gemm_any(s, "adj_bbox_dw", 2, s->d_ab, s->a71, s->g[P_WAB], 44, n71, R, s->acc);
+    gemm_any(s, "zoom_score_dw", 2, s->d_z, s->a72, s->g[P_WZ], 1, n72, R, s->acc);
     { Timed t(c, "bias_grads", 0);
-      tr_colsum(s, s->d_as, R, 11, s->g[P_BAS]); tr_colsum(s, s->d_ab, R, 44, s->g[P_BAB]); tr_colsum(s, s->d_z, R, 1, s->g[P_BZ]); }
+      tr_colsum(s, s->d_as, R, 11, s->g[P_BAS], s->acc); tr_colsum(s, s->d_ab, R, 44, s->g[P_BAB], s->acc); tr_colsum(s, s->d_z, R, 1, s->g[P_BZ], s->acc); }
     gemm_any(s, "adj_score_dx", 1, s->d_as, s->w[P_WAS], s->d71, R, n71, 11, 0);
     gemm_any(s, "adj_bbox_dx", 1, s->d_ab, s->w[P_WAB], s->d71, R, n71, 44, 1);
     gemm_any(s, "zoom_score_dx", 1, s->d_z, s->w[P_WZ], s->d72, R, n72, 1, 0);
     tr_act_bwd(s, s->d71, s->pre71, s->m71, s->drop[1], R, n71);
     tr_act_bwd(s, s->d72, s->pre72, s->m72, s->drop[2], R, n72);
-    gemm_any(s, "int7_1_dw", 2, s->d71, s->a6, s->g[P_W71], n71, n6, R, 0);
-    gemm_any(s, "int7_2_dw", 2, s->d72, s->a6, s->g[P_W72], n72, n6, R, 0);
-    { Timed t(c, "bias_grads", 0); tr_colsum(s, s->d71, R, n71, s->g[P_B71]); tr_colsum(s, s->d72, R, n72, s->g[P_B72]); }
+    gemm_any(s, "int7_1_dw", 2, s->d71, s->a6, s->g[P_W71], n71, n6, R, s->acc);
+    gemm_any(s, "int7_2_dw", 2, s->d72, s->a6, s->g[P_W72], n72, n6, R, s->acc);
+    { Timed t(c, "bias_grads", 0); tr_colsum(s, s->d71, R, n71, s->g[P_B71], s->acc); tr_colsum(s, s->d72, R, n72, s->g[P_B72], s->acc); }
     // int7_1 and int7_2 both read int6: their two dx add
     gemm_any(s, "int7_1_dx", 1, s->d71, s->w[P_W71], s->d6, R, n6, n71, 0);
     gemm_any(s, "int7_2_dx", 1, s->d72, s->w[P_W72], s->d6, R, n6, n72, 1);
     tr_act_bwd(s, s->d6, s->pre6, s->m6, s->drop[0], R, n6);
-    gemm_any(s, "int6_dw", 2, s->d6, s->pool5, s->g[P_W6], n6, K6, R, 0);
-    { Timed t(c, "bias_grads", 0); tr_colsum(s, s->d6, R, n6, s->g[P_B6]); }
+    gemm_any(s, "int6_dw", 2, s->d6, s->pool5, s->g[P_W6], n6, K6, R, s->acc);
+    { Timed t(c, "bias_grads", 0); tr_colsum(s, s->d6, R, n6, s->g[P_B6], s->acc); }
     if (dmap_dev) {
         gemm_any(s, "int6_dx", 1, s->d6, s->w[P_W6], s->dpool, R, K6, n6, 0);
         tr_roi_pool_backward(s, N, H, W, channels_last, dmap_dev);
@@ -200,5 +200,16 @@ int az_solver_fetch(az_solver *s, const char *name, void *out, long long cap_byt
 }
 
 int az_solver_set_precision(az_solver *s, int precision) { return tr_set_precision(s, precision); }
+
+int az_solver_set_accumulate(az_solver *s, int on) { return tr_set_accumulate(s, on); }
+
+int az_solver_load_history(az_solver *s, const float *W6, const float *b6, const float *W71, const float *b71, const float *W72,
+                           const float *b72, const float *Was, const float *bas, const float *Wab, const float *bab,
+                           const float *Wz, const float *bz)
+{
+    if (!s) return AZ_ERR_INVALID;
+    const float *src[NPARAM] = {W6, b6, W71, b71, W72, b72, Was, bas, Wab, bab, Wz, bz};
+    return tr_load_history(s, 0, NPARAM, src);
+}
 
 }  // extern "C"

@@ -27,6 +27,7 @@ struct az_trainer {
     // shape of the last step (what the debug fetch sizes its answers by)
     int R = 0, N = 0, H = 0, W = 0, trained = 0;
     int prec = AZ_TRAIN_FP32;             // operands of every matrix product (*_set_precision)
+    int acc = 0;                          // 1: a step adds its parameter gradients to what g holds (*_set_accumulate)
 };
 
 // ---- memory ------------------------------------------------------------------------------------------------------------------
@@ -60,9 +61,11 @@ int tr_alloc_params(az_trainer *t, int p0, int p1, const size_t *pn);
 int tr_fill_params(az_trainer *t, int p0, int p1, const float *stdv, uint64_t seed);
 int tr_load(az_trainer *t, int p0, int p1, const float *const *src);         // a null array keeps what the trainer holds
 int tr_read(az_trainer *t, int p0, int p1, float *const *dst);
+int tr_load_history(az_trainer *t, int p0, int p1, const float *const *src); // tr_load into h; `trained` stays as it is
 // *_set_hyper on the first n parameters: everything is checked before anything is stored (drop: the trainer's ndrop ratios)
 int tr_set_hyper(az_trainer *t, int n, const float *lr_mult, const float *decay_mult, const float *dropout_ratio, float *drop, int ndrop);
 int tr_set_precision(az_trainer *t, int precision);
+int tr_set_accumulate(az_trainer *t, int on);
 
 // ---- one step --------------------------------------------------------------------------------------------------------------------
 int tr_check_rois(az_trainer *t, int N, const float *rois, int R, const std::string &who);
@@ -80,7 +83,8 @@ void fc_forward(az_trainer *t, const char *name, const float *x, int pw, int R, 
                 unsigned char *mask, unsigned long long key, float ratio);
 // D (+)= product of the given form, split-K through the slabs when the tile count alone would leave the chip idle
 void gemm_any(az_trainer *t, const char *name, int form, const float *A, const float *B, float *D, int M, int N, int K, int accumulate);
-void tr_colsum(az_trainer *t, const float *dy, int R, int N, float *db);                  // db[j] = sum over rows, in row order
+// db[j] (+)= sum over rows, in row order (accumulate: the finished sum is added once to what db holds)
+void tr_colsum(az_trainer *t, const float *dy, int R, int N, float *db, int accumulate);
 // ReLU and dropout backward of a hidden layer, in place
 void tr_act_bwd(az_trainer *t, float *d, const float *pre, const unsigned char *mask, float ratio, int R, int N);
 // SigmoidCrossEntropyLoss / SmoothL1Loss of n elements normalised by num: the gradient into dx, the loss into *loss (device)

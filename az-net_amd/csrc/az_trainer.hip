@@ -256,14 +256,14 @@ __global__ void __launch_bounds__(256) k_solver_act_bwd(float *__restrict__ d, c
     d[e] = pre[e] > 0.0f ? g : 0.0f;
 }
 
-// db[j] = sum over rows, in row order
-__global__ void __launch_bounds__(256) k_solver_colsum(const float *__restrict__ dy, int R, int N, float *__restrict__ db)
+// db[j] = sum over rows, in row order (+ what db holds when accumulate: one add, after the rows)
+__global__ void __launch_bounds__(256) k_solver_colsum(const float *__restrict__ dy, int R, int N, int accumulate, float *__restrict__ db)
 {
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j >= N) return;
     float s = 0.0f;
     for (int r = 0; r < R; ++r) s += dy[(size_t)r * N + j];
-    db[j] = s;
+    db[j] = accumulate ? db[j] + s : s;
 }
 
 // SigmoidCrossEntropyLoss: loss = -1/num sum(x (t - [x >= 0]) - log(1 + exp(x - 2 x [x >= 0]))), dx = (sigmoid(x) - t) / num
@@ -454,6 +454,16 @@ int tr_read(az_trainer *t, int p0, int p1, float *const *dst)
     return AZ_OK;
 }
 
+int tr_load_history(az_trainer *t, int p0, int p1, const float *const *src)
+{
+    az_ctx *c = t->c;
+    HIPCHK(c, hipSetDevice(c->device));
+    for (int p = p0; p < p1; ++p)
+        if (src[p - p0]) HIPCHK(c, hipMemcpyAsync(t->h[p], src[p - p0], t->pn[p] * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return AZ_OK;
+}
+
 int tr_set_hyper(az_trainer *t, int n, const float *lr_mult, const float *decay_mult, const float *dropout_ratio, float *drop, int ndrop)
 {
     const std::string who = std::string(t->tag) + "_set_hyper";
@@ -472,6 +482,14 @@ int tr_set_precision(az_trainer *t, int precision)
     if (precision != AZ_TRAIN_FP32 && precision != AZ_TRAIN_BF16)
         return fail(t->c, AZ_ERR_INVALID, std::string(t->tag) + "_set_precision: AZ_TRAIN_FP32 or AZ_TRAIN_BF16");
     t->prec = precision;
+    return AZ_OK;
+}
+
+int tr_set_accumulate(az_trainer *t, int on)
+{
+    if (!t) return AZ_ERR_INVALID;
+    if (on != 0 && on != 1) return fail(t->c, AZ_ERR_INVALID, std::string(t->tag) + "_set_accumulate: 0 or 1");
+    t->acc = on;
     return AZ_OK;
 }
 
@@ -556,9 +574,9 @@ void gemm_any(az_trainer *t, const char *name, int form, const float *A, const f
                        N, accumulate, D, (float *)nullptr, 0, (unsigned char *)nullptr, 0ull, 0u, 1.0f);
 }
 
-void tr_colsum(az_trainer *t, const float *dy, int R, int N, float *db)
+void tr_colsum(az_trainer *t, const float *dy, int R, int N, float *db, int accumulate)
 {
-    hipLaunchKernelGGL(k_solver_colsum, dim3((N + 255) / 256), dim3(256), 0, t->c->stream, dy, R, N, db);
+    hipLaunchKernelGGL(k_solver_colsum, dim3((N + 255) / 256), dim3(256), 0, t->c->stream, dy, R, N, accumulate, db);
 }
 
 void tr_act_bwd(az_trainer *t, float *d, const float *pre, const unsigned char *mask, float ratio, int R, int N)

@@ -56,6 +56,8 @@ SYMBOLS = [
     "az_det_solver_attach_skip", "az_det_solver_load_skip", "az_det_solver_read_skip", "az_det_solver_set_skip_hyper",
     "az_det_solver_step_skip", "az_det_solver_forward_test_skip", "az_skip_pool_bwd_unit",
     "az_solver_set_precision", "az_det_solver_set_precision", "az_solver_gemm_unit_prec",
+    "az_solver_set_accumulate", "az_det_solver_set_accumulate", "az_solver_load_history", "az_det_solver_load_history",
+    "az_det_solver_load_skip_history",
 ]
 
 
@@ -258,6 +260,11 @@ def load_library(path=None):
     L.az_solver_gemm_unit_prec.argtypes = [vp, ci, ci, fp, fp, fp, ci, ci, ci]
     L.az_solver_set_precision.argtypes = [vp, ci]
     L.az_det_solver_set_precision.argtypes = [vp, ci]
+    L.az_solver_set_accumulate.argtypes = [vp, ci]
+    L.az_det_solver_set_accumulate.argtypes = [vp, ci]
+    L.az_solver_load_history.argtypes = [vp] + [fp] * 12
+    L.az_det_solver_load_history.argtypes = [vp] + [fp] * 8
+    L.az_det_solver_load_skip_history.argtypes = [vp, fp, fp]
     L.az_det_targets.argtypes = [vp, ci, fp, ip, fp, ip, ip, cd, cd, cd, fp, dp]
     L.az_det_target_stats.argtypes = [vp, ci, fp, ip, ci, cd, ci, dp, dp, dp]
     L.az_det_solver_create.argtypes = [vp, ci, ci, ci, ci, ci, u64, ctypes.POINTER(vp)]
@@ -1612,6 +1619,21 @@ class _Trainer(object):
         """AZ_TRAIN_FP32 (0) or AZ_TRAIN_BF16 (1): the operands of every matrix product from the next step on (*_set_precision)."""
         self.ctx._chk(self._fn("set_precision")(self.h, int(precision)))
 
+    def set_accumulate(self, on):
+        """0: a step overwrites the parameter gradients (the default); 1: every following step adds to them, one float32
+        add per element (*_set_accumulate; Caffe's iter_size)."""
+        self.ctx._chk(self._fn("set_accumulate")(self.h, int(on)))
+
+    def load_history(self, hist):
+        """hist: {name: Caffe-layout array} of momentum history for any subset of KEYS; the rest keeps what it holds."""
+        shp = self._shapes()
+        arrs = [_f32(hist[k]).reshape(shp[k]) if k in hist else None for k in self.KEYS]
+        self.ctx._chk(self._fn("load_history")(self.h, *[_p(a, ctypes.c_float) if a is not None else None for a in arrs]))
+
+    def read_history(self):
+        """The momentum history of every parameter in KEYS, shaped as `read` shapes the weights."""
+        return {k: self.fetch("h_" + k) for k in self.KEYS}
+
     def _map(self, conv):
         """(pointer, N, H, W, channels_last) of a float32 CUDA tensor [N,C,H,W] in either memory format."""
         import torch
@@ -1777,6 +1799,16 @@ class AzDetSolver(_Trainer):
         out = {k: np.empty(shp.get(k, (0,)), dtype=np.float32) for k in SKIP_KEYS}
         self.ctx._chk(self.L.az_det_solver_read_skip(self.h, *[_p(out[k], ctypes.c_float) for k in SKIP_KEYS]))
         return out
+
+    def load_skip_history(self, hist):
+        shp = self._skip_shapes()
+        arrs = [_f32(hist[k]).reshape(shp[k]) if k in hist and k in shp else None for k in SKIP_KEYS]
+        self.ctx._chk(self.L.az_det_solver_load_skip_history(self.h, *[_p(a, ctypes.c_float) if a is not None else None for a in arrs]))
+
+    def read_skip_history(self):
+        if getattr(self, "skip", None) is None:
+            raise AzError(AZ_ERR_STATE, "read_skip_history: no skip front attached")
+        return {k: self.fetch("h_" + k) for k in SKIP_KEYS}
 
     def set_skip_hyper(self, lr_mult=None, decay_mult=None):
         a = None if lr_mult is None else _f32(lr_mult).reshape(2)

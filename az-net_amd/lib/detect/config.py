@@ -47,8 +47,9 @@ def _defaults():
         USE_PREFETCH=False, UN_NORMALIZE=False, NUM_PROPOSALS=2000, ANCHORS_PER_IMG=20,
         ADDREGIONS=[[0, 0, 1, 1], [0, 0, 0.8, 0.8], [0, 0.2, 0.8, 1], [0.2, 0, 1, 0.8],
                     [0.2, 0.2, 1, 1]],
-        PRECISION='fp32')    # (not in the reference) operands of the trainers' matrix products: 'fp32' or 'bf16' (rounded on
+        PRECISION='fp32',    # (not in the reference) operands of the trainers' matrix products: 'fp32' or 'bf16' (rounded on
                              # chip, summed in fp32; the master weights stay fp32)
+        SNAPSHOT_STATE=False)    # (not in the reference) every snapshot also writes a .solverstate (SolverWrapper.save_state)
     test = dict(         # config.py:109-133
         SCALES=(600,),       # short-side target of the single test scale
         MAX_SIZE=1000,       # long-side cap (experiments/cfgs/voc.yml:13 lowers it to 800)

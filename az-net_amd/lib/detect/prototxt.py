@@ -24,7 +24,8 @@ SKIP_SOURCES = ("conv3_3", "conv4_3", "conv5_3")
 SKIP_SCALES = (0.25, 0.125, 0.0625)
 SKIP_GAIN = 1000.0
 SOLVER_DEFAULTS = dict(base_lr=0.001, lr_policy="step", gamma=0.1, stepsize=120000, momentum=0.9, weight_decay=0.0005,
-                       clip_gradients=-1.0, display=20, average_loss=1, snapshot_prefix="vgg16_az_net", train_net=None)
+                       clip_gradients=-1.0, display=20, average_loss=1, snapshot_prefix="vgg16_az_net", train_net=None,
+                       iter_size=1)
 
 _TOKEN = re.compile(r"""\s*(?:(\#[^\n]*)|([{}:])|"((?:[^"\\]|\\.)*)"|'((?:[^'\\]|\\.)*)'|([^\s{}:#"']+))""")
 
@@ -113,7 +114,15 @@ def read_solver(path):
         raise ValueError("solver prototxt %s names no train_net" % path)
     if out["lr_policy"] not in ("step", "fixed"):
         raise ValueError("lr_policy %r: this backend implements \"step\" and \"fixed\"" % (out["lr_policy"],))
+    out["iter_size"] = check_iter_size(out["iter_size"])
     return out
+
+
+def check_iter_size(v):
+    """Caffe's iter_size (minibatches accumulated per iteration): an integer >= 1, else a ValueError."""
+    if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+        raise ValueError("iter_size %r: an integer >= 1" % (v,))
+    return v
 
 
 def read_train_net(path):
@@ -311,4 +320,6 @@ def write_solver_prototxt(path, train_net, **kw):
                   "display", "average_loss", "snapshot_prefix"):
             v = d[k]
             f.write('%s: %s\n' % (k, '"%s"' % v if isinstance(v, str) else repr(v)))
+        if check_iter_size(d["iter_size"]) != 1:
+            f.write("iter_size: %d\n" % d["iter_size"])
         f.write("# snapshots are written by SolverWrapper.snapshot\nsnapshot: 0\n")

@@ -112,26 +112,64 @@ class SolverWrapper(object):
                            bk: (p[bk] - self.bbox_means) / (self.bbox_stds + cfg.EPS)})
 
     # ---- one iteration (Caffe Solver::Step(1)) -------------------------------------------------------------------------
-    def _finish_step(self, losses, sumsq, backward):
-        """The half of step() behind the trainer's: `backward()` takes the trainer's map gradients through the trainable
-        convolutions; then the norm of all gradients (sumsq: the head's share), rate, clip and the update."""
+    @property
+    def iter_size(self):
+        return int(self.solver_param.get("iter_size", 1))
+
+    def _minibatches(self, blobs, n):
+        """The n minibatches of one iteration: drawn from the data layer, or the caller's (a dict when n == 1, else a list
+        of n dicts)."""
+        if blobs is None:
+            return [self.layer.forward() for _ in range(n)]
+        if isinstance(blobs, dict):
+            if n != 1:
+                raise ValueError("step: iter_size = %d takes a list of %d minibatches, not one" % (n, n))
+            return [blobs]
+        blobs = list(blobs)
+        if len(blobs) != n or not all(isinstance(b, dict) for b in blobs):
+            raise ValueError("step: iter_size = %d takes a list of %d minibatches" % (n, n))
+        return blobs
+
+    def step(self, blobs=None):
+        """Caffe Solver::Step(1) + SGDSolver::ApplyUpdate with n = iter_size: n minibatches' gradients summed (the trainer
+        accumulates from the second on, autograd in the convolutions' .grad), the losses averaged; the norm and the clip
+        on the sum, the update with clip / n.  The dropout iteration of sub-step k is iter * n + k."""
+        n = self.iter_size
+        subs = self._minibatches(blobs, n)
+        for _, w, b, _, _, _, _ in self.conv_train:
+            w.grad = None
+            b.grad = None
+        mean = None
+        for k, mb in enumerate(subs):
+            if n > 1:
+                self.trainer.set_accumulate(1 if k else 0)
+            losses, sumsq, backward = self._forward_backward(mb, self.iter * n + k)
+            if self.conv_train:
+                backward()
+            if n > 1:
+                row = np.asarray(losses, dtype=np.float32)
+                mean = row.copy() if mean is None else mean + row
+        if n > 1:
+            losses = mean / np.float32(n)
+        return self._apply_update(losses, sumsq, n)
+
+    def _apply_update(self, losses, sumsq, n=1):
+        """The end of step(): the norm of all accumulated gradients (sumsq: the head's share), rate, clip and the update."""
         import torch
         sp = self.solver_param
+        self.last_head_sumsq = sumsq
         if self.conv_train:
-            for _, w, b, _, _, _, _ in self.conv_train:
-                w.grad = None
-                b.grad = None
-            backward()
             # (plumbing: the convolutions' share of the gradient norm, 14.7 M values, is taken with torch)
             sumsq += float(sum((p.grad.double() ** 2).sum() for _, w, b, _, _, _, _ in self.conv_train for p in (w, b)))
         rate = learning_rate(sp, self.iter)
-        clip = clip_scale(sumsq, sp["clip_gradients"])
-        self.last_rate, self.last_clip, self.last_sumsq = rate, clip, sumsq
-        self.trainer.update(rate, sp["momentum"], sp["weight_decay"], clip)
+        clip = clip_scale(sumsq, sp["clip_gradients"])            # on the un-normalised sum: Caffe clips before Normalize
+        scale = clip if n == 1 else clip / n
+        self.last_rate, self.last_clip, self.last_sumsq, self.last_scale = rate, clip, sumsq, scale
+        self.trainer.update(rate, sp["momentum"], sp["weight_decay"], scale)
         for _, w, b, hw, hb, lr, dc in self.conv_train:
             for p, h, q in ((w, hw, 0), (b, hb, 1)):
                 g = p.grad if p.grad.stride() == p.stride() else torch.empty_like(p).copy_(p.grad)
-                ffi.sgd_update(self.ctx, p.detach(), g, h, rate * lr[q], sp["momentum"], sp["weight_decay"] * dc[q], clip)
+                ffi.sgd_update(self.ctx, p.detach(), g, h, rate * lr[q], sp["momentum"], sp["weight_decay"] * dc[q], scale)
         self.iter += 1
         self.losses.append(np.asarray(losses, dtype=np.float32))
         return losses
@@ -169,7 +207,126 @@ class SolverWrapper(object):
         now = self.trainer.read()
         if not (np.array_equal(now[wk], orig_w) and np.array_equal(now[bk], orig_b)):
             self.trainer.load({wk: orig_w, bk: orig_b})
+        if getattr(cfg.TRAIN, "SNAPSHOT_STATE", False):
+            self.save_state()
         return filename
+
+    # ---- the solver's state between two iterations (Caffe's .solverstate; here a NumPy .npz) ------------------------------
+    STATE_FORMAT = 1
+    STATE_KIND = None      # "az" / "det" ("det_skip" with the front)
+
+    def _state_kind(self):
+        return self.STATE_KIND
+
+    def _trainer_state(self):
+        """(weights, history) as the trainer holds them: the box-regression layer normalised, the skip front included."""
+        w, h = dict(self.trainer.read()), dict(self.trainer.read_history())
+        if getattr(self, "skip", None) is not None:
+            w.update(self.trainer.read_skip())
+            h.update(self.trainer.read_skip_history())
+        return w, h
+
+    def _state_arrays(self):
+        avg = max(1, int(self.solver_param["average_loss"]))
+        nloss = len(self.LOSS_NAMES)
+        rng = np.random.get_state()
+        st = dict(format=np.int64(self.STATE_FORMAT), kind=np.array(self._state_kind()), iter=np.int64(self.iter),
+                  iter_size=np.int64(self.iter_size), seed=np.uint64(self.seed & ((1 << 64) - 1)),
+                  bbox_means=np.asarray(self.bbox_means), bbox_stds=np.asarray(self.bbox_stds),
+                  rng_name=np.array(rng[0]), rng_keys=np.asarray(rng[1], dtype=np.uint32), rng_pos=np.int64(rng[2]),
+                  rng_has_gauss=np.int64(rng[3]), rng_cached_gaussian=np.float64(rng[4]),
+                  layer_perm=np.asarray(self.layer._perm, dtype=np.int64), layer_cur=np.int64(self.layer._cur),
+                  roidb_len=np.int64(len(self.layer._roidb)),
+                  losses=np.asarray(self.losses[-avg:], dtype=np.float32).reshape(-1, nloss))
+        w, h = self._trainer_state()
+        for k in w:
+            st["w_" + k], st["h_" + k] = np.asarray(w[k], dtype=np.float32), np.asarray(h[k], dtype=np.float32)
+        if self.backbone is not None:
+            for layer in self.backbone.layers:
+                if layer is not None:
+                    st["conv_w_" + layer[0]] = layer[1].detach().contiguous().cpu().numpy()
+                    st["conv_b_" + layer[0]] = layer[2].detach().contiguous().cpu().numpy()
+            for name, _, _, hw, hb, _, _ in self.conv_train:
+                st["conv_hw_" + name], st["conv_hb_" + name] = hw.contiguous().cpu().numpy(), hb.contiguous().cpu().numpy()
+        return st
+
+    def state_path(self):
+        infix = ("_" + cfg.TRAIN.SNAPSHOT_INFIX if cfg.TRAIN.SNAPSHOT_INFIX != "" else "")
+        return os.path.join(self.output_dir, self.solver_param["snapshot_prefix"] + infix + "_iter_{:d}".format(self.iter) + ".solverstate")
+
+    def save_state(self, path=None):
+        """Everything the next iteration depends on, into `path` (default: beside the snapshot, .solverstate): weights and
+        momentum history of the trainer (as it holds them) and of the convolutions, iter, seed, the np.random stream, the
+        data layer's permutation and cursor, the recent losses.  Only ever between two iterations."""
+        path = self.state_path() if path is None else path
+        d = os.path.dirname(path)
+        if d and not os.path.exists(d):
+            os.makedirs(d)
+        with open(path, "wb") as f:                  # (a file object: np.savez would append ".npz" to a name)
+            np.savez(f, **self._state_arrays())
+        print("Wrote solver state to: {:s}".format(path))
+        return path
+
+    def restore(self, path):
+        """Install a save_state file.  Everything is checked first -- format, kind, iter_size, the key set, every shape, the
+        roidb length, bbox_means / bbox_stds bit for bit (the weights are in those units) -- and a mismatch is a ValueError
+        that names what differs and leaves the wrapper as it was."""
+        try:
+            with np.load(path, allow_pickle=False) as z:
+                st = {k: z[k] for k in z.files}
+        except Exception as e:                       # (a truncated archive: zipfile.BadZipFile, EOFError, ValueError ...)
+            raise ValueError("solver state %s cannot be read: %s: %s" % (path, type(e).__name__, e))
+        for k in ("format", "kind"):
+            if k not in st:
+                raise ValueError("solver state %s: no '%s' entry" % (path, k))
+        if int(st["format"]) != self.STATE_FORMAT:
+            raise ValueError("solver state %s: format %d, this wrapper reads %d" % (path, int(st["format"]), self.STATE_FORMAT))
+        if str(st["kind"]) != self._state_kind():
+            raise ValueError("solver state %s: kind '%s', this wrapper is '%s'" % (path, str(st["kind"]), self._state_kind()))
+        mine = self._state_arrays()
+        if set(st) != set(mine):
+            diff = sorted(set(st) ^ set(mine))
+            raise ValueError("solver state %s: entries differ: %s" % (path, ", ".join(diff)))
+        if int(st["roidb_len"]) != int(mine["roidb_len"]) or st["layer_perm"].shape != mine["layer_perm"].shape:
+            raise ValueError("solver state %s: roidb of %d entries, this wrapper's has %d" % (path, int(st["roidb_len"]), int(mine["roidb_len"])))
+        if int(st["iter_size"]) != self.iter_size:
+            raise ValueError("solver state %s: iter_size %d, the solver file says %d" % (path, int(st["iter_size"]), self.iter_size))
+        for k in sorted(mine):
+            a, b = st[k], mine[k]
+            same = (a.ndim == 2 and a.shape[1] == b.shape[1]) if k == "losses" else a.shape == b.shape
+            if not same or (a.dtype != b.dtype and k not in ("kind", "rng_name")):
+                raise ValueError("solver state %s: %s is %s %s, this wrapper holds %s %s" % (path, k, a.dtype, a.shape, b.dtype, b.shape))
+        for k in ("bbox_means", "bbox_stds"):
+            if st[k].tobytes() != mine[k].tobytes():
+                raise ValueError("solver state %s: %s differs from this wrapper's (other data or another roidb: the weights are "
+                                 "in those units)" % (path, k))
+        cur = int(st["layer_cur"])
+        if not 0 <= cur <= int(st["roidb_len"]) or int(st["iter"]) < 0:
+            raise ValueError("solver state %s: iter or cursor out of range" % path)
+        # ---- nothing below fails on a checked file
+        import torch
+        keys = list(self.HEAD_KEYS)
+        self.trainer.load({k: st["w_" + k] for k in keys})
+        self.trainer.load_history({k: st["h_" + k] for k in keys})
+        if getattr(self, "skip", None) is not None:
+            self.trainer.load_skip({k: st["w_" + k] for k in ffi.SKIP_KEYS})
+            self.trainer.load_skip_history({k: st["h_" + k] for k in ffi.SKIP_KEYS})
+        if self.backbone is not None:
+            with torch.no_grad():
+                for layer in self.backbone.layers:
+                    if layer is not None:
+                        layer[1].copy_(torch.from_numpy(st["conv_w_" + layer[0]]))
+                        layer[2].copy_(torch.from_numpy(st["conv_b_" + layer[0]]))
+                for name, _, _, hw, hb, _, _ in self.conv_train:
+                    hw.copy_(torch.from_numpy(st["conv_hw_" + name]))
+                    hb.copy_(torch.from_numpy(st["conv_hb_" + name]))
+        self.iter, self.seed = int(st["iter"]), int(st["seed"])
+        np.random.set_state((str(st["rng_name"]), st["rng_keys"], int(st["rng_pos"]), int(st["rng_has_gauss"]),
+                             float(st["rng_cached_gaussian"])))
+        self.layer._perm, self.layer._cur = st["layer_perm"].copy(), cur
+        self.losses = [row.copy() for row in st["losses"]]
+        print("Restored solver state from {:s}: iteration {:d}".format(path, self.iter))
+        return self.iter
 
     def train_model(self, max_iters):
         """Network training loop (train_az.py:99-116, train_det.py:98-116)."""
@@ -194,9 +351,12 @@ class SolverWrapper(object):
             self.snapshot()
 
     @classmethod
-    def train_net(cls, solver_prototxt, imdb, output_dir, pretrained_model=None, max_iters=40000, **kw):
-        """Train a network (train_az.py:131-139, train_det.py:131-139); returns the SolverWrapper."""
+    def train_net(cls, solver_prototxt, imdb, output_dir, pretrained_model=None, max_iters=40000, restore=None, **kw):
+        """Train a network (train_az.py:131-139, train_det.py:131-139); returns the SolverWrapper.  restore: a save_state
+        file to continue from (max_iters stays the total)."""
         sw = cls(solver_prototxt, imdb, output_dir, pretrained_model=pretrained_model, **kw)
+        if restore is not None:
+            print("Resuming from iteration {:d} of {:d}".format(sw.restore(restore), max_iters))
         print("Solving...")
         sw.train_model(max_iters)
         print("done solving")

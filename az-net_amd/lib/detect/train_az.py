@@ -21,6 +21,7 @@ class SolverWrapper(solver.SolverWrapper):
     HEAD_OF, HEAD_KEYS, DROPOUT_OF, FILLER_STD = HEAD_OF, ffi.HEAD_KEYS, prototxt.DROPOUT_OF, prototxt.FILLER_STD
     BBOX_KEYS = ("Wab", "bab")
     LOSS_NAMES = ("loss_zoom", "loss_adj", "loss_bbox")
+    STATE_KIND = "az"
 
     def __init__(self, solver_prototxt, imdb, output_dir, pretrained_model=None, backbone=None, trainer=None, ctx=None,
                  dims=None, seed=None):
@@ -55,16 +56,16 @@ class SolverWrapper(solver.SolverWrapper):
         if layers and "int6" in layers:
             self.trainer.load(cm.az_head_from_layers(layers))
 
-    def step(self, blobs=None):
-        if blobs is None:
-            blobs = self.layer.forward()
+    def _forward_backward(self, blobs, it):
+        """One minibatch through the convolutions and the trainer (dropout iteration `it`): (losses, the sum of squares of
+        the trainer's gradients, the call that takes d conv5_3 through the trainable convolutions)."""
         import torch
         conv = self.backbone.forward_train(blobs["data"])
         dmap = torch.empty_like(conv) if self.conv_train else None
         losses, sumsq = self.trainer.step(conv.detach(), blobs["rois"], blobs["adj_labels"], blobs["adj_targets"],
-                                          blobs["adj_loss_weights"], blobs["zoom_labels"], self.seed, self.iter, dmap=dmap)
-        self.last_conv, self.last_blobs, self.last_head_sumsq = conv.detach(), blobs, sumsq
-        return self._finish_step(losses, sumsq, lambda: conv.backward(dmap))
+                                          blobs["adj_loss_weights"], blobs["zoom_labels"], self.seed, it, dmap=dmap)
+        self.last_conv, self.last_blobs = conv.detach(), blobs
+        return losses, sumsq, lambda: conv.backward(dmap)
 
 
 def get_training_roidb(imdb):

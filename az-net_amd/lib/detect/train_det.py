@@ -30,6 +30,7 @@ class SolverWrapper(solver.SolverWrapper):
     FILLER_STD = {k: v or prototxt.DET_FILLER_DEFAULT for k, v in prototxt.DET_FILLER_STD.items()}
     BBOX_KEYS = ("Wb", "bb")
     LOSS_NAMES = ("loss_cls", "loss_bbox")
+    STATE_KIND = "det"
 
     def __init__(self, solver_prototxt, imdb, output_dir, pretrained_model=None, backbone=None, trainer=None, ctx=None,
                  dims=None, seed=None):
@@ -114,9 +115,12 @@ class SolverWrapper(solver.SolverWrapper):
         if self.skip is not None:
             self.trainer.set_skip_hyper(self.net_param["conv_pool5"]["lr_mult"], self.net_param["conv_pool5"]["decay_mult"])
 
-    def step(self, blobs=None):
-        if blobs is None:
-            blobs = self.layer.forward()
+    def _state_kind(self):
+        return "det_skip" if self.skip is not None else "det"
+
+    def _forward_backward(self, blobs, it):
+        """One minibatch through the convolutions and the trainer (dropout iteration `it`): (losses, the sum of squares of
+        the trainer's gradients, the call that takes the map gradients through the trainable convolutions)."""
         import torch
         if self.skip is not None:
             conv, taps = self.backbone.forward_train(blobs["data"], taps=tuple(self.skip["sources"]))
@@ -126,7 +130,7 @@ class SolverWrapper(solver.SolverWrapper):
             if dmaps is not None and all(d is None for d in dmaps):
                 dmaps = None
             losses, sumsq = self.trainer.step_skip(maps, blobs["rois"], blobs["labels"], blobs["bbox_targets"],
-                                                   blobs["bbox_loss_weights"], self.seed, self.iter, dmaps=dmaps)
+                                                   blobs["bbox_loss_weights"], self.seed, it, dmaps=dmaps)
             self.last_maps, self.last_dmaps = maps, dmaps
 
             def backward():
@@ -136,12 +140,12 @@ class SolverWrapper(solver.SolverWrapper):
             conv = self.backbone.forward_train(blobs["data"])
             dmap = torch.empty_like(conv) if self.conv_train else None
             losses, sumsq = self.trainer.step(conv.detach(), blobs["rois"], blobs["labels"], blobs["bbox_targets"],
-                                              blobs["bbox_loss_weights"], self.seed, self.iter, dmap=dmap)
+                                              blobs["bbox_loss_weights"], self.seed, it, dmap=dmap)
 
             def backward():
                 conv.backward(dmap)
-        self.last_conv, self.last_blobs, self.last_head_sumsq = conv.detach(), blobs, sumsq
-        return self._finish_step(losses, sumsq, backward)
+        self.last_conv, self.last_blobs = conv.detach(), blobs
+        return losses, sumsq, backward
 
     def _snapshot_extra(self):
         if self.skip is None:

@@ -32,6 +32,8 @@ TRAIN = [
 TRAIN_EXT = [
     ("--base-lr", "base_lr", "(extension, without --solver) base_lr of the written solver", 0.001, float),
     ("--bf16", "bf16", "(extension) bf16 operands in the trainer's matrix products (cfg.TRAIN.PRECISION = 'bf16')", None, None),
+    ("--snapshot-state", "snapshot_state", "(extension) write a .solverstate beside every snapshot (cfg.TRAIN.SNAPSHOT_STATE)", None, None),
+    ("--restore", "restore", "(extension) continue from this .solverstate; --iters stays the total", None, str),
 ]
 
 

@@ -26,6 +26,8 @@ def main():
     seed = _cli.train_seed(args)
     if args.bf16:
         cfg.TRAIN.PRECISION = 'bf16'
+    if args.snapshot_state:
+        cfg.TRAIN.SNAPSHOT_STATE = True
 
     import torch
     torch.cuda.set_device(args.gpu_id)
@@ -59,7 +61,7 @@ def main():
         backbone, dims = _cli.reduced_net(args.gpu_id, seed + 1, div, synth.FULL_DIMS, ("n6", "n71", "n72"))
         kw = dict(backbone=backbone, dims=dims)
     train_net(solver, imdb, output_dir, pretrained_model=args.pretrained_model, max_iters=args.max_iters, ctx=ctx,
-              seed=seed, **kw)
+              seed=seed, restore=args.restore, **kw)
 
 
 if __name__ == "__main__":

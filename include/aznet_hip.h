@@ -846,6 +846,31 @@ int az_skip_pool_bwd_unit(az_ctx *ctx, int n_src, const int *Cs, const float *sp
                           const int *Hs, const int *Ws, int N, int channels_last, const float *rois, int R,
                           const float *d_raw_host, float *pooled_out, int32_t *argmax_out, float *const *dmaps_out);
 
+/* ---- gradient accumulation and the solver's state between two iterations (all three trainers, both precisions) ------------ */
+/* Caffe's iter_size (Solver::Step: `for (int i = 0; i < param_.iter_size(); ++i) loss += net_->ForwardBackward();` after one
+ * ClearParamDiffs, then SGDSolver::ApplyUpdate: ClipGradients on the summed diffs, then Normalize scales them by
+ * 1 / iter_size, then Regularize and ComputeUpdateValue).  on = 0 (the default): a step overwrites the parameter gradients,
+ * with the launches and arguments it always had.  on = 1: every following *_step / *_step_skip ADDS its parameter gradients
+ * to what the trainer holds, per element  g = g_old + g_step  with one float32 add, where g_step has the bits the same step
+ * writes with the flag off: a split-K product is out[e] + (its slabs in slab order), an unsplit one *d + v, a bias gradient
+ * the rows summed in row order and then added once; conv_pool5's Wp / bp included.  The gradients are zero after create, so
+ * accumulating from the first step on gives 0 + g_step.  d conv5_3 and the skip front's map gradients stay those of the one
+ * step (the caller's autograd accumulates in the convolutions' .grad).  sumsq_out is over the gradient buffers as they
+ * stand, i.e. of the accumulated gradient: what ClipGradients looks at.  The caller divides by iter_size through
+ * *_update's clip_scale.  *_update and *_forward_test leave the flag alone.  Any other value: AZ_ERR_INVALID, flag unchanged. */
+int az_solver_set_accumulate(az_solver *s, int on);
+int az_det_solver_set_accumulate(az_det_solver *s, int on);
+/* SGDSolver::RestoreSolverStateFrom*: the momentum history (history_[i]) of every parameter from host arrays, in the order
+ * and layout of *_load / *_load_skip; a NULL array keeps what the trainer holds.  Reading it back is *_fetch("h_<name>").
+ * Gradients and the "a step has run" state are untouched (an update still needs a step before it).  Without an attached
+ * front az_det_solver_load_skip_history returns AZ_ERR_STATE. */
+int az_solver_load_history(az_solver *s, const float *W6, const float *b6, const float *W71, const float *b71, const float *W72,
+                           const float *b72, const float *Was, const float *bas, const float *Wab, const float *bab,
+                           const float *Wz, const float *bz);
+int az_det_solver_load_history(az_det_solver *s, const float *W6, const float *b6, const float *W7, const float *b7,
+                               const float *Wc, const float *bc, const float *Wb, const float *bb);
+int az_det_solver_load_skip_history(az_det_solver *s, const float *Wp, const float *bp);
+
 /* ---- measurement ------------------------------------------------------------------ */
 /* HIP-event timing (events on the ctx stream) of the launches made by az_propose /
  * az_head_forward.  mode bits: 1 = time only the fc GEMM launches, 2 = time every launch
