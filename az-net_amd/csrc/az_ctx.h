@@ -344,7 +344,8 @@ struct az_ctx {
     int capHis = 0;
     float *pool = nullptr, *pool_tmp = nullptr;
     unsigned long long *pool_n = nullptr, *pool_hist = nullptr;      // [2], [256]
-    long long pool_cap = 0;
+    long long pool_cap = 0, pool_alloc = 0;      // floats the open pool takes (az_tune_begin's capacity); floats allocated
+    bool pool_bad = false;              // a tuner search that appended to the pool failed: refused until the next az_tune_begin
     Buf his_own[2], pool_own[4];        // (hisB, hisZ; pool, pool_tmp, pool_n, pool_hist)
     // grow-on-demand scratch of the evaluation / front-end entry points
     // (slots 0-7: whatever the entry point wants; 8, 9, 10: the arenas of az_voc_eval, az_coco_eval, az_diag_eval)
@@ -381,6 +382,7 @@ struct az_ctx {
         int slot = 0;
         hipStream_t last_s = nullptr;       // the stream the search's last kernels and its result copy are on
         bool copied = false;                // result block already on its way to h_res[slot]
+        bool pooled = false;                // a tuner search that appended its anchors' scores to the score pool
         const float *feat = nullptr;        // the map the search reads (a rerun in another form needs it again)
         int fH = 0, fW = 0;
         unsigned feat_gen = 0;
@@ -418,7 +420,8 @@ struct az_ctx {
     int npass = 0;
     int pass_src[AZ_MAX_LEVELS + 2] = {0};
     int pass_lv[AZ_MAX_LEVELS + 2] = {0};
-    int his_n = 0;                      // rows of the anchor history of the last fetched tuner search
+    int his_n = 0;                      // rows of the anchor history of the last fetched tuner search still in hisB / hisZ
+                                        // (-1: a later tuner search is overwriting them, or the search failed)
     int cand_n = -1;                    // candidates of the last fetched search still in Yall/Sall (-1: overwritten)
     // profiling
     int profiling = 0;

@@ -158,19 +158,22 @@ __device__ __forceinline__ unsigned int fkey(float f)
 
 // pool[*pool_n ...] <- src[0..*nptr); the running size advances in the follow-up 1-thread kernel
 // (same stream), so the host never needs the per-image count.  pool_n[1] counts dropped scores.
+// *nptr counts the rows a search WANTED to record: past cap_src (an overflowed history, err bit 16) nobody wrote them,
+// and src ends there.
 __global__ void __launch_bounds__(256) k_pool_append(const float *__restrict__ src, const int *__restrict__ nptr,
-                                                      float *__restrict__ pool,
+                                                      int cap_src, float *__restrict__ pool,
                                                       const unsigned long long *__restrict__ pool_n, long long cap)
 {
-    const int n = *nptr;
+    const int n = *nptr < cap_src ? *nptr : cap_src;
     const long long base = (long long)pool_n[0];
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n && base + i < cap) pool[base + i] = src[i];
 }
 
-__global__ void k_pool_advance(const int *__restrict__ nptr, unsigned long long *__restrict__ pool_n, long long cap)
+__global__ void k_pool_advance(const int *__restrict__ nptr, int cap_src, unsigned long long *__restrict__ pool_n,
+                               long long cap)
 {
-    const long long n = *nptr, base = (long long)pool_n[0];
+    const long long n = *nptr < cap_src ? *nptr : cap_src, base = (long long)pool_n[0];
     const long long room = cap - base;
     const long long take = n < room ? n : (room > 0 ? room : 0);
     pool_n[0] = (unsigned long long)(base + take);
@@ -238,8 +241,8 @@ void azk_record_anchors(hipStream_t s, const AzCounts *cnt, int level, int capR,
 void azk_pool_append(hipStream_t s, const float *src, const int *nptr, int cap_src, float *pool,
                      unsigned long long *pool_n, long long cap)
 {
-    hipLaunchKernelGGL(k_pool_append, dim3((cap_src + 255) / 256), dim3(256), 0, s, src, nptr, pool, pool_n, cap);
-    hipLaunchKernelGGL(k_pool_advance, dim3(1), dim3(1), 0, s, nptr, pool_n, cap);
+    hipLaunchKernelGGL(k_pool_append, dim3((cap_src + 255) / 256), dim3(256), 0, s, src, nptr, cap_src, pool, pool_n, cap);
+    hipLaunchKernelGGL(k_pool_advance, dim3(1), dim3(1), 0, s, nptr, cap_src, pool_n, cap);
 }
 
 void azk_pool_hist(hipStream_t s, const float *pool, long long n, unsigned int prefix, int shift,

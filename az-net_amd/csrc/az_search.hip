@@ -296,6 +296,7 @@ static int launch_impl_body(az_ctx *c, const az_params *p)
     HIPCHK(c, hipSetDevice(c->device));
     if (!(c->profiling & 4)) clear_events(c);
     c->cand_n = -1;
+    if (tune) c->his_n = -1;                       // (hisB / hisZ are one buffer per context: this search writes them)
     if (c->cal.state == 0 && (rc = calibrate_passes(c)) != AZ_OK) return rc;
     hint_load(c, p->im_h, p->im_w, nlev);          // what this shape's last search looked like (decides the form below)
     bool stat = static_wanted(c, p, tune);
@@ -407,6 +408,7 @@ static int launch_impl_body(az_ctx *c, const az_params *p)
     q.full = c->last_full;
     q.cut = c->last_cut;
     q.pyr = c->pyr_now;
+    q.pooled = tune && c->pool;
     q.npass = c->npass;
     q.feat = c->feat; q.fH = c->d.H; q.fW = c->d.W; q.feat_gen = c->feat_gen;
     q.feat_is_copy = c->feat && (c->feat == c->feat_owned[0] || c->feat == c->feat_owned[1] || c->feat == c->feat_owned[2]);
@@ -473,6 +475,7 @@ int fetch_entry(az_ctx *c, size_t idx, double *boxes_out, float *scores_out, int
     }
     if (q.copied) drop();
     c->last = q.p;
+    c->his_n = -1;                                 // (until this fetch has succeeded)
     const AzCounts &h = *(const AzCounts *)blk;
     if (st) {
         std::memset(st, 0, sizeof(*st));
@@ -600,6 +603,9 @@ int fetch_entry(az_ctx *c, size_t idx, double *boxes_out, float *scores_out, int
         else { c->nofuse_h = q.p.im_h; c->nofuse_w = q.p.im_w; p2.reserved |= 2; }
         return rerun(p2);
     }
+    // (a failed tuner search has appended an incomplete history to the score pool -- past capHis its rows were never
+    //  written: the pool answers nothing until the next az_tune_begin)
+    if (h.err && q.pooled) c->pool_bad = true;
     if (h.err)
         return fail(c, AZ_ERR_CAPACITY,
                     std::string("az_propose: ctx capacity exceeded (flags ") + std::to_string(h.err) +
@@ -636,7 +642,10 @@ int fetch_entry(az_ctx *c, size_t idx, double *boxes_out, float *scores_out, int
     const int n = h.nsel;
     // (the candidate list stays readable only while no later search has been queued: it would be overwriting it)
     c->cand_n = c->pend.empty() ? h.ytot[q.cut ? q.cut : nlev] : -1;
-    c->his_n = h.nhis;
+    // (likewise the anchor history: a tuner search queued behind this one writes the same hisB / hisZ)
+    bool his_live = true;
+    for (const auto &e : c->pend) his_live = his_live && !(e.p.reserved & 4);
+    c->his_n = his_live ? h.nhis : -1;
     if (st) st->n_proposals = n;
     *n_out = n;
     if (n > cap) return fail(c, AZ_ERR_CAPACITY, "az_propose: output capacity too small");

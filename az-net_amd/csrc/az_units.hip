@@ -794,6 +794,8 @@ int az_last_anchors(az_ctx *c, double *regions_out, float *zoom_out, int cap, in
     if (!(c->last.reserved & 4) || !c->hisB)
         return fail(c, AZ_ERR_STATE, "az_last_anchors: the last az_propose was not a tuner search (reserved bit 2)");
     HIPCHK(c, hipSetDevice(c->device));
+    if (c->his_n < 0)
+        return fail(c, AZ_ERR_STATE, "az_last_anchors: the history is gone (the search failed, or a later tuner search has been launched)");
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const int n = c->his_n;
     *n_out = n;
@@ -808,17 +810,19 @@ int az_tune_begin(az_ctx *c, long long capacity)
     if (!c || capacity <= 0) return fail(c, AZ_ERR_INVALID, "az_tune_begin: bad capacity");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (capacity > c->pool_cap) {
-        c->pool = c->pool_tmp = nullptr; c->pool_cap = 0;
+    if (capacity > c->pool_alloc) {
+        c->pool = c->pool_tmp = nullptr; c->pool_cap = c->pool_alloc = 0;
         HIPCHK(c, reserve_group({{&c->pool_own[0], (size_t)capacity * sizeof(float)}, {&c->pool_own[1], (size_t)capacity * sizeof(float)}}));
-        c->pool = c->pool_own[0].as<float>(); c->pool_tmp = c->pool_own[1].as<float>(); c->pool_cap = capacity;
+        c->pool = c->pool_own[0].as<float>(); c->pool_tmp = c->pool_own[1].as<float>(); c->pool_alloc = capacity;
     }
+    c->pool_cap = capacity;                  // (a smaller pool than the last one keeps the allocation, not the capacity)
     if (!c->pool_n) {
         HIPCHK(c, reserve_group({{&c->pool_own[2], 4 * sizeof(unsigned long long)}, {&c->pool_own[3], 256 * sizeof(unsigned long long)}}));
         c->pool_n = c->pool_own[2].as<unsigned long long>(); c->pool_hist = c->pool_own[3].as<unsigned long long>();
     }
     HIPCHK(c, hipMemsetAsync(c->pool_n, 0, 4 * sizeof(unsigned long long), c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->pool_bad = false;
     return AZ_OK;
 }
 
@@ -829,13 +833,16 @@ int az_tune_end(az_ctx *c)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->pool_own[0].reset(); c->pool_own[1].reset();
     c->pool = c->pool_tmp = nullptr;
-    c->pool_cap = 0;
+    c->pool_cap = c->pool_alloc = 0;
+    c->pool_bad = false;
     return AZ_OK;
 }
 
 static int pool_size(az_ctx *c, long long *n, long long *dropped)
 {
     if (!c->pool) return fail(c, AZ_ERR_STATE, "az_tune_begin has not been called");
+    if (c->pool_bad)
+        return fail(c, AZ_ERR_CAPACITY, "az_tune: a tuner search that fed the score pool failed, the pool is incomplete; az_tune_begin again");
     unsigned long long h[2];
     HIPCHK(c, hipMemcpyAsync(h, c->pool_n, sizeof(h), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));

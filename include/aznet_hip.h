@@ -445,14 +445,37 @@ int az_skip_conv(az_ctx *ctx, const float *cat_host, int rows, float *out);
 /* ---- zoom-threshold tuner (lib/detect/tune.py, tools/set_thresh.py) ------------------- */
 /* `Bhis` of the tuner's im_propose (tune.py:303, returned at :316) for the last az_propose run
  * with params.reserved bit 2: every region evaluated, level-major, with its zoom score.
- * regions_out [cap,4] f64, zoom_out [cap] f32; either may be NULL. */
+ * regions_out [cap,4] f64, zoom_out [cap] f32; either may be NULL.
+ * The history is ONE buffer per context: from the moment a later tuner search is launched (az_propose_launch queues
+ * them: they have a fixed proposal count) it is being overwritten, so between the fetch of a tuner search and the fetch
+ * of a tuner search queued behind it az_last_anchors returns AZ_ERR_STATE, as az_last_candidates does for the candidate
+ * list; after that fetch it answers for the later search.  A plain search queued behind leaves the history alone.  A
+ * tuner search whose fetch failed (a history past 2 * max_regions rows is AZ_ERR_CAPACITY, raise az_set_limits) has no
+ * history either: AZ_ERR_STATE.
+ * Thresholds compare as `(double)zoom >= Tz` in every form of the search, which is the reference's comparison: its zoom
+ * scores are float64 by the time `np.where(zoom >= Tz)` sees them (test.py:198,253: an hstack onto np.zeros((0,))).  A
+ * Tz that float32 does not hold (a hand-written 0.35) therefore drops a region whose float32 score is float32(0.35), in
+ * the reference and here alike; a tuned threshold is a widened float32 and meets no such case. */
 int az_last_anchors(az_ctx *ctx, double *regions_out, float *zoom_out, int cap, int *n_out);
 /* tune_thresh (tune.py:318-366) keeps the num_images*ANCHORS_PER_IMG largest zoom scores of a
  * whole image set in a heap and returns the smallest of them.  Here the scores stay in HBM:
  * between az_tune_begin and az_tune_end every tuner-variant az_propose appends its anchors' zoom
  * scores to a device pool of `capacity` floats (no host round trip), and az_tune_kth_largest
  * radix-selects the k-th largest: -inf when the pool holds <= k scores, exactly as the heap
- * never overflowing leaves `thresh = -np.inf` (tune.py:326,347-350). */
+ * never overflowing leaves `thresh = -np.inf` (tune.py:326,347-350).
+ * The n <= k rule: with n pooled scores az_tune_kth_largest gives -inf for n <= k and the k-th largest (ties counted,
+ * -0.0 below +0.0) for n > k; az_tune_top gives all n for n <= k, else every score >= the k-th largest, which is more
+ * than k scores when the k-th ties.  k <= 0 is AZ_ERR_INVALID.  Scores may be any float but NaN: denormals, either zero
+ * and +-inf order as values.  NaN scores are outside the contract (the key order ranks them above +inf; the
+ * reference's heap is undefined on them), and so is the heap's habit of never pushing a -inf score (`scores > thresh`
+ * at thresh = -inf): zoom scores are sigmoid outputs.
+ * The pool takes `capacity` floats, whatever an earlier az_tune_begin allocated; az_tune_begin empties it.  A push past
+ * the capacity is AZ_ERR_CAPACITY and changes nothing; searches that append past it are counted on the device and
+ * az_tune_kth_largest / az_tune_top then return AZ_ERR_CAPACITY ("raise az_tune_begin's capacity", n_total = capacity).
+ * After a tuner search that appended to the pool has FAILED (its fetch returned an error: its history, hence what it
+ * appended, is incomplete) az_tune_kth_largest, az_tune_top and az_tune_push return AZ_ERR_CAPACITY until the next
+ * az_tune_begin: the pool never answers over an incomplete set.  Without az_tune_begin, or after az_tune_end, the three
+ * return AZ_ERR_STATE. */
 int az_tune_begin(az_ctx *ctx, long long capacity);
 int az_tune_end(az_ctx *ctx);
 int az_tune_kth_largest(az_ctx *ctx, long long k, float *value_out, long long *n_total);
