@@ -794,6 +794,14 @@ int skip_front_check(az_ctx *c, const std::string &who, int n_src, const int *Cs
 // the front on the rois in c->urois (row count *Uptr, at most rows_bound): pool5 [U][49][Cout] as the head's fc6 reads it
 void skip_front_launch(az_ctx *c, const int *Uptr, int rows_bound);
 int skip_pool_unit(az_ctx *c, int R, int normalise, float *out);      // az_skip_pool past its checks, the rois staged
+// ---- az_units.hip -------------------------------------------------------------------------------------------------------
+// the context's NMS scratch grown to n boxes, as az_nms grows it (`who`: the entry's name in the error)
+int nms_reserve(az_ctx *c, int n, const char *who);
+// greedy NMS of n_groups groups of records [x1, y1, x2, y2, score] that are on the device already, with the kernels of
+// az_nms_batched / az_nms (k_nms_small for groups of up to 256 boxes, all in one launch; azk_nms on the context's scratch for
+// larger ones); off: the groups' offsets on the host, goff_dev: the same on the device.  Enqueues only.
+int nms_groups_dev(az_ctx *c, const float *dets_dev, const int32_t *off, const int *goff_dev, int *gsel_dev, std::vector<int> &small,
+                   int n_groups, double thresh, long long *keep_dev, int *nkeep_dev, const char *who);
 // ---- az_capi.hip --------------------------------------------------------------------------------------------------------
 int set_feature_map_common(az_ctx *c, const float *src, bool src_is_host, int C, int H, int W, bool wait = true);
 int ensure_lane_head(az_ctx *t);          // the head buffers of a lane / batch slot created without them

@@ -30,6 +30,15 @@ struct az_det_solver : az_trainer {
         double *fac = nullptr;                                  // f = gain / sqrt(ss + eps) [rows][n]
         int rows = 0, trained = 0, has_dcat = 0;                // of the last skip pass (has_dcat: it computed d_cat / d_raw)
     } sk;
+    // hard-example mining (az_det_mine.hip); allocated at the first az_det_solver_mine*
+    struct Mine {
+        float *rec = nullptr, *loss = nullptr, *lcls = nullptr, *lbb = nullptr, *tgt4 = nullptr;   // records [maxR][5]; losses [maxR]; compact targets
+        long long *keep = nullptr;                              // the NMS kernels' keep lists, image by image at its first row
+        int *keep_rows = nullptr, *flag = nullptr;              // the same as global rows (-1 behind a list); "a loss is not finite"
+        int *goff = nullptr, *gsel = nullptr, *nkeep = nullptr, *nsel = nullptr;     // per image (capN of them)
+        int capN = 0, R = 0, N = 0;                             // R, N: of the last mining pass
+        std::vector<int> off, small, h_sel, h_nsel;             // host: row ranges, the small groups, the result before it is handed over
+    } mn;
 };
 
 // ---- az_det_solver.hip: the head behind pool5 [R][C * 49], for both fronts ----------------------------------------------------
@@ -41,6 +50,15 @@ void det_head_backward(az_det_solver *s, int R, bool want_dpool);
 int det_stage_targets(az_det_solver *s, int R, const float *labels, const float *bbox_targets, const float *bbox_loss_weights,
                       long long iteration, const std::string &who);
 void det_softmax_test(az_det_solver *s, int R);
+// ---- az_det_mine.hip ------------------------------------------------------------------------------------------------------------
+// the mining pass's saved tensors by name (mine_loss, mine_loss_cls, mine_loss_bbox, mine_keep, mine_nkeep)
+bool det_mine_fetch(az_det_solver *s, const std::string &name, const void **src, size_t *bytes);
 // ---- az_skip_train.hip ----------------------------------------------------------------------------------------------------------
 // the front's saved tensors by name (cat, skip_argmax, skip_factor, d_y, d_cat, d_raw)
 bool skip_train_fetch(az_det_solver *s, const std::string &name, const void **src, size_t *bytes);
+// what az_det_solver_step_skip / _forward_test_skip refuse before they enqueue anything (`who`: the entry's name)
+int skip_pass_check(az_det_solver *s, const std::string &who, int n_src, const int *Cs, const void *const *maps, const int *Hs,
+                    const int *Ws, int N, const float *rois, int R);
+// what az_det_solver_forward_test_skip enqueues in front of its softmax: roi_pool* .. relu_pool into pool5, then the head, TEST phase
+int skip_test_forward(az_det_solver *s, const void *const *maps_dev, const int *Hs, const int *Ws, int N, int channels_last,
+                      const float *rois, int R);

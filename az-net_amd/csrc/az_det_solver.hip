@@ -267,6 +267,7 @@ int az_det_solver_fetch(az_det_solver *s, const char *name, void *out, long long
     };
     for (const Ent &e : tab) if (nm == e.n) { src = e.p; bytes = e.b; }
     if (!src) skip_train_fetch(s, nm, &src, &bytes);
+    if (!src) det_mine_fetch(s, nm, &src, &bytes);
     if ((nm == "d_cat" || nm == "d_raw") && src && !s->sk.has_dcat)
         return fail(s->c, AZ_ERR_STATE, "az_det_solver_fetch: the last skip pass asked for no map gradient, so it computed no '" + nm + "'");
     return tr_fetch(s, nm, src, bytes, out, cap_bytes, bytes_out);

@@ -162,6 +162,19 @@ int skip_forward(az_det_solver *s, const SkipSrcs &a, const float *rois, int R, 
 
 }  // namespace
 
+int skip_pass_check(az_det_solver *s, const std::string &who, int n_src, const int *Cs, const void *const *maps, const int *Hs,
+                    const int *Ws, int N, const float *rois, int R)
+{
+    return skip_step_check(s, who, n_src, Cs, maps, Hs, Ws, N, rois, R);
+}
+
+int skip_test_forward(az_det_solver *s, const void *const *maps_dev, const int *Hs, const int *Ws, int N, int channels_last,
+                      const float *rois, int R)
+{
+    const SkipSrcs a = skip_srcs(s->sk.n, s->sk.C, Hs, Ws, maps_dev, N, channels_last);
+    return skip_forward(s, a, rois, R, false, 0, 0);
+}
+
 bool skip_train_fetch(az_det_solver *s, const std::string &nm, const void **src, size_t *bytes)
 {
     const az_det_solver::Skip &k = s->sk;

@@ -294,23 +294,7 @@ int az_nms(az_ctx *c, const float *dets, int n, double thresh, int64_t *keep, in
         for (int i = 0; i < nk; ++i) keep[i] = (long long)(unsigned)(hk[i] & 0xFFFFFFFFll);
         return AZ_OK;
     }
-    if (n > c->nms_cap) {
-        HIPCHK(c, hipStreamSynchronize(s));
-        Buf *b = c->nms_own;
-        for (int i = 0; i < 6; ++i) b[i].reset();
-        c->nms_cap = 0;
-        int cap = 1024;
-        while (cap < n) cap *= 2;
-        const size_t W = (size_t)(cap + 63) / 64;
-        if (azk_nms_scan_lds_bytes(cap) > 150000) return fail(c, AZ_ERR_CAPACITY, "az_nms: n too large");
-        HIPCHK(c, reserve_group({{&b[0], (size_t)cap * 5 * 4}, {&b[1], (size_t)cap * 5 * 4}, {&b[2], (size_t)cap * 4 + 16},
-                                 {&b[3], ((size_t)cap * W + azk_nms_band_words(cap)) * 8},      // mask, then band
-                                 {&b[4], (size_t)cap * 4}, {&b[5], (size_t)cap * 8 + 16}}));
-        c->nms_dets = b[0].as<float>(); c->nms_sdets = b[1].as<float>(); c->nms_order = b[2].as<int>();
-        c->nms_mask = b[3].as<unsigned long long>(); c->nms_rank = b[4].as<int>(); c->nms_keep = b[5].as<long long>();
-        HIPCHK(c, hipMemset(c->nms_rank, 0, (size_t)cap * 4));
-        c->nms_cap = cap;
-    }
+    { const int rc = nms_reserve(c, n, "az_nms"); if (rc != AZ_OK) return rc; }
     int *nk = c->nms_order + c->nms_cap;      // spare int after the order array
     HIPCHK(c, hipMemcpyAsync(c->nms_dets, dets, (size_t)n * 5 * 4, hipMemcpyHostToDevice, s));
     if (!(c->profiling & 4)) clear_events(c);
@@ -1097,3 +1081,61 @@ int az_image_blob_dev_on(az_ctx *c, const uint8_t *im, int h, int w, const float
 
 
 }  // extern "C"
+
+// ---- the NMS scratch and NMS on records that are on the device already (az_det_mine.hip) --------------------------------------
+// az_nms's growth of the context's scratch (dets, sdets, order, mask + band, rank, keep) to at least n boxes
+int nms_reserve(az_ctx *c, int n, const char *who)
+{
+    if (n <= c->nms_cap) return AZ_OK;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    Buf *b = c->nms_own;
+    for (int i = 0; i < 6; ++i) b[i].reset();
+    c->nms_cap = 0;
+    int cap = 1024;
+    while (cap < n) cap *= 2;
+    const size_t W = (size_t)(cap + 63) / 64;
+    if (azk_nms_scan_lds_bytes(cap) > 150000) return fail(c, AZ_ERR_CAPACITY, std::string(who) + ": n too large");
+    HIPCHK(c, reserve_group({{&b[0], (size_t)cap * 5 * 4}, {&b[1], (size_t)cap * 5 * 4}, {&b[2], (size_t)cap * 4 + 16},
+                             {&b[3], ((size_t)cap * W + azk_nms_band_words(cap)) * 8},      // mask, then band
+                             {&b[4], (size_t)cap * 4}, {&b[5], (size_t)cap * 8 + 16}}));
+    c->nms_dets = b[0].as<float>(); c->nms_sdets = b[1].as<float>(); c->nms_order = b[2].as<int>();
+    c->nms_mask = b[3].as<unsigned long long>(); c->nms_rank = b[4].as<int>(); c->nms_keep = b[5].as<long long>();
+    HIPCHK(c, hipMemset(c->nms_rank, 0, (size_t)cap * 4));
+    c->nms_cap = cap;
+    return AZ_OK;
+}
+
+// az_nms_batched's work on device-resident records: group g = dets_dev[off[g] .. off[g + 1]) (off: host; goff_dev: the same
+// n_groups + 1 offsets on the device).  Groups of up to azk_nms_small_max() boxes share one k_nms_small launch (gsel_dev
+// receives their list, `small`, which the caller keeps alive until it has waited for the stream), every larger one runs
+// azk_nms on the context's scratch straight from dets_dev.  keep_dev[off[g] ..] receives group g's keep list (index inside the
+// group, descending score), nkeep_dev[g] its length; nothing is copied back and nothing is waited for.
+int nms_groups_dev(az_ctx *c, const float *dets_dev, const int32_t *off, const int *goff_dev, int *gsel_dev, std::vector<int> &small,
+                   int n_groups, double thresh, long long *keep_dev, int *nkeep_dev, const char *who)
+{
+    hipStream_t s = c->stream;
+    std::vector<int> large;
+    small.clear();
+    int biggest = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        const int n = off[g + 1] - off[g];
+        if (n <= 0) continue;
+        (n <= azk_nms_small_max() ? small : large).push_back(g);
+        biggest = std::max(biggest, n);
+    }
+    if (!large.empty()) { const int rc = nms_reserve(c, biggest, who); if (rc != AZ_OK) return rc; }
+    HIPCHK(c, hipMemsetAsync(nkeep_dev, 0, (size_t)n_groups * sizeof(int), s));
+    if (!small.empty()) {
+        HIPCHK(c, hipMemcpyAsync(gsel_dev, small.data(), small.size() * sizeof(int), hipMemcpyHostToDevice, s));
+        Timed t(c, "nms_batched", (int)small.size());
+        azk_nms_small(s, dets_dev, goff_dev, gsel_dev, (int)small.size(), thresh, keep_dev, nkeep_dev);
+    }
+    for (int g : large) {
+        const int n = off[g + 1] - off[g];
+        Timed t(c, "nms", n);
+        azk_nms(s, dets_dev + 5 * (size_t)off[g], n, thresh, c->nms_order, c->nms_sdets, c->nms_mask,
+                c->nms_mask + (size_t)c->nms_cap * ((c->nms_cap + 63) / 64), (unsigned long long *)c->nms_rank, keep_dev + off[g],
+                nkeep_dev + g);
+    }
+    return AZ_OK;
+}

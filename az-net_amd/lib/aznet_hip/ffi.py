@@ -58,6 +58,7 @@ SYMBOLS = [
     "az_solver_set_precision", "az_det_solver_set_precision", "az_solver_gemm_unit_prec",
     "az_solver_set_accumulate", "az_det_solver_set_accumulate", "az_solver_load_history", "az_det_solver_load_history",
     "az_det_solver_load_skip_history",
+    "az_det_solver_mine", "az_det_solver_mine_skip",
 ]
 
 
@@ -284,6 +285,8 @@ def load_library(path=None):
     L.az_det_solver_step_skip.argtypes = [vp, ci, cip, vpp, cip, cip, ci, ci, fp, ci, fp, fp, fp, u64, ll, fp, dp, vpp]
     L.az_det_solver_forward_test_skip.argtypes = [vp, ci, cip, vpp, cip, cip, ci, ci, fp, ci, fp, fp]
     L.az_skip_pool_bwd_unit.argtypes = [vp, ci, cip, fp, vpp, cip, cip, ci, ci, fp, ci, fp, fp, ip, vpp]
+    L.az_det_solver_mine.argtypes = [vp, vp, ci, ci, ci, ci, fp, ci, fp, fp, cd, ci, ip, ip, fp]
+    L.az_det_solver_mine_skip.argtypes = [vp, ci, cip, vpp, cip, cip, ci, ci, fp, ci, fp, fp, cd, ci, ip, ip, fp]
     L.az_image_blob_size.argtypes = [ci, ci, cd, cip, cip]
     L.az_image_blob_host.argtypes = [vp, u8p, ci, ci, fp, cd, fp, ci, ci]
     L.az_image_blob_dev.argtypes = [vp, u8p, ci, ci, fp, cd, vp, ci, ci]
@@ -1573,6 +1576,7 @@ class _Trainer(object):
     _NDROP = 0
     _U8, _I32, _F64 = (), ("argmax",), ()
     _ROWS49 = ()            # saved tensors whose rows are (roi, bin)
+    _FLAT = ()              # saved tensors that are not one row per row of the last pass: returned as they come
 
     def _fn(self, name):
         return getattr(self.L, self._C + "_" + name)
@@ -1687,6 +1691,8 @@ class _Trainer(object):
         dt = (np.uint8 if name in self._U8 else np.int32 if name in self._I32 else np.float64 if name in self._F64 else np.float32)
         out = np.empty(n.value // np.dtype(dt).itemsize, dtype=dt)
         self.ctx._chk(fn(self.h, name.encode(), out.ctypes.data_as(ctypes.c_void_p), n.value, ctypes.byref(n)))
+        if name in self._FLAT:
+            return out
         shp = self._shapes()
         if len(name) > 2 and name[1] == "_" and name[2:] in shp:
             return out.reshape(shp[name[2:]])
@@ -1727,6 +1733,7 @@ class AzSolver(_Trainer):
                              (np.empty(R, np.float32), np.empty((R, 11), np.float32), np.empty((R, 44), np.float32)))
 
 
+DET_MAX_ROIS = 4096                                          # az_det_solver_create's limit on max_rois
 DET_HEAD_KEYS = ("W6", "b6", "W7", "b7", "Wc", "bc", "Wb", "bb")
 SKIP_KEYS = ("Wp", "bp")                                     # conv_pool5 of an attached skip front
 
@@ -1735,8 +1742,9 @@ class AzDetSolver(_Trainer):
     """The detection-net trainer behind conv5_3 (az_det_solver_*): fc6 -> fc7 -> {cls_score, bbox_pred} with fp32 master
     weights, gradients and momentum history in HBM; `step` is forward + backward of a minibatch, `update` Caffe's SGD step."""
     _C, KEYS, _NDROP, _U8 = "az_det_solver", DET_HEAD_KEYS, 2, ("mask6", "mask7")
-    _I32, _F64 = ("argmax", "skip_argmax"), ("skip_factor",)
+    _I32, _F64 = ("argmax", "skip_argmax", "mine_keep", "mine_nkeep"), ("skip_factor",)
     _ROWS49 = ("cat", "skip_argmax", "skip_factor", "d_y", "d_cat", "d_raw")
+    _FLAT = ("mine_loss", "mine_loss_cls", "mine_loss_bbox", "mine_keep", "mine_nkeep")     # of the last mining pass: [R], [N]
 
     def __init__(self, ctx, C, n6, n7, num_classes, max_rois=256, seed=0, head=None):
         self.dims = dict(C=int(C), n6=int(n6), n7=int(n7), ncls=int(num_classes), K6=int(C) * 49)
@@ -1769,6 +1777,34 @@ class AzDetSolver(_Trainer):
         """TEST-phase forward (dropout off): (cls_prob [R, ncls], raw bbox_pred [R, 4 ncls])."""
         lead, _rois, _ = self._pass_args(conv, rois)
         return self._forward(self.L.az_det_solver_forward_test, lead, self._outs(lead[-1]))
+
+    # ---- online hard-example mining (az_det_solver_mine*) ----
+    def _mine(self, fn, lead, labels, targets, nms_thresh, per_image, want_losses):
+        N, R = (lead[1] if fn is self.L.az_det_solver_mine else lead[5]), lead[-1]
+        labels = _f32(labels).reshape(R)
+        targets = None if targets is None else _f32(targets).reshape(R, 4)
+        per_image = int(per_image)
+        sel = np.full((N, max(per_image, 0)), -1, dtype=np.int32)
+        n_sel = np.zeros(N, dtype=np.int32)
+        loss = np.empty(R, np.float32) if want_losses else None
+        f, i32 = ctypes.c_float, ctypes.c_int32
+        self.last_rows = R                     # (a refused call has run no pass: fetch then answers for the pass before it)
+        self.ctx._chk(fn(self.h, *(list(lead) + [_p(labels, f), None if targets is None else _p(targets, f), float(nms_thresh),
+                                                 per_image, _p(sel, i32), _p(n_sel, i32), None if loss is None else _p(loss, f)])))
+        return np.concatenate([sel[i, :n_sel[i]] for i in range(N)]) if N else sel.reshape(-1), n_sel, loss
+
+    def mine(self, conv, rois, labels, targets, nms_thresh, per_image, want_losses=False):
+        """One hard-example mining pass (az_det_solver_mine): TEST-phase forward over all pool rows, a loss per row, per-image
+        NMS with the loss as score.  rois [R,5] with a non-decreasing image index; labels [R]; targets [R,4] (the rows' own
+        class's deltas) or None.  Returns (sel int32 [sum n_sel]: the chosen rows image by image in descending loss, n_sel
+        int32 [N], the row losses f32 [R] or None)."""
+        lead, _rois, _ = self._pass_args(conv, rois)
+        return self._mine(self.L.az_det_solver_mine, lead, labels, targets, nms_thresh, per_image, want_losses)
+
+    def mine_skip(self, maps, rois, labels, targets, nms_thresh, per_image, want_losses=False):
+        """`mine` behind the skip front (az_det_solver_mine_skip)."""
+        lead, _keep, _ = self._skip_args(maps, rois)
+        return self._mine(self.L.az_det_solver_mine_skip, lead, labels, targets, nms_thresh, per_image, want_losses)
 
     # ---- the skip-connection front (az_det_solver_*_skip) ----
     def attach_skip(self, Cs, scales, gain=1000.0, eps=1e-10, seed=0, front=None):

@@ -49,7 +49,11 @@ def _defaults():
                     [0.2, 0.2, 1, 1]],
         PRECISION='fp32',    # (not in the reference) operands of the trainers' matrix products: 'fp32' or 'bf16' (rounded on
                              # chip, summed in fp32; the master weights stay fp32)
-        SNAPSHOT_STATE=False)    # (not in the reference) every snapshot also writes a .solverstate (SolverWrapper.save_state)
+        SNAPSHOT_STATE=False,    # (not in the reference) every snapshot also writes a .solverstate (SolverWrapper.save_state)
+        OHEM=False,          # (not in the reference) detection net: online hard-example mining -- every minibatch is the BATCH_SIZE
+                             # rows of highest loss of the images' whole pools (AzDetSolver.mine), not _sample_rois' random draw
+        OHEM_NMS=0.7,        # (not in the reference) IoU at which a pool row suppresses a row of lower loss in the same image
+        OHEM_POOL=2000)      # (not in the reference) pool rows per image at most: the foreground first, then the background
     test = dict(         # config.py:109-133
         SCALES=(600,),       # short-side target of the single test scale
         MAX_SIZE=1000,       # long-side cap (experiments/cfgs/voc.yml:13 lowers it to 800)

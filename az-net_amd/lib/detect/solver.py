@@ -174,6 +174,10 @@ class SolverWrapper(object):
         self.losses.append(np.asarray(losses, dtype=np.float32))
         return losses
 
+    def _display_extra(self):
+        """One more line for train_model's display iterations, or None."""
+        return None
+
     def _snapshot_extra(self):
         """Layers of the snapshot beside the backbone's and HEAD_OF's: {Caffe name: [blobs]}."""
         return {}
@@ -342,6 +346,9 @@ class SolverWrapper(object):
                 recent = np.sum(np.asarray(self.losses[-avg:], dtype=np.float64), axis=1)
                 each = ", ".join("{:s} = {:.6g}".format(n, float(v)) for n, v in zip(self.LOSS_NAMES, self.losses[-1]))
                 print("Iteration {:d}, loss = {:.6g} ({:s}), lr = {:g}".format(self.iter - 1, float(recent.mean()), each, self.last_rate))
+                extra = self._display_extra()
+                if extra:
+                    print("    " + extra)
             if display > 0 and self.iter % (10 * display) == 0:
                 print("speed: {:.3f}s / iter".format(timer.average_time))
             if self.iter % cfg.TRAIN.SNAPSHOT_ITERS == 0:

@@ -35,6 +35,10 @@ class SolverWrapper(solver.SolverWrapper):
     def __init__(self, solver_prototxt, imdb, output_dir, pretrained_model=None, backbone=None, trainer=None, ctx=None,
                  dims=None, seed=None):
         self.num_classes = int(imdb.num_classes)
+        self.last_mining = self.last_sel = None          # of the last mining pass (TRAIN.OHEM): its figures, the rows it chose
+        if cfg.TRAIN.OHEM and int(cfg.TRAIN.IMS_PER_BATCH) * int(cfg.TRAIN.OHEM_POOL) > ffi.DET_MAX_ROIS:
+            raise ValueError("TRAIN.OHEM: IMS_PER_BATCH * OHEM_POOL = %d * %d rows, the trainer takes %d at most"
+                             % (cfg.TRAIN.IMS_PER_BATCH, cfg.TRAIN.OHEM_POOL, ffi.DET_MAX_ROIS))
         # the configuration and the train net must name the same model (checked before any device work)
         net_file = self._read_solver(solver_prototxt)
         self.skip = None
@@ -72,9 +76,16 @@ class SolverWrapper(solver.SolverWrapper):
             if layers and "fc6" in layers and "fc7" in layers:
                 dims = dict(n6=layers["fc6"][1].size, n7=layers["fc7"][1].size)
         self.trainer = ffi.AzDetSolver(self.ctx, self.backbone.out_channels, dims["n6"], dims["n7"], self.num_classes,
-                                       max_rois=int(cfg.TRAIN.BATCH_SIZE), seed=self.seed)
+                                       max_rois=self._max_rois(), seed=self.seed)
         self._load_fillers()
         self._copy_from(layers)
+
+    @staticmethod
+    def _max_rois():
+        """Rows of the largest pass: a minibatch, or under TRAIN.OHEM the pools of a batch's images."""
+        if cfg.TRAIN.OHEM:
+            return max(int(cfg.TRAIN.BATCH_SIZE), int(cfg.TRAIN.IMS_PER_BATCH) * int(cfg.TRAIN.OHEM_POOL))
+        return int(cfg.TRAIN.BATCH_SIZE)
 
     def _attach_skip(self):
         """The front of the train net on the trainer: scales and gain as the file states them, eps the library's."""
@@ -125,6 +136,8 @@ class SolverWrapper(solver.SolverWrapper):
         if self.skip is not None:
             conv, taps = self.backbone.forward_train(blobs["data"], taps=tuple(self.skip["sources"]))
             maps = [t.detach() for t in taps]
+            if cfg.TRAIN.OHEM:
+                blobs = self._mine(blobs, lambda *a: self.trainer.mine_skip(maps, *a))
             # (a tap in front of the first trainable convolution takes no gradient: no buffer, no gather)
             dmaps = [torch.empty_like(m) if t.requires_grad else None for m, t in zip(maps, taps)] if self.conv_train else None
             if dmaps is not None and all(d is None for d in dmaps):
@@ -138,6 +151,8 @@ class SolverWrapper(solver.SolverWrapper):
                     torch.autograd.backward([t for t, d in zip(taps, dmaps) if d is not None], [d for d in dmaps if d is not None])
         else:
             conv = self.backbone.forward_train(blobs["data"])
+            if cfg.TRAIN.OHEM:
+                blobs = self._mine(blobs, lambda *a: self.trainer.mine(conv.detach(), *a))
             dmap = torch.empty_like(conv) if self.conv_train else None
             losses, sumsq = self.trainer.step(conv.detach(), blobs["rois"], blobs["labels"], blobs["bbox_targets"],
                                               blobs["bbox_loss_weights"], self.seed, it, dmap=dmap)
@@ -146,6 +161,36 @@ class SolverWrapper(solver.SolverWrapper):
                 conv.backward(dmap)
         self.last_conv, self.last_blobs = conv.detach(), blobs
         return losses, sumsq, backward
+
+    def _mine(self, pool, mine):
+        """TRAIN.OHEM: the minibatch that the trainer's mining pass picks from the pool blobs (roi_data_layer.minibatch.
+        get_ohem_minibatch) on the maps of this iteration -- the BATCH_SIZE // IMS_PER_BATCH rows of highest loss per image
+        that survive NMS at OHEM_NMS --, gathered on the host with the targets expanded; notes the pass in last_mining."""
+        from roi_data_layer.minibatch import _get_bbox_regression_labels
+        n_im = int(pool["data"].shape[0])
+        per_image = int(cfg.TRAIN.BATCH_SIZE) // n_im
+        rois, labels, targets = pool["rois"], pool["labels"], pool["targets"]
+        sel = np.zeros(0, np.int32)
+        if rois.shape[0] > 0:
+            sel, n_sel, loss = mine(rois, labels, targets if cfg.TRAIN.BBOX_REG else None, float(cfg.TRAIN.OHEM_NMS), per_image, True)
+        if sel.size == 0:
+            raise ValueError("TRAIN.OHEM: no row selected in any of the batch's images %s (their pools are empty: no proposal "
+                             "at or above FG_THRESH or below it)" % ", ".join(str(i) for i in range(n_im)))
+        lab = labels[sel]
+        bbox_targets, bbox_loss_weights = _get_bbox_regression_labels(np.hstack((lab[:, np.newaxis], targets[sel])), self.num_classes)
+        self.last_mining = dict(pool=int(rois.shape[0]), kept=[int(k) for k in self.trainer.fetch("mine_nkeep")],
+                                selected=[int(k) for k in n_sel], fg=int(np.count_nonzero(lab > 0)),
+                                pool_loss=float(np.mean(loss, dtype=np.float64)), mined_loss=float(np.mean(loss[sel], dtype=np.float64)))
+        self.last_sel = sel
+        return {"data": pool["data"], "rois": np.ascontiguousarray(rois[sel]), "labels": np.ascontiguousarray(lab),
+                "bbox_targets": bbox_targets, "bbox_loss_weights": bbox_loss_weights}
+
+    def _display_extra(self):
+        m = self.last_mining
+        if not cfg.TRAIN.OHEM or m is None:
+            return None
+        return ("mining: pool = {:d}, kept = {}, selected = {} ({:d} fg), pool loss = {:.6g}, mined loss = {:.6g}"
+                .format(m["pool"], m["kept"], m["selected"], m["fg"], m["pool_loss"], m["mined_loss"]))
 
     def _snapshot_extra(self):
         if self.skip is None:

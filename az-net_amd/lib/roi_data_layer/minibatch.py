@@ -31,6 +31,47 @@ def get_minibatch(roidb, num_classes, ctx=None):
     return blobs
 
 
+def ohem_pool_inds(entry):
+    """The pool rows of one roidb entry under TRAIN.OHEM: (indices, number of foreground rows among them).  The foreground
+    (max_overlaps >= FG_THRESH) in roidb order, then the background ([BG_THRESH_LO, BG_THRESH_HI), with _sample_rois'
+    fall-back when that band is empty) in roidb order, cut at OHEM_POOL rows: the objects come first, so a long proposal list
+    never pushes them out.  FG_FRACTION plays no part, and np.random is not asked."""
+    T = cfg.TRAIN
+    overlaps = entry["max_overlaps"]
+    fg = np.flatnonzero(overlaps >= T.FG_THRESH)
+    bg = np.flatnonzero((overlaps < T.BG_THRESH_HI) & (overlaps >= T.BG_THRESH_LO))
+    if bg.size == 0:
+        bg = np.flatnonzero(overlaps < T.FG_THRESH)
+    pool = int(T.OHEM_POOL)
+    keep = np.concatenate((fg, bg)).astype(np.int64)[:pool]
+    return keep, int(min(fg.size, pool))
+
+
+def get_ohem_minibatch(roidb, num_classes, ctx=None):
+    """The blobs of one minibatch under TRAIN.OHEM: every image's whole pool (ohem_pool_inds) instead of a sample -- data,
+    rois (projected, the image index in column 0), labels and the compact targets [R, 4] of each row's own class, which the
+    trainer's mining pass reads (detect.train_det).  np.random is asked for the scale indices only."""
+    n = len(roidb)
+    scale_inds = npr.randint(0, high=len(cfg.TRAIN.SCALES), size=n)
+    if cfg.TRAIN.BATCH_SIZE % n != 0:
+        raise ValueError("TRAIN.BATCH_SIZE = {} is no multiple of the {} images of a batch".format(cfg.TRAIN.BATCH_SIZE, n))
+    im_blob, im_scales = _get_image_blob(roidb, scale_inds, ctx)
+    rois, labels, targets = [], [], []
+    for i, entry in enumerate(roidb):
+        keep, n_fg = ohem_pool_inds(entry)
+        compact = entry["bbox_targets"][keep, :]
+        lab = compact[:, 0].copy()
+        lab[n_fg:] = 0
+        boxes = _project_im_rois(entry["ex_boxes"].astype(np.float32, copy=False)[keep], im_scales[i])
+        tgt = np.asarray(compact[:, 1:5], dtype=np.float32)
+        for a in (boxes, tgt, lab):
+            assert np.all(np.isfinite(a)), "nan or inf in a minibatch (a class whose targets have std 0?)"
+        rois.append(np.hstack((np.full((boxes.shape[0], 1), float(i)), boxes)))
+        labels.append(lab), targets.append(tgt)
+    return {"data": im_blob, "rois": np.vstack(rois), "labels": np.hstack(labels).astype(np.float32, copy=False),
+            "targets": np.vstack(targets)}
+
+
 def _sample_rois(roidb, fg_rois_per_image, rois_per_image, num_classes):
     """A random sample of foreground and background example boxes (minibatch.py:67-124).  np.random is asked for a
     choice only when the pool is not empty; an empty [BG_THRESH_LO, BG_THRESH_HI) band falls back to everything below

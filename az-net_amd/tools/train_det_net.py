@@ -17,7 +17,10 @@ The proposals are cached as proposals.pkl under the output directory of (imdb, A
 Under a skip configuration (--cfg experiments/cfgs/voc_skip.yml: SEAR.FRCNN_CONV names conv3_3, conv4_3, conv5_3) the
 skip-connection detector is trained: without --solver the written train net is the reference's frozen/ net (all
 convolutions fixed; edit its lr_mult / decay_mult and pass it through --solver to fine-tune them), the snapshots are
-vgg16_fast_rcnn_skip_iter_<n>.caffemodel with conv_pool5, and load in tools/test_det_net.py under the same --cfg."""
+vgg16_fast_rcnn_skip_iter_<n>.caffemodel with conv_pool5, and load in tools/test_det_net.py under the same --cfg.
+  --ohem    (extension) online hard-example mining (cfg.TRAIN.OHEM): per iteration the trainer scores every image's whole pool
+            of up to TRAIN.OHEM_POOL rows in a TEST-phase pass, suppresses overlapping rows (TRAIN.OHEM_NMS) and trains on the
+            BATCH_SIZE // IMS_PER_BATCH rows of highest loss per image.  IMS_PER_BATCH * OHEM_POOL may be 4096 at most."""
 import _init_paths  # noqa: F401
 import os
 
@@ -29,7 +32,10 @@ FLAGS = _cli.TRAIN + [
     ("--def", "prototxt", "(ignored) prototxt defining the AZ-net", None, str),
     ("--def_fc", "prototxt_fc", "(ignored) prototxt defining the AZ-net's fully connected part", None, str),
     ("--net", "caffemodel", "AZ-Net model that makes the proposals (.caffemodel / .npz) or synthetic[:width_div]", None, str),
-] + _cli.TRAIN_EXT
+] + _cli.TRAIN_EXT + [
+    ("--ohem", "ohem", "(extension) online hard-example mining: every minibatch is the rows of highest loss of the images' "
+                       "whole proposal pools (cfg.TRAIN.OHEM; OHEM_NMS, OHEM_POOL)", None, None),
+]
 COMMON = [row for row in _cli.COMMON if row[0] in ("--gpu", "--cfg", "--exp")]
 
 
@@ -86,6 +92,8 @@ def main():
         cfg.TRAIN.PRECISION = 'bf16'
     if args.snapshot_state:
         cfg.TRAIN.SNAPSHOT_STATE = True
+    if args.ohem:
+        cfg.TRAIN.OHEM = True
 
     import torch
     torch.cuda.set_device(args.gpu_id)

@@ -869,6 +869,40 @@ int az_skip_pool_bwd_unit(az_ctx *ctx, int n_src, const int *Cs, const float *sp
                           const int *Hs, const int *Ws, int N, int channels_last, const float *rois, int R,
                           const float *d_raw_host, float *pooled_out, int32_t *argmax_out, float *const *dmaps_out);
 
+/* ---- online hard-example mining (Shrivastava et al., CVPR 2016; not in the reference) ------------------------------------------ */
+/* One call mines one minibatch: the TEST-phase forward of az_det_solver_forward_test (dropout = identity, the trainer's
+ * current precision) over all R pool rows, one loss per row, per image greedy NMS over the rows with the loss as score, and
+ * the first per_image survivors of every image.  Nothing but the selection leaves the device.
+ *   rois [R][5] as az_det_solver_step takes them; column 0 (the image index) must not decrease: image i owns the rows that
+ *     name it (possibly none).  labels [R]: whole numbers in [0, num_classes).  targets [R][4]: the normalised deltas of each
+ *     row's own class (ignored where the label is 0); NULL: no box term (TRAIN.BBOX_REG off).
+ *   loss_r = cls_r + bbox_r in float32:
+ *     cls_r = -logf(max(p[label], FLT_MIN)), p = exp(x - max x) / sum exp(x - max x) as az_det_solver_step computes it;
+ *     bbox_r = ((f0 + f1) + f2) + f3 for label > 0, f_q = 0.5 d d if |d| < 1 else |d| - 0.5, d = bbox_pred[r][4 label + q] -
+ *     targets[r][q] (SmoothL1Loss with weight 1, not divided by R); 0 for label 0.
+ *   Selection, per image: az_nms's kernels, arithmetic and order on the records [x1, y1, x2, y2, loss_r] (the rois' float32
+ *     columns 1..4) with nms_thresh: rows visited by descending loss, of equal losses the higher index first; a row is dropped
+ *     when its IoU with a kept row is >= nms_thresh (so nms_thresh > 1 keeps every row).  sel_out [N * per_image] receives,
+ *     image by image and packed, the first min(per_image, kept) kept rows as indices into the R rows; n_sel_out [N] their
+ *     numbers.  row_loss_out [R] (may be NULL): the losses.
+ * Afterwards the trainer is as after az_det_solver_forward_test (an az_det_solver_update without a new step is refused);
+ * parameter gradients, history and the accumulate flag are untouched, so mining between two accumulating steps is safe.
+ * az_det_solver_fetch also knows mine_loss, mine_loss_cls, mine_loss_bbox (f32 [R]), mine_keep (int32 [R]: image i's whole keep
+ * list, before the cut at per_image, from its first row on; -1 behind it) and mine_nkeep (int32 [N]).
+ * AZ_ERR_INVALID before anything is enqueued: what az_det_solver_forward_test refuses, a null labels / sel_out / n_sel_out,
+ * per_image < 1, nms_thresh negative or not finite, a label that is no class, a decreasing image index.  AZ_ERR_STATE:
+ * az_det_solver_mine on a trainer with a skip front, az_det_solver_mine_skip on one without.  A row whose loss, or whose sum of
+ * exponentials, is not finite (a NaN score, which the FLT_MIN clamp would turn into a finite loss; found after the pass through a
+ * device flag): AZ_ERR_INVALID, sel_out and n_sel_out untouched.  The same call from the same
+ * state gives the same bits. */
+int az_det_solver_mine(az_det_solver *s, const float *conv_dev, int N, int H, int W, int channels_last, const float *rois, int R,
+                       const float *labels, const float *targets, double nms_thresh, int per_image, int32_t *sel_out,
+                       int32_t *n_sel_out, float *row_loss_out);
+/* The same behind the skip front (az_det_solver_forward_test_skip's forward). */
+int az_det_solver_mine_skip(az_det_solver *s, int n_src, const int *Cs, const void *const *maps_dev, const int *Hs, const int *Ws,
+                            int N, int channels_last, const float *rois, int R, const float *labels, const float *targets,
+                            double nms_thresh, int per_image, int32_t *sel_out, int32_t *n_sel_out, float *row_loss_out);
+
 /* ---- gradient accumulation and the solver's state between two iterations (all three trainers, both precisions) ------------ */
 /* Caffe's iter_size (Solver::Step: `for (int i = 0; i < param_.iter_size(); ++i) loss += net_->ForwardBackward();` after one
  * ClearParamDiffs, then SGDSolver::ApplyUpdate: ClipGradients on the summed diffs, then Normalize scales them by
