@@ -57,9 +57,9 @@ def int_map(seed, C):
     return a.astype(np.float32)
 
 
-def ternary(rng, n_out, n_in):
-    """{-1, 0, 1}, a quarter of the entries non-zero."""
-    t = rng.integers(0, 8, (n_out, n_in), dtype=np.int8)
+def ternary(rng, n_out, n_in, density=0.25):
+    """{-1, 0, 1}, a quarter of the entries non-zero (or the share `density` = 2 / an integer)."""
+    t = rng.integers(0, int(round(2.0 / density)), (n_out, n_in), dtype=np.int8)
     return (t == 0).astype(np.float32) - (t == 1).astype(np.float32)
 
 
@@ -167,14 +167,15 @@ def int_az_case(dims, seed=0, pool=None):
             "pre": s["pre"], "p64": s["p64"], "tol": s["tol"], "unit_move": s["unit_move"]}
 
 
-def int_det_case(dims, seed=0, pool=None):
-    """The integer-exact detection head of one size set on the 300 rois."""
+def int_det_case(dims, seed=0, pool=None, rois=None, density=0.25):
+    """The integer-exact detection head of one size set on the 300 rois (or on `rois`, with W6 / W7 / Wb at `density`:
+    tests/det_rows_ref.py)."""
     C, n6, n7, ncls = dims
     rng = np.random.Generator(np.random.PCG64(1000 * C + n6 + 7 * ncls + seed))
-    fmap, rois = int_map(seed + C, C), rois300()
+    fmap, rois = int_map(seed + C, C), rois300() if rois is None else rois
     p5 = (pool or (lambda f, r: R.roi_pool(f, r)[0]))(fmap, rois)
-    head = {"W6": ternary(rng, n6, C * 49), "b6": small_ints(rng, n6), "W7": ternary(rng, n7, n6), "b7": small_ints(rng, n7),
-            "Wb": ternary(rng, 4 * ncls, n7), "bb": small_ints(rng, 4 * ncls)}
+    head = {"W6": ternary(rng, n6, C * 49, density), "b6": small_ints(rng, n6), "W7": ternary(rng, n7, n6, density),
+            "b7": small_ints(rng, n7), "Wb": ternary(rng, 4 * ncls, n7, density), "bb": small_ints(rng, 4 * ncls)}
     asum = {}
     h6 = _layer(p5.astype(np.float64), head["W6"], head["b6"], True, asum, "fc6")
     h7 = _layer(h6, head["W7"], head["b7"], True, asum, "fc7")
