@@ -338,6 +338,10 @@ struct az_ctx {
     unsigned char *h_nmsb = nullptr; size_t h_nmsb_cap = 0; int *nms_done = nullptr; int nms_seq = 0;   // ... of az_nms_batched's
     Buf h_nms_own{Buf::MAPPED}, h_nmsg_own{Buf::MAPPED}, h_nmsb_own{Buf::MAPPED}, nms_done_own;
     unsigned nms_tag = 0;               // sequence number carried by every word an NMS kernel writes to host-mapped memory
+    // Soft-NMS / box voting scratch (az_postproc.hip; grown on demand): pp_box_cap boxes, pp_grp_cap groups
+    int pp_box_cap = 0, pp_grp_cap = 0;
+    Buf pp_box_own[4];                  // (dets [.][5] f32, keep i64, scores f32, voted boxes [.][4] f32: grown together)
+    Buf pp_grp_own[3];                  // (offsets [. + 1], the launch's group list, counts: grown together)
     // tuner (az_eval.hip): anchor history of the last search, score pool over an image set
     double *hisB = nullptr;
     float *hisZ = nullptr;

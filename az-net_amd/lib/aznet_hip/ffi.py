@@ -22,6 +22,9 @@ AZ_PYRAMID_MAX = 8         # include/aznet_hip.h
 AZ_SKIP_MAX_SRC = 3        # include/aznet_hip.h
 AZ_SKIP_CHUNK = 128        # include/aznet_hip.h
 AZ_TRAIN_FP32, AZ_TRAIN_BF16 = 0, 1       # include/aznet_hip.h
+AZ_NMS_HARD, AZ_NMS_LINEAR, AZ_NMS_GAUSSIAN = 0, 1, 2      # include/aznet_hip.h
+AZ_SOFT_NMS_MAX = 4096     # include/aznet_hip.h
+NMS_METHODS = {"hard": AZ_NMS_HARD, "linear": AZ_NMS_LINEAR, "gaussian": AZ_NMS_GAUSSIAN}
 AZ_ERR_INVALID, AZ_ERR_HIP, AZ_ERR_CAPACITY, AZ_ERR_STATE, AZ_ERR_NO_DEVICE = -1, -2, -3, -4, -5
 _ERR_NAMES = {-1: "AZ_ERR_INVALID", -2: "AZ_ERR_HIP", -3: "AZ_ERR_CAPACITY", -4: "AZ_ERR_STATE",
               -5: "AZ_ERR_NO_DEVICE"}
@@ -59,6 +62,7 @@ SYMBOLS = [
     "az_solver_set_accumulate", "az_det_solver_set_accumulate", "az_solver_load_history", "az_det_solver_load_history",
     "az_det_solver_load_skip_history",
     "az_det_solver_mine", "az_det_solver_mine_skip",
+    "az_soft_nms_batched", "az_box_vote_batched",
 ]
 
 
@@ -183,6 +187,8 @@ def load_library(path=None):
     L.az_topk_radix.argtypes = [vp, fp, ci, ci, ip, cip]
     L.az_nms.argtypes = [vp, fp, ci, cd, i64p, cip]
     L.az_nms_batched.argtypes = [vp, fp, ip, ci, cd, i64p, ip]
+    L.az_soft_nms_batched.argtypes = [vp, fp, ip, ci, ci, cd, cd, cd, i64p, fp, ip]
+    L.az_box_vote_batched.argtypes = [vp, fp, ip, ci, i64p, ip, cd, fp]
     L.az_load_det_head.argtypes = [vp, ci, ci, ci, ci] + [fp] * 8
     L.az_det_forward.argtypes = [vp, fp, ci, fp, fp]
     L.az_detect.argtypes = [vp, dp, ci, cd, cd, ci, ci, ci, cd, fp, dp]
@@ -898,6 +904,60 @@ class AzContext(object):
         self._chk(self.L.az_nms_batched(self.h, _p(allb, ctypes.c_float), _p(off, ctypes.c_int32), n, float(thresh),
                                         _p(keep, ctypes.c_int64), _p(nk, ctypes.c_int32)))
         return [keep[off[g]:off[g] + nk[g]].copy() for g in range(n)]
+
+    @staticmethod
+    def _groups(dets_list):
+        """(offsets int32 [n + 1], all rows float32 [total, 5]) of a list of [n_g, 5] box sets."""
+        n = len(dets_list)
+        off = np.zeros(n + 1, dtype=np.int32)
+        for g, d in enumerate(dets_list):
+            off[g + 1] = off[g] + np.asarray(d).reshape(-1, 5).shape[0]
+        allb = _f32(np.vstack([np.zeros((0, 5), np.float32)] + [np.asarray(d, dtype=np.float32).reshape(-1, 5)
+                                                                   for d in dets_list]))
+        return off, allb
+
+    def soft_nms_batched(self, dets_list, method, thresh, sigma=0.5, min_score=0.001):
+        """Soft-NMS (az_soft_nms_batched) of many independent box sets ([n_g,5] float32 each) in one call.  method: 'hard',
+        'linear', 'gaussian' or an AZ_NMS_* value.  Returns a list of (keep int64 [nk], scores float32 [nk]): the picked
+        indices in pick order and their scores when they were picked."""
+        n = len(dets_list)
+        off, allb = self._groups(dets_list)
+        if isinstance(method, str):
+            if method not in NMS_METHODS:
+                raise ValueError("NMS method %r: 'hard', 'linear' or 'gaussian'" % (method,))
+            method = NMS_METHODS[method]
+        keep = np.zeros(max(int(off[n]), 1), dtype=np.int64)
+        sc = np.zeros(max(int(off[n]), 1), dtype=np.float32)
+        nk = np.zeros(max(n, 1), dtype=np.int32)
+        self._chk(self.L.az_soft_nms_batched(self.h, _p(allb, ctypes.c_float), _p(off, ctypes.c_int32), n, int(method),
+                                             float(thresh), float(sigma), float(min_score), _p(keep, ctypes.c_int64),
+                                             _p(sc, ctypes.c_float), _p(nk, ctypes.c_int32)))
+        return [(keep[off[g]:off[g] + nk[g]].copy(), sc[off[g]:off[g] + nk[g]].copy()) for g in range(n)]
+
+    def box_vote_batched(self, dets_list, keeps, vote_thresh):
+        """Box voting (az_box_vote_batched): dets_list the ORIGINAL box sets, keeps one index array per set (from nms_batched
+        or soft_nms_batched).  Returns a list of [nk, 4] float32 arrays: the voted box of every kept box, in keep order."""
+        n = len(dets_list)
+        if len(keeps) != n:
+            raise AzError(AZ_ERR_INVALID, "box_vote_batched: one keep list per box set")
+        off, allb = self._groups(dets_list)
+        keep = np.zeros(max(int(off[n]), 1), dtype=np.int64)
+        nk = np.zeros(max(n, 1), dtype=np.int32)
+        lists = [np.asarray(k, dtype=np.int64).ravel() for k in keeps]
+        lens = np.array([k.size for k in lists], dtype=np.int64)
+        long = np.flatnonzero(lens > np.diff(off))
+        if long.size:
+            raise AzError(AZ_ERR_INVALID, "box_vote_batched: keep list %d is longer than its box set" % long[0])
+        if n:
+            flat = np.concatenate(lists)
+            # list g goes to keep[off[g] ...]: its elements' positions in `flat`, moved by off[g] - (where list g starts in flat)
+            keep[np.arange(flat.size) + np.repeat(off[:n] - (np.cumsum(lens) - lens), lens)] = flat
+            nk[:n] = lens
+        out = np.zeros((max(int(off[n]), 1), 4), dtype=np.float32)
+        self._chk(self.L.az_box_vote_batched(self.h, _p(allb, ctypes.c_float), _p(off, ctypes.c_int32), n,
+                                             _p(keep, ctypes.c_int64), _p(nk, ctypes.c_int32), float(vote_thresh),
+                                             _p(out, ctypes.c_float)))
+        return [out[off[g]:off[g] + nk[g]].copy() for g in range(n)]
 
     def load_det_head(self, head):
         """head: dict of Caffe-layout fp32 arrays W6,b6 (fc6), W7,b7 (fc7), Wc,bc (cls_score),

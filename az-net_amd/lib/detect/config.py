@@ -61,8 +61,15 @@ def _defaults():
         SVM=False, BBOX_REG=True, DISPLAY=False,
         NUM_PROPOSALS=300,
         PREFETCH=2,          # (not in the reference) images test_proposals reads ahead in a worker thread; 0: none
-        BATCH_IMAGES=1)      # (not in the reference) > 1: test_proposals searches up to that many consecutive images of one shape
+        BATCH_IMAGES=1,      # (not in the reference) > 1: test_proposals searches up to that many consecutive images of one shape
                              # in lockstep (az_batch_launch): same boxes per image, every level's rois of the batch in one head pass
+        NMS_METHOD='hard',   # (not in the reference) 'hard': apply_nms as it is; 'linear' / 'gaussian': Soft-NMS at TEST.NMS, which
+                             # decays the scores of overlapping detections instead of deleting them (detect.test.postprocess_detections)
+        SOFT_NMS_SIGMA=0.5,  # (not in the reference) the gaussian decay exp(-IoU^2 / sigma)
+        SOFT_NMS_MIN_SCORE=0.001,    # (not in the reference) Soft-NMS drops a detection whose decayed score falls below this
+        BBOX_VOTE=False,     # (not in the reference) every detection kept by NMS / Soft-NMS becomes the score-weighted mean of the
+                             # detections of its class and image that overlap it
+        BBOX_VOTE_THRESH=0.8)        # (not in the reference) ... by at least this IoU
     # the 11 adjacency templates, relative to a region (config.py:149-154)
     subregion = [[0, 0, 1, 1],
                  [-0.5, 0, 0.5, 1], [0.5, 0, 1.5, 1], [0, -0.5, 1, 0.5], [0, 0.5, 1, 1.5],
@@ -104,6 +111,17 @@ def train_precision(name=None):
     if not isinstance(name, str) or name not in TRAIN_PRECISIONS:
         raise ValueError("cfg.TRAIN.PRECISION = %r: 'fp32' or 'bf16'" % (name,))
     return TRAIN_PRECISIONS[name]
+
+
+NMS_METHODS = ('hard', 'linear', 'gaussian')     # include/aznet_hip.h: AZ_NMS_HARD, AZ_NMS_LINEAR, AZ_NMS_GAUSSIAN
+
+
+def nms_method(name=None):
+    """cfg.TEST.NMS_METHOD (or `name`) once checked; anything but the three names is a ValueError."""
+    name = __C.TEST.NMS_METHOD if name is None else name
+    if not isinstance(name, str) or name not in NMS_METHODS:
+        raise ValueError("cfg.TEST.NMS_METHOD = %r: 'hard', 'linear' or 'gaussian'" % (name,))
+    return name
 
 
 def get_output_dir(imdb, net):
@@ -148,6 +166,25 @@ def cfg_from_file(filename):
     with open(filename, 'r') as f:
         yaml_cfg = edict(yaml.safe_load(f))
     _merge_a_into_b(yaml_cfg, __C)
+    for (section, key), value in _CLI.items():
+        __C[section][key] = value
+
+
+# (not in the reference) values given on a command line: they hold against a --cfg file whichever of the two a tool reads first
+_CLI = {}
+
+
+def cfg_set_cli(section, key, value):
+    """cfg[section][key] = value now and again after every later cfg_from_file (a flag wins over the file)."""
+    if key not in __C[section] or type(__C[section][key]) is not type(value):
+        raise KeyError('{}.{} is not a config key of that type'.format(section, key))
+    _CLI[(section, key)] = value
+    __C[section][key] = value
+
+
+def cfg_clear_cli():
+    """Forget the command line's values (the keys keep what they hold)."""
+    _CLI.clear()
 
 
 def cfg_set_mode(mode, thresh=None):

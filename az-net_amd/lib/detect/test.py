@@ -6,6 +6,8 @@ Same names, arguments and return types as the reference for the proposal path:
     apply_nms(all_boxes, thresh)                                    test.py:467-484
     test_net(net, prop_file, imdb)                                  test.py:541-668
     divide_region(regions)                                          test.py:153-161
+    postprocess_detections(all_boxes)                               (not in the reference: apply_nms at cfg.TEST.NMS, or
+                                                                     Soft-NMS and / or box voting by cfg.TEST.NMS_METHOD, BBOX_VOTE)
 `net` is a `HipAZNet` (it also answers net['full'] / net['fc'], so the reference's dict of
 two nets keeps working).  The level loop itself -- roi projection and dedup, RoIPool, fc
 head, decode, filter, zoom selection, divide_region, top-K -- runs inside one az_propose
@@ -537,6 +539,49 @@ def apply_nms(all_boxes, thresh):
     return nms_boxes
 
 
+def postprocess_detections(all_boxes):
+    """What the detection loops and tools/eval_det.py do to the set's all_boxes[class][image] before evaluation (not in the
+    reference beyond its first line).  With cfg.TEST.NMS_METHOD 'hard' and cfg.TEST.BBOX_VOTE off it is
+    apply_nms(all_boxes, cfg.TEST.NMS).  Otherwise: NMS ('hard') or Soft-NMS ('linear' / 'gaussian': SOFT_NMS_SIGMA,
+    SOFT_NMS_MIN_SCORE) at cfg.TEST.NMS, then, with BBOX_VOTE, every kept box voted on by its group's original rows at
+    BBOX_VOTE_THRESH -- one batched call each over the whole set.  A group's result: float32 [nk, 5] in pick order, the voted
+    boxes and the scores at the moment the boxes were picked."""
+    from detect.config import nms_method
+    method, vote = nms_method(), bool(cfg.TEST.BBOX_VOTE)
+    if method == 'hard' and not vote:
+        return apply_nms(all_boxes, cfg.TEST.NMS)
+    num_classes = len(all_boxes)
+    num_images = len(all_boxes[0])
+    out = [[[] for _ in range(num_images)] for _ in range(num_classes)]
+    where, sets = [], []
+    for cls_ind in range(num_classes):
+        for im_ind in range(num_images):
+            dets = all_boxes[cls_ind][im_ind]
+            if isinstance(dets, list) and dets == []:
+                continue
+            where.append((cls_ind, im_ind))
+            sets.append(np.ascontiguousarray(dets, dtype=np.float32).reshape(-1, 5))
+    if not sets:
+        return out
+    ctx = ffi.default_context()
+    if method == 'hard':
+        keeps = ctx.nms_batched(sets, float(cfg.TEST.NMS))
+        scores = [d[k, 4] for d, k in zip(sets, keeps)]
+    else:
+        picked = ctx.soft_nms_batched(sets, method, float(cfg.TEST.NMS), float(cfg.TEST.SOFT_NMS_SIGMA),
+                                      float(cfg.TEST.SOFT_NMS_MIN_SCORE))
+        keeps, scores = [p[0] for p in picked], [p[1] for p in picked]
+    if vote:
+        boxes = ctx.box_vote_batched(sets, keeps, float(cfg.TEST.BBOX_VOTE_THRESH))
+    else:
+        boxes = [d[k, :4] for d, k in zip(sets, keeps)]
+    for (cls_ind, im_ind), b, s in zip(where, boxes, scores):
+        if len(s) == 0:
+            continue
+        out[cls_ind][im_ind] = np.hstack((b, s[:, np.newaxis])).astype(np.float32, copy=False)
+    return out
+
+
 def test_proposals(net, imdb):
     """Proposals for every image of an imdb, written as proposals.pkl with the
     reference's layout {'boxes': [n_i x 4 float64], 'time': avg seconds, 'recall': 0}
@@ -645,7 +690,7 @@ class _Detections(object):
         with open(det_file, 'wb') as f:
             pickle.dump(all_boxes, f, pickle.HIGHEST_PROTOCOL)
         print('Applying NMS to all detections')
-        nms_dets = apply_nms(all_boxes, cfg.TEST.NMS)
+        nms_dets = postprocess_detections(all_boxes)
         if hasattr(imdb, "evaluate_detections"):
             print('Evaluating detections')
             imdb.evaluate_detections(nms_dets, output_dir)

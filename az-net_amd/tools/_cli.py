@@ -35,17 +35,43 @@ TRAIN_EXT = [
     ("--snapshot-state", "snapshot_state", "(extension) write a .solverstate beside every snapshot (cfg.TRAIN.SNAPSHOT_STATE)", None, None),
     ("--restore", "restore", "(extension) continue from this .solverstate; --iters stays the total", None, str),
 ]
+# what happens to the detections before evaluation (type a tuple = one of these values).  Every tool that evaluates
+# detections takes them: build_parser adds the table wherever a tool declares --comp, the competition-mode flag of
+# imdb.evaluate_detections (tools/test_det_net.py, tools/test_shared.py), and parse hands the values to cfg.TEST;
+# tools/eval_det.py, which has a parser of its own, adds and applies it itself.
+POSTPROC = [
+    ("--soft-nms", "soft_nms", "(extension) Soft-NMS instead of NMS at cfg.TEST.NMS (cfg.TEST.NMS_METHOD)", None, ("linear", "gaussian")),
+    ("--bbox-vote", "bbox_vote", "(extension) box voting on the kept detections (cfg.TEST.BBOX_VOTE)", None, None),
+]
 
 
-def build_parser(description, tables):
-    parser = argparse.ArgumentParser(description=description)
+def add_flags(parser, tables):
     for table in tables:
         for flag, dest, text, default, typ in table:
             if typ is None:
                 parser.add_argument(flag, dest=dest, help=text, action="store_true")
+            elif isinstance(typ, tuple):
+                parser.add_argument(flag, dest=dest, help=text, default=default, choices=typ)
             else:
                 parser.add_argument(flag, dest=dest, help=text, default=default, type=typ)
     return parser
+
+
+def build_parser(description, tables):
+    tables = list(tables)
+    if POSTPROC not in tables and any(row[0] == "--comp" for table in tables for row in table):
+        tables.append(POSTPROC)
+    return add_flags(argparse.ArgumentParser(description=description), tables)
+
+
+def set_postproc(args):
+    """--soft-nms / --bbox-vote into cfg.TEST: a flag wins over a --cfg file read before or after (cfg_set_cli), no flag
+    leaves the file's value."""
+    from detect.config import cfg_set_cli
+    if getattr(args, "soft_nms", None):
+        cfg_set_cli("TEST", "NMS_METHOD", args.soft_nms)
+    if getattr(args, "bbox_vote", False):
+        cfg_set_cli("TEST", "BBOX_VOTE", True)
 
 
 def parse(description, tables):
@@ -56,6 +82,7 @@ def parse(description, tables):
     args = parser.parse_args()
     print("Called with args:")
     print(args)
+    set_postproc(args)
     return args
 
 

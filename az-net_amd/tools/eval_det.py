@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Re-evaluate a saved detections.pkl (test_net's all_boxes, before NMS) without rerunning detection.
-NMS at cfg.TEST.NMS first (as test_net does), unless --no-nms.  A VOC or COCO imdb goes through its own
-evaluate_detections: VOC results files and XML ground truth with difficult flags (voc_eval.m's AP block,
+NMS at cfg.TEST.NMS first (as test_net does: detect.test.postprocess_detections, so --soft-nms / --bbox-vote or the
+cfg.TEST keys behind them re-score a saved run under Soft-NMS and box voting), unless --no-nms.
+A VOC or COCO imdb goes through its own evaluate_detections: VOC results files and XML ground truth with difficult flags (voc_eval.m's AP block,
 <cls>_pr.mat in --out), or the COCO results json in --out and COCOeval's 12 summary lines (box IoU).
 Any other imdb with a gt_roidb is evaluated the VOC way on its ground truth, difficult taken as 0 and the
 detections rounded as a results file would hold them."""
@@ -11,6 +12,8 @@ import os
 import pickle
 
 import numpy as np
+
+import _cli
 
 
 def _rounded(dets):
@@ -56,7 +59,7 @@ def eval_on_roidb(imdb, all_boxes, output_dir):
     return r["ap"], r["ap_auc"]
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser(description="Evaluate a saved detections.pkl (PASCAL VOC AP / COCO AP)")
     ap.add_argument("dets", help="detections.pkl written by test_net")
     ap.add_argument("--imdb", dest="imdb_name", default="voc_2007_test")
@@ -65,14 +68,19 @@ def main():
     ap.add_argument("--comp", dest="comp_mode", action="store_true", help="competition mode (keep results files)")
     ap.add_argument("--cfg", dest="cfg_file", default=None)
     ap.add_argument("--gpu", dest="gpu_id", type=int, default=0)
-    args = ap.parse_args()
+    return _cli.add_flags(ap, [_cli.POSTPROC])
+
+
+def main():
+    args = build_parser().parse_args()
     from detect.config import cfg, cfg_from_file
     if args.cfg_file:
         cfg_from_file(args.cfg_file)
+    _cli.set_postproc(args)
     import torch
     torch.cuda.set_device(args.gpu_id)
     from datasets.factory import get_imdb
-    from detect.test import apply_nms
+    from detect.test import postprocess_detections
     with open(args.dets, "rb") as f:
         all_boxes = pickle.load(f)
     imdb = get_imdb(args.imdb_name)
@@ -81,7 +89,7 @@ def main():
                          % (args.dets, len(all_boxes), len(all_boxes[0]), imdb.name, imdb.num_classes, imdb.num_images))
     if not args.no_nms:
         print("Applying NMS to all detections")
-        all_boxes = apply_nms(all_boxes, cfg.TEST.NMS)
+        all_boxes = postprocess_detections(all_boxes)
     out = args.output_dir or os.path.dirname(os.path.abspath(args.dets))
     print("Evaluating detections")
     if hasattr(imdb, "evaluate_detections"):

@@ -339,6 +339,51 @@ int az_nms(az_ctx *ctx, const float *dets, int n, double thresh, int64_t *keep, 
 int az_nms_batched(az_ctx *ctx, const float *dets, const int32_t *offsets, int n_groups, double thresh,
                    int64_t *keep, int32_t *n_keep);
 
+/* ---- Soft-NMS and box voting (not in the reference; opt-in behind cfg.TEST.NMS_METHOD / BBOX_VOTE) ---------------------------- */
+/* Two test-time refinements of apply_nms's step: Soft-NMS (Bodla et al., ICCV 2017) decays the scores of overlapping
+ * detections instead of deleting them; box voting (Gidaris & Komodakis, ICCV 2015) replaces each surviving box by the
+ * score-weighted mean of the group's boxes that overlap it.  Groups, offsets and the keep / n_keep layout are az_nms_batched's:
+ * group g owns the rows dets[offsets[g] .. offsets[g+1]) of [x1, y1, x2, y2, score] float32, a group of n rows.
+ *   IoU of rows i and j is az_nms's float32 arithmetic, one rounding per operation (the library is built without
+ *   contraction):  area = (x2 - x1 + 1) * (y2 - y1 + 1);  w = max(0, min(x2_i, x2_j) - max(x1_i, x1_j) + 1), h likewise;
+ *   inter = w * h;  den = (area_i + area_j) - inter;  ovr = inter / den.
+ * az_soft_nms_batched.  Every box starts alive with its input score.  Rounds repeat while a box is alive: the alive box of
+ * highest CURRENT score is picked (equal scores: the higher original index, az_nms's rule), emitted with that score and
+ * leaves the pool; every other alive box j gets s_j = s_j * w_j in float32 with
+ *     AZ_NMS_HARD      w = (double)ovr >= thresh ? 0 : 1
+ *     AZ_NMS_LINEAR    w = (double)ovr >= thresh ? 1 - ovr : 1
+ *     AZ_NMS_GAUSSIAN  w = expf(-(ovr * ovr) / (float)sigma)          (thresh unused)
+ * and is dropped, without being emitted, when (double)s_j < min_score.  The comparison with thresh is `>=`, as in az_nms (the
+ * Soft-NMS paper's code uses `>`).  keep[offsets[g] ..] receives the picked group-local indices in pick order,
+ * scores_out[offsets[g] ..] their scores at the moment they were picked, n_keep[g] their number.  AZ_NMS_HARD with min_score in
+ * (0, smallest positive input score] returns az_nms's keep list exactly; with min_score = 0 a suppressed box stays in the
+ * pool with score 0 and is emitted later.  Stated domain: finite scores >= 0; anything else is unspecified, as NaN is for
+ * az_nms -- but whatever the values, a group ends after at most n rounds and no index leaves [0, n).
+ * Groups of 1 .. 256 boxes share one launch (k_soft_nms_small: a workgroup per group, a box per thread), groups of 257 ..
+ * 4096 another (k_soft_nms_large: a workgroup per group, four boxes per thread); a group of more than 4096 boxes is
+ * AZ_ERR_CAPACITY (4096 is az_topk's largest k: no image of the pipeline exceeds it).
+ * az_box_vote_batched.  dets are the groups' ORIGINAL rows, keep / n_keep a keep list per group in az_nms_batched's layout
+ * (from az_nms_batched or az_soft_nms_batched).  For each kept box k the voters are all rows j of its group with
+ * (double)ovr(k, j) >= vote_thresh (the box itself among them); in float64 and in ascending j:  sw += s_j;  sc[q] += s_j *
+ * b_j[q]  (s_j the rows' original scores; the product of two float32 values is exact in float64); the voted coordinate is
+ * (float)(sc[q] / sw), and with sw == 0 the box stays as it was.  boxes_out [total][4]: row offsets[g] + k receives the
+ * voted box of group g's k-th kept box; scores are not touched.  One thread walks one kept box's voters in index order, so
+ * the same call gives the same bits.
+ * Both: AZ_ERR_INVALID, before anything is enqueued and with the outputs untouched, for a method outside the three
+ * constants, sigma <= 0 (or not finite) with AZ_NMS_GAUSSIAN, a negative (or NaN) min_score, a NaN thresh (hard, linear) / vote_thresh,
+ * offsets that do not start at 0 or decrease, an n_keep[g] outside [0, n], a keep index outside its group, a NULL array that
+ * is needed; AZ_ERR_CAPACITY likewise for a group of more than 4096 boxes.  Empty groups and n_groups == 0 are fine.
+ * Device scratch is kept in the context and grown on demand. */
+#define AZ_NMS_HARD 0
+#define AZ_NMS_LINEAR 1
+#define AZ_NMS_GAUSSIAN 2
+#define AZ_SOFT_NMS_MAX 4096   /* boxes per group */
+int az_soft_nms_batched(az_ctx *ctx, const float *dets, const int32_t *offsets, int n_groups, int method,
+                        double thresh, double sigma, double min_score,
+                        int64_t *keep, float *scores_out, int32_t *n_keep);
+int az_box_vote_batched(az_ctx *ctx, const float *dets, const int32_t *offsets, int n_groups,
+                        const int64_t *keep, const int32_t *n_keep, double vote_thresh, float *boxes_out);
+
 /* ---- Fast R-CNN head on the shared conv map (BASELINE config 3) ---------------------- */
 /* Replaces caffe.Net(frcnn/test_fc.prototxt, caffemodel) (tools/test_shared.py): the detection
  * head models/Pascal/VGG16/frcnn/test_fc.prototxt:14-145 -- fc6 [n6, C*49], fc7 [n7, n6],
