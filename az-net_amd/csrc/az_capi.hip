@@ -102,6 +102,8 @@ int az_set_gemm_mode(az_ctx *c, int parts)
 {
     if (!c || !(parts == 0 || parts == 2 || parts == 3)) return fail(c, AZ_ERR_INVALID, "az_set_gemm_mode: 0, 2 or 3");
     if (c->head_loaded) return fail(c, AZ_ERR_STATE, "az_set_gemm_mode must precede az_load_head");
+    if (parts && c->det_loaded && (c->det_r6 || c->det_r7))
+        return fail(c, AZ_ERR_STATE, "az_set_gemm_mode: a low-rank detection head is loaded (az_load_det_head_lowrank is fp32 only)");
     c->gemm_parts = parts;
     return AZ_OK;
 }

@@ -303,6 +303,10 @@ struct az_ctx {
     int det_n6 = 0, det_n7 = 0, det_ncls = 0, det_S6 = 1, det_S7 = 1;
     DevList allocs_det;
     float *dW6 = nullptr, *db6 = nullptr, *dW7 = nullptr, *db7 = nullptr, *dWt = nullptr, *dbt = nullptr;
+    // truncated-SVD layers (az_load_det_head_lowrank; rank 0 = the layer at full rank): L [r, in] tiled like dW6 / dW7, U [out, r]
+    // row-major (az_lowrank.hip), the L stage's chunk counts, its output rows [maxR][max r] and its zero bias
+    int det_r6 = 0, det_r7 = 0, det_SL6 = 0, det_SL7 = 0;
+    float *dL6 = nullptr, *dU6 = nullptr, *dL7 = nullptr, *dU7 = nullptr, *dlr_t = nullptr, *dlr_zero = nullptr;
     // 16-bit-term modes: the detection head's fc6 on the same kernel as int6 (its own weight planes, weight scale and
     // -- two fp16 terms -- its own {pool5 scale, 1 / (sx * sw)} pair)
     unsigned short *dW6p = nullptr; float *dgscale = nullptr; float det_w6_scale = 0.f;

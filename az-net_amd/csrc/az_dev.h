@@ -372,6 +372,13 @@ int azk_fc_gemm_terms(hipStream_t s, const unsigned short *Xp, int ldx, size_t x
                       int parts, const float *scales);
 void azk_fc_reduce(hipStream_t s, const float *part, const float *bias, const int *Mptr, int capM, int N,
                    int S, float *y, int ldy, int relu);
+// ---- truncated-SVD layers (az_lowrank.hip) ----
+// the U stage: y[M, N] (ldy) = act(x[M, K] (ldx) . W[N, K]^T + b) over the whole K in one launch, W row-major; M = *Mptr,
+// N and K positive multiples of 4, K <= AZ_LOWRANK_MAX.  The order of an element's K terms depends on K alone.
+void azk_lowrank_gemm(hipStream_t s, const float *x, int ldx, const float *W, const float *bias, const int *Mptr,
+                      int capM, int N, int K, int relu, float *y, int ldy);
+// K chunks of the L stage (x[M, K] . L[r, K]^T on azk_fc_gemm): a function of (K, r) alone
+int azk_lowrank_split(int K, int r);
 // int7_1|int7_2's slab sum + bias + ReLU, then adj_score + adj_bbox + zoom_score (56 outputs) + bias +
 // sigmoid + box decode/clip, in one launch
 // (vector-ALU products, see az_head.hip).  WtT is the stacked weight block k-major, zero-padded:

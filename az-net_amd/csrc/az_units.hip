@@ -343,15 +343,12 @@ int az_nms(az_ctx *c, const float *dets, int n, double thresh, int64_t *keep, in
 static const size_t DET_SEG_HDR = (sizeof(AzDetSeg) + 255) / 256 * 256;
 static size_t det_seg_bytes(const az_ctx *c) { return DET_SEG_HDR + (size_t)c->maxR * 4 * sizeof(double); }
 
-int az_load_det_head(az_ctx *c, int C, int n6, int n7, int ncls, const float *W6, const float *b6,
-                     const float *W7, const float *b7, const float *Wc, const float *bc, const float *Wb,
-                     const float *bb)
+// az_load_det_head / az_load_det_head_lowrank past their argument checks.  r6 / r7 == 0: that layer at full rank, W6 / W7
+// its [out, in] weight, L6 / L7 unused; otherwise W6 / W7 is the layer's U factor [out, r] and L6 / L7 its L factor [r, in].
+static int load_det_head(az_ctx *c, int C, int n6, int n7, int ncls, int r6, int r7, const float *L6, const float *W6,
+                         const float *b6, const float *L7, const float *W7, const float *b7, const float *Wc,
+                         const float *bc, const float *Wb, const float *bb)
 {
-    if (!c) return AZ_ERR_INVALID;
-    if (!W6 || !b6 || !W7 || !b7 || !Wc || !bc || !Wb || !bb) return fail(c, AZ_ERR_INVALID, "az_load_det_head: null pointer");
-    if (C <= 0 || (C & 3) || n6 <= 0 || (n6 & 3) || n7 <= 0 || (n7 & 3) || ncls < 2 || ncls > 256)
-        return fail(c, AZ_ERR_INVALID, "az_load_det_head: C, n6, n7 multiples of 4; 2 <= ncls <= 256");
-    if (c->head_loaded && C != c->d.C) return fail(c, AZ_ERR_INVALID, "az_load_det_head: C differs from the AZ head's");
     int rc = ensure_geom(c);
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
@@ -359,16 +356,31 @@ int az_load_det_head(az_ctx *c, int C, int n6, int n7, int ncls, const float *W6
     c->allocs_det.release();
     if (!c->head_loaded) c->pool5 = nullptr;     // (without an AZ head pool5 was the detection head's own: gone with the list)
     c->det_loaded = false;
+    c->dW6 = c->dW7 = c->dL6 = c->dL7 = c->dU6 = c->dU7 = c->dlr_t = c->dlr_zero = nullptr;
     const size_t R = (size_t)c->maxR, K6 = (size_t)C * 49, NO = (size_t)5 * ncls;
     c->det_n6 = n6; c->det_n7 = n7; c->det_ncls = ncls;
+    c->det_r6 = r6; c->det_r7 = r7;
     c->det_S6 = azk_fc_split((int)K6); c->det_S7 = azk_fc_split(n6);
+    c->det_SL6 = r6 ? azk_lowrank_split((int)K6, r6) : 0; c->det_SL7 = r7 ? azk_lowrank_split(n6, r7) : 0;
     DevList &list = c->allocs_det;
-    AZ_A(dW6, azk_tiled_elems(n6, (int)K6)); AZ_A(db6, n6); AZ_A(dW7, azk_tiled_elems(n7, n6)); AZ_A(db7, n7);
+    if (r6) { AZ_A(dL6, azk_tiled_elems(r6, (int)K6)); AZ_A(dU6, (size_t)n6 * r6); }
+    else AZ_A(dW6, azk_tiled_elems(n6, (int)K6));
+    if (r7) { AZ_A(dL7, azk_tiled_elems(r7, n6)); AZ_A(dU7, (size_t)n7 * r7); }
+    else AZ_A(dW7, azk_tiled_elems(n7, n6));
+    if (r6 || r7) {
+        // the L stages' output rows [R][r] (one buffer: the stream orders fc6_U before fc7_L) and their zero bias
+        const size_t rm = (size_t)(r6 > r7 ? r6 : r7);
+        AZ_A(dlr_t, R * rm); AZ_A(dlr_zero, rm);
+        HIPCHK(c, hipMemsetAsync(c->dlr_zero, 0, rm * sizeof(float), c->stream));
+    }
+    AZ_A(db6, n6); AZ_A(db7, n7);
     AZ_A(dWt, azk_tiled_elems((int)NO, n7)); AZ_A(dbt, NO);
     AZ_A(dh6, R * n6); AZ_A(dh7, R * n7);
+    const size_t rows6 = r6 ? (size_t)r6 : (size_t)n6;      // rows of the [., C*49] matrix that is permuted through dpart
     {
-        size_t pm = (size_t)c->det_S6 * R * n6;
-        const size_t p7 = (size_t)c->det_S7 * R * n7, pt = (size_t)AZK_TAIL_SPLIT * R * NO, pw = (size_t)n6 * K6;
+        size_t pm = r6 ? (size_t)c->det_SL6 * R * r6 : (size_t)c->det_S6 * R * n6;
+        const size_t p7 = r7 ? (size_t)c->det_SL7 * R * r7 : (size_t)c->det_S7 * R * n7;
+        const size_t pt = (size_t)AZK_TAIL_SPLIT * R * NO, pw = rows6 * K6;
         pm = pm > p7 ? pm : p7; pm = pm > pt ? pm : pt; pm = pm > pw ? pm : pw;
         AZ_A(dpart, pm);
     }
@@ -379,18 +391,19 @@ int az_load_det_head(az_ctx *c, int C, int n6, int n7, int ncls, const float *W6
     c->dseg_host = c->dseg_own.as<unsigned char>();
     if (!c->pool5) { AZ_A(pool5, R * K6); }     // normally the AZ head's buffer is shared
     c->dW6p = nullptr; c->dgscale = nullptr;
-    if (c->gemm_parts && c->pool5p && azk_fc_terms_prepare(c->gemm_parts) == 0) {
+    if (!r6 && c->gemm_parts && c->pool5p && azk_fc_terms_prepare(c->gemm_parts) == 0) {
         AZ_A(dW6p, (size_t)c->gemm_parts * azk_weight_plane_elems(n6, (int)K6)); AZ_A(dgscale, 4);
         HIPCHK(c, hipMemsetAsync(c->dgscale, 0, 4 * sizeof(float), c->stream));
     }
     if (!c->head_loaded) { c->d.C = C; c->d.pooled = 7; c->d.K6 = (int)K6; }
     {
         Buf tg;
-        HIPCHK(c, tg.reserve(std::max(std::max((size_t)n6 * K6, (size_t)n7 * n6), NO * n7) * 4));
+        const size_t in7 = r7 ? (size_t)r7 * n6 : (size_t)n7 * n6;
+        HIPCHK(c, tg.reserve(std::max(std::max(rows6 * K6, in7), NO * n7) * 4));
         float *tmp = tg.as<float>();
-        HIPCHK(c, hipMemcpy(c->dpart, W6, (size_t)n6 * K6 * 4, hipMemcpyHostToDevice));
-        azk_permute_k(c->stream, c->dpart, tmp, n6, C, 1);          // bin-major columns, like the AZ head
-        azk_tile_weights(c->stream, tmp, c->dW6, n6, (int)K6);
+        HIPCHK(c, hipMemcpy(c->dpart, r6 ? L6 : W6, rows6 * K6 * 4, hipMemcpyHostToDevice));
+        azk_permute_k(c->stream, c->dpart, tmp, (long long)rows6, C, 1);          // bin-major columns, like the AZ head
+        azk_tile_weights(c->stream, tmp, r6 ? c->dL6 : c->dW6, (int)rows6, (int)K6);
         if (c->dW6p) {
             c->det_w6_scale = 0.f;
             if (c->gemm_parts == 2) {
@@ -402,8 +415,8 @@ int az_load_det_head(az_ctx *c, int C, int n6, int n7, int ncls, const float *W6
             azk_split_weight_planes(c->stream, tmp, c->dW6p, n6, (int)K6, c->gemm_parts, c->det_w6_scale);
         }
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipMemcpy(tmp, W7, (size_t)n7 * n6 * 4, hipMemcpyHostToDevice));
-        azk_tile_weights(c->stream, tmp, c->dW7, n7, n6);
+        HIPCHK(c, hipMemcpy(tmp, r7 ? L7 : W7, in7 * 4, hipMemcpyHostToDevice));
+        azk_tile_weights(c->stream, tmp, r7 ? c->dL7 : c->dW7, r7 ? r7 : n7, n6);
         HIPCHK(c, hipStreamSynchronize(c->stream));
         // rows 0..ncls-1 cls_score, ncls..5*ncls-1 bbox_pred
         HIPCHK(c, hipMemcpy(tmp, Wc, (size_t)ncls * n7 * 4, hipMemcpyHostToDevice));
@@ -411,6 +424,9 @@ int az_load_det_head(az_ctx *c, int C, int n6, int n7, int ncls, const float *W6
         azk_tile_weights(c->stream, tmp, c->dWt, (int)NO, n7);
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
+    // the U factors stay row-major [out, r]: the U stage reads Caffe's layout as it is
+    if (r6) HIPCHK(c, hipMemcpy(c->dU6, W6, (size_t)n6 * r6 * 4, hipMemcpyHostToDevice));
+    if (r7) HIPCHK(c, hipMemcpy(c->dU7, W7, (size_t)n7 * r7 * 4, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(c->db6, b6, (size_t)n6 * 4, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(c->db7, b7, (size_t)n7 * 4, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(c->dbt, bc, (size_t)ncls * 4, hipMemcpyHostToDevice));
@@ -418,6 +434,77 @@ int az_load_det_head(az_ctx *c, int C, int n6, int n7, int ncls, const float *W6
     HIPCHK(c, hipDeviceSynchronize());
     c->det_loaded = true;
     if (c->skip.loaded && c->skip.Cout != C) c->skip = az_ctx::SkipFront();     // (a skip front folds to the head's C)
+    return AZ_OK;
+}
+
+int az_load_det_head(az_ctx *c, int C, int n6, int n7, int ncls, const float *W6, const float *b6,
+                     const float *W7, const float *b7, const float *Wc, const float *bc, const float *Wb,
+                     const float *bb)
+{
+    if (!c) return AZ_ERR_INVALID;
+    if (!W6 || !b6 || !W7 || !b7 || !Wc || !bc || !Wb || !bb) return fail(c, AZ_ERR_INVALID, "az_load_det_head: null pointer");
+    if (C <= 0 || (C & 3) || n6 <= 0 || (n6 & 3) || n7 <= 0 || (n7 & 3) || ncls < 2 || ncls > 256)
+        return fail(c, AZ_ERR_INVALID, "az_load_det_head: C, n6, n7 multiples of 4; 2 <= ncls <= 256");
+    if (c->head_loaded && C != c->d.C) return fail(c, AZ_ERR_INVALID, "az_load_det_head: C differs from the AZ head's");
+    return load_det_head(c, C, n6, n7, ncls, 0, 0, nullptr, W6, b6, nullptr, W7, b7, Wc, bc, Wb, bb);
+}
+
+// Truncated-SVD head (Fast R-CNN section 4.4): fc6 and / or fc7 as L [r, in] (no bias) then U [out, r] (+ bias, ReLU).
+int az_load_det_head_lowrank(az_ctx *c, int C, int n6, int n7, int ncls, int r6, int r7, const float *L6,
+                             const float *U6, const float *b6, const float *L7, const float *U7, const float *b7,
+                             const float *Wc, const float *bc, const float *Wb, const float *bb)
+{
+    if (!c) return AZ_ERR_INVALID;
+    if (!U6 || !b6 || !U7 || !b7 || !Wc || !bc || !Wb || !bb)
+        return fail(c, AZ_ERR_INVALID, "az_load_det_head_lowrank: null pointer");
+    if (C <= 0 || (C & 3) || n6 <= 0 || (n6 & 3) || n7 <= 0 || (n7 & 3) || ncls < 2 || ncls > 256)
+        return fail(c, AZ_ERR_INVALID, "az_load_det_head_lowrank: C, n6, n7 multiples of 4; 2 <= ncls <= 256");
+    if (c->head_loaded && C != c->d.C) return fail(c, AZ_ERR_INVALID, "az_load_det_head_lowrank: C differs from the AZ head's");
+    const long long K6 = (long long)C * 49;
+    auto rank_ok = [](int r, long long out, long long in) {
+        return r == 0 || (r >= 4 && !(r & 3) && r <= out && r <= in && r <= AZ_LOWRANK_MAX);
+    };
+    if (!rank_ok(r6, n6, K6) || !rank_ok(r7, n7, n6))
+        return fail(c, AZ_ERR_INVALID, "az_load_det_head_lowrank: a rank is 0 (full) or a multiple of 4 in [4, min(out, in, AZ_LOWRANK_MAX)]");
+    if ((r6 != 0) != (L6 != nullptr) || (r7 != 0) != (L7 != nullptr))
+        return fail(c, AZ_ERR_INVALID, "az_load_det_head_lowrank: L is NULL exactly for a layer of rank 0");
+    if (c->gemm_parts && (r6 || r7))
+        return fail(c, AZ_ERR_STATE, "az_load_det_head_lowrank: fp32 only (the 16-bit-term GEMM modes do not run a low-rank head)");
+    return load_det_head(c, C, n6, n7, ncls, r6, r7, L6, U6, b6, L7, U7, b7, Wc, bc, Wb, bb);
+}
+
+int az_lowrank_split(int K, int r) { return (K > 0 && r > 0) ? azk_lowrank_split(K, r) : AZ_ERR_INVALID; }
+
+// The U-stage kernel alone (tests): Y [M, N] = act(X [M, K] . W [N, K]^T + b), host arrays.
+int az_lowrank_gemm_unit(az_ctx *c, const float *X, const float *W, const float *b, int M, int N, int K, int relu,
+                         float *Y)
+{
+    if (!c) return AZ_ERR_INVALID;
+    if (M < 0 || N <= 0 || (N & 3) || K <= 0 || (K & 3) || K > AZ_LOWRANK_MAX)
+        return fail(c, AZ_ERR_INVALID, "az_lowrank_gemm_unit: M >= 0; N, K positive multiples of 4; K <= AZ_LOWRANK_MAX");
+    if (M > c->maxR) return fail(c, AZ_ERR_CAPACITY, "az_lowrank_gemm_unit: more rows than the region capacity");
+    if (M == 0) return AZ_OK;
+    if (!X || !W || !b || !Y) return fail(c, AZ_ERR_INVALID, "az_lowrank_gemm_unit: null pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    constexpr int GUARD = 64;                     // rows behind row M that the launch must leave as they are
+    const size_t ny = (size_t)(M + GUARD) * N;
+    Buf bx, bw, bb, by, bm;
+    HIPCHK(c, bx.reserve((size_t)M * K * 4)); HIPCHK(c, bw.reserve((size_t)N * K * 4)); HIPCHK(c, bb.reserve((size_t)N * 4));
+    HIPCHK(c, by.reserve(ny * 4)); HIPCHK(c, bm.reserve(sizeof(int)));
+    HIPCHK(c, hipMemcpy(bx.p, X, (size_t)M * K * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(bw.p, W, (size_t)N * K * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(bb.p, b, (size_t)N * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(bm.p, &M, sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemset(by.p, 0xA5, ny * 4));
+    azk_lowrank_gemm(c->stream, bx.as<float>(), K, bw.as<float>(), bb.as<float>(), bm.as<int>(), M + GUARD, N, K,
+                     relu ? 1 : 0, by.as<float>(), N);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    std::vector<unsigned> guard((size_t)GUARD * N);
+    HIPCHK(c, hipMemcpy(guard.data(), by.as<float>() + (size_t)M * N, guard.size() * 4, hipMemcpyDeviceToHost));
+    for (unsigned g : guard)
+        if (g != 0xA5A5A5A5u) return fail(c, AZ_ERR_HIP, "az_lowrank_gemm_unit: the kernel wrote a row past M");
+    HIPCHK(c, hipMemcpy(Y, by.p, (size_t)M * N * 4, hipMemcpyDeviceToHost));
     return AZ_OK;
 }
 
@@ -448,19 +535,41 @@ static void launch_det_head(az_ctx *c, const int *Uptr, int im_h, int im_w, doub
       azk_roi_pool(c->stream, c->feat, d, c->spatial_scale, c->urois, Uptr, c->maxR, c->pool5, terms ? c->pool5p : nullptr,
                    terms ? azk_act_plane_elems(c->maxR, K6) : 0, terms ? c->gemm_parts : 0, 0, 0,
                    (terms && c->gemm_parts == 2) ? c->dgscale : nullptr, feats, feat_hw); }
-    { Timed t(c, "det_fc6_gemm", 0, 1);
-      if (terms)
-          azk_fc_gemm_terms(c->stream, c->pool5p, K6, azk_act_plane_elems(c->maxR, K6), c->dW6p, K6,
-                            azk_weight_plane_elems(c->det_n6, K6), Uptr, c->maxR, c->det_n6, K6, c->det_S6,
-                            azk_fc_chunk(K6, c->det_S6), c->dpart, c->gemm_parts, c->dgscale);
-      else
-          gemm(c->pool5, K6, c->dW6, c->det_n6, K6, c->det_S6, c->dpart); }
-    { Timed t(c, "det_fc6_reduce", 0);
-      azk_fc_reduce(c->stream, c->dpart, c->db6, Uptr, c->maxR, c->det_n6, c->det_S6, c->dh6, c->det_n6, 1); }
-    { Timed t(c, "det_fc7_gemm", 0, 1);
-      gemm(c->dh6, c->det_n6, c->dW7, c->det_n7, c->det_n6, c->det_S7, c->dpart); }
-    { Timed t(c, "det_fc7_reduce", 0);
-      azk_fc_reduce(c->stream, c->dpart, c->db7, Uptr, c->maxR, c->det_n7, c->det_S7, c->dh7, c->det_n7, 1); }
+    // a truncated-SVD layer: t = L x on the split-K GEMM (its own chunk count, linear slab sum), then the U stage
+    // (dlr_t [maxR][max(r6, r7)] serves both layers: all launches are on c->stream, so fc7_L's slab sum overwrites it only
+    //  after fc6_U has read it; dlr_zero is the zero bias that makes azk_fc_reduce a plain slab sum)
+    auto lowrank =[&](const float *x, int K, const float *L, int SL, int r, const float *U, const float *b, int N, float *y,
+                       const char *nL, const char *nR, const char *nU) {
+        { Timed t(c, nL, 0, 1);
+          azk_fc_gemm(c->stream, x, K, L, K, Uptr, c->maxR, r, K, SL, c->dpart); }
+        { Timed t(c, nR, 0);
+          azk_fc_reduce(c->stream, c->dpart, c->dlr_zero, Uptr, c->maxR, r, SL, c->dlr_t, r, 0); }
+        { Timed t(c, nU, 0, 1);
+          azk_lowrank_gemm(c->stream, c->dlr_t, r, U, b, Uptr, c->maxR, N, r, 1, y, N); }
+    };
+    if (c->det_r6)
+        lowrank(c->pool5, K6, c->dL6, c->det_SL6, c->det_r6, c->dU6, c->db6, c->det_n6, c->dh6, "det_fc6_L",
+                "det_fc6_L_reduce", "det_fc6_U");
+    else {
+        { Timed t(c, "det_fc6_gemm", 0, 1);
+          if (terms)
+              azk_fc_gemm_terms(c->stream, c->pool5p, K6, azk_act_plane_elems(c->maxR, K6), c->dW6p, K6,
+                                azk_weight_plane_elems(c->det_n6, K6), Uptr, c->maxR, c->det_n6, K6, c->det_S6,
+                                azk_fc_chunk(K6, c->det_S6), c->dpart, c->gemm_parts, c->dgscale);
+          else
+              gemm(c->pool5, K6, c->dW6, c->det_n6, K6, c->det_S6, c->dpart); }
+        { Timed t(c, "det_fc6_reduce", 0);
+          azk_fc_reduce(c->stream, c->dpart, c->db6, Uptr, c->maxR, c->det_n6, c->det_S6, c->dh6, c->det_n6, 1); }
+    }
+    if (c->det_r7)
+        lowrank(c->dh6, c->det_n6, c->dL7, c->det_SL7, c->det_r7, c->dU7, c->db7, c->det_n7, c->dh7, "det_fc7_L",
+                "det_fc7_L_reduce", "det_fc7_U");
+    else {
+        { Timed t(c, "det_fc7_gemm", 0, 1);
+          gemm(c->dh6, c->det_n6, c->dW7, c->det_n7, c->det_n6, c->det_S7, c->dpart); }
+        { Timed t(c, "det_fc7_reduce", 0);
+          azk_fc_reduce(c->stream, c->dpart, c->db7, Uptr, c->maxR, c->det_n7, c->det_S7, c->dh7, c->det_n7, 1); }
+    }
     { Timed t(c, "det_tail_gemm", 0, 1);
       azk_fc_gemm(c->stream, c->dh7, c->det_n7, c->dWt, c->det_n7, Uptr, c->maxR, NO, c->det_n7, AZK_TAIL_SPLIT,
                   c->dpart); }

@@ -149,12 +149,31 @@ def az_head_from_layers(layers):
 
 
 def det_head_from_layers(layers):
-    """Fast R-CNN head of models/*/VGG16/frcnn/test_fc.prototxt: fc6, fc7, cls_score, bbox_pred."""
-    W6, b6 = _fc(layers, "fc6")
-    W7, b7 = _fc(layers, "fc7")
+    """Fast R-CNN head of models/*/VGG16/frcnn/test_fc.prototxt: fc6, fc7, cls_score, bbox_pred.
+    A file compressed by truncated SVD (tools/compress_net.py; Fast R-CNN's compress_net) holds fc6_L (one blob [r, in], no
+    bias) + fc6_U ([out, r] and the bias) in fc6's place, and / or the fc7 pair: the dict then carries L6, U6, b6 (L7, U7,
+    b7) instead of W6, b6 (W7, b7), which AzContext.load_det_head runs as two stages.  Half a pair is a ValueError."""
+    head = {}
+    for i in (6, 7):
+        nl, nu = "fc%d_L" % i, "fc%d_U" % i
+        if (nl in layers) != (nu in layers):
+            raise ValueError("a compressed fc%d needs both %s and %s: the file has only %s" % (i, nl, nu, nl if nl in layers else nu))
+        if nl in layers:
+            if "fc%d" % i in layers:
+                raise ValueError("the file has fc%d and its compressed pair %s / %s" % (i, nl, nu))
+            if len(layers[nu]) < 2 or not layers[nl]:
+                raise ValueError("%s needs a weight blob, %s a weight and a bias blob" % (nl, nu))
+            U, b = _fc(layers, nu)
+            Lw = np.asarray(layers[nl][0], dtype=np.float32)
+            if Lw.size % U.shape[1]:
+                raise ValueError("%s %s does not chain into %s %s" % (nl, Lw.shape, nu, U.shape))
+            head["L%d" % i] = np.ascontiguousarray(Lw.reshape(U.shape[1], -1))
+            head["U%d" % i], head["b%d" % i] = U, b
+        else:
+            head["W%d" % i], head["b%d" % i] = _fc(layers, "fc%d" % i)
     Wc, bc = _fc(layers, "cls_score")
     Wb, bb = _fc(layers, "bbox_pred")
-    head = {"W6": W6, "b6": b6, "W7": W7, "b7": b7, "Wc": Wc, "bc": bc, "Wb": Wb, "bb": bb}
+    head.update({"Wc": Wc, "bc": bc, "Wb": Wb, "bb": bb})
     # the skip-connection detector (models/COCO/VGG16_skip): its front travels with the head it feeds, so that whatever
     # builds a HipDetNet / HipFrcnnNet from this dict gets the model the file holds
     front = skip_front_from_layers(layers)

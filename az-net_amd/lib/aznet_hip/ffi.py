@@ -63,7 +63,9 @@ SYMBOLS = [
     "az_det_solver_load_skip_history",
     "az_det_solver_mine", "az_det_solver_mine_skip",
     "az_soft_nms_batched", "az_box_vote_batched",
+    "az_load_det_head_lowrank", "az_lowrank_gemm_unit", "az_lowrank_split",
 ]
+AZ_LOWRANK_MAX = 2048      # include/aznet_hip.h
 
 
 class AzParams(ctypes.Structure):
@@ -190,6 +192,9 @@ def load_library(path=None):
     L.az_soft_nms_batched.argtypes = [vp, fp, ip, ci, ci, cd, cd, cd, i64p, fp, ip]
     L.az_box_vote_batched.argtypes = [vp, fp, ip, ci, i64p, ip, cd, fp]
     L.az_load_det_head.argtypes = [vp, ci, ci, ci, ci] + [fp] * 8
+    L.az_load_det_head_lowrank.argtypes = [vp, ci, ci, ci, ci, ci, ci] + [fp] * 10
+    L.az_lowrank_gemm_unit.argtypes = [vp, fp, fp, fp, ci, ci, ci, ci, fp]
+    L.az_lowrank_split.argtypes = [ci, ci]
     L.az_det_forward.argtypes = [vp, fp, ci, fp, fp]
     L.az_detect.argtypes = [vp, dp, ci, cd, cd, ci, ci, ci, cd, fp, dp]
     L.az_set_feature_pyramid_dev_nhwc.argtypes = [vp, ctypes.POINTER(ctypes.c_void_p), ci, ci, ci, ci]
@@ -331,6 +336,19 @@ def _scales(scales):
 
 def _p(a, ct):
     return a.ctypes.data_as(ctypes.POINTER(ct))
+
+
+def is_lowrank_head(head):
+    """A detection-head dict that carries truncated-SVD factors (L6 / U6 and / or L7 / U7)."""
+    return isinstance(head, dict) and any(k in head for k in ("L6", "U6", "L7", "U7"))
+
+
+def lowrank_split(K, r):
+    """az_lowrank_split: the number of K chunks of an L stage [., K] x [K, r] -- host arithmetic, no GPU needed."""
+    n = int(load_library().az_lowrank_split(int(K), int(r)))
+    if n < 1:
+        raise AzError(n, "az_lowrank_split(%d, %d)" % (K, r))
+    return n
 
 
 class AzContext(object):
@@ -961,7 +979,10 @@ class AzContext(object):
 
     def load_det_head(self, head):
         """head: dict of Caffe-layout fp32 arrays W6,b6 (fc6), W7,b7 (fc7), Wc,bc (cls_score),
-        Wb,bb (bbox_pred)."""
+        Wb,bb (bbox_pred).  A head that carries truncated-SVD factors (L6 / U6 and / or L7 / U7: aznet_hip.compress,
+        caffemodel.det_head_from_layers of a compressed file) goes through load_det_head_lowrank."""
+        if is_lowrank_head(head):
+            return self.load_det_head_lowrank(head)
         W6 = _f32(head["W6"])
         n6, K6 = W6.shape
         assert K6 % 49 == 0
@@ -974,6 +995,47 @@ class AzContext(object):
         self.det_dims = dict(C=C, n6=n6, n7=n7, ncls=ncls)
         if self.skip_dims is not None and self.skip_dims["Cout"] != C:
             self.skip_dims = None      # (az_load_det_head dropped the front: it folds to the head's C)
+
+    def load_det_head_lowrank(self, head):
+        """az_load_det_head_lowrank.  head: as load_det_head's, with fc6 given as L6 [r6, C*49], U6 [n6, r6], b6 instead of
+        W6, b6 and / or fc7 as L7 [r7, n6], U7 [n7, r7], b7 instead of W7, b7 (a layer given as W stays at full rank)."""
+        def layer(i):
+            if ("L%d" % i in head) != ("U%d" % i in head):
+                raise ValueError("a low-rank head needs both L%d and U%d" % (i, i))
+            if "L%d" % i in head:
+                Lf, U = _f32(head["L%d" % i]), _f32(head["U%d" % i])
+                if Lf.ndim != 2 or U.ndim != 2 or U.shape[1] != Lf.shape[0]:
+                    raise ValueError("L%d %s and U%d %s do not chain" % (i, Lf.shape, i, U.shape))
+                return Lf, U, Lf.shape[0], U.shape[0], Lf.shape[1]
+            W = _f32(head["W%d" % i])
+            return None, W, 0, W.shape[0], W.shape[1]
+        L6, U6, r6, n6, K6 = layer(6)
+        L7, U7, r7, n7, in7 = layer(7)
+        assert K6 % 49 == 0
+        C = K6 // 49
+        ncls = head["Wc"].shape[0]
+        assert in7 == n6 and head["Wc"].shape == (ncls, n7) and head["Wb"].shape == (4 * ncls, n7)
+        b6, b7, Wc, bc, Wb, bb = [_f32(head[k]) for k in ("b6", "b7", "Wc", "bc", "Wb", "bb")]
+        assert b6.size == n6 and b7.size == n7
+        pf = lambda a: _p(a, ctypes.c_float) if a is not None else None
+        self._chk(self.L.az_load_det_head_lowrank(self.h, C, n6, n7, ncls, r6, r7, pf(L6), pf(U6), pf(b6), pf(L7), pf(U7),
+                                                  pf(b7), pf(Wc), pf(bc), pf(Wb), pf(bb)))
+        self.det_dims = dict(C=C, n6=n6, n7=n7, ncls=ncls, r6=r6, r7=r7)
+        if self.skip_dims is not None and self.skip_dims["Cout"] != C:
+            self.skip_dims = None      # (the load dropped the front: it folds to the head's C)
+
+    def lowrank_gemm_unit(self, X, W, b, relu=True, M=None):
+        """az_lowrank_gemm_unit (tests): the U-stage kernel alone -> act(X[:M] . W^T + b), [M, N] float32."""
+        X, W, b = _f32(X), _f32(W), _f32(b).reshape(-1)
+        K = X.shape[1] if X.ndim == 2 else 0
+        M = X.shape[0] if M is None else int(M)
+        N = W.shape[0]
+        if X.ndim != 2 or W.ndim != 2 or W.shape[1] != K or b.size != N or M > X.shape[0]:
+            raise AzError(AZ_ERR_INVALID, "lowrank_gemm_unit: X [M, K], W [N, K], b [N]")
+        Y = np.zeros((max(M, 1), N), dtype=np.float32)
+        self._chk(self.L.az_lowrank_gemm_unit(self.h, _p(X, ctypes.c_float), _p(W, ctypes.c_float), _p(b, ctypes.c_float),
+                                              M, N, K, 1 if relu else 0, _p(Y, ctypes.c_float)))
+        return Y[:M]
 
     def det_forward(self, rois):
         rois = _f32(rois).reshape(-1, 5)

@@ -204,10 +204,13 @@ class HipDetNet(_NetDict):
         """skip_front: the skip-connection detector's front (synth.make_skip_front / caffemodel.skip_front_from_layers;
         default: det_head["skip_front"], which caffemodel.det_head_from_layers sets for a file with conv_pool5):
         the head then pools every roi from the maps the front names (cfg.SEAR.FRCNN_CONV) instead of conv5_3 alone, and
-        the shared AZ net's compute_conv returns those maps."""
+        the shared AZ net's compute_conv returns those maps.
+        det_head may carry truncated-SVD factors (L6, U6 and / or L7, U7 in place of W6 / W7: aznet_hip.compress, or
+        caffemodel.det_head_from_layers of a file written by tools/compress_net.py): it is loaded through
+        az_load_det_head_lowrank and every entry below runs the compressed layers (fp32 contexts only)."""
         self.ctx = az_net.ctx
         self.az_net = az_net
-        self.ctx.load_det_head(det_head)
+        self.ctx.load_det_head(det_head)           # (a dict with L / U factors: AzContext.load_det_head_lowrank)
         if skip_front is None:
             skip_front = det_head.get("skip_front") if isinstance(det_head, dict) else None   # (caffemodel.det_head_from_layers of a skip model)
         self.num_classes = self.ctx.det_dims["ncls"]
@@ -267,9 +270,10 @@ class HipFrcnnNet(_NetDict):
 
     def __init__(self, det_head, backbone, device=0, name="vgg16_frcnn_hip", max_regions=None, skip_front=None):
         """skip_front: the skip-connection detector's front (see HipDetNet); the backbone must then take `taps`
-        (VGG16Conv5.forward), compute_conv returns the dict of maps and detect goes through az_detect_skip."""
+        (VGG16Conv5.forward), compute_conv returns the dict of maps and detect goes through az_detect_skip.
+        det_head may carry truncated-SVD factors (see HipDetNet): it goes through az_load_det_head_lowrank."""
         self.ctx = ffi.AzContext(device, max_regions=max_regions, gemm_mode=0)
-        self.ctx.load_det_head(det_head)
+        self.ctx.load_det_head(det_head)           # (a dict with L / U factors: AzContext.load_det_head_lowrank)
         if skip_front is None:
             skip_front = det_head.get("skip_front") if isinstance(det_head, dict) else None   # (caffemodel.det_head_from_layers of a skip model)
         self.skip_front, self.skip_names = None, None

@@ -394,6 +394,36 @@ int az_box_vote_batched(az_ctx *ctx, const float *dets, const int32_t *offsets, 
 int az_load_det_head(az_ctx *ctx, int C, int n6, int n7, int ncls, const float *W6, const float *b6,
                      const float *W7, const float *b7, const float *Wc, const float *bc,
                      const float *Wb, const float *bb);
+/* The same head with fc6 and / or fc7 compressed by truncated SVD (Fast R-CNN, section 4.4; opt-in, not in the reference
+ * tree).  A layer y = relu(W x + b) of rank r is two products: t = L x with L = diag(s[:r]) Vt[:r] [r, in] (linear: no
+ * bias, no ReLU: the paper's fc6_L / fc7_L), then y = relu(U t + b) with U = U[:, :r] [out, r] (fc6_U / fc7_U), all fp32,
+ * Caffe [out, in] layout.  r6 / r7 == 0 leaves that layer at full rank: its L is NULL and its U holds the full weight
+ * ([n6, C*49] resp. [n7, n6]); otherwise the rank is a multiple of 4 with 4 <= r <= min(out, in, AZ_LOWRANK_MAX) and L
+ * is not NULL.  cls_score and bbox_pred are untouched.  Sizes and refusals otherwise as az_load_det_head: AZ_ERR_INVALID,
+ * with the head loaded before left in place.  In the 16-bit-term GEMM modes a head with a compressed layer is refused
+ * (AZ_ERR_STATE, the head loaded before left in place; it does not run at full rank), and az_set_gemm_mode(2 | 3)
+ * with one loaded is AZ_ERR_STATE.  A later az_load_det_head replaces a low-rank head, and the reverse.  Every entry that runs
+ * the detection head (az_det_forward, az_detect, az_detect_batch, az_detect_pyramid, az_detect_skip,
+ * az_det_forward_skip) then runs the compressed layers: the L stage on the split-K GEMM with az_lowrank_split(in, r)
+ * chunks and a linear slab sum, the U stage in one launch over the whole K = r with bias and ReLU applied in registers
+ * (az_lowrank.hip).  Neither stage's order of summation depends on the row count: a roi's bits do not depend on which
+ * rois share the launch.  The profiling names are det_fc6_L, det_fc6_L_reduce, det_fc6_U (likewise fc7).  The
+ * trainers keep full-rank weights of their own.  This is a different model from the full head: U L only approximates W. */
+#define AZ_LOWRANK_MAX 2048    /* largest rank = largest K of the U stage */
+int az_load_det_head_lowrank(az_ctx *ctx, int C, int n6, int n7, int ncls, int r6, int r7, const float *L6,
+                             const float *U6, const float *b6, const float *L7, const float *U7, const float *b7,
+                             const float *Wc, const float *bc, const float *Wb, const float *bb);
+/* The U-stage kernel alone (tests): Y [M, N] = act(X [M, K] . W [N, K]^T + b [N]), host arrays, act = ReLU if relu != 0.
+ * Each element's K terms are added by one fp32 fmaf chain in an order fixed by K, then the bias.  N and K are positive
+ * multiples of 4 and K <= AZ_LOWRANK_MAX, 0 <= M; anything else is AZ_ERR_INVALID, M above the region capacity
+ * AZ_ERR_CAPACITY, both before any device work.  M == 0 is a no-op (AZ_OK, Y untouched, pointers not read).  The launch
+ * reads M from device memory, as the head's launches do, and the device copy of Y carries 64 pre-filled rows behind row M: if
+ * the kernel changed one of them the call returns AZ_ERR_HIP. */
+int az_lowrank_gemm_unit(az_ctx *ctx, const float *X, const float *W, const float *b, int M, int N, int K, int relu,
+                         float *Y);
+/* The number of K chunks of an L stage [., K] x [K, r] (host arithmetic, ctx-free): a function of (K, r) alone -- the
+ * number of chunks is part of a row's bits.  K or r not positive: AZ_ERR_INVALID. */
+int az_lowrank_split(int K, int r);
 /* frcnn_net['fc'].forward(rois=..., conv5_3=...) (lib/detect/test.py:302-307): cls_prob [R,ncls],
  * bbox_pred [R,4*ncls], f32. */
 int az_det_forward(az_ctx *ctx, const float *rois, int R, float *cls_prob, float *bbox_pred);
