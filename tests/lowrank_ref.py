@@ -1,5 +1,6 @@
 """References and cases for the truncated-SVD detection head (test infrastructure, plain NumPy; the yardstick of
-tests/test_lowrank_host.py and tests/test_gpu_lowrank.py).
+tests/test_lowrank_host.py and tests/test_gpu_lowrank.py; the sizes other than DIMS, SIZES below: tests/test_lowrank_sizes_host.py
+and tests/test_gpu_lowrank_sizes.py).
 
   * compress_layer restated: U, s, Vt = svd(W) in float64, L = diag(s[:r]) Vt[:r], U = U[:, :r], cast to float32 once.
   * the two-stage head on pooled rows in float64 and in float32: a layer given as (L, U, b) is t = L x (no bias, no
@@ -22,6 +23,69 @@ UNIT_M = (1, 31, 32, 33, 63, 65, 257)    # + max_rois of the small context
 UNIT_N = (4, 36, 132, 260, 516)
 UNIT_K = (4, 36, 64, 100, 256, 260, 1024, 2048)
 UNIT_CAP = 320                           # max_regions of the small context
+UNIT_GUARD = 64                          # rows behind row M that az_lowrank_gemm_unit checks: its launch is sized for M + 64
+LR_TILE, LR_GRID = 64, 1024              # k_lowrank_gemm's tile edge and the launcher's cap on the grid
+
+# ---- off the one size (tests/test_lowrank_sizes_host.py, tests/test_gpu_lowrank_sizes.py) ------------------------------------
+# name: ((C, n6, n7), max_regions, ((ncls, r6, r7), ...)); what each reaches is in tests/test_gpu_lowrank_sizes.py
+SIZES = {
+    "WIDE": ((4, 2116, 8), 2304, ((21, 36, 0), (21, 4, 4))),
+    "DEEP": ((160, 260, 516), 512, ((21, 36, 0), (81, 132, 132), (21, 260, 256))),
+    "TINY": ((4, 8, 8), 64, ((2, 4, 4), (21, 8, 0), (21, 0, 8))),
+    "LONG": ((672, 132, 8), 64, ((21, 132, 0), (21, 128, 0))),
+    "DIMS": (DIMS, 512, ((21, 132, 0), (81, 260, 260), (21, 0, 256), (21, 256, 132))),
+}
+WIDE_ROWS = (1, 64, 65, 300, 1024, 1025, 1984, 2047, 2048)        # rois[:n] and rois[2048 - n:]
+TINY_ROWS = (1, 31, 64)                 # TINY and LONG
+SECOND_TURN = slice(1920, 2048)          # WIDE at 2048 rows: m-tiles 30 and 31 are the 64 workgroups' second items
+# the U-stage kernel alone on a context of 2304 regions: (M, N, K), then (M of the operands, the row counts M' <= M run on them)
+UNIT_BIG_CAP = 2304
+UNIT_BIG = ((2112, 2116, 4), (2112, 2116, 36), (2112, 2116, 100), (2240, 2052, 36))
+UNIT_BIG_MASKED = ((2112, 2116, 36), (2049, 1985))
+# random heads: (size, r6, r7)
+RANDOM_SIZES = (("DEEP", 132, 132), ("DIMS", 260, 260))
+RANDOM_WIDE = (36, 0)
+CHUNK = 160                              # the reference launches of the WIDE random head: 3 m-tiles x 34 n-tiles, one turn
+FEW = ((2000, 1), (2000, 161), (2000, 2000))
+BATCHES = ((1000, 1000), (300, 700, 1048))
+# the loads of part 5, in order: (r6, r7) or None for the full head
+LOAD_ORDER = ((260, 260), (4, 0), None, (0, 256))
+
+
+def tiles(M, N, capM):
+    """The launcher's arithmetic restated: (n-tiles, m-tiles of the M rows the device finds, workgroups launched)."""
+    nt, mt = -(-N // LR_TILE), -(-M // LR_TILE)
+    return nt, mt, max(1, min(-(-capM // LR_TILE) * nt, LR_GRID))
+
+
+def fc_chunk(K, S):
+    """azk_fc_chunk: ceil(K / S) rounded up to the GEMM's K step."""
+    return (-(-K // S) + 31) // 32 * 32
+
+
+def split_ref(K, r):
+    """azk_lowrank_split restated: 512 // (n-tiles of 128) chunks at most, counted with chunks of at least 128."""
+    S = max(512 // (-(-r // 128)), 1)
+    return -(-K // max(fc_chunk(K, S), 128))
+
+
+def size_rois(name):
+    """The roi set of a size: WIDE all of det_rows_ref.rois2048; DEEP and DIMS rois300 followed by the first 512 of
+    rois2048 (two launches on a context of 512 regions); TINY and LONG the first 64 of rois300."""
+    import det_rows_ref as DR
+    if name == "WIDE":
+        return DR.rois2048()
+    if name in ("TINY", "LONG"):
+        return H.rois300()[:64]
+    return np.concatenate([H.rois300(), DR.rois2048()[:512]], 0)
+
+
+def layer_shapes(name, r6, r7):
+    """((K, r) of each L stage, (N, K) of each U stage) of a head of that size."""
+    C, n6, n7 = SIZES[name][0]
+    Ls = [(K, r) for K, r in ((49 * C, r6), (n6, r7)) if r]
+    Us = [(N, r) for N, r in ((n6, r6), (n7, r7)) if r]
+    return Ls, Us
 
 
 def compress_layer(W, r):
@@ -82,16 +146,17 @@ def unit_case(M, N, K, seed=0):
 
 
 # ---- planted exact factorisations -----------------------------------------------------------------------------------------
-def planted_head(ncls, r6, r7, seed=0, pool=None):
-    """A reduced head (DIMS) whose compressed layers have small-integer factors: L rows with 64 (fc6) / 8 (fc7) entries
+def planted_head(ncls, r6, r7, seed=0, pool=None, dims=None, rois=None):
+    """A reduced head (DIMS, or `dims` = (C, n6, n7), on rois300 or on `rois`) whose compressed layers have small-integer factors: L rows with 64 (fc6) / 8 (fc7) entries
     +-1, U rows with min(r, 8) entries +-1, integer biases; a layer of rank 0 is a sparse integer W.  bbox_pred is sparse
     integer, cls_score sparse integer times 2^-k with max |logit| <= 4.  Returns the case: head (factors), full (the
     product head), fmap, rois, pool5, bbox (exact, float32), p64 (float64 softmax of the exact logits), abs_sum (the bound
     on every partial sum of either evaluation, asserted below 2^24)."""
-    C, n6, n7 = DIMS
-    rng = np.random.Generator(np.random.PCG64(5000 + 100 * r6 + r7 + 7 * ncls + seed))
-    fmap, rois = H.int_map(seed + C, C), H.rois300()
+    C, n6, n7 = dims or DIMS
+    rng = np.random.Generator(np.random.PCG64(5000 + 100 * r6 + r7 + 7 * ncls + seed + (0 if (dims or DIMS) == DIMS else 1000 * C + n6)))
+    fmap, rois = H.int_map(seed + C, C), H.rois300() if rois is None else rois
     p5 = (pool or (lambda f, r: __import__("train_step_ref").roi_pool(f, r)[0]))(fmap, rois).astype(np.float64)
+    p5 = p5.reshape(rois.shape[0], -1)
     head, asum = {}, 0.0
 
     def stage(x, W, b=None):
@@ -133,10 +198,11 @@ def planted_head(ncls, r6, r7, seed=0, pool=None):
 
 
 # ---- random heads -----------------------------------------------------------------------------------------------------------
-def random_case(r6, r7, ncls=21, seed=0):
-    """synth.make_det_head at DIMS compressed by the restated compress_layer, on a synth.make_feature_map map."""
+def random_case(r6, r7, ncls=21, seed=0, dims=None, rois=None):
+    """synth.make_det_head at DIMS (or `dims`) compressed by the restated compress_layer, on a synth.make_feature_map map
+    with rois300 (or `rois`)."""
     from aznet_hip import synth
-    C, n6, n7 = DIMS
+    C, n6, n7 = dims or DIMS
     full = synth.make_det_head(seed=600 + seed, C=C, n6=n6, n7=n7, ncls=ncls)
     head = {k: v for k, v in full.items() if k not in ("W6", "W7")}
     for i, r in ((6, r6), (7, r7)):
@@ -145,4 +211,13 @@ def random_case(r6, r7, ncls=21, seed=0):
         else:
             head["W%d" % i] = full["W%d" % i]
     return {"head": head, "uncompressed": full, "fmap": synth.make_feature_map(40 + seed + C, C, H.MAP_H, H.MAP_W),
-            "rois": H.rois300()}
+            "rois": H.rois300() if rois is None else rois}
+
+
+def sized_planted(name, ncls, r6, r7, pool=None):
+    """The planted head of a size of SIZES on that size's rois."""
+    return planted_head(ncls, r6, r7, pool=pool, dims=SIZES[name][0], rois=size_rois(name))
+
+
+def sized_random(name, r6, r7):
+    return random_case(r6, r7, dims=SIZES[name][0], rois=size_rois(name))
