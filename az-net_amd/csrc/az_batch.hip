@@ -138,17 +138,12 @@ void head_pass_batch(az_ctx *L, az_ctx::Batch &B, const AzHeadDims &d, const int
     //  scale, so the images of a batch share a pass there as well; mode 2's fp16 terms are scaled per map: not taken)
     azk_roi_pool(s, nullptr, d, L->spatial_scale, B.rois_cat, Mptr, L->maxR, L->pool5, L->pool5p,
                  azk_act_plane_elems(L->maxR, d.K6), L->gemm_parts, 0, 0, nullptr, B.feats, B.feat_hw);
-    const bool can12 = (d.n6 / 128) * L->S6 >= 256 && d.n6 % 128 == 0 && d.K6 % 32 == 0 &&
-                       azk_fc_chunk(d.K6, L->S6) * L->S6 == d.K6 && azk_fc_chunk(d.K6, L->S6) >= 64 &&
-                       L->gemm12_min_rows < 0x7fffffff;
     // (only the device knows the row count; both kernels are correct and bit-identical for any: the last batch's rows decide)
     if (L->gemm_parts)
         azk_fc_gemm_terms(s, L->pool5p, d.K6, azk_act_plane_elems(L->maxR, d.K6), L->W6p, d.K6, azk_weight_plane_elems(d.n6, d.K6), Mptr,
                           L->maxR, d.n6, d.K6, L->S6, azk_fc_chunk(d.K6, L->S6), L->part, L->gemm_parts, L->gscale);
-    else if (can12 && many_rows)
-        azk_fc_gemm12(s, L->pool5, d.K6, L->W6, d.K6, Mptr, L->maxR, d.n6, d.K6, L->S6, azk_fc_chunk(d.K6, L->S6), L->part, 0, nullptr);
     else
-        azk_fc_gemm(s, L->pool5, d.K6, L->W6, d.K6, Mptr, L->maxR, d.n6, d.K6, L->S6, L->part, 1 << 30, nullptr);
+        fc_gemm_fp32(L, s, L->pool5, d.K6, L->W6, Mptr, d.n6, d.K6, L->S6, L->part, many_rows);
     azk_fc_reduce(s, L->part, L->b6, Mptr, L->maxR, d.n6, L->S6, L->h6, d.n6, 1);
     float *p7 = L->part7 ? L->part7 : L->part;
     azk_fc_gemm(s, L->h6, d.n6, L->W7, d.n6, Mptr, L->maxR, d.n7, d.n6, L->S7, p7, 1 << 30, nullptr);

@@ -6,7 +6,7 @@
 //   k_det_row_loss   one wave per row: the row's softmax cross-entropy (k_solver_softmax_loss's arithmetic) plus the SmoothL1
 //                    of its own class's four deltas (k_solver_smooth_l1's with weight 1), the row's NMS record
 //                    [x1, y1, x2, y2, loss] and a flag when a loss, or the sum of a row's exponentials, is not finite
-//   NMS              nms_groups_dev (az_units.hip): the kernels of az_nms_batched / az_nms on the records where they lie
+//   NMS              nms_groups_dev (az_nms.hip): the kernels of az_nms_batched / az_nms on the records where they lie
 //   k_mine_select    per image: keep list -> global row indices, the first per_image of them -> sel
 // Nothing but the selection (and, on request, the row losses) comes back to the host.  No floating-point atomics: the same
 // call from the same state gives the same bits.  Parameter gradients, history and the accumulate flag are not touched.

@@ -337,6 +337,7 @@ void azk_tile_weights(hipStream_t s, const float *rowmajor, float *tiled, int N,
 // min_rows > 0: the kernel leaves at once when *Mptr is smaller (a launch whose row count only the device knows is
 // sent to both kernels, azk_fc_gemm with max_strips = (min_rows - 1) / 32).
 int azk_fc_gemm12_prepare();      // per device, with that device current; != 0: keep azk_fc_gemm for every launch
+bool azk_fc_gemm12_fits(int N, int K, int S);     // the layer shapes azk_fc_gemm12 takes (any other: it launches azk_fc_gemm)
 // ts (may be NULL): two words the launch folds its own span into (AzSpan)
 void azk_fc_gemm12(hipStream_t s, const float *x, int ldx, const float *W, int ldw, const int *Mptr, int capM, int N,
                    int K, int S, int Kc, float *part, int min_rows = 0, unsigned long long *ts = nullptr);

@@ -270,7 +270,7 @@ static __device__ __forceinline__ int next_pow2(int v)
 // (key << 14 | position): run heads in ascending key order are the unique rois, the head of a run is its first
 // occurrence.  Writes index / inv / the unique rois and their anchor boxes, returns U.  The caller guarantees
 // Pn <= 16384 and Pn <= batch (one dedup chunk: keys < 1000^5 < 2^50); `ssort` / `stmp` hold Pn words each.
-static __device__ int roi_dedup_sorted(const double *Bn, int Pn, double scale, float dedup, unsigned long long *ssort,
+[[maybe_unused]] static __device__ int roi_dedup_sorted(const double *Bn, int Pn, double scale, float dedup, unsigned long long *ssort,
                                        unsigned long long *stmp, unsigned *bins, unsigned *mm, int *wsum, float *rois,
                                        int *index, int *inv, float *urois, double *ubox, int *sidx = nullptr)
 {

@@ -50,12 +50,6 @@ __device__ __forceinline__ float4 ld128(__amdgpu_buffer_rsrc_t r, unsigned voff,
     return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
 }
 
-__device__ __forceinline__ float4 zero_if(float4 v, bool ok)
-{
-    v.x = ok ? v.x : 0.f; v.y = ok ? v.y : 0.f; v.z = ok ? v.z : 0.f; v.w = ok ? v.w : 0.f;
-    return v;
-}
-
 // One (m-tile, n-tile, K-chunk) work item.
 struct Item12 {
     int m0, nst, n0, k0, kend, t;       // t: which m-tile of the launch
@@ -120,7 +114,7 @@ __device__ __forceinline__ int tile12(const float *__restrict__ X, int ldx, cons
 #pragma unroll
         for (int i = 0; i < W_NLB; ++i) rb[i] = ld128(d.rsB, voB[i], sob);
     };
-    // (K and the chunk length are multiples of the K-step here -- the launcher checks --, so no tail masking.
+    // (K and the chunk length are multiples of the K-step here -- azk_fc_gemm12 checks --, so no tail masking.
     //  The second weight vector exists for waves 0-3 only; the others store theirs to a junk slot: a conditional
     //  store would let the compiler sink the LOAD into the branch, right in front of its use.)
     float *junk = sB + 2 * W_BN * W_LDT + (tid & 511) * 4;
@@ -421,9 +415,20 @@ int azk_fc_gemm12_prepare()
                                (int)lds12_bytes()) == hipSuccess ? 0 : -1;
 }
 
+// What the kernel assumes of a layer [N][K] in S chunks: whole n-tiles, enough (n-tile, chunk) groups to give each of the
+// 256 workgroups one, and -- it masks no tail -- K and an exact chunk length of azk_fc_chunk(K, S), at least two K-steps,
+// in whole K-steps.  (tests/det_rows_ref.py restates it as `can12`.)
+bool azk_fc_gemm12_fits(int N, int K, int S)
+{
+    const int Kc = azk_fc_chunk(K, S);
+    return (N / W_BN) * S >= 256 && N % W_BN == 0 && K % W_BK == 0 && Kc * S == K && Kc >= 2 * W_BK;
+}
+
 void azk_fc_gemm12(hipStream_t s, const float *x, int ldx, const float *W, int ldw, const int *Mptr, int capM, int N,
                    int K, int S, int Kc, float *part, int min_rows, unsigned long long *ts)
 {
+    // (a layer that does not fit, or another chunk length: k_fc_splitk, the same bits)
+    if (!azk_fc_gemm12_fits(N, K, S) || Kc != azk_fc_chunk(K, S)) return azk_fc_gemm(s, x, ldx, W, ldw, Mptr, capM, N, K, S, part, 1 << 30, ts);
     hipLaunchKernelGGL(k_fc_splitk12, dim3(256), dim3(W_NT), lds12_bytes(), s, x, ldx, W, ldw, Mptr, capM, N, K, S, Kc, part, min_rows,
                        ts);
 }

@@ -1,5 +1,5 @@
 // az_units.hip -- the C ABI's unit entry points (one stage of the path at a time: host in, host out, same kernels), the
-// Fast R-CNN head on the shared map, NMS, the zoom-threshold tuner, recall evaluation and the image front-end.
+// Fast R-CNN head on the shared map, the zoom-threshold tuner, recall evaluation and the image front-end.
 #include "az_ctx.h"
 
 extern "C" {
@@ -251,93 +251,6 @@ int az_topk_radix(az_ctx *c, const float *scores, int n, int k, int32_t *idx_out
     return topk_unit(c, scores, n, k, idx_out, n_out, true, "az_topk_radix");
 }
 
-int az_nms(az_ctx *c, const float *dets, int n, double thresh, int64_t *keep, int *n_keep)
-{
-    if (!c) return AZ_ERR_INVALID;
-    if (n < 0 || (n && (!dets || !keep)) || !n_keep) return fail(c, AZ_ERR_INVALID, "az_nms: bad arguments");
-    *n_keep = 0;
-    if (n == 0) return AZ_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    if (n <= azk_nms_small_max()) {
-        // the reference's own call-site size (apply_nms, test.py:467-484: <= 100 boxes per class): ONE launch, no copy
-        // commands -- the workgroup reads the boxes from and writes the keep list to host-mapped memory
-        HIPCHK(c, c->h_nms_own.reserve(8192));
-        c->h_nms = c->h_nms_own.as<unsigned char>();
-        float *hd = (float *)c->h_nms;                                  // [256][5] f32 = 5120 B
-        long long *hk = (long long *)(c->h_nms + 5120);                 // [256] i64 = 2048 B, then the count
-        int *hn = (int *)(c->h_nms + 5120 + 2048);
-        std::memcpy(hd, dets, (size_t)n * 5 * sizeof(float));
-        const unsigned tag = nms_next_tag(c);
-        *hn = 0;
-        if (!(c->profiling & 4)) clear_events(c);
-        { Timed t(c, "nms", n);
-          azk_nms_one_small(s, hd, n, thresh, hk, hn, tag); }
-        // Poll the result in the mapped block -- a stream synchronisation costs an interrupt round trip (~10-15 us) on top of
-        // a kernel of about that length.  Count and keep entries carry the call's tag (words may land out of order); the
-        // stream's own completion is picked up by whatever uses it next (same stream: ordered).  (Profiling, or no answer
-        // within a millisecond: the plain wait, after which everything is visible.)
-        const unsigned want = tag & 0x3FFFFFu;
-        bool got = false;
-        if (!c->profiling) {
-            const volatile int *vn = hn;
-            for (int spin = 0; spin < 200000 && !got; ++spin) got = ((unsigned)*vn >> 9) == want;
-            if (got) got = nms_keep_tagged(hk, (int)((unsigned)*vn & 0x1FFu), tag, 200000);
-        }
-        if (!got) HIPCHK(c, hipStreamSynchronize(s));
-        HIPCHK(c, hipGetLastError());
-        const unsigned word = (unsigned)*(const volatile int *)hn;
-        const int nk = (int)(word & 0x1FFu);
-        if ((word >> 9) != want || nk > n || !nms_keep_tagged(hk, nk, tag, 0))
-            return fail(c, AZ_ERR_HIP, "az_nms: the kernel left no result");
-        *n_keep = nk;
-        for (int i = 0; i < nk; ++i) keep[i] = (long long)(unsigned)(hk[i] & 0xFFFFFFFFll);
-        return AZ_OK;
-    }
-    { const int rc = nms_reserve(c, n, "az_nms"); if (rc != AZ_OK) return rc; }
-    int *nk = c->nms_order + c->nms_cap;      // spare int after the order array
-    HIPCHK(c, hipMemcpyAsync(c->nms_dets, dets, (size_t)n * 5 * 4, hipMemcpyHostToDevice, s));
-    if (!(c->profiling & 4)) clear_events(c);
-    if (!c->profiling) {
-        // keep list and count straight into host-mapped memory, the count last (k_nms_scan): no copy-back commands, no
-        // stream synchronisation -- the host polls the count
-        const size_t need = (size_t)n * 8 + 64;
-        if (need > c->h_nmsg_cap) {
-            HIPCHK(c, hipStreamSynchronize(s));
-            c->h_nmsg = nullptr; c->h_nmsg_cap = 0;
-            HIPCHK(c, c->h_nmsg_own.reserve(need, need * 2));
-            c->h_nmsg = c->h_nmsg_own.as<unsigned char>(); c->h_nmsg_cap = need * 2;
-        }
-        volatile long long *hn = (volatile long long *)c->h_nmsg;      // (tag << 32) | count
-        long long *hk = (long long *)(c->h_nmsg + 64);                 // (tag << 32) | index
-        const unsigned tag = nms_next_tag(c);
-        *hn = 0;
-        azk_nms(s, c->nms_dets, n, thresh, c->nms_order, c->nms_sdets, c->nms_mask, c->nms_mask + (size_t)c->nms_cap * ((c->nms_cap + 63) / 64), (unsigned long long *)c->nms_rank, hk, (int *)c->h_nmsg, tag);
-        bool got = false;
-        for (long spin = 0; spin < 4000000 && !got; ++spin) got = (unsigned)((unsigned long long)*hn >> 32) == tag;
-        if (got) got = nms_keep_tagged(hk, (int)(*hn & 0xFFFFFFFFll), tag, 200000);
-        if (!got) HIPCHK(c, hipStreamSynchronize(s));
-        HIPCHK(c, hipGetLastError());
-        const long long word = *hn;
-        const int h_nk2 = (int)(word & 0xFFFFFFFFll);
-        if ((unsigned)((unsigned long long)word >> 32) != tag || h_nk2 < 0 || h_nk2 > n || !nms_keep_tagged(hk, h_nk2, tag, 0))
-            return fail(c, AZ_ERR_HIP, "az_nms: the kernels left no result");
-        *n_keep = h_nk2;
-        for (int i = 0; i < h_nk2; ++i) keep[i] = (long long)(unsigned)(hk[i] & 0xFFFFFFFFll);
-        return AZ_OK;
-    }
-    { Timed t(c, "nms", n);
-      azk_nms(s, c->nms_dets, n, thresh, c->nms_order, c->nms_sdets, c->nms_mask, c->nms_mask + (size_t)c->nms_cap * ((c->nms_cap + 63) / 64), (unsigned long long *)c->nms_rank, c->nms_keep, nk); }
-    int h_nk = 0;
-    HIPCHK(c, hipMemcpyAsync(&h_nk, nk, 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    HIPCHK(c, hipGetLastError());
-    *n_keep = h_nk;
-    if (h_nk) HIPCHK(c, hipMemcpy(keep, c->nms_keep, (size_t)h_nk * 8, hipMemcpyDeviceToHost));
-    return AZ_OK;
-}
-
-
 // --------------------------------------------------------------------------------------
 // Fast R-CNN head on the shared conv map (lib/detect/test.py:259-318,432-445).
 static const size_t DET_SEG_HDR = (sizeof(AzDetSeg) + 255) / 256 * 256;
@@ -520,12 +433,7 @@ static void launch_det_head(az_ctx *c, const int *Uptr, int im_h, int im_w, doub
     const int K6 = d.C * 49, NO = 5 * c->det_ncls;
     d.K6 = K6;
     // many rows (the reference's 300 proposals per image): fc6 / fc7 on the many-row GEMM, as int6 (same bits either way)
-    auto gemm = [&](const float *x, int ldx, const float *W, int N, int K, int S, float *part) {
-        const bool can12 = (N / 128) * S >= 256 && N % 128 == 0 && K % 32 == 0 && azk_fc_chunk(K, S) * S == K &&
-                           azk_fc_chunk(K, S) >= 64 && c->gemm12_min_rows < 0x7fffffff && rows_bound >= c->gemm12_min_rows;
-        if (can12) azk_fc_gemm12(c->stream, x, ldx, W, K, Uptr, c->maxR, N, K, S, azk_fc_chunk(K, S), part);
-        else azk_fc_gemm(c->stream, x, ldx, W, K, Uptr, c->maxR, N, K, S, part);
-    };
+    const bool many_rows = rows_bound >= c->gemm12_min_rows;
     const bool terms = c->gemm_parts && c->dW6p;             // (16-bit-term modes: fc6, 86 % of this head's FLOPs, as int6)
     if (terms && c->gemm_parts == 2)
         azk_feat_scale(c->stream, c->feat, (long long)d.C * d.H * d.W, c->dgscale, c->det_w6_scale);
@@ -557,7 +465,7 @@ static void launch_det_head(az_ctx *c, const int *Uptr, int im_h, int im_w, doub
                                 azk_weight_plane_elems(c->det_n6, K6), Uptr, c->maxR, c->det_n6, K6, c->det_S6,
                                 azk_fc_chunk(K6, c->det_S6), c->dpart, c->gemm_parts, c->dgscale);
           else
-              gemm(c->pool5, K6, c->dW6, c->det_n6, K6, c->det_S6, c->dpart); }
+              fc_gemm_fp32(c, c->stream, c->pool5, K6, c->dW6, Uptr, c->det_n6, K6, c->det_S6, c->dpart, many_rows); }
         { Timed t(c, "det_fc6_reduce", 0);
           azk_fc_reduce(c->stream, c->dpart, c->db6, Uptr, c->maxR, c->det_n6, c->det_S6, c->dh6, c->det_n6, 1); }
     }
@@ -566,7 +474,7 @@ static void launch_det_head(az_ctx *c, const int *Uptr, int im_h, int im_w, doub
                 "det_fc7_L_reduce", "det_fc7_U");
     else {
         { Timed t(c, "det_fc7_gemm", 0, 1);
-          gemm(c->dh6, c->det_n6, c->dW7, c->det_n7, c->det_n6, c->det_S7, c->dpart); }
+          fc_gemm_fp32(c, c->stream, c->dh6, c->det_n6, c->dW7, Uptr, c->det_n7, c->det_n6, c->det_S7, c->dpart, many_rows); }
         { Timed t(c, "det_fc7_reduce", 0);
           azk_fc_reduce(c->stream, c->dpart, c->db7, Uptr, c->maxR, c->det_n7, c->det_S7, c->dh7, c->det_n7, 1); }
     }
@@ -763,116 +671,6 @@ int az_detect_batch(az_ctx *c, int n, const float *const *maps, int C, const int
         const int rc = fetch_dets(c, P, scores_out + (size_t)box_off[i0] * nc, boxes_out + (size_t)box_off[i0] * nc * 4);
         if (rc) return rc;
         i0 = i1;
-    }
-    return AZ_OK;
-}
-
-// --------------------------------------------------------------------------------------
-// apply_nms (lib/detect/test.py:467-484) calls nms once per class per image: n_groups independent
-// problems, here in one call.  Groups of up to 256 boxes (all of them, at that call site) share ONE
-// launch, a workgroup each; larger groups go through az_nms one by one.
-int az_nms_batched(az_ctx *c, const float *dets, const int32_t *offsets, int n_groups, double thresh,
-                   int64_t *keep, int32_t *n_keep)
-{
-    if (!c || n_groups < 0 || (n_groups && (!offsets || !n_keep)))
-        return fail(c, AZ_ERR_INVALID, "az_nms_batched: bad arguments");
-    if (n_groups == 0) return AZ_OK;
-    const int total = offsets[n_groups];
-    std::vector<int> small, large;
-    for (int g = 0; g < n_groups; ++g) {
-        const int n = offsets[g + 1] - offsets[g];
-        if (n < 0) return fail(c, AZ_ERR_INVALID, "az_nms_batched: offsets must ascend");
-        n_keep[g] = 0;
-        if (n == 0) continue;
-        (n <= azk_nms_small_max() ? small : large).push_back(g);
-    }
-    if (total > 0 && (!dets || !keep)) return fail(c, AZ_ERR_INVALID, "az_nms_batched: NULL array");
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    if (!small.empty() && !c->profiling && total <= 16384) {
-        // The reference's call site (apply_nms: 20 classes x <= 100 boxes per image): everything -- boxes, offsets, group
-        // list, keep lists, counts -- lives in ONE host-mapped block; one launch, no copy commands, and the host polls a
-        // flag that the last workgroup to finish raises (a stream synchronisation plus five copies cost 70 of 96 us).
-        const size_t o_off = ((size_t)total * 5 * sizeof(float) + 15) & ~(size_t)15;
-        const size_t o_sel = o_off + (((size_t)n_groups + 1) * sizeof(int) + 15 & ~(size_t)15);
-        const size_t o_keep = o_sel + ((small.size() * sizeof(int) + 15) & ~(size_t)15);
-        const size_t o_nk = o_keep + (size_t)total * sizeof(long long);
-        const size_t o_flag = o_nk + (((size_t)n_groups * sizeof(int) + 15) & ~(size_t)15);
-        const size_t need = o_flag + 64;
-        if (need > c->h_nmsb_cap) {
-            HIPCHK(c, hipStreamSynchronize(s));
-            c->h_nmsb = nullptr; c->h_nmsb_cap = 0;
-            HIPCHK(c, c->h_nmsb_own.reserve(need, need + need / 2));
-            c->h_nmsb = c->h_nmsb_own.as<unsigned char>(); c->h_nmsb_cap = need + need / 2;
-        }
-        if (!c->nms_done) {
-            HIPCHK(c, c->nms_done_own.reserve(16));
-            c->nms_done = c->nms_done_own.as<int>();
-            HIPCHK(c, hipMemsetAsync(c->nms_done, 0, 16, s));
-        }
-        unsigned char *b = c->h_nmsb;
-        std::memcpy(b, dets, (size_t)total * 5 * sizeof(float));
-        std::memcpy(b + o_off, offsets, ((size_t)n_groups + 1) * sizeof(int));
-        std::memcpy(b + o_sel, small.data(), small.size() * sizeof(int));
-        std::memset(b + o_nk, 0, (size_t)n_groups * sizeof(int));
-        volatile int *flag = (volatile int *)(b + o_flag);
-        const int seq = ++c->nms_seq;
-        const unsigned tag = nms_next_tag(c), want = tag & 0x3FFFFFu;
-        *flag = 0;
-        azk_nms_small(s, (const float *)b, (const int *)(b + o_off), (const int *)(b + o_sel), (int)small.size(), thresh,
-                      (long long *)(b + o_keep), (int *)(b + o_nk), c->nms_done, (int *)(b + o_flag), seq, tag);
-        // the flag says "all workgroups are done"; each count and keep word is still taken by its own tag (see nms_next_tag)
-        const long long *hk = (const long long *)(b + o_keep);
-        const volatile int *hn = (const volatile int *)(b + o_nk);
-        auto all_tagged = [&](long spins) {
-            for (int g : small) {
-                long k = 0;
-                while (((unsigned)hn[g] >> 9) != want) if (++k > spins) return false;
-                if (!nms_keep_tagged(hk + offsets[g], (int)((unsigned)hn[g] & 0x1FFu), tag, spins)) return false;
-            }
-            return true;
-        };
-        bool got = false;
-        for (int spin = 0; spin < 400000 && !got; ++spin) got = *flag == seq;
-        if (got) got = all_tagged(200000);
-        if (!got) HIPCHK(c, hipStreamSynchronize(s));
-        HIPCHK(c, hipGetLastError());
-        if (!all_tagged(0)) return fail(c, AZ_ERR_HIP, "az_nms_batched: the kernel left no result");
-        for (int g : small) {
-            const int nk = (int)((unsigned)hn[g] & 0x1FFu);
-            if (nk > offsets[g + 1] - offsets[g]) return fail(c, AZ_ERR_HIP, "az_nms_batched: bad count");
-            n_keep[g] = nk;
-            for (int k = 0; k < nk; ++k) keep[offsets[g] + k] = (long long)(unsigned)(hk[(size_t)offsets[g] + k] & 0xFFFFFFFFll);
-        }
-    } else
-    if (!small.empty()) {
-        int rc;
-        if ((rc = scratch_grow(c, 0, (size_t)total * 5 * sizeof(float))) != AZ_OK) return rc;
-        if ((rc = scratch_grow(c, 1, ((size_t)n_groups + 1) * sizeof(int))) != AZ_OK) return rc;
-        if ((rc = scratch_grow(c, 2, small.size() * sizeof(int))) != AZ_OK) return rc;
-        if ((rc = scratch_grow(c, 3, (size_t)total * sizeof(long long))) != AZ_OK) return rc;
-        if ((rc = scratch_grow(c, 4, (size_t)n_groups * sizeof(int))) != AZ_OK) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->scratch[0].p, dets, (size_t)total * 5 * sizeof(float), hipMemcpyHostToDevice, s));
-        HIPCHK(c, hipMemcpyAsync(c->scratch[1].p, offsets, ((size_t)n_groups + 1) * sizeof(int), hipMemcpyHostToDevice, s));
-        HIPCHK(c, hipMemcpyAsync(c->scratch[2].p, small.data(), small.size() * sizeof(int), hipMemcpyHostToDevice, s));
-        HIPCHK(c, hipMemsetAsync(c->scratch[4].p, 0, (size_t)n_groups * sizeof(int), s));
-        if (!(c->profiling & 4)) clear_events(c);
-        { Timed t(c, "nms_batched", (int)small.size());
-          azk_nms_small(s, (const float *)c->scratch[0].p, (const int *)c->scratch[1].p, (const int *)c->scratch[2].p, (int)small.size(), thresh,
-                        (long long *)c->scratch[3].p, (int *)c->scratch[4].p); }
-        std::vector<long long> hk((size_t)total);
-        HIPCHK(c, hipMemcpyAsync(hk.data(), c->scratch[3].p, (size_t)total * sizeof(long long), hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipMemcpyAsync(n_keep, c->scratch[4].p, (size_t)n_groups * sizeof(int), hipMemcpyDeviceToHost, s));
-        HIPCHK(c, hipStreamSynchronize(s));           // `small`, `hk` live on this frame
-        HIPCHK(c, hipGetLastError());
-        for (int g : small)
-            for (int k = 0; k < n_keep[g]; ++k) keep[offsets[g] + k] = hk[(size_t)offsets[g] + k];
-    }
-    for (int g : large) {
-        int nk = 0;
-        int rc = az_nms(c, dets + 5 * (size_t)offsets[g], offsets[g + 1] - offsets[g], thresh, keep + offsets[g], &nk);
-        if (rc) return rc;
-        n_keep[g] = nk;
     }
     return AZ_OK;
 }
@@ -1190,61 +988,3 @@ int az_image_blob_dev_on(az_ctx *c, const uint8_t *im, int h, int w, const float
 
 
 }  // extern "C"
-
-// ---- the NMS scratch and NMS on records that are on the device already (az_det_mine.hip) --------------------------------------
-// az_nms's growth of the context's scratch (dets, sdets, order, mask + band, rank, keep) to at least n boxes
-int nms_reserve(az_ctx *c, int n, const char *who)
-{
-    if (n <= c->nms_cap) return AZ_OK;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    Buf *b = c->nms_own;
-    for (int i = 0; i < 6; ++i) b[i].reset();
-    c->nms_cap = 0;
-    int cap = 1024;
-    while (cap < n) cap *= 2;
-    const size_t W = (size_t)(cap + 63) / 64;
-    if (azk_nms_scan_lds_bytes(cap) > 150000) return fail(c, AZ_ERR_CAPACITY, std::string(who) + ": n too large");
-    HIPCHK(c, reserve_group({{&b[0], (size_t)cap * 5 * 4}, {&b[1], (size_t)cap * 5 * 4}, {&b[2], (size_t)cap * 4 + 16},
-                             {&b[3], ((size_t)cap * W + azk_nms_band_words(cap)) * 8},      // mask, then band
-                             {&b[4], (size_t)cap * 4}, {&b[5], (size_t)cap * 8 + 16}}));
-    c->nms_dets = b[0].as<float>(); c->nms_sdets = b[1].as<float>(); c->nms_order = b[2].as<int>();
-    c->nms_mask = b[3].as<unsigned long long>(); c->nms_rank = b[4].as<int>(); c->nms_keep = b[5].as<long long>();
-    HIPCHK(c, hipMemset(c->nms_rank, 0, (size_t)cap * 4));
-    c->nms_cap = cap;
-    return AZ_OK;
-}
-
-// az_nms_batched's work on device-resident records: group g = dets_dev[off[g] .. off[g + 1]) (off: host; goff_dev: the same
-// n_groups + 1 offsets on the device).  Groups of up to azk_nms_small_max() boxes share one k_nms_small launch (gsel_dev
-// receives their list, `small`, which the caller keeps alive until it has waited for the stream), every larger one runs
-// azk_nms on the context's scratch straight from dets_dev.  keep_dev[off[g] ..] receives group g's keep list (index inside the
-// group, descending score), nkeep_dev[g] its length; nothing is copied back and nothing is waited for.
-int nms_groups_dev(az_ctx *c, const float *dets_dev, const int32_t *off, const int *goff_dev, int *gsel_dev, std::vector<int> &small,
-                   int n_groups, double thresh, long long *keep_dev, int *nkeep_dev, const char *who)
-{
-    hipStream_t s = c->stream;
-    std::vector<int> large;
-    small.clear();
-    int biggest = 0;
-    for (int g = 0; g < n_groups; ++g) {
-        const int n = off[g + 1] - off[g];
-        if (n <= 0) continue;
-        (n <= azk_nms_small_max() ? small : large).push_back(g);
-        biggest = std::max(biggest, n);
-    }
-    if (!large.empty()) { const int rc = nms_reserve(c, biggest, who); if (rc != AZ_OK) return rc; }
-    HIPCHK(c, hipMemsetAsync(nkeep_dev, 0, (size_t)n_groups * sizeof(int), s));
-    if (!small.empty()) {
-        HIPCHK(c, hipMemcpyAsync(gsel_dev, small.data(), small.size() * sizeof(int), hipMemcpyHostToDevice, s));
-        Timed t(c, "nms_batched", (int)small.size());
-        azk_nms_small(s, dets_dev, goff_dev, gsel_dev, (int)small.size(), thresh, keep_dev, nkeep_dev);
-    }
-    for (int g : large) {
-        const int n = off[g + 1] - off[g];
-        Timed t(c, "nms", n);
-        azk_nms(s, dets_dev + 5 * (size_t)off[g], n, thresh, c->nms_order, c->nms_sdets, c->nms_mask,
-                c->nms_mask + (size_t)c->nms_cap * ((c->nms_cap + 63) / 64), (unsigned long long *)c->nms_rank, keep_dev + off[g],
-                nkeep_dev + g);
-    }
-    return AZ_OK;
-}

@@ -1,6 +1,6 @@
 """CPU: the premises of tests/test_gpu_det_rows.py, on the reference alone -- no GPU (cases: tests/det_rows_ref.py).
 
-  * both layers of both shapes satisfy launch_det_head's `can12`, and no size of head_sizes_ref.DET_SIZES does -- which is
+  * both layers of both shapes satisfy `can12` (azk_fc_gemm12_fits), and no size of head_sizes_ref.DET_SIZES does -- which is
     why the detection head's many-row path needs a file of its own;
   * the 2048 rois are distinct under the oracle's 1/16 dedup, lie inside the image, and are the float32 projection of the
     boxes that az_detect is given;
