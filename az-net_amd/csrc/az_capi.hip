@@ -38,19 +38,21 @@ static void destroy_twin(az_ctx *c);
 static void destroy_batch(az_ctx *c);
 
 // One head buffer set for the dims / limits / GEMM mode of `t`, allocated in o->allocs (o's error is set on failure):
-// pool5, the split-K slabs (`part`: both layers' slabs, at least part_min elements), h6, h7, int7's slabs and, in the
-// 16-bit-term modes, the operand planes and the scale block, cleared on stream s and waited for.
+// pool5, the split-K slabs (`part`: both layers' slabs, at least part_min elements), h6, h7, int7's slabs, the L stage's
+// rows t6 of a truncated-SVD int6 and, in the 16-bit-term modes, the operand planes and the scale block, cleared on stream s and waited for.
 static int alloc_head_set(az_ctx *o, const az_ctx *t, size_t part_min, hipStream_t s, const char *clear_msg, az_ctx::HeadSet *h)
 {
     const size_t R = (size_t)t->maxR;
     const AzHeadDims &d = t->d;
-    const size_t p6 = (size_t)t->S6 * R * d.n6, p7 = (size_t)t->S7 * R * d.n7, planes = (size_t)t->gemm_parts * azk_act_plane_elems((int)R, d.K6);
+    // (int6's slabs: the full layer's, or the L stage's of a truncated-SVD int6)
+    const size_t p6 = t->r6 ? (size_t)t->SL6 * R * t->r6 : (size_t)t->S6 * R * d.n6, p7 = (size_t)t->S7 * R * d.n7, planes = (size_t)t->gemm_parts * azk_act_plane_elems((int)R, d.K6);
     auto A = [&](auto **p, size_t n) { return dalloc(o, o->allocs, p, n); };
     int rc = A(&h->pool5, R * d.K6);
     if (!rc) rc = A(&h->part, std::max(std::max(p6, p7), part_min));
     if (!rc) rc = A(&h->h6, R * d.n6);
     if (!rc) rc = A(&h->h7, R * d.n7);
     if (!rc) rc = A(&h->part7, p7);
+    if (!rc && t->r6) rc = A(&h->t6, R * t->r6);
     if (!rc && t->gemm_parts) rc = A(&h->pool5p, planes);
     if (!rc && t->gemm_parts) rc = A(&h->gscale, 4);
     if (rc) return rc;
@@ -65,6 +67,7 @@ static int alloc_head_set(az_ctx *o, const az_ctx *t, size_t part_min, hipStream
 static void use_head_set(az_ctx *t, const az_ctx::HeadSet &h)
 {
     t->pool5 = h.pool5; t->part = h.part; t->h6 = h.h6; t->h7 = h.h7; t->part7 = h.part7; t->pool5p = h.pool5p; t->gscale = h.gscale;
+    t->t6 = h.t6;
 }
 
 int az_destroy(az_ctx *c)
@@ -108,17 +111,23 @@ int az_set_gemm_mode(az_ctx *c, int parts)
     return AZ_OK;
 }
 
-int az_load_head(az_ctx *c, int C, int n6, int n71, int n72, const float *W6, const float *b6,
-                 const float *W71, const float *b71, const float *W72, const float *b72, const float *Was,
-                 const float *bas, const float *Wab, const float *bab, const float *Wz, const float *bz)
+}  // extern "C"
+
+// az_load_head / az_load_head_lowrank (`who`) past the checks that are one entry's alone.  r6 == 0: int6 at full rank, W6 its
+// [n6, C*49] weight, L6 unused; otherwise W6 is int6's U factor [n6, r6] and L6 its L factor [r6, C*49].  Whatever is refused
+// is refused before the loaded head is touched.
+static int load_head(az_ctx *c, const char *who, int C, int n6, int n71, int n72, int r6, const float *L6, const float *W6,
+                     const float *b6, const float *W71, const float *b71, const float *W72, const float *b72, const float *Was,
+                     const float *bas, const float *Wab, const float *bab, const float *Wz, const float *bz)
 {
     if (!c) return AZ_ERR_INVALID;
-    if (!W6 || !b6 || !W71 || !b71 || !W72 || !b72 || !Was || !bas || !Wab || !bab || !Wz || !bz)
-        return fail(c, AZ_ERR_INVALID, "az_load_head: null weight pointer");
+    const std::string me(who);
+    if (!W6 || !b6 || !W71 || !b71 || !W72 || !b72 || !Was || !bas || !Wab || !bab || !Wz || !bz || ((r6 != 0) != (L6 != nullptr)))
+        return fail(c, AZ_ERR_INVALID, me + ": null weight pointer");
     if (C <= 0 || (C & 3) || n6 <= 0 || (n6 & 3) || n71 <= 0 || (n71 & 3) || n72 <= 0 || (n72 & 3))
-        return fail(c, AZ_ERR_INVALID, "az_load_head: C, n6, n71, n72 must be positive multiples of 4");
+        return fail(c, AZ_ERR_INVALID, me + ": C, n6, n71, n72 must be positive multiples of 4");
     if (azk_tail_lds_bytes(n71 + n72) > 64 * 1024)
-        return fail(c, AZ_ERR_INVALID, "az_load_head: n71 + n72 too large for the tail kernel's LDS tile");
+        return fail(c, AZ_ERR_INVALID, me + ": n71 + n72 too large for the tail kernel's LDS tile");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->stream2) HIPCHK(c, hipStreamSynchronize(c->stream2));
@@ -132,6 +141,10 @@ int az_load_head(az_ctx *c, int C, int n6, int n71, int n72, const float *W6, co
     c->allocs.release();
     c->spare.ready = false; c->spare.ev_live = false;      // (its buffers were in `allocs`, released above; the slots are gone)
     c->head_loaded = false;
+    c->W6 = c->L6 = c->U6 = c->lr_zero = c->t6 = nullptr;
+    // (captured launch sequences hold the old head's launches and buffers)
+    for (auto &g : c->graphs) hipGraphExecDestroy(g.second.exec);
+    c->graphs.clear();
     {
         int rg = ensure_geom(c);
         if (rg) return rg;
@@ -141,14 +154,21 @@ int az_load_head(az_ctx *c, int C, int n6, int n71, int n72, const float *W6, co
     d.H = d.W = 0;
     c->S6 = azk_fc_split(d.K6);
     c->S7 = azk_fc_split(d.n6);
+    if (c->r6 != r6 && !c->cal.pinned) c->cal = az_ctx::PassCal();      // (measured head-pass costs are measured again on the other int6; a table the caller set stays)
+    c->r6 = r6; c->SL6 =r6 ? azk_az_lowrank_split(d.K6, r6) : 0;
+    const int rows6 = r6 ? r6 : n6;           // rows of the [., C*49] matrix that is permuted and tiled
     int rc;
     DevList &list = c->allocs;
-    AZ_A(W6, azk_tiled_elems(n6, d.K6)); AZ_A(b6, n6); AZ_A(W7, azk_tiled_elems(d.n7, n6)); AZ_A(b7, d.n7);
+    if (r6) {
+        AZ_A(L6, azk_tiled_elems(r6, d.K6)); AZ_A(U6, (size_t)n6 * r6); AZ_A(lr_zero, r6);
+        HIPCHK(c, hipMemsetAsync(c->lr_zero, 0, (size_t)r6 * sizeof(float), c->stream));
+    } else AZ_A(W6, azk_tiled_elems(n6, d.K6));
+    AZ_A(b6, n6); AZ_A(W7, azk_tiled_elems(d.n7, n6)); AZ_A(b7, d.n7);
     AZ_A(Wt, 64 * azk_tail_weight_rows(d.n7)); AZ_A(bt, 64);
     if (c->gemm_parts) AZ_A(W6p, (size_t)c->gemm_parts * azk_weight_plane_elems(n6, d.K6));
     {   // (`part` also stages W6 for the column permutation, and az_roi_pool's rows in Caffe's order: more than the slabs when S6 n6 < K6)
         az_ctx::HeadSet hs;
-        if ((rc = alloc_head_set(c, c, std::max((size_t)n6 * d.K6, (size_t)c->maxR * d.K6), c->stream, "az_load_head: clearing the operand planes", &hs)) != AZ_OK) return rc;
+        if ((rc = alloc_head_set(c, c, std::max((size_t)rows6 * d.K6, (size_t)c->maxR * d.K6), c->stream, "az_load_head: clearing the operand planes", &hs)) != AZ_OK) return rc;
         use_head_set(c, hs);
     }
     // Weights: Caffe [out, in] row-major is already the K-contiguous "B^T" layout the GEMM reads.
@@ -157,10 +177,10 @@ int az_load_head(az_ctx *c, int C, int n6, int n71, int n72, const float *W6, co
     // The GEMM streams weights tile-major (azk_tile_weights): permute / stack in a row-major temporary, then tile.
     // (`tmp` serves both layers: the larger of the two row-major blocks)
     Buf tg;
-    HIPCHK(c, tg.reserve(std::max((size_t)n6 * d.K6, (size_t)d.n7 * n6) * 4));
+    HIPCHK(c, tg.reserve(std::max((size_t)rows6 * d.K6, (size_t)d.n7 * n6) * 4));
     float *tmp = tg.as<float>();
-    HIPCHK(c, hipMemcpy(c->part, W6, (size_t)n6 * d.K6 * 4, hipMemcpyHostToDevice));
-    azk_permute_k(c->stream, c->part, tmp, n6, C, 1);
+    HIPCHK(c, hipMemcpy(c->part, r6 ? L6 : W6, (size_t)rows6 * d.K6 * 4, hipMemcpyHostToDevice));
+    azk_permute_k(c->stream, c->part, tmp, rows6, C, 1);
     if (c->gemm_parts) {          // 16-bit terms of the (permuted, row-major) int6 weights
         c->w6_scale = 0.f;
         if (c->gemm_parts == 2) {
@@ -172,8 +192,10 @@ int az_load_head(az_ctx *c, int C, int n6, int n71, int n72, const float *W6, co
         }
         azk_split_weight_planes(c->stream, tmp, c->W6p, n6, d.K6, c->gemm_parts, c->w6_scale);
     }
-    azk_tile_weights(c->stream, tmp, c->W6, n6, d.K6);
+    azk_tile_weights(c->stream, tmp, r6 ? c->L6 : c->W6, rows6, d.K6);
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    // (the U factor stays row-major [n6, r6]: the U stage reads Caffe's layout as it is)
+    if (r6) HIPCHK(c, hipMemcpy(c->U6, W6, (size_t)n6 * r6 * 4, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(c->b6, b6, (size_t)n6 * 4, hipMemcpyHostToDevice));
     // int7_1 and int7_2 both read int6: one GEMM with the two weight blocks stacked along N.
     HIPCHK(c, hipMemcpy(tmp, W71, (size_t)n71 * n6 * 4, hipMemcpyHostToDevice));
@@ -207,6 +229,31 @@ int az_load_head(az_ctx *c, int C, int n6, int n71, int n72, const float *W6, co
     c->head_loaded = true;
     return AZ_OK;
 }
+
+extern "C" {
+
+int az_load_head(az_ctx *c, int C, int n6, int n71, int n72, const float *W6, const float *b6,
+                 const float *W71, const float *b71, const float *W72, const float *b72, const float *Was,
+                 const float *bas, const float *Wab, const float *bab, const float *Wz, const float *bz)
+{
+    return load_head(c, "az_load_head", C, n6, n71, n72, 0, nullptr, W6, b6, W71, b71, W72, b72, Was, bas, Wab, bab, Wz, bz);
+}
+
+// Truncated-SVD int6 (Fast R-CNN section 4.4): L6 [r6, C*49] (no bias) then U6 [n6, r6] (+ b6, ReLU); the rest as az_load_head.
+int az_load_head_lowrank(az_ctx *c, int C, int n6, int n71, int n72, int r6, const float *L6, const float *U6, const float *b6,
+                         const float *W71, const float *b71, const float *W72, const float *b72, const float *Was,
+                         const float *bas, const float *Wab, const float *bab, const float *Wz, const float *bz)
+{
+    if (!c) return AZ_ERR_INVALID;
+    if (!L6) return fail(c, AZ_ERR_INVALID, "az_load_head_lowrank: null weight pointer");
+    if (r6 < 4 || (r6 & 3) || r6 > AZ_LOWRANK_MAX || r6 > n6 || (C > 0 && r6 > (long long)C * 49))
+        return fail(c, AZ_ERR_INVALID, "az_load_head_lowrank: r6 is a multiple of 4 in [4, min(n6, C * 49, AZ_LOWRANK_MAX)]");
+    if (c->gemm_parts)
+        return fail(c, AZ_ERR_STATE, "az_load_head_lowrank: fp32 only (the 16-bit-term GEMM modes of az_set_gemm_mode do not run a low-rank int6)");
+    return load_head(c, "az_load_head_lowrank", C, n6, n71, n72, r6, L6, U6, b6, W71, b71, W72, b72, Was, bas, Wab, bab, Wz, bz);
+}
+
+int az_az_lowrank_split(int K, int r) { return (K > 0 && r > 0) ? azk_az_lowrank_split(K, r) : AZ_ERR_INVALID; }
 
 }  // extern "C"
 
@@ -353,6 +400,7 @@ static int make_lane(az_ctx *c, az_ctx **out, bool with_head, const char *what)
     t->d = c->d; t->d.H = t->d.W = 0;
     t->S6 = c->S6; t->S7 = c->S7; t->gemm_parts = c->gemm_parts; t->w6_scale = c->w6_scale; t->spatial_scale = c->spatial_scale;
     t->W6 = c->W6; t->b6 = c->b6; t->W7 = c->W7; t->b7 = c->b7; t->Wt = c->Wt; t->bt = c->bt; t->W6p = c->W6p;
+    t->r6 = c->r6; t->SL6 = c->SL6; t->L6 = c->L6; t->U6 = c->U6; t->lr_zero = c->lr_zero;
     t->head_bufs = false;
     if (with_head && (rc = ensure_lane_head(t)) != AZ_OK) return bail(rc, "head buffers");
     t->env = c->env; t->plan_cache_max = c->plan_cache_max; t->gemm12_min_rows = c->gemm12_min_rows; t->gemm12_dual_rows = c->gemm12_dual_rows;
@@ -663,6 +711,7 @@ int az_set_pass_costs(az_ctx *c, int n, const int32_t *rows, const double *us)
     for (int i = 0; i < n; ++i) { c->cal.rows[i] = rows[i]; c->cal.us[i] = us[i]; }
     c->cal.n = n;
     c->cal.state = n ? 1 : 0;
+    c->cal.pinned = n > 0;                    // (the caller's table: a head reload does not measure over it)
     if (c->twin) c->twin->cal = c->cal;
     return AZ_OK;
 }

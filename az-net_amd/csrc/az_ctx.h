@@ -73,6 +73,11 @@ struct az_ctx {
     float spatial_scale = 0.0625f;                 // test_fc.prototxt:22
     // weights (HBM)
     float *W6 = nullptr, *b6 = nullptr, *W7 = nullptr, *b7 = nullptr, *Wt = nullptr, *bt = nullptr;
+    // truncated-SVD int6 (az_load_head_lowrank; r6 == 0: int6 at full rank, W6): L6 [r6, K6] permuted and tiled like W6, U6
+    // [n6, r6] row-major (az_lowrank.hip), the L stage's chunk count (azk_az_lowrank_split) and its zero bias [r6]; t6
+    // [maxR][r6], the L stage's rows, belongs to the head buffer set: every lane has its own
+    int r6 = 0, SL6 = 0;
+    float *L6 = nullptr, *U6 = nullptr, *lr_zero = nullptr, *t6 = nullptr;
     // feature map
     const float *feat = nullptr;        // channel-last copy of the current map (what RoIPool reads)
     // [H][W][C] copies of NCHW maps, three of them used in turn (two until round 5): the map of a search that is still queued (and might have to
@@ -260,7 +265,7 @@ struct az_ctx {
     // lane -- but takes the OWNER's one spare set in turn: `ev` (recorded behind each such search) orders the next user's
     // stream behind the previous one.  The searches were chip-wide one after the other anyway.
     struct HeadSet {                          // (views; alloc_head_set, az_capi.hip)
-        float *pool5 = nullptr, *part = nullptr, *h6 = nullptr, *h7 = nullptr, *part7 = nullptr, *gscale = nullptr;
+        float *pool5 = nullptr, *part = nullptr, *h6 = nullptr, *h7 = nullptr, *part7 = nullptr, *gscale = nullptr, *t6 = nullptr;
         unsigned short *pool5p = nullptr;
     };
     struct SpareHead : HeadSet {
@@ -286,7 +291,7 @@ struct az_ctx {
     Event comm_ev[2];
     // cost of one head pass (RoIPool + int6 + reduce + int7 + heads) at a few row counts, measured on THIS device with HIP
     // events the first time a search is launched (calibrate_passes): what the choice between the search forms goes by
-    struct PassCal { int state = 0; int n = 0; int rows[6] = {0}; double us[6] = {0}; } cal;   // state 0: not yet, 1: measured, -1: off
+    struct PassCal { int state = 0; int n = 0; int rows[6] = {0}; double us[6] = {0}; bool pinned = false; } cal;   // state 0: not yet, 1: measured, -1: off; pinned: the caller's table (az_set_pass_costs)
     double *pred_w = nullptr; float *score_w = nullptr, *zoom_w = nullptr; unsigned char *keep_w = nullptr; unsigned *key_w = nullptr;   // second *_v set
     int last_pair_mask = 0;                   // levels whose head pass carried pair-speculation rows (search in flight / last)
     // pair speculation: all-children offsets / child -> row of the level whose pass carries the rows; looked-up outputs
@@ -511,6 +516,10 @@ void prep_scale(az_ctx *c);               // two-term (fp16) mode: the scale of 
 // one fp32 fc layer's split-K GEMM on the many-row kernel (a layer that fits it, `many_rows`, the kernel not disabled) or not
 void fc_gemm_fp32(const az_ctx *c, hipStream_t s, const float *x, int ldx, const float *W, const int *Mptr, int N, int K, int S,
                   float *part, bool many_rows, unsigned long long *ts = nullptr);
+// a truncated-SVD int6 (c->r6 != 0) on the rows pool5 [*Mptr][K6] -> h6, on stream s in the buffers of `c` (a lane):
+// fc6_L (the split-K GEMM, c->SL6 chunks) + fc6_L_reduce (linear slab sum into t6) + fc6_U (az_lowrank.hip: bias, ReLU).
+// timed: the three launches recorded as a search's are (launch_head); a batch's pass records none
+void int6_lowrank(az_ctx *c, hipStream_t s, const int *Mptr, bool many_rows, int level, bool timed);
 // one head pass; rows_hint: the row count where the host knows it, -1: many rows at this level in the last search
 void launch_head(az_ctx *c, const int *Uptr, int level, int im_h, int im_w, double eps, float *zoom, float *score,
                  float *delta, double min_side = 0.0, bool keep_flags = false, int coop_tail = 0,

@@ -99,6 +99,24 @@ void fc_gemm_fp32(const az_ctx *c, hipStream_t s, const float *x, int ldx, const
         azk_fc_gemm(s, x, ldx, W, K, Mptr, c->maxR, N, K, S, part, 1 << 30, ts);
 }
 
+// A truncated-SVD int6: t6 = pool5 . L6^T on the split-K GEMM (SL6 chunks, a fixed function of (K6, r6); lr_zero is the
+// zero bias that makes azk_fc_reduce a plain slab sum), then h6 = relu(t6 . U6^T + b6) in one launch (k_lowrank_gemm at
+// every row count: a 128 x 128-tile variant for many rows was measured slower).  The L stage's two
+// kernels give a row the same bits whatever `many_rows` says.
+void int6_lowrank(az_ctx *c, hipStream_t s, const int *Mptr, bool many_rows, int level, bool timed)
+{
+    const AzHeadDims &d = c->d;
+    const int prof_keep = c->profiling;
+    if (!timed) c->profiling &= ~(1 | 2);
+    { Timed t(c, "fc6_L", level, 1);
+      fc_gemm_fp32(c, s, c->pool5, d.K6, c->L6, Mptr, c->r6, d.K6, c->SL6, c->part, many_rows); }
+    { Timed t(c, "fc6_L_reduce", level);
+      azk_fc_reduce(s, c->part, c->lr_zero, Mptr, c->maxR, c->r6, c->SL6, c->t6, c->r6, 0); }
+    { Timed t(c, "fc6_U", level, 1);
+      azk_lowrank_gemm(s, c->t6, c->r6, c->U6, c->b6, Mptr, c->maxR, d.n6, c->r6, 1, c->h6, d.n6); }
+    c->profiling = prof_keep;
+}
+
 // One forward of the head on the `U` rois in ctx->urois (anchors in ctx->ubox); scores and
 // deltas go to the given arrays, decoded boxes to ctx->pred_u.
 void launch_head(az_ctx *c, const int *Uptr, int level, int im_h, int im_w, double eps, float *zoom, float *score,
@@ -135,20 +153,24 @@ void launch_head(az_ctx *c, const int *Uptr, int level, int im_h, int im_w, doub
         return c->span_ring + 2 * (size_t)sl;
     };
     const int prof_keep = c->profiling;
-    unsigned long long *ts6 = c->gemm_parts ? nullptr : span_slot("fc6_gemm");
-    if (ts6) c->profiling &= ~(1 | 2);                     // (no event pair around a launch that times itself)
-    { Timed t(c, "fc6_gemm", level, 1);
-      if (c->gemm_parts)
-          azk_fc_gemm_terms(c->stream, c->pool5p, d.K6, azk_act_plane_elems(c->maxR, d.K6), c->W6p, d.K6, azk_weight_plane_elems(d.n6, d.K6), Uptr,
-                           c->maxR, d.n6, d.K6, c->S6, azk_fc_chunk(d.K6, c->S6), c->part, c->gemm_parts, c->gscale);
-      else
-          // many rows: the caller knows the row count on the host (a one-pass plan) -- one weight tile per 12 strips --, or
-          // only the device knows it (rows_hint == -1) and the last search had many rows at this level
-          fc_gemm_fp32(c, c->stream, c->pool5, d.K6, c->W6, Uptr, d.n6, d.K6, c->S6, c->part,
-                       rows_hint >= c->gemm12_min_rows || rows_hint == -1, ts6); }
-    c->profiling = prof_keep;
-    { Timed t(c, "fc6_reduce", level);
-      azk_fc_reduce(c->stream, c->part, c->b6, Uptr, c->maxR, d.n6, c->S6, c->h6, d.n6, 1); }
+    const bool many6 = rows_hint >= c->gemm12_min_rows || rows_hint == -1;
+    // (a truncated-SVD int6 in the same place on the same stream; the self-timing span stays with the full layer)
+    if (c->r6) int6_lowrank(c, c->stream, Uptr, many6, level, true);
+    else {
+        unsigned long long *ts6 = c->gemm_parts ? nullptr : span_slot("fc6_gemm");
+        if (ts6) c->profiling &= ~(1 | 2);                     // (no event pair around a launch that times itself)
+        { Timed t(c, "fc6_gemm", level, 1);
+          if (c->gemm_parts)
+              azk_fc_gemm_terms(c->stream, c->pool5p, d.K6, azk_act_plane_elems(c->maxR, d.K6), c->W6p, d.K6, azk_weight_plane_elems(d.n6, d.K6), Uptr,
+                               c->maxR, d.n6, d.K6, c->S6, azk_fc_chunk(d.K6, c->S6), c->part, c->gemm_parts, c->gscale);
+          else
+              // many rows: the caller knows the row count on the host (a one-pass plan) -- one weight tile per 12 strips --, or
+              // only the device knows it (rows_hint == -1) and the last search had many rows at this level
+              fc_gemm_fp32(c, c->stream, c->pool5, d.K6, c->W6, Uptr, d.n6, d.K6, c->S6, c->part, many6, ts6); }
+        c->profiling = prof_keep;
+        { Timed t(c, "fc6_reduce", level);
+          azk_fc_reduce(c->stream, c->part, c->b6, Uptr, c->maxR, d.n6, c->S6, c->h6, d.n6, 1); }
+    }
     // int7 stays in stage 1 -- RoIPool, int6, slab sum, int7 back to back on `stream`: the chip-wide kernels of consecutive
     // images follow each other without an event hop (each ~13 us on the critical path: slab sum -> int7 on the second
     // stream, int7 -> the next image's RoIPool back on the first); stage 2 = the heads (+ geometry, or stage 3).  int7 writes

@@ -380,6 +380,8 @@ void azk_lowrank_gemm(hipStream_t s, const float *x, int ldx, const float *W, co
                       int capM, int N, int K, int relu, float *y, int ldy);
 // K chunks of the L stage (x[M, K] . L[r, K]^T on azk_fc_gemm): a function of (K, r) alone
 int azk_lowrank_split(int K, int r);
+// K chunks of the AZ head's L stage (fc_gemm_fp32): a function of (K, r) alone that keeps the many-row kernel eligible
+int azk_az_lowrank_split(int K, int r);
 // int7_1|int7_2's slab sum + bias + ReLU, then adj_score + adj_bbox + zoom_score (56 outputs) + bias +
 // sigmoid + box decode/clip, in one launch
 // (vector-ALU products, see az_head.hip).  WtT is the stacked weight block k-major, zero-padded:

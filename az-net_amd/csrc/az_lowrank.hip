@@ -147,3 +147,30 @@ int azk_lowrank_split(int K, int r)
     if (Kc < 128) Kc = 128;
     return (K + Kc - 1) / Kc;
 }
+
+// K chunks of the AZ head's L stage (pool5 [M, K6] x L6^T [K6, r6] through fc_gemm_fp32): a fixed function of (K, r) -- the
+// number of chunks is part of a row's bits, so the row count has no say.  Among the splits S that keep the many-row kernel
+// eligible (azk_fc_gemm12_fits: whole n-tiles, nt = r / 128, nt S >= 256, S chunks of exactly K / S in whole K steps) the
+// one with the least
+//     4 ceil(nt S / 256) (K / S)  +  nt S
+// (ties: the smaller S).  First term: k_fc_splitk12 deals its nt S (n-tile, chunk) groups statically to 256 workgroups, so
+// the launch lasts as long as the workgroup with the most groups, each K / S deep.  Second term: every chunk writes a slab
+// of M x r floats that the slab sum reads again; its weight against the first is the measured one (688 and 2672 rows at
+// K = 25088, r = 1024, DESIGN 4y: a slab costs what 2 K elements of a group cost).  There: 56 chunks of 448 (448 groups: 192
+// workgroups run two, 64 one), measured ahead of 49, 98, 112 and 196 at both row counts.  Where no split fits (r no
+// multiple of 128, K no multiple of 32, a shallow K) the launch stays on k_fc_splitk whatever the row count, with
+// azk_lowrank_split's chunks.
+int azk_az_lowrank_split(int K, int r)
+{
+    long long best = -1;
+    int bestS = 0;
+    if (r % 128 == 0) {
+        const int nt = r / 128;
+        for (int S = (256 + nt - 1) / nt; S <= K / 64; ++S) {
+            if (!azk_fc_gemm12_fits(r, K, S)) continue;
+            const long long cost = 4LL * (((long long)nt * S + 255) / 256) * (K / S) + (long long)nt * S;
+            if (best < 0 || cost < best) { best = cost; bestS = S; }
+        }
+    }
+    return bestS ? bestS : azk_lowrank_split(K, r);
+}

@@ -137,15 +137,35 @@ def _fc(layers, name):
 
 def az_head_from_layers(layers):
     """AZ head of models/*/VGG16/az-net/test_fc.prototxt: int6, int7_1, int7_2, adj_score,
-    adj_bbox, zoom_score -> the dict az_load_head / synth.make_head use."""
-    W6, b6 = _fc(layers, "int6")
+    adj_bbox, zoom_score -> the dict az_load_head / synth.make_head use.
+    A file whose int6 was compressed by truncated SVD (tools/compress_net.py --int6) holds int6_L (one blob [r, in], no
+    bias) + int6_U ([out, r] and the bias) in int6's place: the dict then carries L6, U6, b6 instead of W6, b6, which
+    AzContext.load_head runs as two stages.  The rules are det_head_from_layers': half a pair, int6 beside its pair and
+    factors that do not chain are ValueErrors."""
+    head = {}
+    nl, nu = "int6_L", "int6_U"
+    if (nl in layers) != (nu in layers):
+        raise ValueError("a compressed int6 needs both %s and %s: the file has only %s" % (nl, nu, nl if nl in layers else nu))
+    if nl in layers:
+        if "int6" in layers:
+            raise ValueError("the file has int6 and its compressed pair %s / %s" % (nl, nu))
+        if len(layers[nu]) < 2 or not layers[nl]:
+            raise ValueError("%s needs a weight blob, %s a weight and a bias blob" % (nl, nu))
+        U, b6 = _fc(layers, nu)
+        Lw = np.asarray(layers[nl][0], dtype=np.float32)
+        if Lw.size % U.shape[1]:
+            raise ValueError("%s %s does not chain into %s %s" % (nl, Lw.shape, nu, U.shape))
+        head["L6"], head["U6"] = np.ascontiguousarray(Lw.reshape(U.shape[1], -1)), U
+    else:
+        head["W6"], b6 = _fc(layers, "int6")
     W71, b71 = _fc(layers, "int7_1")
     W72, b72 = _fc(layers, "int7_2")
     Was, bas = _fc(layers, "adj_score")
     Wab, bab = _fc(layers, "adj_bbox")
     Wz, bz = _fc(layers, "zoom_score")
-    return {"W6": W6, "b6": b6, "W71": W71, "b71": b71, "W72": W72, "b72": b72, "Was": Was, "bas": bas,
-            "Wab": Wab, "bab": bab, "Wz": Wz, "bz": bz}
+    head.update({"b6": b6, "W71": W71, "b71": b71, "W72": W72, "b72": b72, "Was": Was, "bas": bas,
+            "Wab": Wab, "bab": bab, "Wz": Wz, "bz": bz})
+    return head
 
 
 def det_head_from_layers(layers):

@@ -1,11 +1,12 @@
-"""Truncated-SVD compression of the detection head's fc layers (Fast R-CNN, section 4.4; the paper's compress_net tool).
+"""Truncated-SVD compression of the detection head's fc layers and of the AZ head's int6 (Fast R-CNN, section 4.4; the
+paper's compress_net tool).
 
 A layer y = relu(W x + b), W [out, in], becomes t = L x (no bias, no ReLU: fc*_L) and y = relu(U t + b) (fc*_U) with
     U_, s, Vt = svd(W);  L = diag(s[:r]) Vt[:r]  [r, in];  U = U_[:, :r]  [out, r].
 U L is the best rank-r approximation of W in the Frobenius norm, with error sqrt(sum_{i >= r} s_i^2) (Eckart-Young).
 The SVD runs in float64 -- on the GPU through torch when one is there, in NumPy otherwise -- and the factors are cast to
-float32 once, at the end.  Inference only: AzContext.load_det_head_lowrank runs such a head; the trainers keep full
-weights."""
+float32 once, at the end.  Inference only: AzContext.load_det_head_lowrank / load_head_lowrank run such a head; the
+trainers keep full weights."""
 import numpy as np
 
 
@@ -57,4 +58,14 @@ def compress_det_head(head, r6=1024, r7=256):
     return out
 
 
-__all__ = ["compress_layer", "compress_det_head", "rel_error"]
+def compress_az_head(head, r6=1024):
+    """The AZ-head dict (W6, b6, W71, b71, W72, b72, Was, bas, Wab, bab, Wz, bz) with int6 at rank r6: W6 -> L6 [r6, C*49],
+    U6 [n6, r6]; b6 and every other layer are passed through.  -> (the dict AzContext.load_head / HipAZNet take, the
+    relative error ||W6 - U6 L6||_F / ||W6||_F).  A different model from the full head: thresholds tuned on the full net
+    have to be tuned again."""
+    out = {k: v for k, v in head.items() if k != "W6"}
+    out["L6"], out["U6"] = compress_layer(head["W6"], r6)
+    return out, rel_error(head["W6"], out["L6"], out["U6"])
+
+
+__all__ = ["compress_layer", "compress_det_head", "compress_az_head", "rel_error"]

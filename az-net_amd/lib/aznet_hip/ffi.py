@@ -64,6 +64,7 @@ SYMBOLS = [
     "az_det_solver_mine", "az_det_solver_mine_skip",
     "az_soft_nms_batched", "az_box_vote_batched",
     "az_load_det_head_lowrank", "az_lowrank_gemm_unit", "az_lowrank_split",
+    "az_load_head_lowrank", "az_az_lowrank_split",
 ]
 AZ_LOWRANK_MAX = 2048      # include/aznet_hip.h
 
@@ -195,6 +196,8 @@ def load_library(path=None):
     L.az_load_det_head_lowrank.argtypes = [vp, ci, ci, ci, ci, ci, ci] + [fp] * 10
     L.az_lowrank_gemm_unit.argtypes = [vp, fp, fp, fp, ci, ci, ci, ci, fp]
     L.az_lowrank_split.argtypes = [ci, ci]
+    L.az_load_head_lowrank.argtypes = [vp, ci, ci, ci, ci, ci] + [fp] * 13
+    L.az_az_lowrank_split.argtypes = [ci, ci]
     L.az_det_forward.argtypes = [vp, fp, ci, fp, fp]
     L.az_detect.argtypes = [vp, dp, ci, cd, cd, ci, ci, ci, cd, fp, dp]
     L.az_set_feature_pyramid_dev_nhwc.argtypes = [vp, ctypes.POINTER(ctypes.c_void_p), ci, ci, ci, ci]
@@ -351,6 +354,15 @@ def lowrank_split(K, r):
     return n
 
 
+def az_lowrank_split(K, r):
+    """az_az_lowrank_split: the number of K chunks of the AZ head's L stage [., K] x [K, r] -- host arithmetic, no GPU
+    needed."""
+    n = int(load_library().az_az_lowrank_split(int(K), int(r)))
+    if n < 1:
+        raise AzError(n, "az_az_lowrank_split(%d, %d)" % (K, r))
+    return n
+
+
 class AzContext(object):
     """One GPU's search context (az_ctx).  Not thread-safe; one per process/GPU."""
 
@@ -401,7 +413,11 @@ class AzContext(object):
 
     # ---- setup --------------------------------------------------------------------
     def load_head(self, head):
-        """head: dict of Caffe-layout fp32 arrays W6,b6,W71,b71,W72,b72,Was,bas,Wab,bab,Wz,bz."""
+        """head: dict of Caffe-layout fp32 arrays W6,b6,W71,b71,W72,b72,Was,bas,Wab,bab,Wz,bz.  A head that carries
+        truncated-SVD factors of int6 (L6 / U6: compress.compress_az_head, caffemodel.az_head_from_layers of a compressed
+        file) goes through load_head_lowrank."""
+        if isinstance(head, dict) and ("L6" in head or "U6" in head):
+            return self.load_head_lowrank(head)
         W6 = _f32(head["W6"])
         n6, K6 = W6.shape
         assert K6 % 49 == 0
@@ -414,6 +430,28 @@ class AzContext(object):
                                                  "bab", "Wz", "bz")]
         self._chk(self.L.az_load_head(self.h, C, n6, n71, n72, *[_p(a, ctypes.c_float) for a in arrs]))
         self.dims = dict(C=C, n6=n6, n71=n71, n72=n72, K6=K6)
+
+    def load_head_lowrank(self, head):
+        """az_load_head_lowrank.  head: as load_head's, with int6 given as L6 [r6, C*49], U6 [n6, r6], b6 instead of W6, b6."""
+        if "L6" not in head or "U6" not in head:
+            raise ValueError("a low-rank AZ head needs both L6 and U6")
+        if "W6" in head:
+            raise ValueError("a low-rank AZ head carries L6 and U6 in W6's place, not beside it")
+        L6, U6 = _f32(head["L6"]), _f32(head["U6"])
+        if L6.ndim != 2 or U6.ndim != 2 or U6.shape[1] != L6.shape[0]:
+            raise ValueError("L6 %s and U6 %s do not chain" % (L6.shape, U6.shape))
+        (r6, K6), n6 = L6.shape, U6.shape[0]
+        assert K6 % 49 == 0
+        C = K6 // 49
+        n71, n72 = head["W71"].shape[0], head["W72"].shape[0]
+        assert head["W71"].shape == (n71, n6) and head["W72"].shape == (n72, n6)
+        assert head["Was"].shape == (11, n71) and head["Wab"].shape == (44, n71)
+        assert head["Wz"].shape == (1, n72)
+        arrs = [L6, U6] + [_f32(head[k]) for k in ("b6", "W71", "b71", "W72", "b72", "Was", "bas", "Wab",
+                                                     "bab", "Wz", "bz")]
+        assert arrs[2].size == n6
+        self._chk(self.L.az_load_head_lowrank(self.h, C, n6, n71, n72, r6, *[_p(a, ctypes.c_float) for a in arrs]))
+        self.dims = dict(C=C, n6=n6, n71=n71, n72=n72, K6=K6, r6=r6)
 
     def set_feature_map(self, fmap, wait=True, producer_done=False):
         """fmap: [1,C,H,W] or [C,H,W]; a NumPy array (copied to HBM) or a CUDA torch tensor

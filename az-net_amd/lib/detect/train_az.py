@@ -39,6 +39,7 @@ class SolverWrapper(solver.SolverWrapper):
     def _build(self, layers, dims):
         from aznet_hip import synth, caffemodel as cm
         self._default_device(layers)
+        self._refuse_compressed(layers)
         head = cm.az_head_from_layers(layers) if layers and "int6" in layers else None
         if dims is None:
             dims = dict(synth.FULL_DIMS)
@@ -50,9 +51,17 @@ class SolverWrapper(solver.SolverWrapper):
         if head is None:
             self._load_fillers()
 
+    @staticmethod
+    def _refuse_compressed(layers):
+        """The trainers keep full-rank weights: a file whose int6 was compressed (tools/compress_net.py --int6) is refused."""
+        if layers and ("int6_L" in layers or "int6_U" in layers):
+            raise ValueError("the pretrained model holds int6_L / int6_U, a truncated-SVD int6: train the full-rank net and "
+                             "compress its snapshot afterwards (tools/compress_net.py --int6)")
+
     def _copy_from(self, layers):
         """net.copy_from onto a trainer that was handed in (layers: the pretrained model's, or None)."""
         from aznet_hip import caffemodel as cm
+        self._refuse_compressed(layers)
         if layers and "int6" in layers:
             self.trainer.load(cm.az_head_from_layers(layers))
 

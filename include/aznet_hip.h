@@ -187,6 +187,31 @@ int az_load_head(az_ctx *ctx, int C, int n6, int n71, int n72,
                  const float *W6, const float *b6, const float *W71, const float *b71,
                  const float *W72, const float *b72, const float *Was, const float *bas,
                  const float *Wab, const float *bab, const float *Wz, const float *bz);
+/* The same head with int6 compressed by truncated SVD (Fast R-CNN, section 4.4; opt-in, not in the reference tree; the
+ * detection head's twin is az_load_det_head_lowrank below).  int6, y = relu(W6 x + b6), runs as t = L6 x with L6 =
+ * diag(s[:r6]) Vt[:r6] [r6, C*49] (linear: no bias, no ReLU: int6_L) and y = relu(U6 t + b6) with U6 = U[:, :r6] [n6, r6]
+ * (int6_U), all fp32, Caffe [out, in] layout; int7_1, int7_2, adj_score, adj_bbox and zoom_score stay as they are.
+ * r6 is a multiple of 4 with 4 <= r6 <= min(n6, C*49, AZ_LOWRANK_MAX); that and every size rule of az_load_head:
+ * AZ_ERR_INVALID.  On a context in a 16-bit-term GEMM mode (az_set_gemm_mode 2 | 3) the call is AZ_ERR_STATE (and
+ * az_set_gemm_mode is refused once any AZ head is loaded).  A refused call leaves the head loaded before in place and
+ * answering.  az_load_head replaces a low-rank head and the reverse; either drops the lanes, batch slots and captured
+ * graphs built on the head before.  Every form of the search and az_head_forward then run, in int6's place and on the
+ * same stream, three launches: fc6_L (the split-K GEMM with az_az_lowrank_split(C*49, r6) chunks, on the many-row kernel
+ * where int6 would have been), fc6_L_reduce (a linear slab sum) and fc6_U (the whole K = r6 in one launch, bias and ReLU in
+ * registers: az_lowrank.hip's k_lowrank_gemm) -- those are the profiling names; the self-timing span (az_set_profiling bit 3) stays with the full head's
+ * fc6_gemm.  No stage's order of summation depends on the row count.  This is a different model from the full head: its
+ * zoom scores move, so thresholds tuned on the full net (thresh.pkl) have to be tuned again on the compressed one. */
+int az_load_head_lowrank(az_ctx *ctx, int C, int n6, int n71, int n72, int r6, const float *L6, const float *U6,
+                         const float *b6, const float *W71, const float *b71, const float *W72, const float *b72,
+                         const float *Was, const float *bas, const float *Wab, const float *bab, const float *Wz,
+                         const float *bz);
+/* The number of K chunks of the AZ head's L stage [., K] x [K, r] (host arithmetic, ctx-free): a function of (K, r) alone.
+ * Among the splits that keep the many-row GEMM eligible (whole 128-wide n-tiles of r, nt = r / 128; at least 256 (n-tile,
+ * chunk) groups; chunks of exactly K / S in whole K steps of 32, at least two steps each) the one with the least
+ * 4 ceil(nt S / 256) (K / S) + nt S -- the longest workgroup's K depth on that kernel's 256 workgroups against the slab
+ * traffic, weighted as measured; ties: the smaller S: 56 at (25088, 1024).  Where none exists:
+ * az_lowrank_split(K, r), on the plain split-K kernel.  K or r not positive: AZ_ERR_INVALID. */
+int az_az_lowrank_split(int K, int r);
 
 /* Replaces feeding `conv5_3` to net['fc'] (lib/detect/test.py:229-236).  The map (NCHW f32,
  * batch 1) is transposed once into ctx-owned HBM in the channel-last layout RoIPool reads;
