@@ -40,6 +40,7 @@ struct AzEnv {
     int pair_spec = 1;         // AZ_PAIR_SPEC=0|2: pair speculation never / whenever possible (1: by the context's history)
     int full_spec = 1;         // AZ_FULL_SPEC=0|2|3: whole-tree speculation never / whenever possible / the closure whenever possible (1: by history)
     int two_stage = 1;         // AZ_TWO_STAGE=0|2|4: one-pass searches never staged / staged on two lanes as well / two stages, never three
+    bool iterloc_sync = true;  // AZ_ITERLOC_SYNC=0: az_detect_iter reads no round's row count back (every round enqueued at max_rows rows, one wait)
 };
 
 inline AzEnv az_read_env()
@@ -51,6 +52,7 @@ inline AzEnv az_read_env()
     if (num("AZ_PLAN_CACHE", 0) > 0) v.plan_cache = num("AZ_PLAN_CACHE", 0);
     if (getenv("AZ_GEMM12_MIN")) v.gemm12_min = num("AZ_GEMM12_MIN", 0) > 0 ? num("AZ_GEMM12_MIN", 0) : 0x7fffffff;
     v.pair_spec = num("AZ_PAIR_SPEC", 1); v.full_spec = num("AZ_FULL_SPEC", 1); v.two_stage = num("AZ_TWO_STAGE", 1);
+    v.iterloc_sync = num("AZ_ITERLOC_SYNC", 1) != 0;
     return v;
 }
 

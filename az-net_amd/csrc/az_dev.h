@@ -403,6 +403,21 @@ void azk_det_epilogue(hipStream_t s, const float *part, int S, int ncls, const f
 void azk_det_gather(hipStream_t s, const int *Pptr, const int *inv, int ncls, const float *prob_u,
                     const double *pred_u, float *prob, double *pred);
 
+// ---- launchers (az_iterloc.hip): iterative localisation, the sources of the next round and their class column ----------
+// The next round's proposals among N candidates in ascending flat index f: score >= min_score (f32), at most max_rows of
+// them (the higher score, ties to the lower f; the kept ones stay in ascending f).  One workgroup.
+//   prev_n == nullptr: the candidates are the (row i, class j >= 1) pairs of prob [P][ncls] / pred [P][4 ncls],
+//                      f = (j - 1) * P + i; src_out = i;
+//   otherwise:         the min(*prev_n, max_rows) extras pscore / pbox / pcls of the previous round; src_out = f.
+// B [max_rows][4] gets the kept boxes, cls_out / src_out their class / source, *count_out and *Pptr their number; *Uptr is
+// cleared (azk_rois_dedup adds into it).
+void azk_iter_select(hipStream_t s, const float *prob, const double *pred, int P, int ncls, const int *prev_n,
+                     const float *pscore, const double *pbox, const int *pcls, float min_score, int max_rows, double *B,
+                     int *cls_out, int *src_out, int *count_out, int *Pptr, int *Uptr);
+// score_out[e] / box_out[e] = column cls[e] of the unique row inv[e] of prob_u [.][ncls] / pred_u [.][4 ncls], e < min(*Nptr, cap)
+void azk_iter_take(hipStream_t s, const int *Nptr, int cap, const int *inv, const int *cls, int ncls, const float *prob_u,
+                   const double *pred_u, float *score_out, double *box_out);
+
 // ---- launchers (az_select.hip) ---------------------------------------------------------
 // Top-k by score (descending, ties: lower index first).  With Yall/Sall/Yout/Sout non-NULL the
 // selected boxes/scores are gathered in the same launch.

@@ -560,6 +560,114 @@ int az_detect_skip(az_ctx *c, const double *boxes, int P, double scale, double d
     return detect(c, boxes, P, scale, nullptr, dedup, batch_size, im_h, im_w, eps, nullptr, nullptr, scores_out, boxes_out, true);
 }
 
+// az_detect_iter / az_detect_iter_skip past their argument checks.  Round 1 is detect()'s launch sequence; every further
+// round is k_iter_select (az_iterloc.hip: the sources, their boxes into B[0], the device row count) + the same projection,
+// dedup and head pass + k_iter_take (the class column through inv, so dprob / dpred keep round 1's rows until the one
+// download at the end).  The extras of all rounds live in scratch slot 0, round r at row r * max_rows.
+// The 4-byte row count of a round is read back (AzEnv::iterloc_sync, the default): the next launches are sized by it and
+// an empty round ends the loop; without the read-back every round is enqueued at max_rows rows and the host waits once.
+static int detect_iter(az_ctx *c, const double *boxes, int P, double scale, double dedup, int batch_size, int im_h, int im_w,
+                       double eps, int rounds, double min_score, int max_rows, float *scores_out, double *boxes_out,
+                       int32_t *ex_cls, int32_t *ex_src, float *ex_score, double *ex_box, int32_t *ex_count, bool skip)
+{
+    const int NX = rounds - 1;
+    for (int r = 0; r < NX; ++r) ex_count[r] = 0;
+    if (P == 0) return AZ_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    const size_t rows = (size_t)NX * max_rows, o_box = 256, o_score = o_box + rows * 4 * sizeof(double),
+                 o_cls = o_score + rows * sizeof(float), o_src = o_cls + rows * sizeof(int);
+    int rc;
+    if (NX && (rc = scratch_grow(c, 0, o_src + rows * sizeof(int))) != AZ_OK) return rc;
+    unsigned char *ar = c->scratch[0].as<unsigned char>();
+    int *d_cnt = (int *)ar;                                   // [NX] (<= 7 ints)
+    double *d_box = (double *)(ar + o_box);
+    float *d_score = (float *)(ar + o_score);
+    int *d_cls = (int *)(ar + o_cls), *d_src = (int *)(ar + o_src);
+    if (!(c->profiling & 4)) clear_events(c);
+    if ((rc = upload_boxes(c, boxes, P)) != AZ_OK) return rc;
+    if (NX) HIPCHK(c, hipMemsetAsync(d_cnt, 0, 256, s));
+    azk_rois_dedup(s, c->B[0], &c->cnt->P[0], c->maxR, scale, nullptr, (float)dedup, batch_size, c->rois, c->key, c->grp,
+                   c->first, c->index, c->inv, c->urois, c->ubox, &c->cnt->U[0]);
+    launch_det_head(c, &c->cnt->U[0], im_h, im_w, eps, P, nullptr, nullptr, nullptr, skip);
+    azk_det_gather(s, &c->cnt->P[0], c->inv, c->det_ncls, c->dprob_u, c->dpred_u, c->dprob, c->dpred);
+    int32_t n_host[8] = {0};
+    bool counted = true;                                      // n_host holds every enqueued round's count
+    for (int r = 0; r < NX; ++r) {
+        const size_t o = (size_t)r * max_rows, op = r ? o - max_rows : 0;
+        { Timed t(c, "iter_select", r + 1);
+          azk_iter_select(s, c->dprob, c->dpred, P, c->det_ncls, r ? d_cnt + r - 1 : nullptr, d_score + op, d_box + 4 * op,
+                          d_cls + op, (float)min_score, max_rows, c->B[0], d_cls + o, d_src + o, d_cnt + r, &c->cnt->P[0],
+                          &c->cnt->U[0]); }
+        int bound = max_rows;
+        if (c->env.iterloc_sync) {
+            HIPCHK(c, hipMemcpyAsync(&c->h_cnt->scratch[0], d_cnt + r, sizeof(int), hipMemcpyDeviceToHost, s));
+            HIPCHK(c, hipStreamSynchronize(s));
+            n_host[r] = bound = c->h_cnt->scratch[0];
+            if (bound == 0) break;
+        } else counted = false;
+        azk_rois_dedup(s, c->B[0], &c->cnt->P[0], c->maxR, scale, nullptr, (float)dedup, batch_size, c->rois, c->key,
+                       c->grp, c->first, c->index, c->inv, c->urois, c->ubox, &c->cnt->U[0]);
+        launch_det_head(c, &c->cnt->U[0], im_h, im_w, eps, bound, nullptr, nullptr, nullptr, skip);
+        { Timed t(c, "iter_take", r + 1);
+          azk_iter_take(s, d_cnt + r, max_rows, c->inv, d_cls + o, c->det_ncls, c->dprob_u, c->dpred_u, d_score + o,
+                        d_box + 4 * o); }
+    }
+    if ((rc = fetch_dets(c, P, scores_out, boxes_out)) != AZ_OK) return rc;
+    if (!counted) HIPCHK(c, hipMemcpy(n_host, d_cnt, (size_t)NX * sizeof(int), hipMemcpyDeviceToHost));
+    size_t at = 0;
+    for (int r = 0; r < NX; ++r) {
+        const size_t n = (size_t)n_host[r], o = (size_t)r * max_rows;
+        ex_count[r] = n_host[r];
+        if (!n) continue;
+        HIPCHK(c, hipMemcpy(ex_cls + at, d_cls + o, n * sizeof(int), hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(ex_src + at, d_src + o, n * sizeof(int), hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(ex_score + at, d_score + o, n * sizeof(float), hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(ex_box + 4 * at, d_box + 4 * o, n * 4 * sizeof(double), hipMemcpyDeviceToHost));
+        at += n;
+    }
+    return AZ_OK;
+}
+
+static int detect_iter_args(az_ctx *c, const char *who, const double *boxes, int P, double scale, int batch_size, int rounds,
+                            int max_rows, const int32_t *ex_cls, const int32_t *ex_src, const float *ex_score,
+                            const double *ex_box, const int32_t *ex_count)
+{
+    const std::string w(who);
+    if (P < 0 || (P && !boxes) || batch_size <= 0 || !(scale > 0)) return fail(c, AZ_ERR_INVALID, w + ": bad arguments");
+    if (rounds < 1 || rounds > AZ_ITER_LOC_MAX_ROUNDS) return fail(c, AZ_ERR_INVALID, w + ": 1 <= rounds <= AZ_ITER_LOC_MAX_ROUNDS");
+    if (max_rows < 1 || max_rows > AZ_TOPK_MAX) return fail(c, AZ_ERR_INVALID, w + ": 1 <= max_rows <= 4096");
+    if (rounds > 1 && (!ex_cls || !ex_src || !ex_score || !ex_box || !ex_count))
+        return fail(c, AZ_ERR_INVALID, w + ": null extras pointer with rounds > 1");
+    if (P > c->maxR) return fail(c, AZ_ERR_CAPACITY, w + ": too many boxes");
+    if (max_rows > c->maxR) return fail(c, AZ_ERR_CAPACITY, w + ": max_rows above the region capacity");
+    return AZ_OK;
+}
+
+int az_detect_iter(az_ctx *c, const double *boxes, int P, double scale, double dedup, int batch_size, int im_h, int im_w,
+                   double eps, int rounds, double min_score, int max_rows, float *scores_out, double *boxes_out,
+                   int32_t *ex_cls, int32_t *ex_src, float *ex_score, double *ex_box, int32_t *ex_count)
+{
+    int rc = check_det(c);
+    if (rc) return rc;
+    if ((rc = detect_iter_args(c, "az_detect_iter", boxes, P, scale, batch_size, rounds, max_rows, ex_cls, ex_src, ex_score,
+                               ex_box, ex_count)) != AZ_OK) return rc;
+    return detect_iter(c, boxes, P, scale, dedup, batch_size, im_h, im_w, eps, rounds, min_score, max_rows, scores_out,
+                       boxes_out, ex_cls, ex_src, ex_score, ex_box, ex_count, false);
+}
+
+int az_detect_iter_skip(az_ctx *c, const double *boxes, int P, double scale, double dedup, int batch_size, int im_h, int im_w,
+                        double eps, int rounds, double min_score, int max_rows, float *scores_out, double *boxes_out,
+                        int32_t *ex_cls, int32_t *ex_src, float *ex_score, double *ex_box, int32_t *ex_count)
+{
+    int rc = skip_check(c, "az_detect_iter_skip", true);
+    if (rc) return rc;
+    if ((rc = detect_iter_args(c, "az_detect_iter_skip", boxes, P, scale, batch_size, rounds, max_rows, ex_cls, ex_src,
+                               ex_score, ex_box, ex_count)) != AZ_OK) return rc;
+    return detect_iter(c, boxes, P, scale, dedup, batch_size, im_h, im_w, eps, rounds, min_score, max_rows, scores_out,
+                       boxes_out, ex_cls, ex_src, ex_score, ex_box, ex_count, true);
+}
+
 int az_det_forward_skip(az_ctx *c, const float *rois, int R, float *cls_prob, float *bbox_pred)
 {
     int rc = skip_check(c, "az_det_forward_skip", true);

@@ -65,7 +65,10 @@ SYMBOLS = [
     "az_soft_nms_batched", "az_box_vote_batched",
     "az_load_det_head_lowrank", "az_lowrank_gemm_unit", "az_lowrank_split",
     "az_load_head_lowrank", "az_az_lowrank_split",
+    "az_detect_iter", "az_detect_iter_skip",
 ]
+AZ_ITER_LOC_MAX_ROUNDS = 8  # include/aznet_hip.h
+AZ_ITER_LOC_MAX_ROWS = 4096  # include/aznet_hip.h (az_detect_iter: az_topk's largest k)
 AZ_LOWRANK_MAX = 2048      # include/aznet_hip.h
 
 
@@ -208,6 +211,8 @@ def load_library(path=None):
     L.az_load_skip_front.argtypes = [vp, ci, cip, fp, cd, cd, ci, fp, fp]
     L.az_set_skip_maps_dev_nhwc.argtypes = [vp, ci, ctypes.POINTER(ctypes.c_void_p), cip, cip, cip]
     L.az_detect_skip.argtypes = [vp, dp, ci, cd, cd, ci, ci, ci, cd, fp, dp]
+    L.az_detect_iter.argtypes = [vp, dp, ci, cd, cd, ci, ci, ci, cd, ci, cd, ci, fp, dp, ip, ip, fp, dp, ip]
+    L.az_detect_iter_skip.argtypes = L.az_detect_iter.argtypes
     L.az_det_forward_skip.argtypes = [vp, fp, ci, fp, fp]
     L.az_skip_pool.argtypes = [vp, fp, ci, ci, fp]
     L.az_skip_conv.argtypes = [vp, fp, ci, fp]
@@ -1153,6 +1158,36 @@ class AzContext(object):
 
     def detect_skip(self, boxes, scale, im_h, im_w, dedup=1. / 16., batch_size=10000, eps=1e-14):
         return self._detect(self.L.az_detect_skip, (float(scale),), boxes, im_h, im_w, dedup, batch_size, eps)
+
+    def detect_iter(self, boxes, scale, im_h, im_w, rounds, min_score, max_rows, dedup=1. / 16., batch_size=10000, eps=1e-14,
+                    skip=False):
+        """az_detect_iter (skip: az_detect_iter_skip): iterative box localisation.  Returns (scores [P, ncls], boxes
+        [P, 4 ncls], extra); extra is a dict of the later rounds' rows, round after round: cls, src (int32), round (int32: 2,
+        3, ...), score (float32), box ([., 4] float64), and count (int32 [rounds - 1]: the rows of each round)."""
+        boxes = _f64(boxes).reshape(-1, 4)
+        P = boxes.shape[0]
+        nc = self.det_dims["ncls"]
+        rounds, max_rows = int(rounds), int(max_rows)
+        # (sized only for arguments the entry accepts: anything else it refuses before it touches a buffer)
+        ok = 1 <= rounds <= AZ_ITER_LOC_MAX_ROUNDS and 1 <= max_rows <= AZ_ITER_LOC_MAX_ROWS
+        cap = max((rounds - 1) * max_rows, 1) if ok else 1
+        s = np.empty((max(P, 1), nc), dtype=np.float32)
+        b = np.empty((max(P, 1), 4 * nc), dtype=np.float64)
+        cls = np.empty(cap, dtype=np.int32)
+        src = np.empty(cap, dtype=np.int32)
+        sc = np.empty(cap, dtype=np.float32)
+        bx = np.empty((cap, 4), dtype=np.float64)
+        cnt = np.zeros(max(rounds - 1, 1) if ok else 1, dtype=np.int32)
+        fn = self.L.az_detect_iter_skip if skip else self.L.az_detect_iter
+        self._chk(fn(self.h, _p(boxes, ctypes.c_double), P, float(scale), float(dedup), int(batch_size), int(im_h), int(im_w),
+                     float(eps), rounds, float(min_score), max_rows, _p(s, ctypes.c_float), _p(b, ctypes.c_double),
+                     _p(cls, ctypes.c_int32), _p(src, ctypes.c_int32), _p(sc, ctypes.c_float), _p(bx, ctypes.c_double),
+                     _p(cnt, ctypes.c_int32)))
+        cnt = cnt[:rounds - 1]
+        n = int(cnt.sum())
+        extra = dict(cls=cls[:n], src=src[:n], round=np.repeat(np.arange(2, rounds + 1, dtype=np.int32), cnt), score=sc[:n],
+                     box=bx[:n], count=cnt)
+        return s[:P], b[:P], extra
 
     def det_forward_skip(self, rois):
         rois = _f32(rois).reshape(-1, 5)

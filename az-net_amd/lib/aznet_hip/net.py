@@ -241,6 +241,12 @@ class HipDetNet(_NetDict):
             return self.ctx.detect_skip(boxes, scale, im_shape[0], im_shape[1], dedup=dedup, batch_size=batch_size, eps=eps)
         return self.ctx.detect(boxes, scale, im_shape[0], im_shape[1], dedup=dedup, batch_size=batch_size, eps=eps)
 
+    def detect_iter(self, boxes, scale, im_shape, dedup, batch_size, eps, rounds, min_score, max_rows):
+        """detect() followed by rounds - 1 rounds of iterative localisation (az_detect_iter / az_detect_iter_skip):
+        (scores, boxes, extra), see AzContext.detect_iter."""
+        return self.ctx.detect_iter(boxes, scale, im_shape[0], im_shape[1], rounds, min_score, max_rows, dedup=dedup,
+                                    batch_size=batch_size, eps=eps, skip=self.skip_front is not None)
+
     def detect_pyramid(self, boxes, scales, im_shape, dedup, batch_size, eps):
         """_frcnn_forward over the pyramid set the shared context holds (HipAZNet.compute_pyramid / set_pyramid)."""
         return self.ctx.detect_pyramid(boxes, scales, im_shape[0], im_shape[1], dedup=dedup, batch_size=batch_size,
@@ -343,3 +349,16 @@ class HipFrcnnNet(_NetDict):
             self.ctx.set_skip_maps([conv[n] for n in self.skip_names])
             return self.ctx.detect_skip(boxes, scale, im_shape[0], im_shape[1], dedup=dedup, batch_size=batch_size, eps=eps)
         return self.detect_batch([conv], [boxes], [scale], [im_shape], dedup, batch_size, eps)[0]
+
+    def detect_iter(self, conv, boxes, scale, im_shape, dedup, batch_size, eps, rounds, min_score, max_rows):
+        """detect() of one image followed by rounds - 1 rounds of iterative localisation: (scores, boxes, extra), see
+        AzContext.detect_iter.  The map is bound to the context and az_detect_iter / az_detect_iter_skip runs on it: the
+        skip maps through set_skip_maps, conv5_3 as a pyramid of one level (set_feature_pyramid, whose level 0 is the
+        context's single map -- az_set_feature_map_* want an AZ head, which this context has not).  More proposals than the
+        region capacity: AZ_ERR_CAPACITY."""
+        if self.skip_front is not None:
+            self.ctx.set_skip_maps([conv[n] for n in self.skip_names])
+        else:
+            self.ctx.set_feature_pyramid([conv])
+        return self.ctx.detect_iter(boxes, scale, im_shape[0], im_shape[1], rounds, min_score, max_rows, dedup=dedup,
+                                    batch_size=batch_size, eps=eps, skip=self.skip_front is not None)

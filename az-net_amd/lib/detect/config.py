@@ -69,7 +69,14 @@ def _defaults():
         SOFT_NMS_MIN_SCORE=0.001,    # (not in the reference) Soft-NMS drops a detection whose decayed score falls below this
         BBOX_VOTE=False,     # (not in the reference) every detection kept by NMS / Soft-NMS becomes the score-weighted mean of the
                              # detections of its class and image that overlap it
-        BBOX_VOTE_THRESH=0.8)        # (not in the reference) ... by at least this IoU
+        BBOX_VOTE_THRESH=0.8,        # (not in the reference) ... by at least this IoU
+        ITER_LOC=1,          # (not in the reference) rounds of iterative localisation (az_detect_iter): > 1 feeds the class boxes
+                             # that score well back to the detection head as proposals, rounds - 1 times; their rows join the
+                             # candidates of NMS / voting (detect.test.im_detect_refined).  1 .. 8; 1: one pass, as ever
+        ITER_LOC_SCORE=0.05,         # (not in the reference) ... a class box is fed back when its score is at least this (a
+                                     # setting, its effect on AP with trained weights is not measured)
+        ITER_LOC_MAX=1000)   # (not in the reference) ... and at most this many per round, the highest scores (1 .. 4096; about
+                             # three one-shot passes of 300 proposals; a setting as well)
     # the 11 adjacency templates, relative to a region (config.py:149-154)
     subregion = [[0, 0, 1, 1],
                  [-0.5, 0, 0.5, 1], [0.5, 0, 1.5, 1], [0, -0.5, 1, 0.5], [0, 0.5, 1, 1.5],
@@ -122,6 +129,24 @@ def nms_method(name=None):
     if not isinstance(name, str) or name not in NMS_METHODS:
         raise ValueError("cfg.TEST.NMS_METHOD = %r: 'hard', 'linear' or 'gaussian'" % (name,))
     return name
+
+
+ITER_LOC_MAX_ROUNDS, ITER_LOC_MAX_ROWS = 8, 4096     # include/aznet_hip.h: AZ_ITER_LOC_MAX_ROUNDS, az_detect_iter's max_rows
+
+
+def iter_loc(rounds=None, score=None, max_rows=None):
+    """(cfg.TEST.ITER_LOC, ITER_LOC_SCORE, ITER_LOC_MAX) (or the arguments) once checked: rounds an int in 1 .. 8, the score
+    a finite number, max_rows an int in 1 .. 4096; anything else is a ValueError."""
+    rounds = __C.TEST.ITER_LOC if rounds is None else rounds
+    score = __C.TEST.ITER_LOC_SCORE if score is None else score
+    max_rows = __C.TEST.ITER_LOC_MAX if max_rows is None else max_rows
+    if isinstance(rounds, bool) or not isinstance(rounds, (int, np.integer)) or not 1 <= rounds <= ITER_LOC_MAX_ROUNDS:
+        raise ValueError("cfg.TEST.ITER_LOC = %r: an integer in 1 .. %d" % (rounds, ITER_LOC_MAX_ROUNDS))
+    if isinstance(score, bool) or not isinstance(score, (int, float, np.integer, np.floating)) or not np.isfinite(score):
+        raise ValueError("cfg.TEST.ITER_LOC_SCORE = %r: a finite number" % (score,))
+    if isinstance(max_rows, bool) or not isinstance(max_rows, (int, np.integer)) or not 1 <= max_rows <= ITER_LOC_MAX_ROWS:
+        raise ValueError("cfg.TEST.ITER_LOC_MAX = %r: an integer in 1 .. %d" % (max_rows, ITER_LOC_MAX_ROWS))
+    return int(rounds), float(score), int(max_rows)
 
 
 def get_output_dir(imdb, net):

@@ -19,7 +19,7 @@ import pickle
 
 import numpy as np
 
-from detect.config import cfg, get_output_dir
+from detect.config import cfg, get_output_dir, iter_loc
 from utils.timer import Timer
 from utils.blob import im_list_to_blob
 from utils.cython_nms import nms
@@ -456,16 +456,41 @@ def _is_full_net(net):
     return hasattr(net, "keys") and "fc" not in net.keys()
 
 
-def _frcnn_forward(net, im, all_boxes, num_classes, conv=None):
+def _iter_loc_note(what):
+    """AZ_FULL_DEBUG: one line when cfg.TEST.BATCH_IMAGES > 1 meets cfg.TEST.ITER_LOC > 1."""
+    if int(cfg.TEST.get("BATCH_IMAGES", 1)) > 1 and os.environ.get("AZ_FULL_DEBUG") is not None:
+        print("%s: iterative localisation runs image by image (cfg.TEST.BATCH_IMAGES = %d is not taken)"
+              % (what, int(cfg.TEST.get("BATCH_IMAGES", 1))))
+
+
+def _iter_loc_rounds():
+    """cfg.TEST.ITER_LOC* once checked (ValueError), None when ITER_LOC is 1; several cfg.TEST.SCALES with ITER_LOC > 1 is
+    a ValueError that names both: az_detect_iter has no pyramid form."""
+    refine = iter_loc()
+    if refine[0] == 1:
+        return None
+    if len(cfg.TEST.SCALES) > 1:
+        raise ValueError("cfg.TEST.ITER_LOC = %d with cfg.TEST.SCALES = %r: iterative localisation takes one scale (no image "
+                         "pyramids)" % (refine[0], tuple(cfg.TEST.SCALES)))
+    return refine
+
+
+def _frcnn_forward(net, im, all_boxes, num_classes, conv=None, refine=None):
     """Fast R-CNN head over proposals on the cached conv map (test.py:259-318): one az_detect
     call (roi projection + dedup, RoIPool, fc6/fc7, cls_score softmax, bbox_pred decode + clip for
     every class, un-dedup).  Returns scores [R, K] and boxes [R, 4K] as float64, and conv.
     A full net (a HipFrcnnNet, no 'fc' key: test.py:291) runs its own backbone on the image first, then the head
-    (az_detect_batch of one image; more proposals than the region capacity go in pieces of whole dedup chunks)."""
+    (az_detect_batch of one image; more proposals than the region capacity go in pieces of whole dedup chunks).
+    refine = (rounds, min_score, max_rows) (_iter_loc_rounds): the nets' detect_iter in detect's place (az_detect_iter),
+    and a fourth result, the later rounds' rows (AzContext.detect_iter)."""
     boxes = np.ascontiguousarray(all_boxes[:, 0:4], dtype=np.float64)
     scales = _im_scale(im.shape)
     pyramid = len(scales) > 1
     args = (cfg.DEDUP_BOXES, cfg.SEAR.BATCH_SIZE, cfg.EPS)
+    if refine is not None:
+        if pyramid:
+            raise ValueError("iterative localisation (cfg.TEST.ITER_LOC) takes one scale, cfg.TEST.SCALES has %d" % len(scales))
+        return _frcnn_forward_refined(net, im, boxes, scales[0], num_classes, conv, args + tuple(refine))
     if _is_full_net(net):
         fnet = net["full"]
         assert num_classes == fnet.num_classes
@@ -500,6 +525,40 @@ def _frcnn_forward(net, im, all_boxes, num_classes, conv=None):
     else:
         scores, pred = dnet.detect(boxes, scales[0], im.shape, *args)
     return scores.astype(np.float64), pred, conv
+
+
+def _frcnn_forward_refined(net, im, boxes, scale, num_classes, conv, args):
+    """_frcnn_forward's three single-scale routes with detect_iter in detect's place: (scores, boxes, conv, extra)."""
+    if _is_full_net(net):
+        fnet = net["full"]
+        assert num_classes == fnet.num_classes
+        maps = fnet.compute_conv(fnet.image_blob_enqueue(_as_uint8(im), cfg.PIXEL_MEANS, scale))
+        if _skip_mode(fnet):
+            maps = _conv_dict(maps)
+        scores, pred, extra = fnet.detect_iter(maps, boxes, scale, im.shape, *args)
+        return (scores.astype(np.float64), pred, maps if _skip_mode(fnet) else {name: maps for name in cfg.SEAR.FRCNN_CONV},
+                extra)
+    dnet = net["fc"] if isinstance(net, dict) else net
+    assert num_classes == dnet.num_classes
+    if _skip_mode(dnet):
+        if conv is not None:
+            dnet.set_skip_conv(_conv_dict(conv))
+    elif conv is not None:
+        c = conv[cfg.SEAR.FRCNN_CONV[0]]
+        if c is not dnet.az_net._conv:
+            dnet.az_net.set_conv(c)
+    scores, pred, extra = dnet.detect_iter(boxes, scale, im.shape, *args)
+    return scores.astype(np.float64), pred, conv, extra
+
+
+def im_detect_refined(net, im, boxes, num_classes, conv=None):
+    """im_detect followed by cfg.TEST.ITER_LOC - 1 rounds of iterative localisation (not in the reference; az_detect_iter):
+    (scores, boxes, extra).  scores / boxes are im_detect's; extra holds the later rounds' rows -- cls, src, round, score,
+    box ([., 4]), count -- which _Detections.add appends to their class's candidates.  conv: the cached maps of a shared
+    net (im_propose(..., return_conv=True)).  With cfg.TEST.ITER_LOC == 1 extra is empty."""
+    refine = _iter_loc_rounds() or iter_loc()
+    scores, pred_boxes, _, extra = _frcnn_forward(net, im, boxes, num_classes, conv, refine=refine)
+    return scores, pred_boxes, extra
 
 
 def im_detect(net, im, boxes, num_classes):
@@ -660,12 +719,21 @@ class _Detections(object):
         self.top_scores = [[] for _ in range(num_classes)]
         self.all_boxes = [[[] for _ in range(num_images)] for _ in range(num_classes)]
 
-    def add(self, i, scores, boxes):
+    def add(self, i, scores, boxes, extra=None):
+        """extra (im_detect_refined): class j's candidates are the base rows followed by that class's extra rows."""
         import heapq
         for j in range(1, self.num_classes):
-            inds = np.where((scores[:, j] > self.thresh[j]))[0]
-            cls_scores = scores[inds, j]
-            cls_boxes = boxes[inds, j * 4:(j + 1) * 4]
+            if extra is None:
+                inds = np.where((scores[:, j] > self.thresh[j]))[0]
+                cls_scores = scores[inds, j]
+                cls_boxes = boxes[inds, j * 4:(j + 1) * 4]
+            else:
+                m = np.where(extra["cls"] == j)[0]
+                cand_scores = np.concatenate([scores[:, j], extra["score"][m].astype(scores.dtype)])
+                cand_boxes = np.vstack([boxes[:, j * 4:(j + 1) * 4], extra["box"][m].astype(boxes.dtype).reshape(-1, 4)])
+                inds = np.where((cand_scores > self.thresh[j]))[0]
+                cls_scores = cand_scores[inds]
+                cls_boxes = cand_boxes[inds, :]
             top_inds = np.argsort(-cls_scores)[:self.max_per_image]
             cls_scores = cls_scores[top_inds]
             cls_boxes = cls_boxes[top_inds, :]
@@ -702,6 +770,7 @@ def test_net_shared(sc_net, frcnn_net, imdb):
     above an adaptive threshold, at most 100 per image and `800 / (K-1)` per image on average
     over the set (min-heap), write detections.pkl, apply NMS (cfg.TEST.NMS) and hand the result to
     imdb.evaluate_detections when the imdb has one."""
+    refine = _iter_loc_rounds()            # (a bad cfg.TEST.ITER_LOC* raises here, before any device work)
     num_images = len(imdb.image_index)
     num_classes = imdb.num_classes
     dets = _Detections(num_classes, num_images)
@@ -723,6 +792,11 @@ def test_net_shared(sc_net, frcnn_net, imdb):
     if skip:
         _skip_note("test_net_shared")
     queued = _can_queue(hnet) and num_images > 0 and not skip
+    # cfg.TEST.ITER_LOC > 1 (an extension): the head through im_detect_refined, the later rounds' rows join the candidates
+    def head(im, prop, conv):
+        if refine is not None:
+            return im_detect_refined(frcnn_net, im, prop, num_classes, conv)
+        return _frcnn_forward(frcnn_net, im, prop, num_classes, conv)[:2] + (None,)
     # cfg.TEST.BATCH_IMAGES > 1 (an extension): the proposals of consecutive images of one shape in lockstep batches
     # (az_batch_launch), the detection head image by image as before; same detections, same printed lines
     nb = int(cfg.TEST.get("BATCH_IMAGES", 1))
@@ -742,20 +816,25 @@ def test_net_shared(sc_net, frcnn_net, imdb):
             c0 = conv[cfg.SEAR.FRCNN_CONV[0]]
             hnet.ctx.set_feature_map(c0, producer_done=True)
             hnet._conv = c0
-            scores, boxes, _ = _frcnn_forward(frcnn_net, im, prop, num_classes, conv)
+            scores, boxes, extra = head(im, prop, conv)
         elif queued:
             prop, conv = _propose_finish(sc_net, pend, return_conv=True)
-            scores, boxes, _ = _frcnn_forward(frcnn_net, im, prop, num_classes, conv)
+            scores, boxes, extra = head(im, prop, conv)
             if i + 1 < num_images:
                 im = next(images)
                 pend = _propose_start(sc_net, im)
         else:
             im = next(images)
-            scores, boxes = im_detect_shared(sc_net, frcnn_net, im, num_classes)
+            if refine is not None:
+                prop, conv = im_propose(sc_net, im, return_conv=True)
+                scores, boxes, extra = head(im, prop, conv)
+            else:
+                scores, boxes = im_detect_shared(sc_net, frcnn_net, im, num_classes)
+                extra = None
         num_boxes += scores.shape[0]
         _t['im_detect'].toc()
         _t['misc'].tic()
-        dets.add(i, scores, boxes)
+        dets.add(i, scores, boxes, extra)
         _t['misc'].toc()
         print('im_detect: {:d}/{:d} {:.3f}s {:.3f}s'.format(i + 1, num_images, _t['im_detect'].average_time,
                                                           _t['misc'].average_time))
@@ -791,6 +870,7 @@ def test_net(net, prop_file, imdb):
     NMS (cfg.TEST.NMS) and imdb.evaluate_detections when the imdb has one.
     cfg.TEST.BATCH_IMAGES > 1 (an extension): up to that many consecutive images with proposals go through one
     az_detect_batch; same detections, same printed lines in the same order."""
+    refine = _iter_loc_rounds()            # (a bad cfg.TEST.ITER_LOC* raises here, before any device work)
     with open(prop_file, 'rb') as f:
         prop = pickle.load(f)
     prop_boxes = prop['boxes']
@@ -810,11 +890,17 @@ def test_net(net, prop_file, imdb):
     if _skip_mode(fnet):
         _skip_note("test_net")
         nb = 1                     # (az_detect_skip takes one image per call)
+    # cfg.TEST.ITER_LOC > 1 (an extension): image by image through im_detect_refined (az_detect_iter takes one image per call)
+    if refine is not None:
+        _iter_loc_note("test_net")
+        nb = 1
     for g0 in range(0, len(todo), nb):
         idx = todo[g0:g0 + nb]
         ims = [next(images) for _ in idx]
         _t['im_detect'].tic()
-        if nb == 1 or len(cfg.TEST.SCALES) > 1:
+        if refine is not None:
+            results = [im_detect_refined(net, im, prop_boxes[i], num_classes) for im, i in zip(ims, idx)]
+        elif nb == 1 or len(cfg.TEST.SCALES) > 1:
             # (image pyramids: image by image, az_detect_pyramid)
             results = [im_detect(net, im, prop_boxes[i], num_classes) for im, i in zip(ims, idx)]
         else:
@@ -826,10 +912,11 @@ def test_net(net, prop_file, imdb):
             det_avg.append(_t['im_detect'].average_time)
             _t['im_detect'].tic()
         for k, i in enumerate(idx):
-            scores, boxes = results[k]
+            scores, boxes = results[k][:2]
+            extra = results[k][2] if refine is not None else None
             num_boxes += scores.shape[0]
             _t['misc'].tic()
-            dets.add(i, scores, boxes)
+            dets.add(i, scores, boxes, extra)
             _t['misc'].toc()
             print('im_detect: {:d}/{:d} {:.3f}s {:.3f}s'.format(i + 1, num_images, det_avg[k], _t['misc'].average_time))
     nms_dets = dets.finish(todo, imdb, output_dir)

@@ -45,6 +45,15 @@ POSTPROC = [
 ]
 
 
+# iterative box localisation in the detection pass itself (cfg.TEST.ITER_LOC*): the tools that run a detection net take them
+# (build_parser adds the table beside POSTPROC); tools/eval_det.py, which re-scores saved detections and has no net, does not
+ITER_LOC = [
+    ("--iter-loc", "iter_loc", "(extension) rounds of iterative box localisation, 1 = one pass (cfg.TEST.ITER_LOC)", None, int),
+    ("--iter-loc-score", "iter_loc_score", "(extension) a class box is fed back at this score or above (cfg.TEST.ITER_LOC_SCORE)", None, float),
+    ("--iter-loc-max", "iter_loc_max", "(extension) boxes fed back per round at most (cfg.TEST.ITER_LOC_MAX)", None, int),
+]
+
+
 def add_flags(parser, tables):
     for table in tables:
         for flag, dest, text, default, typ in table:
@@ -61,6 +70,7 @@ def build_parser(description, tables):
     tables = list(tables)
     if POSTPROC not in tables and any(row[0] == "--comp" for table in tables for row in table):
         tables.append(POSTPROC)
+        tables.append(ITER_LOC)
     return add_flags(argparse.ArgumentParser(description=description), tables)
 
 
@@ -74,6 +84,19 @@ def set_postproc(args):
         cfg_set_cli("TEST", "BBOX_VOTE", True)
 
 
+def set_iter_loc(args):
+    """--iter-loc / --iter-loc-score / --iter-loc-max into cfg.TEST, as set_postproc does it; a value the keys do not take is
+    a ValueError here (detect.config.iter_loc)."""
+    from detect.config import cfg_set_cli, iter_loc
+    given = {k: getattr(args, k, None) for k in ("iter_loc", "iter_loc_score", "iter_loc_max")}
+    if all(v is None for v in given.values()):
+        return
+    iter_loc(given["iter_loc"], given["iter_loc_score"], given["iter_loc_max"])
+    for k, v in given.items():
+        if v is not None:
+            cfg_set_cli("TEST", k.upper(), v)
+
+
 def parse(description, tables):
     parser = build_parser(description, tables)
     if len(sys.argv) == 1:
@@ -83,6 +106,7 @@ def parse(description, tables):
     print("Called with args:")
     print(args)
     set_postproc(args)
+    set_iter_loc(args)
     return args
 
 

@@ -533,6 +533,32 @@ int az_set_skip_maps_dev_nhwc(az_ctx *ctx, int n_src, const float *const *maps_n
  * replaced by the front on the maps of az_set_skip_maps_dev_nhwc. */
 int az_detect_skip(az_ctx *ctx, const double *boxes, int P, double scale, double dedup, int batch_size, int im_h,
                    int im_w, double eps, float *scores_out, double *boxes_out);
+/* Iterative box localisation (not in the reference; Gidaris & Komodakis, ICCV 2015): az_detect, then up to rounds - 1
+ * further head passes whose proposals are the class boxes of the pass before that score well.  Round 1 is az_detect on
+ * `boxes`: scores_out [P,ncls] f32 / boxes_out [P,4*ncls] f64 carry its bits.  The sources of round 2 are the pairs (row
+ * i, class j >= 1) with scores[i][j] >= (float)min_score (an f32 comparison), in ascending f = (j - 1) * P + i; more than
+ * max_rows of them: the max_rows with the highest score are kept, ties to the lower f (az_topk's rule), still in ascending
+ * f.  Their boxes boxes_out[i][4j .. 4j+3] are the next pass's proposals, treated as az_detect treats `boxes` (projection,
+ * 1/16 dedup per batch_size chunk, un-dedup, decode, clip); of new row e, which came from class j, only column j is kept.
+ * Each later round selects among the extras of the round before alone (same threshold and cap, f = the position in that
+ * round's list); a round without sources ends the loop.  The extras of all rounds come out round after round without
+ * gaps, ex_count[r] of them for round r + 2 (ex_count [rounds-1]): ex_cls (the class), ex_src (the proposal row for round
+ * 2, later the position in the previous round's list), ex_score f32, ex_box [.,4] f64.  The caller sizes the four lists to
+ * (rounds - 1) * max_rows rows.  Boxes and scores stay on the device between rounds; by default the 4-byte row count of
+ * each round is read back (AZ_ITERLOC_SYNC=0: not even that).  1 <= rounds <= AZ_ITER_LOC_MAX_ROUNDS, 1 <= max_rows <=
+ * 4096 (AZ_ERR_INVALID), max_rows or P above the region capacity: AZ_ERR_CAPACITY, a NULL extras pointer with rounds > 1:
+ * AZ_ERR_INVALID, otherwise az_detect's checks; every refusal comes before any device work and leaves the outputs
+ * untouched.  P == 0: AZ_OK, all counts 0.  rounds == 1: az_detect (the extras pointers are not read).  One image, one
+ * scale: there is no pyramid and no batch form of this entry. */
+#define AZ_ITER_LOC_MAX_ROUNDS 8
+int az_detect_iter(az_ctx *ctx, const double *boxes, int P, double scale, double dedup, int batch_size, int im_h, int im_w,
+                   double eps, int rounds, double min_score, int max_rows, float *scores_out, double *boxes_out,
+                   int32_t *ex_cls, int32_t *ex_src, float *ex_score, double *ex_box, int32_t *ex_count);
+/* az_detect_iter with the skip net: the front of az_detect_skip in RoIPool's place in every round; its refusals too. */
+int az_detect_iter_skip(az_ctx *ctx, const double *boxes, int P, double scale, double dedup, int batch_size, int im_h,
+                        int im_w, double eps, int rounds, double min_score, int max_rows, float *scores_out,
+                        double *boxes_out, int32_t *ex_cls, int32_t *ex_src, float *ex_score, double *ex_box,
+                        int32_t *ex_count);
 /* frcnn_net['fc'].forward(rois=..., conv3_3=..., conv4_3=..., conv5_3=...) (lib/detect/test.py:302-307) of the skip
  * net: az_det_forward's twin. */
 int az_det_forward_skip(az_ctx *ctx, const float *rois, int R, float *cls_prob, float *bbox_pred);
