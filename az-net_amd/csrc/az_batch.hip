@@ -139,13 +139,8 @@ void head_pass_batch(az_ctx *L, az_ctx::Batch &B, const AzHeadDims &d, const int
     azk_roi_pool(s, nullptr, d, L->spatial_scale, B.rois_cat, Mptr, L->maxR, L->pool5, L->pool5p,
                  azk_act_plane_elems(L->maxR, d.K6), L->gemm_parts, 0, 0, nullptr, B.feats, B.feat_hw);
     // (only the device knows the row count; both kernels are correct and bit-identical for any: the last batch's rows decide)
-    if (L->gemm_parts)
-        azk_fc_gemm_terms(s, L->pool5p, d.K6, azk_act_plane_elems(L->maxR, d.K6), L->W6p, d.K6, azk_weight_plane_elems(d.n6, d.K6), Mptr,
-                          L->maxR, d.n6, d.K6, L->S6, azk_fc_chunk(d.K6, L->S6), L->part, L->gemm_parts, L->gscale);
-    else if (!L->r6)
-        fc_gemm_fp32(L, s, L->pool5, d.K6, L->W6, Mptr, d.n6, d.K6, L->S6, L->part, many_rows);
-    if (L->r6) int6_lowrank(L, s, Mptr, many_rows, -1, false);      // (a truncated-SVD int6: fp32 only, az_load_head_lowrank)
-    else azk_fc_reduce(s, L->part, L->b6, Mptr, L->maxR, d.n6, L->S6, L->h6, d.n6, 1);
+    fc_layer_forward(L, s, L->fc6, {L->pool5, L->pool5p, azk_act_plane_elems(L->maxR, d.K6), L->part, L->t6, L->h6, L->gscale}, Mptr,
+                     many_rows, {"fc6_gemm", "fc6_reduce", "fc6_L", "fc6_L_reduce", "fc6_U"}, -1, nullptr, false);
     float *p7 = L->part7 ? L->part7 : L->part;
     azk_fc_gemm(s, L->h6, d.n6, L->W7, d.n6, Mptr, L->maxR, d.n7, d.n6, L->S7, p7, 1 << 30, nullptr);
     azk_tail(s, p7, L->S7, L->b7, d.n7, L->Wt, L->bt, B.ubox_cat, Mptr, L->maxR, im_h, im_w, eps, zoom, score, delta,

@@ -45,14 +45,15 @@ static int alloc_head_set(az_ctx *o, const az_ctx *t, size_t part_min, hipStream
     const size_t R = (size_t)t->maxR;
     const AzHeadDims &d = t->d;
     // (int6's slabs: the full layer's, or the L stage's of a truncated-SVD int6)
-    const size_t p6 = t->r6 ? (size_t)t->SL6 * R * t->r6 : (size_t)t->S6 * R * d.n6, p7 = (size_t)t->S7 * R * d.n7, planes = (size_t)t->gemm_parts * azk_act_plane_elems((int)R, d.K6);
+    const size_t p6 = t->fc6.slab_elems(R), p7 = (size_t)t->S7 * R * d.n7, planes = (size_t)t->gemm_parts * azk_act_plane_elems((int)R, d.K6);
     auto A = [&](auto **p, size_t n) { return dalloc(o, o->allocs, p, n); };
+    *h = az_ctx::HeadSet();                   // (a set made again for a head with fewer optional buffers keeps none of the old)
     int rc = A(&h->pool5, R * d.K6);
     if (!rc) rc = A(&h->part, std::max(std::max(p6, p7), part_min));
     if (!rc) rc = A(&h->h6, R * d.n6);
     if (!rc) rc = A(&h->h7, R * d.n7);
     if (!rc) rc = A(&h->part7, p7);
-    if (!rc && t->r6) rc = A(&h->t6, R * t->r6);
+    if (!rc && t->fc6.r) rc = A(&h->t6, R * t->fc6.r);
     if (!rc && t->gemm_parts) rc = A(&h->pool5p, planes);
     if (!rc && t->gemm_parts) rc = A(&h->gscale, 4);
     if (rc) return rc;
@@ -105,7 +106,7 @@ int az_set_gemm_mode(az_ctx *c, int parts)
 {
     if (!c || !(parts == 0 || parts == 2 || parts == 3)) return fail(c, AZ_ERR_INVALID, "az_set_gemm_mode: 0, 2 or 3");
     if (c->head_loaded) return fail(c, AZ_ERR_STATE, "az_set_gemm_mode must precede az_load_head");
-    if (parts && c->det_loaded && (c->det_r6 || c->det_r7))
+    if (parts && c->det_loaded && (c->det_fc6.r || c->det_fc7.r))
         return fail(c, AZ_ERR_STATE, "az_set_gemm_mode: a low-rank detection head is loaded (az_load_det_head_lowrank is fp32 only)");
     c->gemm_parts = parts;
     return AZ_OK;
@@ -141,7 +142,7 @@ static int load_head(az_ctx *c, const char *who, int C, int n6, int n71, int n72
     c->allocs.release();
     c->spare.ready = false; c->spare.ev_live = false;      // (its buffers were in `allocs`, released above; the slots are gone)
     c->head_loaded = false;
-    c->W6 = c->L6 = c->U6 = c->lr_zero = c->t6 = nullptr;
+    c->fc6.W = c->fc6.L = c->fc6.U = c->fc6.zero = c->t6 = nullptr;
     // (captured launch sequences hold the old head's launches and buffers)
     for (auto &g : c->graphs) hipGraphExecDestroy(g.second.exec);
     c->graphs.clear();
@@ -152,51 +153,29 @@ static int load_head(az_ctx *c, const char *who, int C, int n6, int n71, int n72
     AzHeadDims &d = c->d;
     d.C = C; d.pooled = 7; d.K6 = C * 49; d.n6 = n6; d.n71 = n71; d.n72 = n72; d.n7 = n71 + n72;
     d.H = d.W = 0;
-    c->S6 = azk_fc_split(d.K6);
     c->S7 = azk_fc_split(d.n6);
-    if (c->r6 != r6 && !c->cal.pinned) c->cal = az_ctx::PassCal();      // (measured head-pass costs are measured again on the other int6; a table the caller set stays)
-    c->r6 = r6; c->SL6 =r6 ? azk_az_lowrank_split(d.K6, r6) : 0;
-    const int rows6 = r6 ? r6 : n6;           // rows of the [., C*49] matrix that is permuted and tiled
+    if (c->fc6.r != r6 && !c->cal.pinned) c->cal = az_ctx::PassCal();      // (measured head-pass costs are measured again on the other int6; a table the caller set stays)
+    c->fc6 = FcLayer{n6, d.K6, azk_fc_split(d.K6), r6, r6 ? azk_az_lowrank_split(d.K6, r6) : 0};
     int rc;
     DevList &list = c->allocs;
+    if ((rc = fc_layer_alloc(c, list, c->fc6, c->gemm_parts)) != AZ_OK) return rc;
     if (r6) {
-        AZ_A(L6, azk_tiled_elems(r6, d.K6)); AZ_A(U6, (size_t)n6 * r6); AZ_A(lr_zero, r6);
-        HIPCHK(c, hipMemsetAsync(c->lr_zero, 0, (size_t)r6 * sizeof(float), c->stream));
-    } else AZ_A(W6, azk_tiled_elems(n6, d.K6));
-    AZ_A(b6, n6); AZ_A(W7, azk_tiled_elems(d.n7, n6)); AZ_A(b7, d.n7);
+        AZ_A(fc6.zero, r6);
+        HIPCHK(c, hipMemsetAsync(c->fc6.zero, 0, (size_t)r6 * sizeof(float), c->stream));
+    }
+    AZ_A(W7, azk_tiled_elems(d.n7, n6)); AZ_A(b7, d.n7);
     AZ_A(Wt, 64 * azk_tail_weight_rows(d.n7)); AZ_A(bt, 64);
-    if (c->gemm_parts) AZ_A(W6p, (size_t)c->gemm_parts * azk_weight_plane_elems(n6, d.K6));
-    {   // (`part` also stages W6 for the column permutation, and az_roi_pool's rows in Caffe's order: more than the slabs when S6 n6 < K6)
+    const size_t in6 = (size_t)c->fc6.lead() * d.K6;      // the [., C*49] matrix that is permuted and tiled
+    {   // (`part` also stages it for the column permutation, and az_roi_pool's rows in Caffe's order: more than the slabs when S6 n6 < K6)
         az_ctx::HeadSet hs;
-        if ((rc = alloc_head_set(c, c, std::max((size_t)rows6 * d.K6, (size_t)c->maxR * d.K6), c->stream, "az_load_head: clearing the operand planes", &hs)) != AZ_OK) return rc;
+        if ((rc = alloc_head_set(c, c, std::max(in6, (size_t)c->maxR * d.K6), c->stream, "az_load_head: clearing the operand planes", &hs)) != AZ_OK) return rc;
         use_head_set(c, hs);
     }
-    // Weights: Caffe [out, in] row-major is already the K-contiguous "B^T" layout the GEMM reads.
-    // int6 reads pool5, which this library keeps bin-major ([p][c], see az_head.hip): permute
-    // W6's columns to match (c*49 + p  ->  p*C + c).  `part` is big enough to stage it.
-    // The GEMM streams weights tile-major (azk_tile_weights): permute / stack in a row-major temporary, then tile.
-    // (`tmp` serves both layers: the larger of the two row-major blocks)
+    // (`tmp`, the loader's row-major temporary, serves both layers: the larger of the two blocks)
     Buf tg;
-    HIPCHK(c, tg.reserve(std::max((size_t)rows6 * d.K6, (size_t)d.n7 * n6) * 4));
+    HIPCHK(c, tg.reserve(std::max(in6, (size_t)d.n7 * n6) * 4));
     float *tmp = tg.as<float>();
-    HIPCHK(c, hipMemcpy(c->part, r6 ? L6 : W6, (size_t)rows6 * d.K6 * 4, hipMemcpyHostToDevice));
-    azk_permute_k(c->stream, c->part, tmp, rows6, C, 1);
-    if (c->gemm_parts) {          // 16-bit terms of the (permuted, row-major) int6 weights
-        c->w6_scale = 0.f;
-        if (c->gemm_parts == 2) {
-            // two fp16 terms: the weights are scaled by the power of two that brings max |w| into [2^14, 2^15)
-            float mx = 0.f;
-            for (size_t i = 0, n = (size_t)n6 * d.K6; i < n; ++i) { const float a = fabsf(W6[i]); if (a > mx) mx = a; }
-            c->w6_scale = 1.f;
-            if (mx > 0.f && mx < INFINITY) { int e; (void)frexpf(mx, &e); c->w6_scale = ldexpf(1.f, 15 - e); }
-        }
-        azk_split_weight_planes(c->stream, tmp, c->W6p, n6, d.K6, c->gemm_parts, c->w6_scale);
-    }
-    azk_tile_weights(c->stream, tmp, r6 ? c->L6 : c->W6, rows6, d.K6);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    // (the U factor stays row-major [n6, r6]: the U stage reads Caffe's layout as it is)
-    if (r6) HIPCHK(c, hipMemcpy(c->U6, W6, (size_t)n6 * r6 * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->b6, b6, (size_t)n6 * 4, hipMemcpyHostToDevice));
+    if ((rc = fc_layer_load(c, c->fc6, L6, W6, b6, C, c->part, tmp)) != AZ_OK) return rc;
     // int7_1 and int7_2 both read int6: one GEMM with the two weight blocks stacked along N.
     HIPCHK(c, hipMemcpy(tmp, W71, (size_t)n71 * n6 * 4, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(tmp + (size_t)n71 * n6, W72, (size_t)n72 * n6 * 4, hipMemcpyHostToDevice));
@@ -398,9 +377,9 @@ static int make_lane(az_ctx *c, az_ctx **out, bool with_head, const char *what)
     auto bail = [&](int code, const char *msg) { c->err = t->err.empty() ? std::string(what) + ": " + msg : t->err; az_destroy(t); return code; };
     if ((rc = ensure_geom(t)) != AZ_OK) return bail(rc, "geometry buffers");
     t->d = c->d; t->d.H = t->d.W = 0;
-    t->S6 = c->S6; t->S7 = c->S7; t->gemm_parts = c->gemm_parts; t->w6_scale = c->w6_scale; t->spatial_scale = c->spatial_scale;
-    t->W6 = c->W6; t->b6 = c->b6; t->W7 = c->W7; t->b7 = c->b7; t->Wt = c->Wt; t->bt = c->bt; t->W6p = c->W6p;
-    t->r6 = c->r6; t->SL6 = c->SL6; t->L6 = c->L6; t->U6 = c->U6; t->lr_zero = c->lr_zero;
+    // (the weights: int6 as its record, whatever it holds; int7 and the tail)
+    t->fc6 = c->fc6; t->S7 = c->S7; t->W7 = c->W7; t->b7 = c->b7; t->Wt = c->Wt; t->bt = c->bt;
+    t->gemm_parts = c->gemm_parts; t->spatial_scale = c->spatial_scale;
     t->head_bufs = false;
     if (with_head && (rc = ensure_lane_head(t)) != AZ_OK) return bail(rc, "head buffers");
     t->env = c->env; t->plan_cache_max = c->plan_cache_max; t->gemm12_min_rows = c->gemm12_min_rows; t->gemm12_dual_rows = c->gemm12_dual_rows;

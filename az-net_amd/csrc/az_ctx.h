@@ -56,6 +56,21 @@ inline AzEnv az_read_env()
     return v;
 }
 
+// One InnerProduct layer of a head as its forward path reads it (fc_layer_forward): how it is stored and split.  Views, not
+// owners: the buffers are in the head's DevList (fc_layer_load), so a lane takes a layer by copying the record.
+struct FcLayer {
+    int N = 0, K = 0;                   // outputs, inputs
+    int S = 1;                          // K chunks of the full-rank GEMM
+    int r = 0, SL = 0;                  // truncated SVD: rank (0: the layer at full rank) and the L stage's K chunks
+    float *W = nullptr;                 // full rank: [N, K], tiled (azk_tile_weights)
+    float *L = nullptr, *U = nullptr;   // rank r: L [r, K] tiled like W, U [N, r] row-major (az_lowrank.hip)
+    float *b = nullptr, *zero = nullptr;   // bias [N]; [>= r] zeros, the bias that makes the L stage's azk_fc_reduce a plain slab sum
+    unsigned short *Wp = nullptr;       // 16-bit-term modes: the weight planes (null: the layer stays on the fp32 GEMM)
+    float w_scale = 0.f;                // ... and the power-of-two scale of their fp16 terms
+    int lead() const { return r ? r : N; }      // rows of the [., K] matrix the first GEMM reads (W or L)
+    size_t slab_elems(size_t rows) const { return (size_t)(r ? SL : S) * rows * lead(); }   // that GEMM's split-K slabs
+};
+
 struct az_ctx {
     int device = 0;
     AzEnv env;
@@ -65,21 +80,19 @@ struct az_ctx {
     int maxR = 16384, maxCand = 16384 * AZ_NSUB, maxCh = 65536;
     bool head_loaded = false;
     AzHeadDims d{};
-    int S6 = 1, S7 = 1;
     // int6 on the 16-bit matrix cores (az_set_gemm_mode): 0 = off (fp32 MFMA everywhere), 2 = two fp16 terms of
     // x * 2^k / 3 MFMAs per product (~2^-21), 3 = three bf16 terms / 6 MFMAs (every fp32 value exactly)
     int gemm_parts = 0;
-    unsigned short *W6p = nullptr, *pool5p = nullptr;
+    unsigned short *pool5p = nullptr;
     float *gscale = nullptr;            // two-term (fp16) mode: {pool5 scale of this map, 1 / (sx * sw), scratch, scratch}
-    float w6_scale = 0.f;               // power-of-two scale of the fp16 weight terms
     float spatial_scale = 0.0625f;                 // test_fc.prototxt:22
-    // weights (HBM)
-    float *W6 = nullptr, *b6 = nullptr, *W7 = nullptr, *b7 = nullptr, *Wt = nullptr, *bt = nullptr;
-    // truncated-SVD int6 (az_load_head_lowrank; r6 == 0: int6 at full rank, W6): L6 [r6, K6] permuted and tiled like W6, U6
-    // [n6, r6] row-major (az_lowrank.hip), the L stage's chunk count (azk_az_lowrank_split) and its zero bias [r6]; t6
-    // [maxR][r6], the L stage's rows, belongs to the head buffer set: every lane has its own
-    int r6 = 0, SL6 = 0;
-    float *L6 = nullptr, *U6 = nullptr, *lr_zero = nullptr, *t6 = nullptr;
+    // weights (HBM).  int6 is an FcLayer (full rank: az_load_head; truncated SVD: az_load_head_lowrank); t6 [maxR][fc6.r], its
+    // L stage's rows, belongs to the head buffer set: every lane has its own.  int7 (W7, b7, S7) is no FcLayer: its slab
+    // sum lives in azk_tail, so it has no reduce launch of its own and does not go through fc_layer_forward
+    FcLayer fc6;
+    int S7 = 1;
+    float *W7 = nullptr, *b7 = nullptr, *Wt = nullptr, *bt = nullptr;
+    float *t6 = nullptr;
     // feature map
     const float *feat = nullptr;        // channel-last copy of the current map (what RoIPool reads)
     // [H][W][C] copies of NCHW maps, three of them used in turn (two until round 5): the map of a search that is still queued (and might have to
@@ -307,16 +320,14 @@ struct az_ctx {
     int gemm12_dual_rows = 161;               // ... and from which a launch whose row count only the device knows takes it, going by the previous search
     // Fast R-CNN head on the shared map (az_load_det_head)
     bool det_loaded = false;
-    int det_n6 = 0, det_n7 = 0, det_ncls = 0, det_S6 = 1, det_S7 = 1;
+    int det_ncls = 0;
     DevList allocs_det;
-    float *dW6 = nullptr, *db6 = nullptr, *dW7 = nullptr, *db7 = nullptr, *dWt = nullptr, *dbt = nullptr;
-    // truncated-SVD layers (az_load_det_head_lowrank; rank 0 = the layer at full rank): L [r, in] tiled like dW6 / dW7, U [out, r]
-    // row-major (az_lowrank.hip), the L stage's chunk counts, its output rows [maxR][max r] and its zero bias
-    int det_r6 = 0, det_r7 = 0, det_SL6 = 0, det_SL7 = 0;
-    float *dL6 = nullptr, *dU6 = nullptr, *dL7 = nullptr, *dU7 = nullptr, *dlr_t = nullptr, *dlr_zero = nullptr;
-    // 16-bit-term modes: the detection head's fc6 on the same kernel as int6 (its own weight planes, weight scale and
-    // -- two fp16 terms -- its own {pool5 scale, 1 / (sx * sw)} pair)
-    unsigned short *dW6p = nullptr; float *dgscale = nullptr; float det_w6_scale = 0.f;
+    // fc6 / fc7 (full rank: az_load_det_head; either or both as a truncated SVD: az_load_det_head_lowrank) and the tail.
+    // The L stages' output rows dlr_t [maxR][max r] and their zero bias dlr_zero [max r] serve both layers (both records'
+    // `zero` point at dlr_zero).  16-bit-term modes: det_fc6.Wp set = fc6 on the same kernel as int6, with -- two fp16
+    // terms -- its own {pool5 scale, 1 / (sx * sw)} pair in dgscale
+    FcLayer det_fc6, det_fc7;
+    float *dWt = nullptr, *dbt = nullptr, *dlr_t = nullptr, *dlr_zero = nullptr, *dgscale = nullptr;
     float *dh6 = nullptr, *dh7 = nullptr, *dpart = nullptr, *dprob_u = nullptr, *ddelta_u = nullptr, *dprob = nullptr;
     double *dpred_u = nullptr, *dpred = nullptr;
     // the skip-connection front of the detection head (az_skip.hip: az_load_skip_front): up to AZ_SKIP_MAX_SRC borrowed
@@ -518,10 +529,27 @@ void prep_scale(az_ctx *c);               // two-term (fp16) mode: the scale of 
 // one fp32 fc layer's split-K GEMM on the many-row kernel (a layer that fits it, `many_rows`, the kernel not disabled) or not
 void fc_gemm_fp32(const az_ctx *c, hipStream_t s, const float *x, int ldx, const float *W, const int *Mptr, int N, int K, int S,
                   float *part, bool many_rows, unsigned long long *ts = nullptr);
-// a truncated-SVD int6 (c->r6 != 0) on the rows pool5 [*Mptr][K6] -> h6, on stream s in the buffers of `c` (a lane):
-// fc6_L (the split-K GEMM, c->SL6 chunks) + fc6_L_reduce (linear slab sum into t6) + fc6_U (az_lowrank.hip: bias, ReLU).
-// timed: the three launches recorded as a search's are (launch_head); a batch's pass records none
-void int6_lowrank(az_ctx *c, hipStream_t s, const int *Mptr, bool many_rows, int level, bool timed);
+// the power of two that brings max |w| of n weights into [2^14, 2^15): the scale of the two-term mode's fp16 weight terms
+float fc_weight_scale(const float *w, size_t n);
+// One fc layer `f` (N, K, S, r, SL set by the caller) loaded, in two steps: a head's loader allocates its layers first and its
+// pass buffers, one of which stages the upload, behind them (the order of a head's allocations shows in the time of a
+// one-image az_detect_batch of the full-size head: 0.698 -> 0.710 ms with the weights allocated last, MI355X).
+// fc_layer_alloc: W, or L and U of a truncated SVD, the bias and `parts` 16-bit weight planes (0: none), into `list`.
+// fc_layer_load: the [f.lead(), K] matrix -- W, or `L`, whose U factor `W` then is -- uploaded (permC > 0: through `stage`, its
+// Caffe-order columns bin-permuted for permC channels) into the row-major temporary `tmp`, split into the weight planes
+// (f.Wp set: c->gemm_parts of them) and tiled; c->stream waited for; U (row-major as it is) and the bias copied.
+int fc_layer_alloc(az_ctx *c, DevList &list, FcLayer &f, int parts);
+int fc_layer_load(az_ctx *c, FcLayer &f, const float *L, const float *W, const float *b, int permC, float *stage, float *tmp);
+// the buffers of one pass through a layer: x [*Mptr][K] (xp: its 16-bit planes, xp_stride elements each, with the two-term
+// mode's scale block gscale), the split-K slabs, the L stage's rows t [maxR][r], y [*Mptr][N]
+struct FcWork { const float *x; const unsigned short *xp; size_t xp_stride; float *part, *t, *y; const float *gscale; };
+struct FcNames { const char *gemm, *reduce, *L, *L_reduce, *U; };      // profiling labels of the launches
+// y = relu(x . W^T + b) on stream s, one of three ways.  16-bit-term mode (c->gemm_parts and f.Wp): azk_fc_gemm_terms + the
+// slab sum with bias and ReLU.  fp32 at full rank: fc_gemm_fp32 (ts: its self-timing span, no event pair then) + the same
+// slab sum.  Truncated SVD (f.r): the L stage on fc_gemm_fp32 (f.SL chunks), the linear slab sum into w.t (f.zero),
+// then the U stage with bias and ReLU in one launch (az_lowrank.hip).  timed = false: no launch is recorded (a batch's pass)
+void fc_layer_forward(az_ctx *c, hipStream_t s, const FcLayer &f, const FcWork &w, const int *Mptr, bool many_rows,
+                      const FcNames &names, int level, unsigned long long *ts = nullptr, bool timed = true);
 // one head pass; rows_hint: the row count where the host knows it, -1: many rows at this level in the last search
 void launch_head(az_ctx *c, const int *Uptr, int level, int im_h, int im_w, double eps, float *zoom, float *score,
                  float *delta, double min_side = 0.0, bool keep_flags = false, int coop_tail = 0,

@@ -1,5 +1,5 @@
 // az_ctx.hip -- the host helpers every translation unit behind the C ABI shares (declared in az_ctx.h): the geometry buffers,
-// the pinned staging, one head pass with its stream and event staging, the choice between the two fp32 fc GEMMs, the joins
+// the pinned staging, one head pass with its stream and event staging, an fc layer's loader and forward path (FcLayer), the choice between the two fp32 fc GEMMs, the joins
 // and checks an entry point starts with.
 #include "az_ctx.h"
 
@@ -84,7 +84,7 @@ int set_count(az_ctx *c, int *dptr, int v)
 void prep_scale(az_ctx *c)
 {
     if (c->gemm_parts == 2 && c->feat)
-        azk_feat_scale(c->stream, c->feat, (long long)c->d.C * c->d.H * c->d.W, c->gscale, c->w6_scale);
+        azk_feat_scale(c->stream, c->feat, (long long)c->d.C * c->d.H * c->d.W, c->gscale, c->fc6.w_scale);
 }
 
 // One fp32 fc layer's split-K GEMM: the many-row kernel when the layer fits it, the caller expects many rows and the context
@@ -99,21 +99,75 @@ void fc_gemm_fp32(const az_ctx *c, hipStream_t s, const float *x, int ldx, const
         azk_fc_gemm(s, x, ldx, W, K, Mptr, c->maxR, N, K, S, part, 1 << 30, ts);
 }
 
-// A truncated-SVD int6: t6 = pool5 . L6^T on the split-K GEMM (SL6 chunks, a fixed function of (K6, r6); lr_zero is the
-// zero bias that makes azk_fc_reduce a plain slab sum), then h6 = relu(t6 . U6^T + b6) in one launch (k_lowrank_gemm at
-// every row count: a 128 x 128-tile variant for many rows was measured slower).  The L stage's two
-// kernels give a row the same bits whatever `many_rows` says.
-void int6_lowrank(az_ctx *c, hipStream_t s, const int *Mptr, bool many_rows, int level, bool timed)
+float fc_weight_scale(const float *w, size_t n)
 {
-    const AzHeadDims &d = c->d;
+    float mx = 0.f;
+    for (size_t i = 0; i < n; ++i) { const float a = fabsf(w[i]); if (a > mx) mx = a; }
+    if (!(mx > 0.f && mx < INFINITY)) return 1.f;
+    int e;
+    (void)frexpf(mx, &e);
+    return ldexpf(1.f, 15 - e);
+}
+
+int fc_layer_alloc(az_ctx *c, DevList &list, FcLayer &f, int parts)
+{
+    int rc = f.r ? dalloc(c, list, &f.L, azk_tiled_elems(f.r, f.K)) : dalloc(c, list, &f.W, azk_tiled_elems(f.N, f.K));
+    if (!rc && f.r) rc = dalloc(c, list, &f.U, (size_t)f.N * f.r);
+    if (!rc) rc = dalloc(c, list, &f.b, (size_t)f.N);
+    if (!rc && parts) rc = dalloc(c, list, &f.Wp, (size_t)parts * azk_weight_plane_elems(f.N, f.K));
+    return rc;
+}
+
+// Weights: Caffe [out, in] row-major is already the K-contiguous "B^T" layout the GEMM reads.  A layer that reads pool5,
+// which this library keeps bin-major ([p][c], see az_head.hip), gets its columns permuted to match (c*49 + p -> p*C + c).
+// The GEMM streams weights tile-major (azk_tile_weights): permute in a row-major temporary, then tile.
+int fc_layer_load(az_ctx *c, FcLayer &f, const float *L, const float *W, const float *b, int permC, float *stage, float *tmp)
+{
+    const size_t lead = (size_t)f.lead();
+    const int parts = f.Wp ? c->gemm_parts : 0;
+    HIPCHK(c, hipMemcpy(permC ? stage : tmp, f.r ? L : W, lead * f.K * 4, hipMemcpyHostToDevice));
+    if (permC) azk_permute_k(c->stream, stage, tmp, (long long)lead, permC, 1);
+    if (parts) {          // 16-bit terms of the (permuted, row-major) weights; two fp16 terms: of the scaled weights
+        f.w_scale = parts == 2 ? fc_weight_scale(W, (size_t)f.N * f.K) : 0.f;
+        azk_split_weight_planes(c->stream, tmp, f.Wp, f.N, f.K, parts, f.w_scale);
+    }
+    azk_tile_weights(c->stream, tmp, f.r ? f.L : f.W, (int)lead, f.K);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    // (the U factor stays row-major [N, r]: the U stage reads Caffe's layout as it is)
+    if (f.r) HIPCHK(c, hipMemcpy(f.U, W, (size_t)f.N * f.r * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(f.b, b, (size_t)f.N * 4, hipMemcpyHostToDevice));
+    return AZ_OK;
+}
+
+// A truncated-SVD layer: t = x . L^T on the split-K GEMM (SL chunks, a fixed function of (K, r); `zero` is the zero bias
+// that makes azk_fc_reduce a plain slab sum), then y = relu(t . U^T + b) in one launch (k_lowrank_gemm at every row count:
+// a 128 x 128-tile variant for many rows was measured slower).  The L stage's two kernels give a row the
+// same bits whatever `many_rows` says.
+void fc_layer_forward(az_ctx *c, hipStream_t s, const FcLayer &f, const FcWork &w, const int *Mptr, bool many_rows,
+                      const FcNames &names, int level, unsigned long long *ts, bool timed)
+{
     const int prof_keep = c->profiling;
     if (!timed) c->profiling &= ~(1 | 2);
-    { Timed t(c, "fc6_L", level, 1);
-      fc_gemm_fp32(c, s, c->pool5, d.K6, c->L6, Mptr, c->r6, d.K6, c->SL6, c->part, many_rows); }
-    { Timed t(c, "fc6_L_reduce", level);
-      azk_fc_reduce(s, c->part, c->lr_zero, Mptr, c->maxR, c->r6, c->SL6, c->t6, c->r6, 0); }
-    { Timed t(c, "fc6_U", level, 1);
-      azk_lowrank_gemm(s, c->t6, c->r6, c->U6, c->b6, Mptr, c->maxR, d.n6, c->r6, 1, c->h6, d.n6); }
+    const int prof_pass = c->profiling;
+    if (f.r) {
+        { Timed t(c, names.L, level, 1);
+          fc_gemm_fp32(c, s, w.x, f.K, f.L, Mptr, f.r, f.K, f.SL, w.part, many_rows); }
+        { Timed t(c, names.L_reduce, level);
+          azk_fc_reduce(s, w.part, f.zero, Mptr, c->maxR, f.r, f.SL, w.t, f.r, 0); }
+        { Timed t(c, names.U, level, 1);
+          azk_lowrank_gemm(s, w.t, f.r, f.U, f.b, Mptr, c->maxR, f.N, f.r, 1, w.y, f.N); }
+    } else {
+        if (ts) c->profiling &= ~(1 | 2);                      // (no event pair around a launch that times itself)
+        { Timed t(c, names.gemm, level, 1);
+          if (c->gemm_parts && f.Wp)
+              azk_fc_gemm_terms(s, w.xp, f.K, w.xp_stride, f.Wp, f.K, azk_weight_plane_elems(f.N, f.K), Mptr, c->maxR, f.N, f.K,
+                                f.S, azk_fc_chunk(f.K, f.S), w.part, c->gemm_parts, w.gscale);
+          else
+              fc_gemm_fp32(c, s, w.x, f.K, f.W, Mptr, f.N, f.K, f.S, w.part, many_rows, ts); }
+        c->profiling = prof_pass;
+        { Timed t(c, names.reduce, level);
+          azk_fc_reduce(s, w.part, f.b, Mptr, c->maxR, f.N, f.S, w.y, f.N, 1); }
+    }
     c->profiling = prof_keep;
 }
 
@@ -153,24 +207,13 @@ void launch_head(az_ctx *c, const int *Uptr, int level, int im_h, int im_w, doub
         return c->span_ring + 2 * (size_t)sl;
     };
     const int prof_keep = c->profiling;
+    // many rows: the caller knows the row count on the host (a one-pass plan) -- one weight tile per 12 strips --, or only the
+    // device knows it (rows_hint == -1) and the last search had many rows at this level.  The self-timing span is the fp32
+    // full-rank layer's alone
     const bool many6 = rows_hint >= c->gemm12_min_rows || rows_hint == -1;
-    // (a truncated-SVD int6 in the same place on the same stream; the self-timing span stays with the full layer)
-    if (c->r6) int6_lowrank(c, c->stream, Uptr, many6, level, true);
-    else {
-        unsigned long long *ts6 = c->gemm_parts ? nullptr : span_slot("fc6_gemm");
-        if (ts6) c->profiling &= ~(1 | 2);                     // (no event pair around a launch that times itself)
-        { Timed t(c, "fc6_gemm", level, 1);
-          if (c->gemm_parts)
-              azk_fc_gemm_terms(c->stream, c->pool5p, d.K6, azk_act_plane_elems(c->maxR, d.K6), c->W6p, d.K6, azk_weight_plane_elems(d.n6, d.K6), Uptr,
-                               c->maxR, d.n6, d.K6, c->S6, azk_fc_chunk(d.K6, c->S6), c->part, c->gemm_parts, c->gscale);
-          else
-              // many rows: the caller knows the row count on the host (a one-pass plan) -- one weight tile per 12 strips --, or
-              // only the device knows it (rows_hint == -1) and the last search had many rows at this level
-              fc_gemm_fp32(c, c->stream, c->pool5, d.K6, c->W6, Uptr, d.n6, d.K6, c->S6, c->part, many6, ts6); }
-        c->profiling = prof_keep;
-        { Timed t(c, "fc6_reduce", level);
-          azk_fc_reduce(c->stream, c->part, c->b6, Uptr, c->maxR, d.n6, c->S6, c->h6, d.n6, 1); }
-    }
+    fc_layer_forward(c, c->stream, c->fc6, {c->pool5, c->pool5p, azk_act_plane_elems(c->maxR, d.K6), c->part, c->t6, c->h6, c->gscale},
+                     Uptr, many6, {"fc6_gemm", "fc6_reduce", "fc6_L", "fc6_L_reduce", "fc6_U"}, level,
+                     (c->fc6.r || c->gemm_parts) ? nullptr : span_slot("fc6_gemm"));
     // int7 stays in stage 1 -- RoIPool, int6, slab sum, int7 back to back on `stream`: the chip-wide kernels of consecutive
     // images follow each other without an event hop (each ~13 us on the critical path: slab sum -> int7 on the second
     // stream, int7 -> the next image's RoIPool back on the first); stage 2 = the heads (+ geometry, or stage 3).  int7 writes

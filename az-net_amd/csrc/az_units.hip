@@ -269,79 +269,52 @@ static int load_det_head(az_ctx *c, int C, int n6, int n7, int ncls, int r6, int
     c->allocs_det.release();
     if (!c->head_loaded) c->pool5 = nullptr;     // (without an AZ head pool5 was the detection head's own: gone with the list)
     c->det_loaded = false;
-    c->dW6 = c->dW7 = c->dL6 = c->dL7 = c->dU6 = c->dU7 = c->dlr_t = c->dlr_zero = nullptr;
+    c->det_fc6 = c->det_fc7 = FcLayer(); c->dlr_t = c->dlr_zero = nullptr;
     const size_t R = (size_t)c->maxR, K6 = (size_t)C * 49, NO = (size_t)5 * ncls;
-    c->det_n6 = n6; c->det_n7 = n7; c->det_ncls = ncls;
-    c->det_r6 = r6; c->det_r7 = r7;
-    c->det_S6 = azk_fc_split((int)K6); c->det_S7 = azk_fc_split(n6);
-    c->det_SL6 = r6 ? azk_lowrank_split((int)K6, r6) : 0; c->det_SL7 = r7 ? azk_lowrank_split(n6, r7) : 0;
+    c->det_ncls = ncls;
+    FcLayer &f6 = c->det_fc6, &f7 = c->det_fc7;
+    f6 = FcLayer{n6, (int)K6, azk_fc_split((int)K6), r6, r6 ? azk_lowrank_split((int)K6, r6) : 0};
+    f7 = FcLayer{n7, n6, azk_fc_split(n6), r7, r7 ? azk_lowrank_split(n6, r7) : 0};
     DevList &list = c->allocs_det;
-    if (r6) { AZ_A(dL6, azk_tiled_elems(r6, (int)K6)); AZ_A(dU6, (size_t)n6 * r6); }
-    else AZ_A(dW6, azk_tiled_elems(n6, (int)K6));
-    if (r7) { AZ_A(dL7, azk_tiled_elems(r7, n6)); AZ_A(dU7, (size_t)n7 * r7); }
-    else AZ_A(dW7, azk_tiled_elems(n7, n6));
+    // (16-bit-term modes: fc6 as int6 where an AZ head's operand planes exist; a failed LDS opt-in leaves fc6 on the fp32 GEMM)
+    const int parts6 = (!r6 && c->gemm_parts && c->pool5p && azk_fc_terms_prepare(c->gemm_parts) == 0) ? c->gemm_parts : 0;
+    if ((rc = fc_layer_alloc(c, list, f6, parts6)) != AZ_OK || (rc = fc_layer_alloc(c, list, f7, 0)) != AZ_OK) return rc;
     if (r6 || r7) {
         // the L stages' output rows [R][r] (one buffer: the stream orders fc6_U before fc7_L) and their zero bias
         const size_t rm = (size_t)(r6 > r7 ? r6 : r7);
         AZ_A(dlr_t, R * rm); AZ_A(dlr_zero, rm);
         HIPCHK(c, hipMemsetAsync(c->dlr_zero, 0, rm * sizeof(float), c->stream));
+        f6.zero = f7.zero = c->dlr_zero;
     }
-    AZ_A(db6, n6); AZ_A(db7, n7);
     AZ_A(dWt, azk_tiled_elems((int)NO, n7)); AZ_A(dbt, NO);
     AZ_A(dh6, R * n6); AZ_A(dh7, R * n7);
-    const size_t rows6 = r6 ? (size_t)r6 : (size_t)n6;      // rows of the [., C*49] matrix that is permuted through dpart
-    {
-        size_t pm = r6 ? (size_t)c->det_SL6 * R * r6 : (size_t)c->det_S6 * R * n6;
-        const size_t p7 = r7 ? (size_t)c->det_SL7 * R * r7 : (size_t)c->det_S7 * R * n7;
-        const size_t pt = (size_t)AZK_TAIL_SPLIT * R * NO, pw = rows6 * K6;
-        pm = pm > p7 ? pm : p7; pm = pm > pt ? pm : pt; pm = pm > pw ? pm : pw;
-        AZ_A(dpart, pm);
-    }
+    const size_t in6 = (size_t)f6.lead() * K6, in7 = (size_t)f7.lead() * n6;     // fc6's matrix is permuted through dpart
+    AZ_A(dpart, std::max(std::max(f6.slab_elems(R), f7.slab_elems(R)), std::max((size_t)AZK_TAIL_SPLIT * R * NO, in6)));
     AZ_A(dprob_u, R * ncls); AZ_A(ddelta_u, R * 4 * ncls); AZ_A(dpred_u, R * ncls * 4); AZ_A(dprob, R * ncls); AZ_A(dpred, R * ncls * 4);
     AZ_A(dseg_dev, det_seg_bytes(c)); AZ_A(drow_hw, R * 2);
     c->dseg_own.reset(); c->dseg_host = nullptr;
     HIPCHK(c, c->dseg_own.reserve(det_seg_bytes(c)));
     c->dseg_host = c->dseg_own.as<unsigned char>();
     if (!c->pool5) { AZ_A(pool5, R * K6); }     // normally the AZ head's buffer is shared
-    c->dW6p = nullptr; c->dgscale = nullptr;
-    if (!r6 && c->gemm_parts && c->pool5p && azk_fc_terms_prepare(c->gemm_parts) == 0) {
-        AZ_A(dW6p, (size_t)c->gemm_parts * azk_weight_plane_elems(n6, (int)K6)); AZ_A(dgscale, 4);
+    c->dgscale = nullptr;
+    if (parts6) {
+        AZ_A(dgscale, 4);
         HIPCHK(c, hipMemsetAsync(c->dgscale, 0, 4 * sizeof(float), c->stream));
     }
     if (!c->head_loaded) { c->d.C = C; c->d.pooled = 7; c->d.K6 = (int)K6; }
     {
         Buf tg;
-        const size_t in7 = r7 ? (size_t)r7 * n6 : (size_t)n7 * n6;
-        HIPCHK(c, tg.reserve(std::max(std::max(rows6 * K6, in7), NO * n7) * 4));
+        HIPCHK(c, tg.reserve(std::max(std::max(in6, in7), NO * n7) * 4));
         float *tmp = tg.as<float>();
-        HIPCHK(c, hipMemcpy(c->dpart, r6 ? L6 : W6, rows6 * K6 * 4, hipMemcpyHostToDevice));
-        azk_permute_k(c->stream, c->dpart, tmp, (long long)rows6, C, 1);          // bin-major columns, like the AZ head
-        azk_tile_weights(c->stream, tmp, r6 ? c->dL6 : c->dW6, (int)rows6, (int)K6);
-        if (c->dW6p) {
-            c->det_w6_scale = 0.f;
-            if (c->gemm_parts == 2) {
-                float mx = 0.f;
-                for (size_t i = 0, n = (size_t)n6 * K6; i < n; ++i) { const float a = fabsf(W6[i]); if (a > mx) mx = a; }
-                c->det_w6_scale = 1.f;
-                if (mx > 0.f && mx < INFINITY) { int e; (void)frexpf(mx, &e); c->det_w6_scale = ldexpf(1.f, 15 - e); }
-            }
-            azk_split_weight_planes(c->stream, tmp, c->dW6p, n6, (int)K6, c->gemm_parts, c->det_w6_scale);
-        }
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipMemcpy(tmp, r7 ? L7 : W7, in7 * 4, hipMemcpyHostToDevice));
-        azk_tile_weights(c->stream, tmp, r7 ? c->dL7 : c->dW7, r7 ? r7 : n7, n6);
-        HIPCHK(c, hipStreamSynchronize(c->stream));
+        // (fc6: bin-major columns, like the AZ head)
+        if ((rc = fc_layer_load(c, f6, L6, W6, b6, C, c->dpart, tmp)) != AZ_OK) return rc;
+        if ((rc = fc_layer_load(c, f7, L7, W7, b7, 0, nullptr, tmp)) != AZ_OK) return rc;
         // rows 0..ncls-1 cls_score, ncls..5*ncls-1 bbox_pred
         HIPCHK(c, hipMemcpy(tmp, Wc, (size_t)ncls * n7 * 4, hipMemcpyHostToDevice));
         HIPCHK(c, hipMemcpy(tmp + (size_t)ncls * n7, Wb, (size_t)4 * ncls * n7 * 4, hipMemcpyHostToDevice));
         azk_tile_weights(c->stream, tmp, c->dWt, (int)NO, n7);
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
-    // the U factors stay row-major [out, r]: the U stage reads Caffe's layout as it is
-    if (r6) HIPCHK(c, hipMemcpy(c->dU6, W6, (size_t)n6 * r6 * 4, hipMemcpyHostToDevice));
-    if (r7) HIPCHK(c, hipMemcpy(c->dU7, W7, (size_t)n7 * r7 * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->db6, b6, (size_t)n6 * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->db7, b7, (size_t)n7 * 4, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(c->dbt, bc, (size_t)ncls * 4, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(c->dbt + ncls, bb, (size_t)4 * ncls * 4, hipMemcpyHostToDevice));
     HIPCHK(c, hipDeviceSynchronize());
@@ -350,15 +323,24 @@ static int load_det_head(az_ctx *c, int C, int n6, int n7, int ncls, int r6, int
     return AZ_OK;
 }
 
+// what az_load_det_head and az_load_det_head_lowrank (`who`) both refuse first; ptrs: every pointer both take is there
+static int det_head_args(az_ctx *c, const char *who, int C, int n6, int n7, int ncls, bool ptrs)
+{
+    if (!c) return AZ_ERR_INVALID;
+    const std::string me(who);
+    if (!ptrs) return fail(c, AZ_ERR_INVALID, me + ": null pointer");
+    if (C <= 0 || (C & 3) || n6 <= 0 || (n6 & 3) || n7 <= 0 || (n7 & 3) || ncls < 2 || ncls > 256)
+        return fail(c, AZ_ERR_INVALID, me + ": C, n6, n7 multiples of 4; 2 <= ncls <= 256");
+    if (c->head_loaded && C != c->d.C) return fail(c, AZ_ERR_INVALID, me + ": C differs from the AZ head's");
+    return AZ_OK;
+}
+
 int az_load_det_head(az_ctx *c, int C, int n6, int n7, int ncls, const float *W6, const float *b6,
                      const float *W7, const float *b7, const float *Wc, const float *bc, const float *Wb,
                      const float *bb)
 {
-    if (!c) return AZ_ERR_INVALID;
-    if (!W6 || !b6 || !W7 || !b7 || !Wc || !bc || !Wb || !bb) return fail(c, AZ_ERR_INVALID, "az_load_det_head: null pointer");
-    if (C <= 0 || (C & 3) || n6 <= 0 || (n6 & 3) || n7 <= 0 || (n7 & 3) || ncls < 2 || ncls > 256)
-        return fail(c, AZ_ERR_INVALID, "az_load_det_head: C, n6, n7 multiples of 4; 2 <= ncls <= 256");
-    if (c->head_loaded && C != c->d.C) return fail(c, AZ_ERR_INVALID, "az_load_det_head: C differs from the AZ head's");
+    const int rc = det_head_args(c, "az_load_det_head", C, n6, n7, ncls, W6 && b6 && W7 && b7 && Wc && bc && Wb && bb);
+    if (rc) return rc;
     return load_det_head(c, C, n6, n7, ncls, 0, 0, nullptr, W6, b6, nullptr, W7, b7, Wc, bc, Wb, bb);
 }
 
@@ -367,12 +349,8 @@ int az_load_det_head_lowrank(az_ctx *c, int C, int n6, int n7, int ncls, int r6,
                              const float *U6, const float *b6, const float *L7, const float *U7, const float *b7,
                              const float *Wc, const float *bc, const float *Wb, const float *bb)
 {
-    if (!c) return AZ_ERR_INVALID;
-    if (!U6 || !b6 || !U7 || !b7 || !Wc || !bc || !Wb || !bb)
-        return fail(c, AZ_ERR_INVALID, "az_load_det_head_lowrank: null pointer");
-    if (C <= 0 || (C & 3) || n6 <= 0 || (n6 & 3) || n7 <= 0 || (n7 & 3) || ncls < 2 || ncls > 256)
-        return fail(c, AZ_ERR_INVALID, "az_load_det_head_lowrank: C, n6, n7 multiples of 4; 2 <= ncls <= 256");
-    if (c->head_loaded && C != c->d.C) return fail(c, AZ_ERR_INVALID, "az_load_det_head_lowrank: C differs from the AZ head's");
+    const int rc = det_head_args(c, "az_load_det_head_lowrank", C, n6, n7, ncls, U6 && b6 && U7 && b7 && Wc && bc && Wb && bb);
+    if (rc) return rc;
     const long long K6 = (long long)C * 49;
     auto rank_ok = [](int r, long long out, long long in) {
         return r == 0 || (r >= 4 && !(r & 3) && r <= out && r <= in && r <= AZ_LOWRANK_MAX);
@@ -434,52 +412,25 @@ static void launch_det_head(az_ctx *c, const int *Uptr, int im_h, int im_w, doub
     d.K6 = K6;
     // many rows (the reference's 300 proposals per image): fc6 / fc7 on the many-row GEMM, as int6 (same bits either way)
     const bool many_rows = rows_bound >= c->gemm12_min_rows;
-    const bool terms = c->gemm_parts && c->dW6p;             // (16-bit-term modes: fc6, 86 % of this head's FLOPs, as int6)
+    const bool terms = c->gemm_parts && c->det_fc6.Wp;             // (16-bit-term modes: fc6, 86 % of this head's FLOPs, as int6)
     if (terms && c->gemm_parts == 2)
-        azk_feat_scale(c->stream, c->feat, (long long)d.C * d.H * d.W, c->dgscale, c->det_w6_scale);
+        azk_feat_scale(c->stream, c->feat, (long long)d.C * d.H * d.W, c->dgscale, c->det_fc6.w_scale);
     if (skip) skip_front_launch(c, Uptr, rows_bound);
     else
     { Timed t(c, "det_roi_pool", 0);
       azk_roi_pool(c->stream, c->feat, d, c->spatial_scale, c->urois, Uptr, c->maxR, c->pool5, terms ? c->pool5p : nullptr,
                    terms ? azk_act_plane_elems(c->maxR, K6) : 0, terms ? c->gemm_parts : 0, 0, 0,
                    (terms && c->gemm_parts == 2) ? c->dgscale : nullptr, feats, feat_hw); }
-    // a truncated-SVD layer: t = L x on the split-K GEMM (its own chunk count, linear slab sum), then the U stage
-    // (dlr_t [maxR][max(r6, r7)] serves both layers: all launches are on c->stream, so fc7_L's slab sum overwrites it only
-    //  after fc6_U has read it; dlr_zero is the zero bias that makes azk_fc_reduce a plain slab sum)
-    auto lowrank =[&](const float *x, int K, const float *L, int SL, int r, const float *U, const float *b, int N, float *y,
-                       const char *nL, const char *nR, const char *nU) {
-        { Timed t(c, nL, 0, 1);
-          azk_fc_gemm(c->stream, x, K, L, K, Uptr, c->maxR, r, K, SL, c->dpart); }
-        { Timed t(c, nR, 0);
-          azk_fc_reduce(c->stream, c->dpart, c->dlr_zero, Uptr, c->maxR, r, SL, c->dlr_t, r, 0); }
-        { Timed t(c, nU, 0, 1);
-          azk_lowrank_gemm(c->stream, c->dlr_t, r, U, b, Uptr, c->maxR, N, r, 1, y, N); }
-    };
-    if (c->det_r6)
-        lowrank(c->pool5, K6, c->dL6, c->det_SL6, c->det_r6, c->dU6, c->db6, c->det_n6, c->dh6, "det_fc6_L",
-                "det_fc6_L_reduce", "det_fc6_U");
-    else {
-        { Timed t(c, "det_fc6_gemm", 0, 1);
-          if (terms)
-              azk_fc_gemm_terms(c->stream, c->pool5p, K6, azk_act_plane_elems(c->maxR, K6), c->dW6p, K6,
-                                azk_weight_plane_elems(c->det_n6, K6), Uptr, c->maxR, c->det_n6, K6, c->det_S6,
-                                azk_fc_chunk(K6, c->det_S6), c->dpart, c->gemm_parts, c->dgscale);
-          else
-              fc_gemm_fp32(c, c->stream, c->pool5, K6, c->dW6, Uptr, c->det_n6, K6, c->det_S6, c->dpart, many_rows); }
-        { Timed t(c, "det_fc6_reduce", 0);
-          azk_fc_reduce(c->stream, c->dpart, c->db6, Uptr, c->maxR, c->det_n6, c->det_S6, c->dh6, c->det_n6, 1); }
-    }
-    if (c->det_r7)
-        lowrank(c->dh6, c->det_n6, c->dL7, c->det_SL7, c->det_r7, c->dU7, c->db7, c->det_n7, c->dh7, "det_fc7_L",
-                "det_fc7_L_reduce", "det_fc7_U");
-    else {
-        { Timed t(c, "det_fc7_gemm", 0, 1);
-          fc_gemm_fp32(c, c->stream, c->dh6, c->det_n6, c->dW7, Uptr, c->det_n7, c->det_n6, c->det_S7, c->dpart, many_rows); }
-        { Timed t(c, "det_fc7_reduce", 0);
-          azk_fc_reduce(c->stream, c->dpart, c->db7, Uptr, c->maxR, c->det_n7, c->det_S7, c->dh7, c->det_n7, 1); }
-    }
+    // (a truncated-SVD layer's L stage stays on k_fc_splitk whatever the row count: its chunk count, azk_lowrank_split, was
+    //  chosen for that kernel.  dlr_t [maxR][max(r6, r7)] serves both layers: all launches are on c->stream, so fc7_L's slab
+    //  sum overwrites it only after fc6_U has read it)
+    const FcLayer &f6 = c->det_fc6, &f7 = c->det_fc7;
+    fc_layer_forward(c, c->stream, f6, {c->pool5, c->pool5p, azk_act_plane_elems(c->maxR, K6), c->dpart, c->dlr_t, c->dh6, c->dgscale},
+                     Uptr, many_rows && !f6.r, {"det_fc6_gemm", "det_fc6_reduce", "det_fc6_L", "det_fc6_L_reduce", "det_fc6_U"}, 0);
+    fc_layer_forward(c, c->stream, f7, {c->dh6, nullptr, 0, c->dpart, c->dlr_t, c->dh7, nullptr},
+                     Uptr, many_rows && !f7.r, {"det_fc7_gemm", "det_fc7_reduce", "det_fc7_L", "det_fc7_L_reduce", "det_fc7_U"}, 0);
     { Timed t(c, "det_tail_gemm", 0, 1);
-      azk_fc_gemm(c->stream, c->dh7, c->det_n7, c->dWt, c->det_n7, Uptr, c->maxR, NO, c->det_n7, AZK_TAIL_SPLIT,
+      azk_fc_gemm(c->stream, c->dh7, f7.N, c->dWt, f7.N, Uptr, c->maxR, NO, f7.N, AZK_TAIL_SPLIT,
                   c->dpart); }
     { Timed t(c, "det_epilogue", 0);
       azk_det_epilogue(c->stream, c->dpart, AZK_TAIL_SPLIT, c->det_ncls, c->dbt, c->ubox, Uptr, c->maxR, im_h, im_w,
@@ -721,7 +672,7 @@ int az_detect_batch(az_ctx *c, int n, const float *const *maps, int C, const int
 {
     if (!c) return AZ_ERR_INVALID;
     if (!c->det_loaded) return fail(c, AZ_ERR_STATE, "az_load_det_head has not been called");
-    if (c->gemm_parts && c->dW6p)
+    if (c->gemm_parts && c->det_fc6.Wp)
         return fail(c, AZ_ERR_STATE, "az_detect_batch: fp32 only (the 16-bit-term modes scale fc6 per map)");
     if (n < 1 || n > AZ_BATCH_MAX) return fail(c, AZ_ERR_INVALID, "az_detect_batch: 1 <= n <= AZ_BATCH_MAX");
     if (!box_off || box_off[0] != 0 || batch_size <= 0 || !scales || !im_hw)
