@@ -16,12 +16,14 @@
 //                   a byte in HBM past that) -> +1 TP / -1 FP / 0 difficult, in input order
 //   k_voc_class     one workgroup per class: npos, cumsum of TP / FP in rank order -> rec, prec; suffix max of prec
 //                   (MATLAB's max ignores NaN: fmax) -> the 11-point AP (metric_07) and xVOCap's area
+// The overlap, the workgroup scan and the curve / AP body live in az_eval_dev.h: az_ddiag.hip (az_det_diag_eval) calls the same.
 // -ffp-contract=off (Makefile): every product and sum rounds once, as MATLAB's double arithmetic does.
 #include "az_ctx.h"
+#include "az_eval_dev.h"
 
 namespace {
 
-constexpr int VT = 256;               // threads of every workgroup here (4 waves)
+constexpr int VT = EVAL_VT;           // threads of every workgroup here (4 waves)
 constexpr int VITEMS = 8;             // rounds of VT elements per radix tile
 constexpr int VTILE = VT * VITEMS;
 
@@ -55,27 +57,6 @@ __device__ __forceinline__ unsigned voc_digit(int mode, int shift, unsigned idx,
     if (mode == 0) return (unsigned)(key[idx] >> shift) & 255u;
     const unsigned s = seg[idx];
     return ((mode == 1 ? s : s / n_images) >> shift) & 255u;
-}
-
-// inclusive scan over the workgroup in thread order; `carry` is combined in front and updated to the total
-template <typename T, typename Op>
-__device__ __forceinline__ T block_scan(T v, T &carry, T *s_w, Op op)
-{
-    const int lane = threadIdx.x & (AZ_WAVE - 1), w = threadIdx.x / AZ_WAVE;
-    for (int d = 1; d < AZ_WAVE; d <<= 1) {
-        const T u = __shfl_up(v, d, AZ_WAVE);
-        if (lane >= d) v = op(u, v);
-    }
-    if (lane == AZ_WAVE - 1) s_w[w] = v;
-    __syncthreads();
-    T pre = carry;
-    for (int k = 0; k < w; ++k) pre = op(pre, s_w[k]);
-    v = op(pre, v);
-    T tot = carry;
-    for (int k = 0; k < VT / AZ_WAVE; ++k) tot = op(tot, s_w[k]);
-    __syncthreads();
-    carry = tot;
-    return v;
 }
 
 __global__ void __launch_bounds__(VT) k_voc_hist(int D, int mode, int shift, const unsigned *__restrict__ perm_in,
@@ -240,13 +221,8 @@ __global__ void __launch_bounds__(VT) k_voc_match(int S, const int *__restrict__
                         const double *q = gt_box + (size_t)(g0 + j) * 4;
                         g0x = q[0]; g0y = q[1]; g1x = q[2]; g1y = q[3];
                     }
-                    const double iw = (b2 < g1x ? b2 : g1x) - (b0 > g0x ? b0 : g0x) + 1.0;
-                    const double ih = (b3 < g1y ? b3 : g1y) - (b1 > g0y ? b1 : g0y) + 1.0;
-                    if (iw > 0.0 && ih > 0.0) {
-                        const double ua = (b2 - b0 + 1.0) * (b3 - b1 + 1.0) + (g1x - g0x + 1.0) * (g1y - g0y + 1.0) - iw * ih;
-                        const double ov = iw * ih / ua;
-                        if (ov > best) { best = ov; bj = j; }     // j ascends per lane: the first box keeps a tie
-                    }
+                    double ov;                                    // j ascends per lane: the first box keeps a tie
+                    if (voc_overlap(b0, b1, b2, b3, g0x, g0y, g1x, g1y, &ov) && ov > best) { best = ov; bj = j; }
                 }
                 for (int o = AZ_WAVE / 2; o > 0; o >>= 1) {
                     const double ob = __shfl_xor(best, o, AZ_WAVE);
@@ -276,13 +252,6 @@ __global__ void __launch_bounds__(VT) k_voc_match(int S, const int *__restrict__
     }
 }
 
-__device__ __forceinline__ double ap_threshold(int k)
-{
-    // MATLAB's 0:0.1:1: the first half a + k*d, the second half b - (n-k)*d, the middle (a+b)/2
-    if (k == 5) return 0.5;
-    return k < 5 ? (double)k * 0.1 : 1.0 - (double)(10 - k) * 0.1;
-}
-
 __global__ void __launch_bounds__(VT) k_voc_class(int n_images, const int *__restrict__ det_off, const int *__restrict__ gt_off,
                                                    const unsigned char *__restrict__ gt_diff, const unsigned *__restrict__ pc,
                                                    const signed char *__restrict__ match, int metric_07,
@@ -307,65 +276,12 @@ __global__ void __launch_bounds__(VT) k_voc_class(int n_images, const int *__res
     }
     __syncthreads();
     const long long npos = s_np;
-    const double dn = (double)npos;
-    // forward: tp | fp packed (each < 2^31), cumsum, rec and prec
-    unsigned long long carry = 0;
-    for (int p0 = lo; p0 < hi; p0 += VT) {
-        const int p = p0 + t;
-        unsigned long long v = 0;
-        if (p < hi) {
-            const int m = match[pc[p]];
-            v = m > 0 ? (1ull << 32) : (m < 0 ? 1ull : 0ull);
-        }
-        v = block_scan(v, carry, s_u, [](unsigned long long a, unsigned long long b) { return a + b; });
-        if (p < hi) {
-            const double tp = (double)(v >> 32), fp = (double)(v & 0xffffffffull);
-            rec[p] = tp / dn;
-            prec[p] = tp / (fp + tp);
-        }
-    }
-    __syncthreads();
-    // backward: suffix max of prec, NaN ignored unless every value is NaN (MATLAB's max)
-    double dcarry = NAN;
-    for (int p1 = hi; p1 > lo; p1 -= VT) {
-        const int p = p1 - 1 - t;
-        double v = p >= lo ? prec[p] : NAN;
-        v = block_scan(v, dcarry, s_d, [](double a, double b) { return fmax(a, b); });
-        if (p >= lo) smax[p] = v;
-    }
-    __syncthreads();
-    // xVOCap: mrec = [0; rec; 1], mpre = running max of [0; prec; 0] from the end; sum where mrec changes
-    double part = 0.0;
-    for (int p = lo + t; p < hi; p += VT) {
-        const double prev = p > lo ? rec[p - 1] : 0.0;
-        if (rec[p] != prev) part += (rec[p] - prev) * fmax(smax[p], 0.0);
-    }
-    {
-        double zero = 0.0;
-        block_scan(part, zero, s_d, [](double a, double b) { return a + b; });
-        part = zero;
-    }
+    double ap = 0.0, part = 0.0;
+    voc_curve_ap(lo, hi, npos, metric_07, [&](int p) -> unsigned long long {
+        const int m = match[pc[p]];
+        return m > 0 ? (1ull << 32) : (m < 0 ? 1ull : 0ull);
+    }, rec, prec, smax, s_u, s_d, &ap, &part);
     if (t == 0) {
-        const double last = hi > lo ? rec[hi - 1] : 0.0;
-        if (last != 1.0) part += (1.0 - last) * 0.0;
-        double ap = 0.0;
-        if (metric_07) {
-            for (int k = 0; k <= 10; ++k) {
-                const double th = ap_threshold(k);
-                double pk = 0.0;
-                if (npos > 0) {                               // npos = 0: rec is NaN, no rec >= t
-                    int a = lo, b = hi;                       // first p with rec[p] >= th (rec ascends)
-                    while (a < b) {
-                        const int mid = a + ((b - a) >> 1);
-                        if (rec[mid] >= th) b = mid; else a = mid + 1;
-                    }
-                    if (a < hi) pk = smax[a];
-                }
-                ap = ap + pk / 11.0;
-            }
-        } else {
-            ap = part;
-        }
         npos_out[c] = npos;
         ap_out[c] = ap;
         auc_out[c] = part;

@@ -66,6 +66,7 @@ SYMBOLS = [
     "az_load_det_head_lowrank", "az_lowrank_gemm_unit", "az_lowrank_split",
     "az_load_head_lowrank", "az_az_lowrank_split",
     "az_detect_iter", "az_detect_iter_skip",
+    "az_det_diag_eval",
 ]
 AZ_ITER_LOC_MAX_ROUNDS = 8  # include/aznet_hip.h
 AZ_ITER_LOC_MAX_ROWS = 4096  # include/aznet_hip.h (az_detect_iter: az_topk's largest k)
@@ -261,6 +262,9 @@ def load_library(path=None):
     L.az_diag_eval.argtypes = [vp, ci, dp, fp, ip, ip, ctypes.c_longlong, dp, ip, ctypes.c_longlong, dp, ip,
                                ctypes.c_longlong, cd, cd, cd, cd, ip, ci, dp, u8p, ctypes.POINTER(ctypes.c_int64), dp, ip, ip,
                                ip, ctypes.POINTER(ctypes.c_int64), fp]
+    i64p = ctypes.POINTER(ctypes.c_int64)
+    L.az_det_diag_eval.argtypes = [vp, ci, ci, dp, dp, ip, dp, u8p, ip, cd, cd, ci, ip, dp, ci, ctypes.POINTER(ctypes.c_int8),
+                                   dp, ip, dp, ip, u8p, ip, i64p, i64p, i64p, i64p, dp, fp]
     L.az_zoom_labels.argtypes = [vp, dp, ci, dp, ci, cd, cd, u8p]
     L.az_train_ex_rois.argtypes = [vp, tpp, ci, ip, dp, ip, dp, ll, fp, u8p, ip, ci, llp, llp]
     L.az_train_adj_targets.argtypes = [vp, tpp, ci, fp, ip, fp, ip, dp, ip, ci]
@@ -1623,6 +1627,55 @@ class AzContext(object):
             _p(out["deepest_level"], ctypes.c_int32), _p(out["recall_table"], ctypes.c_int64),
             ctypes.byref(ms) if want_kernel_ms else None))
         out.update(anc_off=aoff, gt_off=goff, prop_off=poff, cuts=ct.copy())
+        if want_kernel_ms:
+            out["kernel_ms"] = float(ms.value)
+        return out
+
+    # ---- detection diagnosis (Hoiem et al. 2012 / TIDE 2020 on az_voc_eval's layout) ---------
+    def det_diag_eval(self, n_classes, n_images, det_box, det_conf, det_off, gt_box, gt_difficult, gt_off,
+                      min_overlap=0.5, bg_overlap=0.1, metric_07=True, class_group=None, cuts=(), want_kernel_ms=False):
+        """az_det_diag_eval ("Detection diagnosis") on voc_eval's arguments, plus bg_overlap, class_group
+        [C] int32 (None: every class its own group) and cuts (finite, ascending multiples of npos, at most 16).  Returns a
+        dict: per detection in input order type [D] int8 (0 IGN, 1 TP, 2 DUP, 3 LOC, 4 SIM, 5 OTH, 6 BG), ov_same /
+        ov_other [D] f64, arg_same / other_class [D] int32, loc_fixed [D] u8; gt_claim [G] int32; per class type_table
+        [C,7], miss [C], fp_at [C,len(cuts),7], npos [C] int64 and ap_fix [C,8]; with want_kernel_ms the kernels'
+        device time."""
+        bx = _f64(det_box).reshape(-1, 4)
+        cf = _f64(det_conf).ravel()
+        doff = np.ascontiguousarray(det_off, dtype=np.int32).ravel()
+        gb = _f64(gt_box).reshape(-1, 4)
+        gd = np.ascontiguousarray(gt_difficult, dtype=np.uint8).ravel()
+        goff = np.ascontiguousarray(gt_off, dtype=np.int32).ravel()
+        C = int(n_classes)
+        nseg = C * int(n_images)
+        if doff.size != nseg + 1 or goff.size != nseg + 1:
+            raise AzError(AZ_ERR_INVALID, "det_diag_eval: offsets need n_classes*n_images+1 entries")
+        D, G = int(doff[-1]), int(goff[-1])
+        if bx.shape[0] != D or cf.size != D or gb.shape[0] != G or gd.size != G:
+            raise AzError(AZ_ERR_INVALID, "det_diag_eval: array sizes disagree with the offsets")
+        grp = None
+        if class_group is not None:
+            grp = np.ascontiguousarray(class_group, dtype=np.int32).ravel()
+            if grp.size != C:
+                raise AzError(AZ_ERR_INVALID, "det_diag_eval: class_group needs n_classes entries")
+        ct = _f64(cuts).ravel()
+        if not np.isfinite(ct).all():
+            raise AzError(AZ_ERR_INVALID, "det_diag_eval: the cuts must be finite")
+        out = {"type": np.zeros(D, np.int8), "ov_same": np.zeros(D), "arg_same": np.zeros(D, np.int32),
+               "ov_other": np.zeros(D), "other_class": np.zeros(D, np.int32), "loc_fixed": np.zeros(D, np.uint8),
+               "gt_claim": np.zeros(G, np.int32), "type_table": np.zeros((C, 7), np.int64), "miss": np.zeros(C, np.int64),
+               "fp_at": np.zeros((C, ct.size, 7), np.int64), "npos": np.zeros(C, np.int64), "ap_fix": np.zeros((C, 8))}
+        ms = ctypes.c_float(0.0)
+        i64 = ctypes.c_int64
+        self._chk(self.L.az_det_diag_eval(
+            self.h, C, int(n_images), _p(bx, ctypes.c_double), _p(cf, ctypes.c_double), _p(doff, ctypes.c_int32),
+            _p(gb, ctypes.c_double), _p(gd, ctypes.c_uint8), _p(goff, ctypes.c_int32), float(min_overlap), float(bg_overlap),
+            1 if metric_07 else 0, None if grp is None else _p(grp, ctypes.c_int32), _p(ct, ctypes.c_double), ct.size,
+            _p(out["type"], ctypes.c_int8), _p(out["ov_same"], ctypes.c_double), _p(out["arg_same"], ctypes.c_int32),
+            _p(out["ov_other"], ctypes.c_double), _p(out["other_class"], ctypes.c_int32), _p(out["loc_fixed"], ctypes.c_uint8),
+            _p(out["gt_claim"], ctypes.c_int32), _p(out["type_table"], i64), _p(out["miss"], i64), _p(out["fp_at"], i64),
+            _p(out["npos"], i64), _p(out["ap_fix"], ctypes.c_double), ctypes.byref(ms) if want_kernel_ms else None))
+        out["cuts"] = ct.copy()
         if want_kernel_ms:
             out["kernel_ms"] = float(ms.value)
         return out

@@ -81,22 +81,65 @@ def gt_segments(classes, recs):
     return np.ascontiguousarray(a[:, :4]), a[:, 4].astype(np.uint8), np.array(off, np.int64)
 
 
-def evaluate(n_images, classes, dets, gt_box, gt_diff, gt_off, metric_07=True, min_overlap=MIN_OVERLAP, ctx=None):
-    """dets: per class (image number, conf, boxes) as read_results_file returns them.  Detections are grouped by
-    image with a stable sort (a results file written by image order is unchanged by it).  -> az_voc_eval's dict,
-    with per-class slices of rec / prec."""
+def rounded(dets):
+    """('%.3f' score, '%.1f' of x + 1) of [n,5] detections parsed back: the values a results file carries."""
+    sc = np.array(["{:.3f}".format(v) for v in dets[:, -1].tolist()], dtype=object).astype(np.bytes_).astype(np.float64)
+    b = dets[:, 0:4] + 1
+    bx = np.array(["{:.1f}".format(v) for v in b.ravel().tolist()], dtype=object).astype(np.bytes_).astype(np.float64)
+    return sc, bx.reshape(-1, 4)
+
+
+def roidb_records(imdb):
+    """load_records' layout from any imdb's gt_roidb: 1-based boxes, difficult taken as 0, background rows left out."""
+    roidb = imdb.gt_roidb()
+    recs = []
+    for i in range(imdb.num_images):
+        e = roidb[i]
+        recs.append([(imdb.classes[int(k)], [float(v) + 1 for v in b], 0)
+                     for b, k in zip(np.asarray(e["boxes"], np.float64), e["gt_classes"]) if int(k) > 0])
+    return recs
+
+
+def all_boxes_dets(imdb, all_boxes):
+    """test_net's all_boxes[class][image] ([n,5] or []) -> per class (image number, conf, boxes), rounded as the
+    class's results file would hold them and in its order; [] and empty entries are skipped, as the file skips them."""
+    dets = []
+    for j in range(1, imdb.num_classes):
+        img, conf, box = [], [], []
+        for i in range(imdb.num_images):
+            d = all_boxes[j][i]
+            if isinstance(d, list) or d.shape[0] == 0:
+                continue
+            sc, bx = rounded(np.asarray(d))
+            img.append(np.full(sc.size, i, np.int64))
+            conf.append(sc)
+            box.append(bx)
+        dets.append((np.concatenate([np.zeros(0, np.int64)] + img), np.concatenate([np.zeros(0)] + conf),
+                     np.vstack([np.zeros((0, 4))] + box)))
+    return dets
+
+
+def det_segments(n_images, dets):
+    """dets: per class (image number, conf, boxes) as read_results_file returns them -> (boxes [D,4], conf [D], off) in
+    az_voc_eval's class-major layout.  Detections are grouped by image with a stable sort (a results file written by
+    image order is unchanged by it)."""
     boxes, confs, off = [], [], [0]
     for img, conf, box in dets:
         o = np.argsort(img, kind="stable")
         boxes.append(box[o])
         confs.append(conf[o])
         off.extend((off[-1] + np.cumsum(np.bincount(img, minlength=n_images)[:n_images])).tolist())
-    det_off = np.array(off, np.int64)
+    return np.vstack([np.zeros((0, 4))] + boxes), np.concatenate([np.zeros(0)] + confs), np.array(off, np.int64)
+
+
+def evaluate(n_images, classes, dets, gt_box, gt_diff, gt_off, metric_07=True, min_overlap=MIN_OVERLAP, ctx=None):
+    """dets: per class (image number, conf, boxes) as read_results_file returns them (det_segments lays them out).
+    -> az_voc_eval's dict, with per-class slices of rec / prec."""
+    det_box, det_conf, det_off = det_segments(n_images, dets)
     if det_off[-1] >= 2 ** 31 or gt_off[-1] >= 2 ** 31:
         raise ffi.AzError(ffi.AZ_ERR_CAPACITY, "voc_eval: more than int32 detections")
     ctx = ctx or ffi.default_context()
-    r = ctx.voc_eval(len(classes), n_images, np.vstack([np.zeros((0, 4))] + boxes), np.concatenate([np.zeros(0)] + confs),
-                     det_off, gt_box, gt_diff, gt_off, min_overlap, metric_07)
+    r = ctx.voc_eval(len(classes), n_images, det_box, det_conf, det_off, gt_box, gt_diff, gt_off, min_overlap, metric_07)
     r["class_off"] = det_off[::n_images] if n_images else np.zeros(len(classes) + 1, np.int64)
     return r
 

@@ -11,43 +11,15 @@ import argparse
 import os
 import pickle
 
-import numpy as np
-
 import _cli
-
-
-def _rounded(dets):
-    """('%.3f' score, '%.1f' of x + 1) parsed back: the values a results file carries."""
-    sc = np.array(["{:.3f}".format(v) for v in dets[:, -1].tolist()], dtype=object).astype(np.bytes_).astype(np.float64)
-    b = dets[:, 0:4] + 1
-    bx = np.array(["{:.1f}".format(v) for v in b.ravel().tolist()], dtype=object).astype(np.bytes_).astype(np.float64)
-    return sc, bx.reshape(-1, 4)
 
 
 def eval_on_roidb(imdb, all_boxes, output_dir):
     from datasets import voc_eval
     classes = [c for c in imdb.classes if c != "__background__"]
-    roidb = imdb.gt_roidb()
     n = imdb.num_images
-    recs = []
-    for i in range(n):
-        e = roidb[i]
-        recs.append([(imdb.classes[int(k)], [float(v) + 1 for v in b], 0)
-                     for b, k in zip(np.asarray(e["boxes"], np.float64), e["gt_classes"]) if int(k) > 0])
-    gb, gd, goff = voc_eval.gt_segments(classes, recs)
-    dets = []
-    for j in range(1, imdb.num_classes):
-        img, conf, box = [], [], []
-        for i in range(n):
-            d = all_boxes[j][i]
-            if isinstance(d, list) or d.shape[0] == 0:
-                continue
-            sc, bx = _rounded(np.asarray(d))
-            img.append(np.full(sc.size, i, np.int64))
-            conf.append(sc)
-            box.append(bx)
-        dets.append((np.concatenate([np.zeros(0, np.int64)] + img), np.concatenate([np.zeros(0)] + conf),
-                     np.vstack([np.zeros((0, 4))] + box)))
+    gb, gd, goff = voc_eval.gt_segments(classes, voc_eval.roidb_records(imdb))
+    dets = voc_eval.all_boxes_dets(imdb, all_boxes)
     r = voc_eval.evaluate(n, classes, dets, gb, gd, goff, metric_07=True)
     os.makedirs(output_dir, exist_ok=True)
     lines, tail = voc_eval.report(classes, r["ap"], r["ap_auc"])

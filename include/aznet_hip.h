@@ -704,6 +704,54 @@ int az_diag_eval(az_ctx *ctx, int n_images,
                  uint8_t *anchor_label_out, int64_t *level_table_out, double *gt_best_iou_out, int32_t *gt_best_rank_out,
                  int32_t *gt_first_hit_out, int32_t *gt_deepest_level_out, int64_t *recall_table_out, float *kernel_ms_out);
 
+/* ---- detection diagnosis (Hoiem et al., ECCV 2012; TIDE, Bolya et al., ECCV 2020) ------------------------------- */
+/* Why a VOC evaluation's AP is what it is, restated in DESIGN §4, "Detection diagnosis", in one call over a whole set.
+ * The segments, the ranking (stable -confidence per class) and the overlap are az_voc_eval's.  New inputs: bg_overlap
+ * (Hoiem's 0.1), class_group[n_classes] (int32; NULL: every class is its own group), cuts[n_cuts] (f64, finite, ascending,
+ * n_cuts <= 16).  Per detection d of segment (c, i), in input order; every output may be NULL:
+ *   ov_same_out [D] f64 / arg_same_out [D] i32     the largest overlap with the segment's boxes (difficult ones too; pairs
+ *                                with iw > 0 and ih > 0 only; the first maximum) and that box's position in the segment;
+ *                                0.0 / -1 where nothing overlaps
+ *   ov_other_out [D] f64 / other_class_out [D] i32 the same over image i's boxes of every class c' != c, the first maximum
+ *                                in (class, position) order, and that box's class
+ *   type_out [D] i8              the first that fits, in each class's rank order:
+ *                                0 IGN  ov_same >= min_overlap and the box is difficult
+ *                                1 TP   ... not difficult and unclaimed: the box is claimed (gt_claim = d)
+ *                                2 DUP  ... not difficult and claimed already
+ *                                3 LOC  ov_same >= bg_overlap
+ *                                4 SIM  ov_other >= bg_overlap and class_group[c] == class_group[other_class]
+ *                                5 OTH  ov_other >= bg_overlap, another group
+ *                                6 BG   anything else
+ *                                TP / IGN / the rest are az_voc_eval's match 1 / 0 / -1
+ *   loc_fixed_out [D] u8         TIDE's rule, after the segment's matching: a LOC row, in rank order, is fixed when its
+ *                                arg_same box is not difficult, no detection claimed it (a lower-ranked TP counts) and no
+ *                                higher-ranked LOC row was fixed onto it
+ *   gt_claim_out [G] i32         the input index of the detection that claimed the box, or -1
+ * Per class:
+ *   type_table_out [n_classes][7] i64   the count of each type
+ *   miss_out [n_classes] i64     non-difficult boxes that nothing claimed;  npos_out [n_classes] i64: non-difficult boxes
+ *   fp_at_out [n_classes][n_cuts][7] i64   the types of the class's first min(floor(cuts[k] * (double)npos), its
+ *                                detections) detections in rank order
+ *   ap_fix_out [n_classes][8] f64   the class's AP by k_voc_class's arithmetic (11-point with metric_07, else the area)
+ *                                under 0 plain; 1 DUP rows removed (neither TP nor FP); 2 LOC rows: the fixed ones TP, the
+ *                                others removed; 3 SIM / 4 OTH / 5 BG removed; 6 missed objects removed (npos = the TP
+ *                                count; no TP: NaN under the area metric); 7 all of these (npos = TP + fixed rows)
+ *   kernel_ms_out [1] f32        device time of the launches (two events around them)
+ * Offsets are validated as az_voc_eval validates them (same codes); a NaN threshold, bg_overlap < 0,
+ * bg_overlap > min_overlap, n_cuts > 16 and negative, NaN, infinite or descending cuts are AZ_ERR_INVALID; all before any device
+ * work and with the outputs untouched.  After AZ_ERR_HIP the per-detection and per-box outputs are undefined (the
+ * per-class tables are written only on success).  D = 0 and G = 0 are valid.  Device scratch is kept in the context (the slot
+ * az_voc_eval uses: the two never overlap). */
+int az_det_diag_eval(az_ctx *ctx, int n_classes, int n_images,
+                     const double *det_box, const double *det_conf, const int32_t *det_off,
+                     const double *gt_box, const uint8_t *gt_difficult, const int32_t *gt_off,
+                     double min_overlap, double bg_overlap, int metric_07,
+                     const int32_t *class_group, const double *cuts, int n_cuts,
+                     int8_t *type_out, double *ov_same_out, int32_t *arg_same_out,
+                     double *ov_other_out, int32_t *other_class_out, uint8_t *loc_fixed_out,
+                     int32_t *gt_claim_out, int64_t *type_table_out, int64_t *miss_out,
+                     int64_t *fp_at_out, int64_t *npos_out, double *ap_fix_out, float *kernel_ms_out);
+
 /* ---- image front-end (_get_image_blob, lib/detect/test.py:27-59) ------------------------- */
 /* uint8 BGR HWC image (host) -> float32 [3, oh, ow] blob: subtract cfg.PIXEL_MEANS, then
  * cv2.resize(fx=fy=scale, INTER_LINEAR) semantics on f32 (half-pixel centres, edge clamp,
