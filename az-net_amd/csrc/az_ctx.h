@@ -2,7 +2,7 @@
 // az_ctx.hip (the shared host helpers), az_capi.hip (lifecycle, head, maps, lanes, public launch / fetch, measurement,
 // exchange), az_plan.hip / az_shape.hip / az_search.hip / az_batch.hip (the forms of a search: cost model and planner,
 // per-shape caches, launch sequence and collecting a result, lockstep batches; az_search.h), az_units.hip (unit entry points,
-// detection head, tuner, recall, front-end), az_nms.hip (NMS).  Only what must be visible at the call site has a body here.
+// tuner, recall, front-end), az_detect.hip (the detection head: loaders, one pass, the az_detect* entries), az_nms.hip (NMS).  Only what must be visible at the call site has a body here.
 // Who owns what: az_res.h.  Every allocation, pinned block, event and stream below is held by an owner (DevList, Buf, Event,
 // Stream, EventPool) that releases it when the context is deleted; the raw pointers beside them are views.
 #pragma once
@@ -558,6 +558,11 @@ int scratch_grow(az_ctx *c, int i, size_t bytes);   // scratch slot i of the eva
 void join_s2(az_ctx *c);                  // `stream` behind everything enqueued on the second and third streams
 int check_geom(az_ctx *c);                // what a geometry entry point starts with: join_s2 + ensure_geom
 int check_ready(az_ctx *c, bool need_feat, bool join = true);     // ... a head entry point: the head loaded (a map set)
+// ---- az_units.hip (shared with az_detect.hip) ---------------------------------------------------------------------------
+// the prologue of the entries that take P boxes: counters cleared, the boxes in B[0], P[0] = P
+int upload_boxes(az_ctx *c, const double *boxes, int P);
+// ... of those that take R rois [R][5]: checked ("bad rois" / "too many rois"), counters cleared, the rois in urois, ubox zeroed, U[0] = R
+int stage_rois(az_ctx *c, const float *rois, int R);
 // ---- az_search.hip ------------------------------------------------------------------------------------------------------
 // one search enqueued on THIS context's stream / its result collected (idx: position in c->pend) / its record staged
 int launch_impl(az_ctx *c, const az_params *p);

@@ -1,7 +1,7 @@
 // az_pyramid.hip -- multi-scale test pyramids (cfg.TEST.SCALES with several entries): the pyramid's arguments, its map
 // set and the pyramid search.  The search is the plain level loop of az_search.hip with the pyramid projection of
 // k_first_rois (az_geom.hip, pyramid_roi_and_key in az_geom_dev.h) and RoIPool through the map table (az_ctx.h: pyr_now);
-// the detection entries share their bodies with their single-scale twins in az_units.hip.
+// the detection entries share their bodies with their single-scale twins in az_units.hip and az_detect.hip.
 #include "az_ctx.h"
 
 int pyramid_args(az_ctx *c, const double *scales, int S, AzPyrScales *sc, const char *who)

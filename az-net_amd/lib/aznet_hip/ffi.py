@@ -1084,26 +1084,32 @@ class AzContext(object):
                                               M, N, K, 1 if relu else 0, _p(Y, ctypes.c_float)))
         return Y[:M]
 
-    def det_forward(self, rois):
+    def _det_forward(self, fn, rois):
+        """az_det_forward / az_det_forward_skip (fn): the head alone on rois [R, 5]."""
         rois = _f32(rois).reshape(-1, 5)
         R = rois.shape[0]
         nc = self.det_dims["ncls"]
         p = np.empty((max(R, 1), nc), dtype=np.float32)
         b = np.empty((max(R, 1), 4 * nc), dtype=np.float32)
-        self._chk(self.L.az_det_forward(self.h, _p(rois, ctypes.c_float), R, _p(p, ctypes.c_float),
-                                        _p(b, ctypes.c_float)))
+        self._chk(fn(self.h, _p(rois, ctypes.c_float), R, _p(p, ctypes.c_float), _p(b, ctypes.c_float)))
         return p[:R], b[:R]
+
+    def det_forward(self, rois):
+        return self._det_forward(self.L.az_det_forward, rois)
 
     def detect(self, boxes, scale, im_h, im_w, dedup=1. / 16., batch_size=10000, eps=1e-14):
         return self._detect(self.L.az_detect, (float(scale),), boxes, im_h, im_w, dedup, batch_size, eps)
 
+    def _det_out(self, P):
+        """The detections of P boxes as the az_detect* entries write them: (scores [P, ncls] f32, boxes [P, 4 ncls] f64)."""
+        nc = self.det_dims["ncls"]
+        return np.empty((max(P, 1), nc), dtype=np.float32), np.empty((max(P, 1), 4 * nc), dtype=np.float64)
+
     def _detect(self, fn, proj, boxes, im_h, im_w, dedup, batch_size, eps):
-        """az_detect / az_detect_pyramid (fn), proj: the arguments that name the scale or the pyramid."""
+        """az_detect / az_detect_skip / az_detect_pyramid (fn), proj: the arguments that name the scale or the pyramid."""
         boxes = _f64(boxes).reshape(-1, 4)
         P = boxes.shape[0]
-        nc = self.det_dims["ncls"]
-        s = np.empty((max(P, 1), nc), dtype=np.float32)
-        b = np.empty((max(P, 1), 4 * nc), dtype=np.float64)
+        s, b = self._det_out(P)
         self._chk(fn(self.h, _p(boxes, ctypes.c_double), P, *proj, float(dedup), int(batch_size), int(im_h), int(im_w),
                      float(eps), _p(s, ctypes.c_float), _p(b, ctypes.c_double)))
         return s[:P], b[:P]
@@ -1170,13 +1176,11 @@ class AzContext(object):
         3, ...), score (float32), box ([., 4] float64), and count (int32 [rounds - 1]: the rows of each round)."""
         boxes = _f64(boxes).reshape(-1, 4)
         P = boxes.shape[0]
-        nc = self.det_dims["ncls"]
         rounds, max_rows = int(rounds), int(max_rows)
         # (sized only for arguments the entry accepts: anything else it refuses before it touches a buffer)
         ok = 1 <= rounds <= AZ_ITER_LOC_MAX_ROUNDS and 1 <= max_rows <= AZ_ITER_LOC_MAX_ROWS
         cap = max((rounds - 1) * max_rows, 1) if ok else 1
-        s = np.empty((max(P, 1), nc), dtype=np.float32)
-        b = np.empty((max(P, 1), 4 * nc), dtype=np.float64)
+        s, b = self._det_out(P)
         cls = np.empty(cap, dtype=np.int32)
         src = np.empty(cap, dtype=np.int32)
         sc = np.empty(cap, dtype=np.float32)
@@ -1194,14 +1198,7 @@ class AzContext(object):
         return s[:P], b[:P], extra
 
     def det_forward_skip(self, rois):
-        rois = _f32(rois).reshape(-1, 5)
-        R = rois.shape[0]
-        nc = self.det_dims["ncls"]
-        p = np.empty((max(R, 1), nc), dtype=np.float32)
-        b = np.empty((max(R, 1), 4 * nc), dtype=np.float32)
-        self._chk(self.L.az_det_forward_skip(self.h, _p(rois, ctypes.c_float), R, _p(p, ctypes.c_float),
-                                             _p(b, ctypes.c_float)))
-        return p[:R], b[:R]
+        return self._det_forward(self.L.az_det_forward_skip, rois)
 
     def skip_pool(self, rois, normalise=True):
         """concat5 of the rois, [R*49, sum Cs] (row = roi * 49 + bin): the raw ROIPooling maxima (normalise=False) or

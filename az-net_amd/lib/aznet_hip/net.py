@@ -193,7 +193,58 @@ class HipAZNet(_NetDict):
         return out
 
 
-class HipDetNet(_NetDict):
+class _DetNet(_NetDict):
+    """What HipDetNet and HipFrcnnNet share: the detection head and the optional skip front in self.ctx, and `run`, the one
+    place that binds the maps (HipDetNet | HipFrcnnNet) and chooses the AzContext entry of a detection call:
+        several scales    set_pyramid | set_feature_pyramid(maps)            detect_pyramid (refine: refused by _frcnn_forward)
+        one, skip front   set_skip_conv | set_skip_maps                      detect_skip, refine: detect_iter(skip=True)
+        one               set_conv | refine: set_feature_pyramid([conv])     detect | one-image detect_batch, refine: detect_iter
+    det_head may carry truncated-SVD factors (L6, U6 and / or L7, U7 in place of W6 / W7: aznet_hip.compress, or
+    caffemodel.det_head_from_layers of a file written by tools/compress_net.py): it is loaded through
+    az_load_det_head_lowrank and every entry runs the compressed layers (fp32 contexts only)."""
+
+    def _load(self, det_head, skip_front, name):
+        """skip_front: the skip-connection detector's front (synth.make_skip_front / caffemodel.skip_front_from_layers;
+        default: det_head["skip_front"], which caffemodel.det_head_from_layers sets for a file with conv_pool5)."""
+        self.ctx.load_det_head(det_head)           # (a dict with L / U factors: AzContext.load_det_head_lowrank)
+        if skip_front is None:
+            skip_front = det_head.get("skip_front") if isinstance(det_head, dict) else None
+        self.num_classes = self.ctx.det_dims["ncls"]
+        self.name = name
+        self.blobs = {k: _Blob() for k in ("data", "rois", "conv5_3")}
+        self.skip_front, self.skip_names, self._skip_maps = None, None, None
+        if skip_front is not None:
+            self.attach_skip_front(skip_front)
+
+    def attach_skip_front(self, front):
+        """Load `front` into the net's context; compute_conv then returns the maps it names."""
+        self.ctx.load_skip_front(front)
+        self.skip_front, self.skip_names, self._skip_maps = front, _skip_names(front), None
+
+    def run(self, boxes, scales, im_shape, args, maps=None, refine=None, pyramid=None):
+        """One detection call: (scores, boxes, extra-or-None).  scales: the list of test scales (several, or pyramid=True:
+        over the pyramid set); args = (dedup, batch_size, eps); maps: what to bind first (_bind; None: what the context
+        holds); refine = (rounds, min_score, max_rows): iterative localisation, extra as AzContext.detect_iter returns it."""
+        dedup, batch_size, eps = args
+        kw = dict(dedup=dedup, batch_size=batch_size, eps=eps)
+        h, w = im_shape[0], im_shape[1]
+        skip = self.skip_front is not None
+        if pyramid is None:
+            pyramid = len(scales) > 1
+        if maps is not None:
+            self._bind(maps, pyramid, refine is not None)
+        if pyramid:
+            s, b = self.ctx.detect_pyramid(boxes, scales, h, w, **kw)
+        elif refine is not None:
+            return self.ctx.detect_iter(boxes, scales[0], h, w, *refine, skip=skip, **kw)
+        elif skip:
+            s, b = self.ctx.detect_skip(boxes, scales[0], h, w, **kw)
+        else:
+            s, b = self._detect_one(maps, boxes, scales[0], im_shape, kw)
+        return s, b, None
+
+
+class HipDetNet(_DetNet):
     """Fast R-CNN detection net on the shared conv map: stands where the reference's
     `frcnn_nets = {'fc': caffe.Net(frcnn/test_fc.prototxt, ...)}` stood (tools/test_shared.py).
     It shares the AZ net's az_ctx, so both heads read the same channel-last map in HBM.
@@ -201,29 +252,15 @@ class HipDetNet(_NetDict):
     NAMES = ("fc",)
 
     def __init__(self, det_head, az_net, name="vgg16_frcnn_hip", skip_front=None):
-        """skip_front: the skip-connection detector's front (synth.make_skip_front / caffemodel.skip_front_from_layers;
-        default: det_head["skip_front"], which caffemodel.det_head_from_layers sets for a file with conv_pool5):
-        the head then pools every roi from the maps the front names (cfg.SEAR.FRCNN_CONV) instead of conv5_3 alone, and
-        the shared AZ net's compute_conv returns those maps.
-        det_head may carry truncated-SVD factors (L6, U6 and / or L7, U7 in place of W6 / W7: aznet_hip.compress, or
-        caffemodel.det_head_from_layers of a file written by tools/compress_net.py): it is loaded through
-        az_load_det_head_lowrank and every entry below runs the compressed layers (fp32 contexts only)."""
+        """With a skip front the head pools every roi from the maps the front names (cfg.SEAR.FRCNN_CONV) instead of
+        conv5_3 alone, and the shared AZ net's compute_conv returns those maps."""
         self.ctx = az_net.ctx
         self.az_net = az_net
-        self.ctx.load_det_head(det_head)           # (a dict with L / U factors: AzContext.load_det_head_lowrank)
-        if skip_front is None:
-            skip_front = det_head.get("skip_front") if isinstance(det_head, dict) else None   # (caffemodel.det_head_from_layers of a skip model)
-        self.num_classes = self.ctx.det_dims["ncls"]
-        self.name = name
-        self.skip_front, self.skip_names, self._skip_maps = None, None, None
-        if skip_front is not None:
-            self.attach_skip_front(skip_front)
-        self.blobs = {k: _Blob() for k in ("data", "rois") + (self.skip_names or ("conv5_3",))}
+        self._load(det_head, skip_front, name)
 
     def attach_skip_front(self, front):
         """Load `front` into the shared context and make the AZ net's compute_conv return the maps it names."""
-        self.ctx.load_skip_front(front)
-        self.skip_front, self.skip_names, self._skip_maps = front, _skip_names(front), None
+        _DetNet.attach_skip_front(self, front)
         self.az_net.taps = self.skip_names[:-1]
         self.blobs = {k: _Blob() for k in ("data", "rois") + self.skip_names}
 
@@ -236,21 +273,26 @@ class HipDetNet(_NetDict):
             self._skip_maps = maps
             self.az_net._conv = maps[-1]
 
-    def detect(self, boxes, scale, im_shape, dedup, batch_size, eps):
+    def _bind(self, maps, pyramid, iterative):
+        """maps: the {name: map} dict of the skip model, or conv5_3 / the pyramid's list of maps; bound unless it is bound."""
         if self.skip_front is not None:
-            return self.ctx.detect_skip(boxes, scale, im_shape[0], im_shape[1], dedup=dedup, batch_size=batch_size, eps=eps)
-        return self.ctx.detect(boxes, scale, im_shape[0], im_shape[1], dedup=dedup, batch_size=batch_size, eps=eps)
+            self.set_skip_conv(maps)
+        elif maps is not self.az_net._conv:
+            (self.az_net.set_pyramid if pyramid else self.az_net.set_conv)(maps)
+
+    def _detect_one(self, maps, boxes, scale, im_shape, kw):
+        return self.ctx.detect(boxes, scale, im_shape[0], im_shape[1], **kw)
+
+    def detect(self, boxes, scale, im_shape, dedup, batch_size, eps):
+        return self.run(boxes, [scale], im_shape, (dedup, batch_size, eps))[:2]
 
     def detect_iter(self, boxes, scale, im_shape, dedup, batch_size, eps, rounds, min_score, max_rows):
-        """detect() followed by rounds - 1 rounds of iterative localisation (az_detect_iter / az_detect_iter_skip):
-        (scores, boxes, extra), see AzContext.detect_iter."""
-        return self.ctx.detect_iter(boxes, scale, im_shape[0], im_shape[1], rounds, min_score, max_rows, dedup=dedup,
-                                    batch_size=batch_size, eps=eps, skip=self.skip_front is not None)
+        """detect() followed by rounds - 1 rounds of iterative localisation: (scores, boxes, extra), see AzContext.detect_iter."""
+        return self.run(boxes, [scale], im_shape, (dedup, batch_size, eps), refine=(rounds, min_score, max_rows))
 
     def detect_pyramid(self, boxes, scales, im_shape, dedup, batch_size, eps):
         """_frcnn_forward over the pyramid set the shared context holds (HipAZNet.compute_pyramid / set_pyramid)."""
-        return self.ctx.detect_pyramid(boxes, scales, im_shape[0], im_shape[1], dedup=dedup, batch_size=batch_size,
-                                       eps=eps)
+        return self.run(boxes, scales, im_shape, (dedup, batch_size, eps), pyramid=True)[:2]
 
     def forward(self, blobs=None, **kw):
         rois = np.ascontiguousarray(kw["rois"], dtype=np.float32)
@@ -258,14 +300,14 @@ class HipDetNet(_NetDict):
             if all(n in kw for n in self.skip_names):
                 self.set_skip_conv(kw)
             p, b = self.ctx.det_forward_skip(rois)
-            return {"cls_prob": p, "bbox_pred": b}
-        if "conv5_3" in kw and kw["conv5_3"] is not self.az_net._conv:
-            self.az_net.set_conv(kw["conv5_3"])
-        p, b = self.ctx.det_forward(rois)
+        else:
+            if "conv5_3" in kw:
+                self._bind(kw["conv5_3"], False, False)
+            p, b = self.ctx.det_forward(rois)
         return {"cls_prob": p, "bbox_pred": b}
 
 
-class HipFrcnnNet(_NetDict):
+class HipFrcnnNet(_DetNet):
     """Fast R-CNN detection net with its OWN conv layers, for detection over saved proposals: stands where the
     reference's `nets = {'full': caffe.Net(frcnn/test.prototxt, caffemodel)}` stood (tools/test_det_net.py, used by
     test_net, lib/detect/test.py:541-668).  It owns an az_ctx with only the detection head loaded (fp32) and a backbone:
@@ -275,28 +317,14 @@ class HipFrcnnNet(_NetDict):
     NAMES = ("full",)
 
     def __init__(self, det_head, backbone, device=0, name="vgg16_frcnn_hip", max_regions=None, skip_front=None):
-        """skip_front: the skip-connection detector's front (see HipDetNet); the backbone must then take `taps`
-        (VGG16Conv5.forward), compute_conv returns the dict of maps and detect goes through az_detect_skip.
-        det_head may carry truncated-SVD factors (see HipDetNet): it goes through az_load_det_head_lowrank."""
+        """With a skip front the backbone must take `taps` (VGG16Conv5.forward), compute_conv returns the dict of maps
+        and detect goes through az_detect_skip."""
         self.ctx = ffi.AzContext(device, max_regions=max_regions, gemm_mode=0)
-        self.ctx.load_det_head(det_head)           # (a dict with L / U factors: AzContext.load_det_head_lowrank)
-        if skip_front is None:
-            skip_front = det_head.get("skip_front") if isinstance(det_head, dict) else None   # (caffemodel.det_head_from_layers of a skip model)
-        self.skip_front, self.skip_names = None, None
-        if skip_front is not None:
-            self.attach_skip_front(skip_front)
+        self._load(det_head, skip_front, name)
         if ffi._default_ctx is None or getattr(ffi._default_ctx, "h", None) is None:
             ffi.set_default_context(self.ctx)      # apply_nms and the other drop-in helpers use this GPU
         self.backbone = backbone
         self.device = int(device)
-        self.num_classes = self.ctx.det_dims["ncls"]
-        self.name = name
-        self.blobs = {k: _Blob() for k in ("data", "rois", "conv5_3")}
-
-    def attach_skip_front(self, front):
-        """Load `front` into this net's context; compute_conv then returns the maps it names."""
-        self.ctx.load_skip_front(front)
-        self.skip_front, self.skip_names = front, _skip_names(front)
 
     def _torch_device(self):
         import torch
@@ -331,34 +359,34 @@ class HipFrcnnNet(_NetDict):
         self.ctx.set_feature_pyramid(maps)
         return maps
 
+    def _bind(self, maps, pyramid, iterative):
+        """maps: the pyramid's list of maps, the {name: map} dict of the skip model, or conv5_3 -- which only the
+        iterative route binds, as a pyramid of one level (set_feature_pyramid, whose level 0 is the context's single map:
+        az_set_feature_map_* want an AZ head, which this context has not); the plain route hands it to az_detect_batch."""
+        if pyramid:
+            self.ctx.set_feature_pyramid(maps)
+        elif self.skip_front is not None:
+            self.ctx.set_skip_maps([maps[n] for n in self.skip_names])
+        elif iterative:
+            self.ctx.set_feature_pyramid([maps])
+
+    def _detect_one(self, conv, boxes, scale, im_shape, kw):
+        return self.ctx.detect_batch([conv], [boxes], [scale], [im_shape], **kw)[0]
+
+    def detect(self, conv, boxes, scale, im_shape, dedup, batch_size, eps):
+        """One image: az_detect_batch with its pieces, or (a skip front) az_detect_skip on the dict of maps `conv` -- the
+        region capacity then bounds the proposals of one call, AZ_ERR_CAPACITY beyond it (as it does for detect_iter)."""
+        return self.run(boxes, [scale], im_shape, (dedup, batch_size, eps), maps=conv)[:2]
+
+    def detect_iter(self, conv, boxes, scale, im_shape, dedup, batch_size, eps, rounds, min_score, max_rows):
+        """detect() followed by rounds - 1 rounds of iterative localisation: (scores, boxes, extra), see AzContext.detect_iter."""
+        return self.run(boxes, [scale], im_shape, (dedup, batch_size, eps), maps=conv, refine=(rounds, min_score, max_rows))
+
     def detect_pyramid(self, maps, boxes, scales, im_shape, dedup, batch_size, eps):
         """_frcnn_forward of one image over its pyramid maps (az_detect_pyramid)."""
-        if maps is not None:
-            self.ctx.set_feature_pyramid(maps)
-        return self.ctx.detect_pyramid(boxes, scales, im_shape[0], im_shape[1], dedup=dedup, batch_size=batch_size,
-                                       eps=eps)
+        return self.run(boxes, scales, im_shape, (dedup, batch_size, eps), maps=maps, pyramid=True)[:2]
 
     def detect_batch(self, convs, boxes_list, scales, im_shapes, dedup, batch_size, eps):
         if self.skip_front is not None:
             raise ValueError("the skip-connection detector runs one image per call (az_detect_skip): no az_detect_batch")
         return self.ctx.detect_batch(convs, boxes_list, scales, im_shapes, dedup=dedup, batch_size=batch_size, eps=eps)
-
-    def detect(self, conv, boxes, scale, im_shape, dedup, batch_size, eps):
-        if self.skip_front is not None:
-            # (the region capacity bounds the proposals of one call: AZ_ERR_CAPACITY beyond it)
-            self.ctx.set_skip_maps([conv[n] for n in self.skip_names])
-            return self.ctx.detect_skip(boxes, scale, im_shape[0], im_shape[1], dedup=dedup, batch_size=batch_size, eps=eps)
-        return self.detect_batch([conv], [boxes], [scale], [im_shape], dedup, batch_size, eps)[0]
-
-    def detect_iter(self, conv, boxes, scale, im_shape, dedup, batch_size, eps, rounds, min_score, max_rows):
-        """detect() of one image followed by rounds - 1 rounds of iterative localisation: (scores, boxes, extra), see
-        AzContext.detect_iter.  The map is bound to the context and az_detect_iter / az_detect_iter_skip runs on it: the
-        skip maps through set_skip_maps, conv5_3 as a pyramid of one level (set_feature_pyramid, whose level 0 is the
-        context's single map -- az_set_feature_map_* want an AZ head, which this context has not).  More proposals than the
-        region capacity: AZ_ERR_CAPACITY."""
-        if self.skip_front is not None:
-            self.ctx.set_skip_maps([conv[n] for n in self.skip_names])
-        else:
-            self.ctx.set_feature_pyramid([conv])
-        return self.ctx.detect_iter(boxes, scale, im_shape[0], im_shape[1], rounds, min_score, max_rows, dedup=dedup,
-                                    batch_size=batch_size, eps=eps, skip=self.skip_front is not None)

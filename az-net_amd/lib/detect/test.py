@@ -481,74 +481,35 @@ def _frcnn_forward(net, im, all_boxes, num_classes, conv=None, refine=None):
     every class, un-dedup).  Returns scores [R, K] and boxes [R, 4K] as float64, and conv.
     A full net (a HipFrcnnNet, no 'fc' key: test.py:291) runs its own backbone on the image first, then the head
     (az_detect_batch of one image; more proposals than the region capacity go in pieces of whole dedup chunks).
-    refine = (rounds, min_score, max_rows) (_iter_loc_rounds): the nets' detect_iter in detect's place (az_detect_iter),
-    and a fourth result, the later rounds' rows (AzContext.detect_iter)."""
+    Which entry runs -- one scale, a pyramid, the skip-connection detector (test.py:300-304: one blob per name in
+    cfg.SEAR.FRCNN_CONV) -- is the net's choice (aznet_hip.net: _DetNet.run); here only the maps are found.
+    refine = (rounds, min_score, max_rows) (_iter_loc_rounds): iterative localisation (az_detect_iter), and a fourth
+    result, the later rounds' rows (AzContext.detect_iter)."""
     boxes = np.ascontiguousarray(all_boxes[:, 0:4], dtype=np.float64)
     scales = _im_scale(im.shape)
-    pyramid = len(scales) > 1
-    args = (cfg.DEDUP_BOXES, cfg.SEAR.BATCH_SIZE, cfg.EPS)
-    if refine is not None:
-        if pyramid:
-            raise ValueError("iterative localisation (cfg.TEST.ITER_LOC) takes one scale, cfg.TEST.SCALES has %d" % len(scales))
-        return _frcnn_forward_refined(net, im, boxes, scales[0], num_classes, conv, args + tuple(refine))
+    if refine is not None and len(scales) > 1:
+        raise ValueError("iterative localisation (cfg.TEST.ITER_LOC) takes one scale, cfg.TEST.SCALES has %d" % len(scales))
     if _is_full_net(net):
-        fnet = net["full"]
-        assert num_classes == fnet.num_classes
-        if _skip_mode(fnet):
-            # the skip-connection detector (test.py:300-304: one blob per name in cfg.SEAR.FRCNN_CONV): the tapped maps of
-            # its own backbone, then az_detect_skip
-            maps = _conv_dict(fnet.compute_conv(fnet.image_blob_enqueue(_as_uint8(im), cfg.PIXEL_MEANS, scales[0])))
-            scores, pred = fnet.detect(maps, boxes, scales[0], im.shape, *args)
-            return scores.astype(np.float64), pred, maps
-        if pyramid:
-            # an image pyramid: its padded maps, each roi pooled from the level its scaled area is closest to 224^2 at
-            maps = fnet.compute_pyramid(_as_uint8(im), cfg.PIXEL_MEANS, scales)
-            scores, pred = fnet.detect_pyramid(None, boxes, scales, im.shape, *args)
+        dnet = net["full"]
+        assert num_classes == dnet.num_classes
+        skip = _skip_mode(dnet)
+        if len(scales) > 1:
+            # an image pyramid: its padded maps (bound by compute_pyramid), each roi pooled from the level its scaled area
+            # is closest to 224^2 at
+            maps, bind = dnet.compute_pyramid(_as_uint8(im), cfg.PIXEL_MEANS, scales), None
         else:
-            maps = fnet.compute_conv(fnet.image_blob_enqueue(_as_uint8(im), cfg.PIXEL_MEANS, scales[0]))
-            scores, pred = fnet.detect(maps, boxes, scales[0], im.shape, *args)
-        return scores.astype(np.float64), pred, {name: maps for name in cfg.SEAR.FRCNN_CONV}
-    # shared detection on the map (or pyramid) the AZ search left in the context, or the cached one in `conv`
-    dnet = net["fc"] if isinstance(net, dict) else net
-    assert num_classes == dnet.num_classes
-    if _skip_mode(dnet):
-        if conv is not None:
-            dnet.set_skip_conv(_conv_dict(conv))
-        scores, pred = dnet.detect(boxes, scales[0], im.shape, *args)
-        return scores.astype(np.float64), pred, conv
-    if conv is not None:
-        c = conv[cfg.SEAR.FRCNN_CONV[0]]
-        if c is not dnet.az_net._conv:
-            (dnet.az_net.set_pyramid if pyramid else dnet.az_net.set_conv)(c)
-    if pyramid:
-        scores, pred = dnet.detect_pyramid(boxes, scales, im.shape, *args)
+            maps = dnet.compute_conv(dnet.image_blob_enqueue(_as_uint8(im), cfg.PIXEL_MEANS, scales[0]))
+            bind = maps = _conv_dict(maps) if skip else maps
+        conv = maps if skip else {name: maps for name in cfg.SEAR.FRCNN_CONV}
     else:
-        scores, pred = dnet.detect(boxes, scales[0], im.shape, *args)
-    return scores.astype(np.float64), pred, conv
-
-
-def _frcnn_forward_refined(net, im, boxes, scale, num_classes, conv, args):
-    """_frcnn_forward's three single-scale routes with detect_iter in detect's place: (scores, boxes, conv, extra)."""
-    if _is_full_net(net):
-        fnet = net["full"]
-        assert num_classes == fnet.num_classes
-        maps = fnet.compute_conv(fnet.image_blob_enqueue(_as_uint8(im), cfg.PIXEL_MEANS, scale))
-        if _skip_mode(fnet):
-            maps = _conv_dict(maps)
-        scores, pred, extra = fnet.detect_iter(maps, boxes, scale, im.shape, *args)
-        return (scores.astype(np.float64), pred, maps if _skip_mode(fnet) else {name: maps for name in cfg.SEAR.FRCNN_CONV},
-                extra)
-    dnet = net["fc"] if isinstance(net, dict) else net
-    assert num_classes == dnet.num_classes
-    if _skip_mode(dnet):
-        if conv is not None:
-            dnet.set_skip_conv(_conv_dict(conv))
-    elif conv is not None:
-        c = conv[cfg.SEAR.FRCNN_CONV[0]]
-        if c is not dnet.az_net._conv:
-            dnet.az_net.set_conv(c)
-    scores, pred, extra = dnet.detect_iter(boxes, scale, im.shape, *args)
-    return scores.astype(np.float64), pred, conv, extra
+        # shared detection on the map (or pyramid) the AZ search left in the context, or the cached one in `conv`
+        dnet = net["fc"] if isinstance(net, dict) else net
+        assert num_classes == dnet.num_classes
+        skip = _skip_mode(dnet)
+        bind = None if conv is None else _conv_dict(conv) if skip else conv[cfg.SEAR.FRCNN_CONV[0]]
+    scores, pred, extra = dnet.run(boxes, scales, im.shape, (cfg.DEDUP_BOXES, cfg.SEAR.BATCH_SIZE, cfg.EPS), bind, refine)
+    out = (scores.astype(np.float64), pred, conv)
+    return out if refine is None else out + (extra,)
 
 
 def im_detect_refined(net, im, boxes, num_classes, conv=None):

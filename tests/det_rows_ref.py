@@ -4,7 +4,8 @@ tests/test_det_rows_host.py and tests/test_gpu_det_rows.py).
 The detection head reaches k_fc_splitk12 (az_head12.hip) in ways the AZ head never does: fc7 qualifies as well as fc6 (a
 short work-item chain whose A operand is a ReLU output), the kernel is chosen by the number of boxes BEFORE the 1/16 dedup
 while the row count is what the device finds after it, and the rows of several images share a launch (launch_det_head in
-az_units.hip).  Two shapes, the smallest at which both layers still satisfy `can12` (azk_fc_gemm12_fits, az_head12.hip):
+az_detect.hip, which reads what a pass needs from one DetPass record).  Two shapes, the smallest at which both layers still
+satisfy `can12` (azk_fc_gemm12_fits, az_head12.hip):
 
   FULL   (512, 4096, 4096, 21)   fc6 16 chunks of 1568, fc7 8 chunks of 512: the reference's own shape
   SHORT  (512, 2048, 4096, 81)   fc6 16 n-tiles x 16 chunks = 256 groups, the minimum; fc7 K = 2048: 8 chunks of 256 = 8 K-steps

@@ -1,7 +1,9 @@
 """GPU: the detection head on the many-row GEMM (k_fc_splitk12, az_head12.hip) across row counts (cases and premises:
 tests/det_rows_ref.py, tests/test_det_rows_host.py).
 
-What forks on the detection head's row count, and where it is visited (launch_det_head, az_units.hip; the choice of kernel: fc_gemm_fp32, az_ctx.hip):
+What forks on the detection head's row count, and where it is visited (launch_det_head, az_detect.hip: it
+takes the pass's DetPass record -- projection, pool source, image sizes --, the row-count pointer and the host's row bound; the
+choice of kernel: fc_gemm_fp32, az_ctx.hip):
   A  integer-exact heads, FULL and SHORT, GEMM mode 0: det_forward of rois[:n] and rois[2048 - n:] at every n of
      det_rows_ref.ROWS_A -- k_fc_splitk below 161 rows, the switch, the half strip (M & 31 in 1..16), the full but masked
      last strip (17..31), a multiple of 32, the m-tile seams 384 | 385, 768 | 769, six m-tiles, M = the context's capacity.
