@@ -15,19 +15,18 @@
 // summarize runs on the host over the copied precision / recall, with NumPy's pairwise mean.
 // -ffp-contract=off (Makefile): every product and sum rounds once, as maskApi.c's and NumPy's double arithmetic do.
 #include "az_ctx.h"
+#include "az_eval_dev.h"
 
 #include <vector>
 
 namespace {
 
-constexpr int CT = 256;               // threads of every workgroup here (4 waves)
-constexpr int NT = 10, NR = 101, NA = 4, NM = 3;
-constexpr int MAXDET = 100;           // maxDets[-1]: evaluateImg keeps a segment's first 100 detections
+constexpr int CT = EVAL_VT;           // threads of every workgroup here (4 waves)
+constexpr int NT = COCO_NT, NR = COCO_NR, NA = 4, NM = 3;
+constexpr int MAXDET = COCO_MAXDET;
 constexpr int NL = NA * NT;           // (area range, threshold) lanes of k_coco_match
-
-// np.linspace(.5, .95, 10) and np.linspace(0, 1, 101): i * step + start, the last one set to stop
-__device__ __forceinline__ double iou_thr(int t) { return t == NT - 1 ? 0.95 : (double)t * ((0.95 - 0.5) / 9.0) + 0.5; }
-__device__ __forceinline__ double rec_thr(int r) { return r == NR - 1 ? 1.0 : (double)r * 0.01; }
+// iou_thr, rec_thr, bb_iou and accumulate's curve (coco_curve) live in az_eval_dev.h: az_cdiag.hip (az_coco_diag_eval)
+// calls the same.
 __device__ __forceinline__ double area_lo(int a) { return a == 2 ? 1024.0 : (a == 3 ? 9216.0 : 0.0); }
 __device__ __forceinline__ double area_hi(int a) { return a == 1 ? 1024.0 : (a == 2 ? 9216.0 : 1e10); }
 
@@ -79,16 +78,7 @@ __global__ void __launch_bounds__(CT) k_coco_match(int S, int D, const int *__re
                     for (int k = 0; k < NA; ++k)
                         if (crowd || ar < area_lo(k) || ar > area_hi(k)) fl |= 1u << k;
                     if (crowd) fl |= 16u;
-                    // maskApi.c bbIou
-                    const double w = fmin(dw + dx, gw + gx) - fmax(dx, gx);
-                    if (w > 0.0) {
-                        const double h = fmin(dh + dy, gh + gy) - fmax(dy, gy);
-                        if (h > 0.0) {
-                            const double i = w * h;
-                            const double u = crowd ? da : da + gw * gh - i;
-                            o = i / u;
-                        }
-                    }
+                    bb_iou(dx, dy, dw, dh, da, gx, gy, gw, gh, crowd, &o);
                 }
                 for (int jj = 0; jj < cnt; ++jj) {
                     const double oj = __shfl(o, jj, AZ_WAVE);
@@ -121,27 +111,6 @@ __global__ void __launch_bounds__(CT) k_coco_match(int S, int D, const int *__re
     }
 }
 
-// inclusive scan over the workgroup in thread order; `carry` is added in front and updated to the total
-__device__ __forceinline__ unsigned long long block_scan_add(unsigned long long v, unsigned long long &carry,
-                                                             unsigned long long *s_w)
-{
-    const int lane = threadIdx.x & (AZ_WAVE - 1), w = threadIdx.x / AZ_WAVE;
-    for (int d = 1; d < AZ_WAVE; d <<= 1) {
-        const unsigned long long u = __shfl_up(v, d, AZ_WAVE);
-        if (lane >= d) v += u;
-    }
-    if (lane == AZ_WAVE - 1) s_w[w] = v;
-    __syncthreads();
-    unsigned long long pre = carry, tot = carry;
-    for (int k = 0; k < CT / AZ_WAVE; ++k) {
-        if (k < w) pre += s_w[k];
-        tot += s_w[k];
-    }
-    __syncthreads();
-    carry = tot;
-    return pre + v;
-}
-
 __global__ void __launch_bounds__(CT) k_coco_acc(int K, int n_images, const int *__restrict__ det_off,
                                                   const int *__restrict__ gt_off, const double *__restrict__ gt_area,
                                                   const unsigned char *__restrict__ gt_crowd, const unsigned *__restrict__ pc,
@@ -164,71 +133,16 @@ __global__ void __launch_bounds__(CT) k_coco_acc(int K, int n_images, const int 
     for (int j = glo + t; j < ghi; j += CT) np += (gt_crowd[j] || gt_area[j] < lo || gt_area[j] > hi) ? 0u : 1u;
     {
         unsigned long long zero = 0;
-        block_scan_add(np, zero, s_w);
+        block_scan(np, zero, s_w, [](unsigned long long x, unsigned long long y) { return x + y; });
         np = zero;
     }
-    if (np == 0) {                                   // accumulate leaves -1
-        for (int e = t; e < NT * NR; e += CT) precision[(size_t)e * tstride + col] = -1.0;
-        if (t < NT) recall[(size_t)t * tstride + col] = -1.0;
-        return;
-    }
-    const double dn = (double)np;
-    if (t < NR) {
-        const double th = rec_thr(t);
-        long long x = 0, y = (long long)np;          // smallest c with c / npig >= th (c = npig gives 1.0)
-        while (x < y) {
-            const long long mid = (x + y) >> 1;
-            if ((double)mid / dn >= th) y = mid; else x = mid + 1;
-        }
-        c_r[t] = (int)x;
-    }
-    for (int e = t; e < NT * NR; e += CT) bucket[e / NR][e % NR] = 0ull;
-    __syncthreads();
-    unsigned long long carry[NT];
-    for (int q = 0; q < NT; ++q) carry[q] = 0;
-    int nd = 0;
-    for (int p0 = dlo; p0 < dhi; p0 += CT) {
-        const int p = p0 + t;
-        unsigned tb = 0, fb = 0;
-        bool keep = false;
-        if (p < dhi) {
-            const unsigned d = pc[p];
-            keep = segrank[d] < maxdet;
-            if (keep) {
-                tb = (unsigned)(tpm[d] >> (NT * a)) & 1023u;
-                fb = (unsigned)(fpm[d] >> (NT * a)) & 1023u;
-            }
-        }
-        nd += __syncthreads_count(keep);
-        for (int q = 0; q < NT; ++q) {
-            const unsigned long long v = block_scan_add(((unsigned long long)((tb >> q) & 1u) << 32) | ((fb >> q) & 1u),
-                                                        carry[q], s_w);
-            if ((tb >> q) & 1u) {
-                const long long j = (long long)(v >> 32);
-                const double tp = (double)j, fp = (double)(v & 0xffffffffull);
-                const double pr = tp / (fp + tp + 2.220446049250313e-16);   // np.spacing(1)
-                int x = 0, y = NR - 1;                                   // last r with c_r[r] <= j (c_r[0] = 0)
-                while (x < y) {
-                    const int mid = (x + y + 1) >> 1;
-                    if (c_r[mid] <= j) x = mid; else y = mid - 1;
-                }
-                atomicMax(&bucket[q][x], (unsigned long long)__double_as_longlong(pr));   // pr >= 0: bits order as values
-            }
-        }
-    }
-    __syncthreads();
-    for (int e = t; e < NT * NR; e += CT) {
-        const int q = e / NR, r = e % NR;
-        unsigned long long b = 0;
-        for (int x = r; x < NR; ++x) b = bucket[q][x] > b ? bucket[q][x] : b;
-        precision[(size_t)e * tstride + col] = __longlong_as_double((long long)b);
-    }
-    if (t < NT) {
-        double tot = 0.0;
-        for (int q = 0; q < NT; ++q)
-            if (q == t) tot = (double)(carry[q] >> 32);
-        recall[(size_t)t * tstride + col] = nd ? tot / dn : 0.0;
-    }
+    coco_curve<NT>(dlo, dhi, np, [&](int p, unsigned *tb, unsigned *fb) {
+        const unsigned d = pc[p];
+        if (segrank[d] >= maxdet) return false;
+        *tb = (unsigned)(tpm[d] >> (NT * a)) & 1023u;
+        *fb = (unsigned)(fpm[d] >> (NT * a)) & 1023u;
+        return true;
+    }, precision, recall, tstride, col, col, s_w, bucket, c_r);
 }
 
 size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }

@@ -271,25 +271,9 @@ int az_det_diag_eval(az_ctx *c, int n_classes, int n_images, const double *det_b
     size_t hist_n = 0, sums_n = 0;
     rank_scratch_sizes(D, &hist_n, &sums_n);
     if (hist_n >= 0x7fffffffULL) return fail(c, AZ_ERR_CAPACITY, "az_det_diag_eval: too many detections");
-    // the image-major index of the ground truth: image -> its boxes' rows in gt_box and their classes, (class, position) order
-    std::vector<int> ioff((size_t)n_images + 1, 0), ig((size_t)G), ic((size_t)G);
-    for (int k = 0; k < n_classes; ++k)
-        for (int i = 0; i < n_images; ++i) {
-            const long long s = (long long)k * n_images + i;
-            ioff[(size_t)i + 1] += gt_off[s + 1] - gt_off[s];
-        }
-    for (int i = 0; i < n_images; ++i) ioff[(size_t)i + 1] += ioff[i];
-    {
-        std::vector<int> fill(ioff.begin(), ioff.end() - 1);
-        for (int k = 0; k < n_classes; ++k)
-            for (int i = 0; i < n_images; ++i) {
-                const long long s = (long long)k * n_images + i;
-                for (int g = gt_off[s]; g < gt_off[s + 1]; ++g) {
-                    ig[(size_t)fill[i]] = g;
-                    ic[(size_t)fill[i]++] = k;
-                }
-            }
-    }
+    // the image-major index of the ground truth (az_eval_dev.h)
+    std::vector<int> ioff, ig, ic;
+    image_index(n_classes, n_images, gt_off, G, ioff, ig, ic);
     // one arena: inputs, the index, the ranking's scratch, per-detection and per-box results, one set of curves, the tables
     size_t off = 0;
     auto take = [&](size_t bytes) { const size_t o = off; off += align_up(bytes); return o; };

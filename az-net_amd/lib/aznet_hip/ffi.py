@@ -66,7 +66,7 @@ SYMBOLS = [
     "az_load_det_head_lowrank", "az_lowrank_gemm_unit", "az_lowrank_split",
     "az_load_head_lowrank", "az_az_lowrank_split",
     "az_detect_iter", "az_detect_iter_skip",
-    "az_det_diag_eval",
+    "az_det_diag_eval", "az_coco_diag_eval",
 ]
 AZ_ITER_LOC_MAX_ROUNDS = 8  # include/aznet_hip.h
 AZ_ITER_LOC_MAX_ROWS = 4096  # include/aznet_hip.h (az_detect_iter: az_topk's largest k)
@@ -265,6 +265,8 @@ def load_library(path=None):
     i64p = ctypes.POINTER(ctypes.c_int64)
     L.az_det_diag_eval.argtypes = [vp, ci, ci, dp, dp, ip, dp, u8p, ip, cd, cd, ci, ip, dp, ci, ctypes.POINTER(ctypes.c_int8),
                                    dp, ip, dp, ip, u8p, ip, i64p, i64p, i64p, i64p, dp, fp]
+    L.az_coco_diag_eval.argtypes = [vp, ci, ci, dp, dp, ip, dp, dp, u8p, ip, cd, ip, dp, ip, dp, ip, ctypes.POINTER(ctypes.c_int8),
+                                    u8p, ip, i64p, i64p, i64p, dp, dp, fp]
     L.az_zoom_labels.argtypes = [vp, dp, ci, dp, ci, cd, cd, u8p]
     L.az_train_ex_rois.argtypes = [vp, tpp, ci, ip, dp, ip, dp, ll, fp, u8p, ip, ci, llp, llp]
     L.az_train_adj_targets.argtypes = [vp, tpp, ci, fp, ip, fp, ip, dp, ip, ci]
@@ -370,6 +372,26 @@ def az_lowrank_split(K, r):
     if n < 1:
         raise AzError(n, "az_az_lowrank_split(%d, %d)" % (K, r))
     return n
+
+
+def coco_diag_means(prec_fix):
+    """What coco_diag_eval adds to az_coco_diag_eval's curves prec_fix [8,10,101,K] on the host: ap_fix [K,10,8], the mean
+    over recThrs of the entries > -1 (NaN where none), and stats_fix [8,3], AP / AP50 / AP75 per variant by COCOeval
+    summarize's expression np.mean(s[s > -1]) over s [T,R,K] (-1 where none)."""
+    p = np.ascontiguousarray(prec_fix, np.float64)
+    K = p.shape[3]
+    q = np.ascontiguousarray(p.transpose(3, 1, 0, 2))    # [K,10,8,101]: a curve is all -1 or has no -1, but for a caller's own array
+    ok = q > -1
+    every, some = ok.all(-1), ok.any(-1)
+    with np.errstate(invalid="ignore"):
+        ap = np.where(every, q.mean(-1), np.nan) if K else np.zeros((0, 10, 8))
+    for k, t, v in zip(*np.nonzero(some & ~every)):
+        ap[k, t, v] = np.mean(q[k, t, v][ok[k, t, v]])
+    stats = np.zeros((8, 3))
+    for v in range(8):
+        for j, s in enumerate((p[v], p[v, 0:1], p[v, 5:6])):
+            stats[v, j] = -1 if len(s[s > -1]) == 0 else np.mean(s[s > -1])
+    return {"ap_fix": ap, "stats_fix": stats}
 
 
 class AzContext(object):
@@ -1673,6 +1695,55 @@ class AzContext(object):
             _p(out["gt_claim"], ctypes.c_int32), _p(out["type_table"], i64), _p(out["miss"], i64), _p(out["fp_at"], i64),
             _p(out["npos"], i64), _p(out["ap_fix"], ctypes.c_double), ctypes.byref(ms) if want_kernel_ms else None))
         out["cuts"] = ct.copy()
+        if want_kernel_ms:
+            out["kernel_ms"] = float(ms.value)
+        return out
+
+    def coco_diag_eval(self, n_classes, n_images, det_box, det_score, det_off, gt_box, gt_area, gt_crowd, gt_off,
+                       bg_overlap=0.1, class_group=None, want_kernel_ms=False):
+        """az_coco_diag_eval ("Detection diagnosis, COCO protocol") on coco_eval's arguments, plus bg_overlap
+        (in [0, 0.5]) and class_group [K] int32 (None: every class its own group); area range all, maxDets 100, the ten
+        thresholds.  Returns a dict: per detection in input order ov_same / ov_other [D] f64, arg_same / other_class [D]
+        int32, type [10,D] int8 (-1 past the segment's first 100, 0 IGN, 1 TP, 2 DUP, 3 LOC, 4 SIM, 5 OTH, 6 BG),
+        loc_fixed [10,D] u8; gt_claim [10,G] int32; per class npos [K], type_table [K,10,7], miss [K,10] int64; the
+        curves prec_fix [8,10,101,K] and recall_fix [8,10,K] (variant 0 is coco_eval's precision[:, :, :, 0, 2]); and
+        from them ap_fix [K,10,8] (the mean over recThrs of the entries > -1, NaN where none) and stats_fix [8,3]
+        (AP, AP50, AP75 per variant by summarize's np.mean(s[s > -1]), -1 where none); with want_kernel_ms the
+        kernels' device time."""
+        bx = _f64(det_box).reshape(-1, 4)
+        sc = _f64(det_score).ravel()
+        doff = np.ascontiguousarray(det_off, dtype=np.int32).ravel()
+        gb = _f64(gt_box).reshape(-1, 4)
+        ga = _f64(gt_area).ravel()
+        gc = np.ascontiguousarray(gt_crowd, dtype=np.uint8).ravel()
+        goff = np.ascontiguousarray(gt_off, dtype=np.int32).ravel()
+        K = int(n_classes)
+        nseg = K * int(n_images)
+        if doff.size != nseg + 1 or goff.size != nseg + 1:
+            raise AzError(AZ_ERR_INVALID, "coco_diag_eval: offsets need n_classes*n_images+1 entries")
+        D, G = int(doff[-1]), int(goff[-1])
+        if bx.shape[0] != D or sc.size != D or gb.shape[0] != G or ga.size != G or gc.size != G:
+            raise AzError(AZ_ERR_INVALID, "coco_diag_eval: array sizes disagree with the offsets")
+        grp = None
+        if class_group is not None:
+            grp = np.ascontiguousarray(class_group, dtype=np.int32).ravel()
+            if grp.size != K:
+                raise AzError(AZ_ERR_INVALID, "coco_diag_eval: class_group needs n_classes entries")
+        out = {"ov_same": np.zeros(D), "arg_same": np.zeros(D, np.int32), "ov_other": np.zeros(D),
+               "other_class": np.zeros(D, np.int32), "type": np.zeros((10, D), np.int8), "loc_fixed": np.zeros((10, D), np.uint8),
+               "gt_claim": np.zeros((10, G), np.int32), "npos": np.zeros(K, np.int64), "type_table": np.zeros((K, 10, 7), np.int64),
+               "miss": np.zeros((K, 10), np.int64), "prec_fix": np.zeros((8, 10, 101, K)), "recall_fix": np.zeros((8, 10, K))}
+        ms = ctypes.c_float(0.0)
+        i64 = ctypes.c_int64
+        self._chk(self.L.az_coco_diag_eval(
+            self.h, K, int(n_images), _p(bx, ctypes.c_double), _p(sc, ctypes.c_double), _p(doff, ctypes.c_int32),
+            _p(gb, ctypes.c_double), _p(ga, ctypes.c_double), _p(gc, ctypes.c_uint8), _p(goff, ctypes.c_int32),
+            float(bg_overlap), None if grp is None else _p(grp, ctypes.c_int32), _p(out["ov_same"], ctypes.c_double),
+            _p(out["arg_same"], ctypes.c_int32), _p(out["ov_other"], ctypes.c_double), _p(out["other_class"], ctypes.c_int32),
+            _p(out["type"], ctypes.c_int8), _p(out["loc_fixed"], ctypes.c_uint8), _p(out["gt_claim"], ctypes.c_int32),
+            _p(out["npos"], i64), _p(out["type_table"], i64), _p(out["miss"], i64), _p(out["prec_fix"], ctypes.c_double),
+            _p(out["recall_fix"], ctypes.c_double), ctypes.byref(ms) if want_kernel_ms else None))
+        out.update(coco_diag_means(out["prec_fix"]))
         if want_kernel_ms:
             out["kernel_ms"] = float(ms.value)
         return out

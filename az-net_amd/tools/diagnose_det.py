@@ -5,7 +5,13 @@ NMS at cfg.TEST.NMS first, exactly as tools/eval_det.py applies it (detect.test.
 detection typed after Hoiem et al. (ECCV 2012) -- true positive, duplicate, localisation, similar class, other class,
 background -- the missed objects, and the AP with each kind of error fixed (TIDE, ECCV 2020), in one device call over
 the whole set.  Prints the tables and writes <out>/det_diagnosis.pkl.  The reference has no counterpart: it left
-evaluation to MATLAB.  The VOC protocol on any imdb with ground truth (a COCO imdb through its gt_roidb)."""
+evaluation to MATLAB.
+--protocol voc (the default): VOCevaldet's rules on any imdb with ground truth (a COCO imdb through its gt_roidb) -- one
+threshold 0.5, the +1 overlap, difficult boxes, the 11-point or area AP, and the cut table of the top-ranked detections.
+--protocol coco: COCOeval's rules -- ten thresholds .50:.95, crowd boxes, the first 100 detections per image and
+category, the 101-point AP; the AP / AP50 / AP75 that eval_det.py prints for a COCO imdb, each with its seven dAP columns,
+and the type tables at IoU .50 and .75.  A COCO imdb is packed from its annotation file as evaluation packs it (no file
+is written), any other imdb from gt_roidb.  Writes <out>/det_diagnosis_coco.pkl.  Area range all only; no cut table."""
 import _init_paths  # noqa: F401
 import argparse
 import os
@@ -22,6 +28,9 @@ def build_parser():
     ap.add_argument("--no-nms", dest="no_nms", action="store_true", help="diagnose the detections as saved")
     ap.add_argument("--bg-overlap", dest="bg_overlap", type=float, default=0.1,
                     help="overlap from which a false positive is a localisation error or a confusion (default 0.1)")
+    ap.add_argument("--protocol", dest="protocol", choices=("voc", "coco"), default="voc",
+                    help="voc: VOCevaldet's rules, one threshold, det_diagnosis.pkl (default); coco: COCOeval's rules, "
+                         "AP@[.5:.95] / AP50 / AP75 with area all and maxDets 100, det_diagnosis_coco.pkl")
     ap.add_argument("--cfg", dest="cfg_file", default=None)
     ap.add_argument("--gpu", dest="gpu_id", type=int, default=0)
     return _cli.add_flags(ap, [_cli.POSTPROC])
@@ -49,12 +58,12 @@ def main():
         all_boxes = postprocess_detections(all_boxes)
     from aznet_hip import ffi
     ctx = ffi.default_context(args.gpu_id)               # --gpu's device: the context the NMS above ran on, or a new one there
-    d = diagnose(imdb, all_boxes, bg_overlap=args.bg_overlap, ctx=ctx)
+    d = diagnose(imdb, all_boxes, bg_overlap=args.bg_overlap, ctx=ctx, protocol=args.protocol)
     for line in summary_lines(d):
         print(line)
     out = args.output_dir or os.path.dirname(os.path.abspath(args.dets))
     os.makedirs(out, exist_ok=True)
-    path = os.path.join(out, "det_diagnosis.pkl")
+    path = os.path.join(out, "det_diagnosis_coco.pkl" if args.protocol == "coco" else "det_diagnosis.pkl")
     with open(path, "wb") as f:
         pickle.dump(d, f, pickle.HIGHEST_PROTOCOL)
     print("wrote", path)

@@ -752,6 +752,59 @@ int az_det_diag_eval(az_ctx *ctx, int n_classes, int n_images,
                      int32_t *gt_claim_out, int64_t *type_table_out, int64_t *miss_out,
                      int64_t *fp_at_out, int64_t *npos_out, double *ap_fix_out, float *kernel_ms_out);
 
+/* The same diagnosis under the COCO protocol, restated in DESIGN §4, "Detection diagnosis, COCO protocol": why
+ * az_coco_eval's AP@[.5:.95] is what it is.  The inputs are az_coco_eval's (class-major (category, image) segments, xywh
+ * f64 boxes, det_score, gt_area, gt_crowd) plus bg_overlap and class_group[n_classes] (int32; NULL: every class is its
+ * own group).  Fixed settings: area range ALL, maxDets 100, each of the ten thresholds thr = linspace(.5, .95, 10); the
+ * per-area-range diagnosis (AP small / medium / large with fixes) and the cut table of az_det_diag_eval (fp_at) are out of
+ * scope.  The ranking, the IoU (maskApi's bbIou) and the matching are az_coco_eval's, instruction for instruction.  A box
+ * COUNTS when it is not a crowd box and its area field lies in [0, 1e10] (COCOeval's gtIgnore = 0 in area range all);
+ * wherever "non-crowd" is said below, such boxes are meant.  Every output may be NULL.
+ * Per detection d of segment (k, i), in input order, among the segment's first 100 by stable -score (past them: 0.0 / -1):
+ *   ov_same_out [D] f64 / arg_same_out [D] i32     the largest IoU with the segment's non-crowd boxes (pairs with w > 0 and
+ *                                h > 0 only; the first maximum in position order) and that box's position in the segment;
+ *                                0.0 / -1 where nothing overlaps.  They do not depend on the threshold
+ *   ov_other_out [D] f64 / other_class_out [D] i32 the same over image i's non-crowd boxes of every other category, the
+ *                                first maximum in (category, position) order, and that box's category
+ *   type_out [10][D] i8          per threshold t the first rule that fits:
+ *                                -1      past the segment's first 100: not evaluated (as dt_match_out's -1)
+ *                                0 IGN   evaluateImg matched it to a crowd box, or it is unmatched and its area w*h lies
+ *                                        outside [0, 1e10]: exactly az_coco_eval's dtIgnore for area range all
+ *                                1 TP    evaluateImg matched it to a non-crowd box m: gt_claim[t][m] = d; m is
+ *                                        az_coco_eval's dt_match_out[0][t][d]
+ *                                2 DUP   unmatched and ov_same >= thr[t] (every such box is taken already)
+ *                                3 LOC   unmatched and ov_same >= bg_overlap
+ *                                4 SIM   unmatched, ov_other >= bg_overlap, class_group[k] == class_group[other_class]
+ *                                5 OTH   unmatched, ov_other >= bg_overlap, another group
+ *                                6 BG    anything else
+ *   loc_fixed_out [10][D] u8     TIDE's rule, after the segment's matching at t: a LOC row, in rank order, is fixed when
+ *                                no detection claimed its arg_same box at t (a lower-ranked TP counts) and no higher-ranked
+ *                                LOC row was fixed onto that box at t
+ * Per box:   gt_claim_out [10][G] i32   the input index of the detection that claimed the box at t, or -1 (crowd boxes: -1)
+ * Per class: npos_out [K] i64           non-crowd boxes
+ *            type_table_out [K][10][7] i64   the count of each type at t
+ *            miss_out [K][10] i64       non-crowd boxes unclaimed at t
+ * The curves: prec_fix_out [8][10][101][K] f64 / recall_fix_out [8][10][K] f64 -- accumulate's interpolated precision at
+ * recThrs = linspace(0, 1, 101) and its final recall for (k, area all, maxDets 100), in k_coco_acc's arithmetic
+ * (np.spacing(1) in the precision, the envelope, searchsorted(.., 'left'), -1 where the variant's npig is 0), under
+ *   0 plain (az_coco_eval's precision[:, :, :, 0, 2]);  1 DUP rows ignored;  2 fixed LOC rows count as TP, the other LOC rows
+ *   are ignored;  3 SIM / 4 OTH / 5 BG rows ignored;  6 missed objects removed (npig = the TP count at t);  7 all of
+ *   these (npig = TP + fixed rows at t).
+ * The means (AP, AP50, AP75 per variant) are summarize's np.mean(s[s > -1]) and are taken by the caller.
+ *   kernel_ms_out [1] f32        device time of the launches (two events around them)
+ * Offsets are validated as az_coco_eval validates them (same codes); a NaN or negative bg_overlap or bg_overlap > 0.5 is
+ * AZ_ERR_INVALID; all before any device work and with the outputs untouched.  After AZ_ERR_HIP the per-detection and
+ * per-box outputs are undefined (the tables and curves are written only on success).  D = 0 and G = 0 are valid.  Device
+ * scratch is kept in the context (the slot az_coco_eval uses: calls are synchronous, the two never overlap). */
+int az_coco_diag_eval(az_ctx *ctx, int n_classes, int n_images,
+                      const double *det_box, const double *det_score, const int32_t *det_off,
+                      const double *gt_box, const double *gt_area, const uint8_t *gt_crowd, const int32_t *gt_off,
+                      double bg_overlap, const int32_t *class_group,
+                      double *ov_same_out, int32_t *arg_same_out, double *ov_other_out, int32_t *other_class_out,
+                      int8_t *type_out, uint8_t *loc_fixed_out, int32_t *gt_claim_out,
+                      int64_t *npos_out, int64_t *type_table_out, int64_t *miss_out,
+                      double *prec_fix_out, double *recall_fix_out, float *kernel_ms_out);
+
 /* ---- image front-end (_get_image_blob, lib/detect/test.py:27-59) ------------------------- */
 /* uint8 BGR HWC image (host) -> float32 [3, oh, ow] blob: subtract cfg.PIXEL_MEANS, then
  * cv2.resize(fx=fy=scale, INTER_LINEAR) semantics on f32 (half-pixel centres, edge clamp,
